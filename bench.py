@@ -21,11 +21,23 @@ carries `"backend": "gloo"` and `devices_used` < n_gpus).  Started by a launcher
 equal the world size.  The line reports `n_gpus`, the backend, the world size the process group saw and every
 rank's own block timings (`ranks`).
 
-Order of events: spin-up -> pre-roll (>= 0.25 s of untimed steps, so that the GPU is at its working
-clocks whatever `--warmup` says) -> W warm-up steps -> `--repeats` blocks of EXACTLY K steps, each
-bracketed by barrier + synchronize on both sides and timed with the host clock (max over ranks) and
-with HIP events on the stream the kernels run on -> only then the state download, the ice fraction
-and the CPU baseline.  `ms_per_step` / `value` are the MEDIAN block; every block is printed.
+Order of events: spin-up -> pre-roll (>= 0.25 s of untimed steps on a scratch handle of the same
+workload, so that the GPU is at its working clocks whatever `--warmup` says while the measured state
+stays a function of the arguments alone) -> W warm-up steps -> `--repeats` blocks of EXACTLY K steps
+(default: one block, so that `--steps` is the number of timed steps), each bracketed by barrier +
+synchronize on both sides and timed with the host clock (max over ranks) and with HIP events on the
+stream the kernels run on -> `--dump-outputs` -> only then, with `--full`, the state download, the
+ice fraction and the CPU baseline.  `ms_per_step` / `value` are the MEDIAN block; every block is printed.
+
+A plain run does only what the headline figure needs.  `--full` adds what takes time of its own: five
+timed blocks by default, the CPU baseline (`cpu_baseline`), the host-transfer rates (`host_transfer`)
+and the ice-covered fraction of the timed state; without it those keys are null.
+
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step, one
+float64 `DIR/<name>.npy` per array (rank 0's block of columns): the prognostic fields of one launch per
+step or fused-K, all ten variables of the step workload, the annual means (`avg_<var>`) of the integrate
+workload.  Arrays of more than DUMP_BUDGET_BYTES together are cut to the same seeded sample of whole
+columns (`dump_columns`), so that two builds can be compared output for output.
 
 Other workloads (never the headline; `metric` names them):
   --workload miz_180x1 / miz_1440x1 [--steps-per-launch K]   1-D shapes of configs[0] / [1]; with K > 1
@@ -60,6 +72,8 @@ import __graft_entry__ as graft  # noqa: E402
 BYTES_PER_CELL_STEP = 96.0       # MIZ, state only
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PREROLL_S = 0.25
+DUMP_BUDGET_BYTES = 60 * 2**20   # --dump-outputs: all arrays together, float64
+DUMP_SEED = 20261016
 
 WORKLOADS = {
     # name: (model, grid kind, nlat, ncol, nt)
@@ -127,6 +141,26 @@ def cells_bytes(nlat, ncol):
     return 8.0 * nlat * ncol
 
 
+def dump_columns(ncol, nlat, narrays, budget=DUMP_BUDGET_BYTES):
+    """Columns that --dump-outputs writes: all of them when `narrays` float64 arrays of ncol x nlat fit the budget,
+    else a seeded sample of whole columns (sorted) — the same in every run of the same workload."""
+    k = min(ncol, budget // (narrays * nlat * 8))
+    if k >= ncol:
+        return np.arange(ncol)
+    if k < 1:
+        raise ValueError(f"--dump-outputs: one column of {narrays} arrays of {nlat} latitudes exceeds {budget} bytes")
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ncol, size=k, replace=False))
+
+
+def write_outputs(dirname, arrays, nlat):
+    """arrays: name -> ncol x nlat array; written as DIR/<name>.npy in float64, cut to dump_columns."""
+    ncol = next(iter(arrays.values())).shape[0]
+    cols = dump_columns(ncol, nlat, len(arrays))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(np.asarray(a)[cols], dtype=np.float64))
+
+
 def spawn_ranks(ngpus: int, argv: list) -> int:
     """`python bench.py --gpus N` (N > 1, no launcher): start N ranks as a CHILD process group and relay
     rank 0's line.  This process must not have touched the GPU (devices are counted from the driver's
@@ -188,7 +222,8 @@ def main():
                     help="GPUs of this node to run on (one rank each); default: the launcher's world size, else 1")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median is reported (default 1, with --full 5)")
     ap.add_argument("--spinup", type=int, default=2000)
     ap.add_argument("--preroll", type=float, default=PREROLL_S,
                     help="seconds of untimed steps right before the warm-up (0 under a counter-collecting profiler)")
@@ -200,11 +235,19 @@ def main():
                          "launch per step)")
     ap.add_argument("--steps-per-launch", type=int, default=1,
                     help="K > 1: fused-K stepping (ebm_run_fused), reported as its own metric")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work with --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: five timed blocks by default, the CPU baseline, host-transfer rates and "
+                         "the ice-covered fraction of the timed state")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, a fixed sample of "
+                         "columns where the whole would exceed 60 MiB)")
     ap.add_argument("--launch-chains", type=int, default=1, choices=(1, 2),
                     help="2: ebm_options.launch_chains = 2 — the two halves of the columns stepped by two independent chains of "
                          "launches on two streams (bit-identical; reported as its own metric, never the headline)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and (args.gpus or 1) > 1:
@@ -264,21 +307,26 @@ def main():
     # (the reference's own shapes are one meridian: latency-bound, two latitudes per thread — an explicit choice of the
     #  caller, never derived by the library from the column count: energybalancemodel.jl_amd/infrastructure.py)
     cells_opt = 2 if (ncol == 1 and nlat <= 1536 and model == "MIZ" and os.environ.get("EBM_CELLS_PER_THREAD") is None) else None
-    eng = pkg.Engine(model, st.grid_kind, st.x, pkg.engine.param_vector(par, pkg.default_parval),
-                     st.dt, ncol, device=device, cells_per_thread=cells_opt,
-                     launch_chains=(chains if chains > 1 else None), use_graph=(False if chains > 1 else None),
-                     integrate_steps_per_launch=args.integrate_steps_per_launch,
-                     fused_state_in_lds={"auto": None, "registers": False, "lds": True}[args.fused_state])
-    if model == "Classic":
-        Ts = 30.0 - 45.0 * st.x ** 2
-        E0 = np.where(Ts >= 0, par["cw"] * Ts, par["Lf"] * Ts / 7.5)
-        eng.set_field("E", np.tile(E0, (ncol, 1)))
-        eng.set_field("Tg", np.tile(Ts, (ncol, 1)))
-    eng.set_column_forcing(fcol)
-    eng.set_time_table(st.t)
+    def open_engine():
+        """A handle of this workload in its initial state, forcing and time table set."""
+        e = pkg.Engine(model, st.grid_kind, st.x, pkg.engine.param_vector(par, pkg.default_parval),
+                       st.dt, ncol, device=device, cells_per_thread=cells_opt,
+                       launch_chains=(chains if chains > 1 else None), use_graph=(False if chains > 1 else None),
+                       integrate_steps_per_launch=args.integrate_steps_per_launch,
+                       fused_state_in_lds={"auto": None, "registers": False, "lds": True}[args.fused_state])
+        if model == "Classic":
+            Ts = 30.0 - 45.0 * st.x ** 2
+            E0 = np.where(Ts >= 0, par["cw"] * Ts, par["Lf"] * Ts / 7.5)
+            e.set_field("E", np.tile(E0, (ncol, 1)))
+            e.set_field("Tg", np.tile(Ts, (ncol, 1)))
+        e.set_column_forcing(fcol)
+        e.set_time_table(st.t)
+        return e
+
+    eng = open_engine()
     clock = {"step": 0}
 
-    def advance(n):
+    def advance(n, eng=eng, clock=clock):
         """n steps on the stream (asynchronous), the way this workload takes them."""
         if integrate:
             # a `year` of n steps of the same dt: annual-mean sums of all ten variables on every step,
@@ -310,19 +358,20 @@ def main():
     eng.run(0, args.spinup, None, False)
     clock["step"] = args.spinup
     eng.sync()
-    # pre-roll: a fixed amount of untimed work right before the timed region
+    # pre-roll: a fixed amount of untimed work right before the timed region.  Its step count follows from a measured
+    # time, so it runs on a scratch handle of the same workload: the timed state, and the point of the seasonal cycle it is
+    # timed at (the T0 iteration count, hence the time per step, depends on it), are the same in every run
     t0 = time.perf_counter()
     probe = max(1, min(args.steps, 64))
     advance(probe)
     eng.sync()
     per_step = (time.perf_counter() - t0) / probe
     preroll = 0 if integrate else int(min(200000, max(0, args.preroll / max(per_step, 1e-7))))
-    if preroll > nt:
-        # short years (the 180-band workloads: 2000 steps): whole years only, so that every run is timed at the same point of
-        # the seasonal cycle — the T0 iteration count, hence the time per step, depends on it (+-3 % otherwise)
-        preroll = (preroll // nt) * nt
     if preroll:
-        advance(preroll)
+        scratch = open_engine()
+        advance(preroll, scratch, {"step": 0})
+        scratch.sync()
+        scratch.close()
     advance(args.warmup) if args.warmup else None
     eng.sync()
     eng.reset_counters()
@@ -343,6 +392,15 @@ def main():
             elapsed = float(t.item())
         blocks_wall.append(elapsed)
         blocks_ev.append(ev_ms)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step, before anything below moves the state on
+        if integrate:
+            outputs = {f"avg_{v}": clock["out"]["avg"][i, 0] for i, v in enumerate(MIZ_VARS)}
+        else:
+            names = eng.prognostic + (eng.diagnostic if every_step_diag else ())
+            outputs = {k: eng.get_field(k) for k in names}
+        write_outputs(args.dump_outputs, outputs, nlat)
+        del outputs
     # every rank's own view of the timed blocks (rank 0 prints them: the MAX above hides who was slow)
     mine = {"rank": rank, "device": device, "blocks_ms_per_step": [b * 1e3 / args.steps for b in own_wall],
             "blocks_event_ms_per_step": [b / args.steps for b in blocks_ev]}
@@ -373,11 +431,11 @@ def main():
         per_step_ms = max((statistics.median(two) - elapsed * 1e3) / args.steps, 1e-9)
         year_end_ms = max(0.0, elapsed * 1e3 - per_step_ms * args.steps)
 
-    # ---- after the timed region: diagnostics of the state that was timed, CPU baseline --------------
+    # ---- after the timed region, --full only: diagnostics of the state that was timed, CPU baseline --------------
     cpu = None
     ice_fraction = None
     host_transfer = None
-    if model.startswith("MIZ"):
+    if args.full and model.startswith("MIZ"):
         # the fp64 T0 (the CPU baseline's warm start) exists only after a step that writes the diagnostics: the library
         # refuses to hand out a stale one (EBM_ERR_STALE) — one more step, with diagnostics, after the timed region
         eng.run(clock["step"], 1, None, True)

@@ -7,6 +7,7 @@ on the card, so the session keeps to the pytest process plus at most two ranks o
   3. bench.py four ways with short settings                             -> test_bench_lines_are_self_consistent
   4. examples/hysteresis_ensemble.py, small                             -> test_hysteresis_example_runs
   5. bench.py --gpus 2 (RCCL: refused on one GPU; gloo: rehearsal), one rank over RCCL -> test_bench_gpus_n_starts_n_ranks
+  6. bench.py plain, twice, with --dump-outputs                          -> test_bench_plain_run_and_its_outputs
 
 and writes `<stage>.done` (a JSON with the return code) as each of the first two finishes, and the bench lines at the end.
 This process never initialises the GPU itself; every job is its own child.  SIGTERM ends the job that is running.
@@ -66,7 +67,7 @@ with open(os.path.join(TMP, "two_rank.log"), "w") as log:
 done("two_rank", rc)
 
 RUNS = [
-    ["--steps", "20", "--repeats", "3", "--spinup", "200", "--preroll", "0.02", "--cpu-budget", "1"],
+    ["--full", "--steps", "20", "--repeats", "3", "--spinup", "200", "--preroll", "0.02", "--cpu-budget", "1"],
     ["--workload", "miz_180x1", "--steps", "64", "--steps-per-launch", "16", "--repeats", "2", "--spinup", "100", "--cpu-budget", "0"],
     ["--workload", "miz_1024x512x32_integrate", "--steps", "4", "--repeats", "2", "--spinup", "20", "--cpu-budget", "0"],
     ["--workload", "classic_1024x512", "--steps", "50", "--repeats", "2", "--cpu-budget", "0"],
@@ -98,5 +99,13 @@ rc, so, se = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "
 lines = [l for l in so.splitlines() if l.strip().startswith("{")]
 out.append({"args": one, "backend": "nccl-one-rank", "rc": rc, "nlines": len(lines),
             "line": json.loads(lines[-1]) if lines and rc == 0 else None, "stderr_tail": se[-1500:]})
+# 6. a plain run of the headline (no --full) twice, each writing its outputs: with the default pre-roll and with none
+plain = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--spinup", "200"]
+for extra in ([], ["--preroll", "0"]):
+    dump = os.path.join(TMP, "outputs_preroll" if not extra else "outputs_no_preroll")
+    rc, so, se = run([sys.executable, os.path.join(ROOT, "bench.py")] + plain + extra + ["--dump-outputs", dump])
+    lines = [l for l in so.splitlines() if l.strip()]
+    out.append({"args": plain + extra, "rc": rc, "nlines": len(lines), "line": json.loads(lines[-1]) if lines and rc == 0 else None,
+                "dump": dump, "stderr_tail": se[-600:]})
 with open(os.path.join(TMP, "bench_lines.json"), "w") as fh:
     json.dump(out, fh)

@@ -353,7 +353,7 @@ def test_no_device_memory_is_left_behind(pkg):
 
 def test_bench_lines_are_self_consistent(pkg):
     """bench.py itself, run four ways with short settings by a child that conftest started before this process touched the
-    GPU (headline + CPU baseline, fused-K, integrate, classic): exactly one JSON line each, the contract's keys, and the
+    GPU (headline with --full and its CPU baseline, fused-K, integrate, classic): exactly one JSON line each, the contract's keys, and the
     numbers consistent with each other — value = cells x steps / time, the median block, roofline.achieved = algorithmic
     bytes / HIP-event launch time, frac = achieved / 8 TB/s, the metric string of BASELINE.json on the headline only."""
     import json
@@ -437,6 +437,63 @@ def test_bench_gpus_n_starts_n_ranks(pkg):
     one = runs[7]
     assert one["backend"] == "nccl-one-rank" and one["rc"] == 0 and one["nlines"] == 1, one["stderr_tail"]
     assert one["line"]["backend"] == "nccl" and one["line"]["world_size_seen"] == 1 and one["line"]["n_gpus"] == 1
+
+
+def test_bench_plain_run_and_its_outputs(pkg):
+    """`bench.py --gpus 1 --steps 20 --warmup 5` without --full (started by conftest's child, twice: with the default
+    pre-roll and with none): one timed block of exactly --steps steps, the headline's keys, no CPU baseline or host
+    transfer; --dump-outputs writes the five prognostic fields of the timed state, float64, a seeded sample of columns
+    within 64 MB — the same in both runs, and bit-identical to the same steps taken here through the Engine."""
+    import importlib.util
+    import json
+    proc = conftest.BENCH_LINES["proc"]
+    if proc is None:
+        pytest.skip("bench child not started (no -m gpu session start)")
+    assert proc.wait(timeout=900) == 0
+    runs = json.load(open(conftest.BENCH_LINES["out"]))[8:10]
+    assert len(runs) == 2
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    nlat, ncol, nt, spinup, warmup, steps = 4096, 2048, 1048576, 200, 5, 20
+    cols = bench.dump_columns(ncol, nlat, len(PROG))
+    assert 0 < len(cols) < ncol and len(cols) * nlat * 8 * len(PROG) <= 64e6
+    dumps = []
+    for r in runs:
+        assert r["rc"] == 0 and r["nlines"] == 1, r["stderr_tail"]
+        d = r["line"]
+        assert d["metric"] == "grid-cell-steps/sec (2D 4096x2048 MIZ model)" and d["unit"] == "grid-cell-steps/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["n_gpus"] == 1
+        assert d["steps"] == steps and d["warmup"] == warmup and d["repeats"] == 1 and len(d["blocks_ms_per_step"]) == 1
+        assert d["ms_per_step"] == d["blocks_ms_per_step"][0] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (nlat * ncol) - 1.0) < 1e-9
+        assert d["cpu_baseline"] is None and d["host_transfer"] is None and d["config"]["ice_covered_fraction"] is None
+        assert sorted(os.listdir(r["dump"])) == sorted(k + ".npy" for k in PROG)
+        arrs = {k: np.load(os.path.join(r["dump"], k + ".npy")) for k in PROG}
+        assert all(a.dtype == np.float64 and a.shape == (len(cols), nlat) for a in arrs.values())
+        assert sum(os.path.getsize(os.path.join(r["dump"], k + ".npy")) for k in PROG) <= 64e6
+        dumps.append(arrs)
+    assert runs[0]["line"]["preroll_steps"] > 0 and runs[1]["line"]["preroll_steps"] == 0
+    for k in PROG:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+    # the same steps through the Engine: spin-up, bench's probe of min(steps, 64) steps, warm-up, the timed block
+    st = pkg.SpaceTime("sin", nlat, nt, 1)
+    par = pkg.default_parameters("MIZ")
+    eng = pkg.Engine("MIZ", st.grid_kind, st.x, pkg.engine.param_vector(par, pkg.default_parval), st.dt, ncol, device=0)
+    try:
+        eng.set_column_forcing(0.5 * np.sin(2.0 * np.pi * np.arange(ncol) / ncol))
+        eng.set_time_table(st.t)
+        first = 0
+        for n in (spinup, min(steps, 64), warmup, steps):
+            eng.run(first, n, None, False)
+            first += n
+        eng.sync()
+        for k in PROG:
+            want = eng.get_field(k)[cols]
+            assert np.array_equal(dumps[0][k], want, equal_nan=True), k
+    finally:
+        eng.close()
+    assert any((a != 0).any() for a in dumps[0].values())                                     # not the zero initial state
 
 
 def test_hysteresis_example_runs(pkg):

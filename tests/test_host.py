@@ -436,6 +436,32 @@ def test_bench_names_the_kernel_the_library_picks():
     assert name("MIZ", 64, {"threads": 768, "cells_per_thread": 2}, 9999, 256, True) == "miz_fused_kernel"
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: every column while the arrays fit the budget, else the same seeded sample of whole columns in every
+    call (two builds must see the same cells); files are float64 and within 64 MB together, also for the headline's
+    five 2048 x 4096 fields and the integrate workload's ten 16384 x 1024 means."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert np.array_equal(bench.dump_columns(8, 180, 10), np.arange(8))
+    for ncol, nlat, narr in ((2048, 4096, 5), (2048, 4096, 10), (16384, 1024, 10)):
+        a, b = bench.dump_columns(ncol, nlat, narr), bench.dump_columns(ncol, nlat, narr)
+        assert np.array_equal(a, b) and len(np.unique(a)) == len(a) and (np.diff(a) > 0).all()
+        assert 0 <= a[0] and a[-1] < ncol and 0.9 * bench.DUMP_BUDGET_BYTES < len(a) * nlat * 8 * narr <= 64e6
+    rng = np.random.default_rng(1)
+    arrays = {"x": rng.random((64, 32)), "y": rng.random((64, 32)).astype(np.float32)}
+    bench.write_outputs(str(tmp_path / "out"), arrays, 32)
+    cols = bench.dump_columns(64, 32, 2)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a[cols].astype(np.float64))
+    cols = bench.dump_columns(64, 32, 2, budget=2 * 32 * 8 * 10)
+    assert len(cols) == 10 and np.array_equal(cols, bench.dump_columns(64, 32, 2, budget=2 * 32 * 8 * 10))
+    with pytest.raises(ValueError):
+        bench.dump_columns(4, 4096, 10, budget=1000)
+
+
 def test_visible_gpu_count_reads_the_driver_topology(pkg, tmp_path, monkeypatch):
     """Launch decisions count GPUs without initialising HIP: KFD topology nodes with SIMDs, narrowed by the
     *_VISIBLE_DEVICES variables the runtime honours."""

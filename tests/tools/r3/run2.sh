@@ -3,7 +3,7 @@ O=gpurun_out/r3b; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; rc=$?
 echo "pytest rc=$rc"; tail -15 $O/pytest.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
-python bench.py --steps 50 --warmup 10 > $O/bench_head.json 2> $O/bench_head.err && \
+python bench.py --full --steps 50 --warmup 10 > $O/bench_head.json 2> $O/bench_head.err && \
 python bench.py --workload miz_4096x2048_step --steps 50 --cpu-budget 0 > $O/bench_step.json 2> $O/bench_step.err && \
 python bench.py --workload miz_1024x512x32_integrate --steps 20 --cpu-budget 0 > $O/bench_integ.json 2> $O/bench_integ.err && \
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_step -- python3 bench.py --workload miz_4096x2048_step --steps 100 --cpu-budget 0 > $O/prof_step.json 2> $O/prof_step.err

@@ -5,8 +5,8 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_confi
 echo "pytest rc=$rc"; tail -5 $O/pytest.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
 grep -h "sensitivity\|dT0/dphi" gpurun_out/measured_errors.jsonl | cut -c1-420
-python bench.py --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err && \
-python bench.py --workload miz_1024x512x32_integrate --steps 20 --cpu-budget 0 > $O/bench_integ.json 2> $O/bench_integ.err
+python bench.py --full --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err && \
+python bench.py --full --workload miz_1024x512x32_integrate --steps 20 --cpu-budget 0 > $O/bench_integ.json 2> $O/bench_integ.err
 for f in $O/bench_*.json; do python - "$f" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

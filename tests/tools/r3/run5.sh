@@ -5,7 +5,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pyte
 echo "pytest rc=$rc"; tail -12 $O/pytest.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
 grep -h "zonal\|explained" gpurun_out/measured_errors.jsonl | cut -c1-380
-python bench.py --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err
+python bench.py --full --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r3e/bench_head.json"))

@@ -4,7 +4,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_zonal8 -- python
 find $O/prof_zonal8 -name "*kernel_stats.csv" | head -1 | xargs -r grep zonal_sweep
 EBM_LIB=$GRAFT_REPO_ROOT/build/libebm_zunr16.so rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_zonal16 -- python3 tests/tools/zonal_profile.py 32 6 > $O/z16.log 2>&1
 find $O/prof_zonal16 -name "*kernel_stats.csv" | head -1 | xargs -r grep zonal_sweep
-python bench.py --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err
+python bench.py --full --steps 50 --warmup 10 --cpu-budget 0 > $O/bench_head.json 2> $O/bench_head.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r3h/bench_head.json"))

@@ -18,5 +18,5 @@ for W in "miz_180x1 --steps 2000" "miz_180x1 --steps 2048 --steps-per-launch 64"
          "classic_1024x512 --steps 2000" "classic_1024x512 --steps 2048 --steps-per-launch 64" "miz_imex_4096x2048"; do
   python bench.py --workload $W --cpu-budget 0 >> $O/other_workloads.jsonl 2>> $O/other_workloads.err
 done
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 300 $O/bench_default.json

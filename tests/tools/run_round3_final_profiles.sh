@@ -10,7 +10,7 @@ echo "pytest rc=$rc"; tail -3 $O/pytest.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
 cp gpurun_out/measured_errors.jsonl $O/measured_errors.jsonl
 set -e
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -- python3 bench.py --cpu-budget 0 > $O/prof_headline.json 2> $O/prof_headline.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_step -- python3 bench.py --workload miz_4096x2048_step --cpu-budget 0 > $O/prof_step.json 2> $O/prof_step.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_integrate -- python3 bench.py --workload miz_1024x512x32_integrate --steps 200 --repeats 2 --cpu-budget 0 --integrate-steps-per-launch 1 > $O/prof_integrate.json 2> $O/prof_integrate.err
