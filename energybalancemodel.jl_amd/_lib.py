@@ -26,6 +26,7 @@ EXPORTS = (
     "ebm_create", "ebm_create_ex", "ebm_options_default", "ebm_field_step", "ebm_get_field_as_of", "ebm_destroy", "ebm_last_error", "ebm_version", "ebm_set_field",
     "ebm_get_field", "ebm_hemispheric_mean", "ebm_hemispheric_mean_device", "ebm_get_field_device",
     "ebm_field_device_ptr", "ebm_diffusion", "ebm_zonal_diffusion", "ebm_set_column_forcing", "ebm_set_column_schedule",
+    "ebm_set_column_params",
     "ebm_set_step_clock", "ebm_set_time_table",
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_integrate", "ebm_integrate_hemispheric", "ebm_sync", "ebm_get_counters",
     "ebm_reset_counters", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
@@ -95,6 +96,7 @@ def load():
                                          C.POINTER(C.c_longlong)]
     lib.ebm_set_column_forcing.argtypes = [C.c_void_p, _dp]
     lib.ebm_set_column_schedule.argtypes = [C.c_void_p, _dp]
+    lib.ebm_set_column_params.argtypes = [C.c_void_p, _dp]
     lib.ebm_set_step_clock.argtypes = [C.c_void_p, C.c_longlong]
     lib.ebm_set_time_table.argtypes = [C.c_void_p, C.c_int, _dp]
     lib.ebm_step.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]

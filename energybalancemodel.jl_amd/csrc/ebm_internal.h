@@ -53,7 +53,8 @@ enum OutMode {
                          // per thread; ebm_integrate's stretches without snapshots)
 };
 
-// Per-latitude constant tables: one slab, table i at geom + i*gstride (gstride = pitch).
+// Per-latitude constant tables: one slab, table i at geom + i*gstride (gstride = pitch); one slab per parameter set,
+// set_stride apart (G_X is the same in every set).
 //   G_X              st.x
 //   G_0..G_4         physics stencil, bit-exact restatement of the reference:
 //                      identity grid: sub, diag, sup of par.D*get_diffop  (infrastructure.jl:480-497)
@@ -75,7 +76,9 @@ struct StepArgs {
     long long gstride;
     const double *fcol;              // per-column forcing offset or nullptr
     const double *fsched;            // per-column Forcing schedules [ncol][kSchedWords] or nullptr
-    const Params *p;                 // device memory
+    const Params *p;                 // device memory: the parameter sets, set i at p[i]
+    const int *pset;                 // column -> parameter set [ncol] (ebm_set_column_params), or nullptr: every column set 0
+    long long set_stride;            // geometry slab of set i at geom + i*set_stride (G_COUNT*gstride)
     unsigned long long *counters;    // 64 shards x {solves, cap hits} (MIZ)
     unsigned short *amask;           // MIZ warm start as an active set: [ncol][threads], bit i <=> T0 < Tm in cell i of the thread
     int pitch, nlat, ncol;
@@ -146,8 +149,10 @@ hipError_t launch_divide(const double *a, const double *b, double *q, int n, hip
 hipError_t launch_hemispheric_mean(const double *field, const double *x, int pitch, int nlat, int ncol, double *out,
                                    hipStream_t s);
 // out = base + D d/dx[(1-x^2) d temp/dx] per column ([ncol][pitch] device arrays; base may be null)
+// (parameter set of column c: pset[c], or 0 if pset is null — see StepArgs)
 hipError_t launch_diffusion(const double *temp, const double *base, double *out, const double *geom, long long gstride,
-                            const Params *p, int grid_kind, int pitch, int nlat, int ncol, hipStream_t s);
+                            const Params *p, const int *pset, long long set_stride, int grid_kind, int pitch, int nlat,
+                            int ncol, hipStream_t s);
 // annual_mean (src/infrastructure.jl:536-544): dst[v][col][k] = sum[v]/nt with `sum` in the pair-split
 // layout of the step kernels, then sum = 0; all nvars variables (var_stride apart) in one launch
 hipError_t launch_finish_mean(double *dst, double *sum, double nt, int ncol, int nvars, long long var_stride,

@@ -120,6 +120,14 @@ typedef double ebm_dvec2 __attribute__((ext_vector_type(2)));
 // pointer hipcc falls back to per-lane vector loads once the kernel has stored anything).
 typedef const __attribute__((address_space(4))) Params ConstParams;
 
+// The parameter set of a column (ebm_set_column_params): one scalar load per workgroup, from the constant address space
+// like the parameter block itself, and none without a table (every column set 0).  The column is the GLOBAL one
+// (col0 + blockIdx.x: launch chains).
+__device__ __forceinline__ int param_set(const StepArgs &a, int col) {
+    typedef const __attribute__((address_space(4))) int ConstInt;
+    return a.pset ? reinterpret_cast<ConstInt *>(reinterpret_cast<uintptr_t>(a.pset))[col] : 0;
+}
+
 // ---- Julia IEEE semantics ----------------------------------------------------------------
 __device__ __forceinline__ double jl_min(double x, double y) {
     // Base.min(::Float64, ::Float64): NaN-propagating, -0.0 < +0.0
@@ -718,8 +726,10 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
     double *sEw = smem + 6 * T + t, *sh = sEw + C * T, *sTw = sh + C * T;
-    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p));
-    const double *const gX = a.geom + G_X * a.gstride;
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
+    const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;         // wave-uniform
     const double Tm = p.Tm;
     EBM_STAMP(0);
@@ -748,8 +758,8 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         // would live as per-lane 64-bit pointers instead of the wave-uniform base + 32-bit offset form)
         unsigned kl = k0;
         asm volatile("" : "+v"(kl));
-        load_chunk<C>(a.geom + G_LO * a.gstride, kl, tlo);
-        load_chunk<C>(a.geom + G_UP * a.gstride, kl, tup);
+        load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
+        load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
         if (it == 0) {
             double Ew[C], hk[C], xk[C], r[C];
             load_chunk<C>(st + S_Ew * a.fstride, kl, Ew);
@@ -813,9 +823,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     if constexpr (GRID == 0 && !IMEX) {
         // sub-, main and super-diagonal of par.D*get_diffop: on the identity grid the physics stencil
         // and the solver's plain coefficients are the same three tables (build_tables)
-        load_chunk<C>(a.geom + G_LO * a.gstride, k0, g0);
-        load_chunk<C>(a.geom + G_DI * a.gstride, k0, g1);
-        load_chunk<C>(a.geom + G_UP * a.gstride, k0, g2);
+        load_chunk<C>(geom + G_LO * a.gstride, k0, g0);
+        load_chunk<C>(geom + G_DI * a.gstride, k0, g1);
+        load_chunk<C>(geom + G_UP * a.gstride, k0, g2);
     }
     double tb[C];
     {
@@ -849,9 +859,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             if constexpr (GRID == 0) {                    // the three diagonals are fetched per use, not kept across the solve
                 unsigned kg = k0;
                 asm volatile("" : "+v"(kg));
-                load_chunk<C>(a.geom + G_LO * a.gstride, kg, g0);
-                load_chunk<C>(a.geom + G_DI * a.gstride, kg, g1);
-                load_chunk<C>(a.geom + G_UP * a.gstride, kg, g2);
+                load_chunk<C>(geom + G_LO * a.gstride, kg, g0);
+                load_chunk<C>(geom + G_DI * a.gstride, kg, g1);
+                load_chunk<C>(geom + G_UP * a.gstride, kg, g2);
             }
             if (GRID == 1) Fl_ = interface_flux((int)k0, nlat, xl, xk[0], hl, tb[0], xxl_);
 #pragma unroll
@@ -885,8 +895,8 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         {
             // rows of I - (dt/cw)*Dif (padding rows: lo = up = 0, decoupled) and the right-hand side
             double ra[C], rb[C], rc[C], dE[C], dif[C], tlo[C], tup[C];
-            load_chunk<C>(a.geom + G_LO * a.gstride, k0, tlo);
-            load_chunk<C>(a.geom + G_UP * a.gstride, k0, tup);
+            load_chunk<C>(geom + G_LO * a.gstride, k0, tlo);
+            load_chunk<C>(geom + G_UP * a.gstride, k0, tup);
             increments(dif, dE, tbl, tbr);
 #pragma unroll
             for (int i = 0; i < C; ++i) {
@@ -1071,8 +1081,10 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     const int nlat = a.nlat;
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
-    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p));
-    const double *const gX = a.geom + G_X * a.gstride;
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
+    const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;
     const double Tm = p.Tm;
     unsigned short *const wmask = a.amask + (size_t)col * T + t;
@@ -1085,9 +1097,9 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     load_chunk<C>(st + S_D * a.fstride, k0, Dk);
     load_chunk<C>(st + S_phi * a.fstride, k0, ph);
     load_chunk<C>(gX, k0, xk);
-    load_chunk<C>(a.geom + G_LO * a.gstride, k0, tlo);   // == G_0 / G_2 on the identity grid (build_tables)
-    load_chunk<C>(a.geom + G_UP * a.gstride, k0, tup);
-    if constexpr (GRID == 0) load_chunk<C>(a.geom + G_DI * a.gstride, k0, g1);
+    load_chunk<C>(geom + G_LO * a.gstride, k0, tlo);   // == G_0 / G_2 on the identity grid (build_tables)
+    load_chunk<C>(geom + G_UP * a.gstride, k0, tup);
+    if constexpr (GRID == 0) load_chunk<C>(geom + G_DI * a.gstride, k0, g1);
     const double xl = gX[k0 > 0 ? k0 - 1 : 0], xr = gX[k0 + C];
     int nit = 0, nfail = 0;
     const int nloop = a.nfused;
@@ -1252,8 +1264,10 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
 #define sEw(i) EBM_RES(1, i)
 #define sh(i) EBM_RES(2, i)
 #define sD(i) EBM_RES(3, i)
-    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p));
-    const double *const gX = a.geom + G_X * a.gstride;
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
+    const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;
     const double Tm = p.Tm;
     unsigned short *const cmask = a.amask + (size_t)col * T;           // wave-uniform
@@ -1308,8 +1322,8 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
             unsigned kl = ks;
             asm volatile("" : "+v"(kl));
             windows(ts);
-            load_chunk<C>(a.geom + G_LO * a.gstride, kl, tlo);
-            load_chunk<C>(a.geom + G_UP * a.gstride, kl, tup);
+            load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
+            load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
             if (it == 0) {
                 double xk[C], r[C];
                 load_chunk<C>(gX, kl, xk);
@@ -1370,9 +1384,9 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
                 if constexpr (GRID == 0) {
                     unsigned kg = kl;
                     asm volatile("" : "+v"(kg));
-                    load_chunk<C>(a.geom + G_LO * a.gstride, kg, g0);
-                    load_chunk<C>(a.geom + G_DI * a.gstride, kg, g1);
-                    load_chunk<C>(a.geom + G_UP * a.gstride, kg, g2);
+                    load_chunk<C>(geom + G_LO * a.gstride, kg, g0);
+                    load_chunk<C>(geom + G_DI * a.gstride, kg, g1);
+                    load_chunk<C>(geom + G_UP * a.gstride, kg, g2);
                 }
                 if (GRID == 1) Fl_ = interface_flux((int)kl, nlat, xl, xk[0], tbl, tb[0], xxl_);
 #pragma unroll
@@ -1403,8 +1417,8 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
             double sol[C];
             {
                 double ra[C], rb[C], rc[C], dE[C], dif[C], qlo[C], qup[C];
-                load_chunk<C>(a.geom + G_LO * a.gstride, kl, qlo);
-                load_chunk<C>(a.geom + G_UP * a.gstride, kl, qup);
+                load_chunk<C>(geom + G_LO * a.gstride, kl, qlo);
+                load_chunk<C>(geom + G_UP * a.gstride, kl, qup);
                 increments(dif, dE);
 #pragma unroll
                 for (int i = 0; i < C; ++i) {
@@ -1457,9 +1471,9 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
                 // the three diagonals of the cell's pair arrive with its first cell (16-byte loads, L2 hits), not all
                 // twelve words before the loop
                 if ((i & 1) == 0) {
-                    const double2 q0 = *reinterpret_cast<const double2 *>(a.geom + G_LO * a.gstride + (kl + i));
-                    const double2 q1 = *reinterpret_cast<const double2 *>(a.geom + G_DI * a.gstride + (kl + i));
-                    const double2 q2 = *reinterpret_cast<const double2 *>(a.geom + G_UP * a.gstride + (kl + i));
+                    const double2 q0 = *reinterpret_cast<const double2 *>(geom + G_LO * a.gstride + (kl + i));
+                    const double2 q1 = *reinterpret_cast<const double2 *>(geom + G_DI * a.gstride + (kl + i));
+                    const double2 q2 = *reinterpret_cast<const double2 *>(geom + G_UP * a.gstride + (kl + i));
                     g0[GRID == 0 ? i : 0] = q0.x;  g0[GRID == 0 ? i + 1 : 0] = q0.y;
                     g1[GRID == 0 ? i : 0] = q1.x;  g1[GRID == 0 ? i + 1 : 0] = q1.y;
                     g2[GRID == 0 ? i : 0] = q2.x;  g2[GRID == 0 ? i + 1 : 0] = q2.y;
@@ -1552,7 +1566,9 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
     const int nlat = a.nlat;
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
-    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p));
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;          // wave-uniform
     double E[C], Tg[C];
     load_chunk<C>(st + C_E * a.fstride, k0, E);
@@ -1561,7 +1577,7 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
     for (int step = 0; step < nloop; ++step) {
         // per-latitude statics (get_statics, src/classic.jl:18-29): re-read every step (L2 hits) rather
         // than kept in 48 registers across the fused loop
-        const double *ge = a.geom;
+        const double *ge = geom;
         if constexpr (LOOP) asm volatile("" : "+s"(ge));
         double xk[C], aw[C], Sb[C], kd[C], ca[C], cc[C];
         load_chunk<C>(ge + G_X * a.gstride, k0, xk);
@@ -1628,7 +1644,7 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
 // Active set of a T0 field (after ebm_set_field(T0)): bit i of amask[col][t] <=> T0 < Tm in cell t*C+i.
 __global__ void mask_from_t0_kernel(const StepArgs a, int C) {
     const int T = blockDim.x, t = threadIdx.x, col = blockIdx.x;
-    const double Tm = a.p->Tm;
+    const double Tm = a.p[param_set(a, col)].Tm;
     const double *T0 = a.state + S_T0 * a.fstride + (size_t)col * (size_t)a.pitch + (size_t)t * C;
     unsigned m = 0;
     for (int i = 0; i < C; ++i)
@@ -1680,11 +1696,15 @@ __global__ void hemispheric_mean_kernel(const double *__restrict__ field, const 
 // same device functions (and hence the same bits) the step kernels use inside their fused physics.
 template <int GRID>
 __global__ void diffusion_kernel(const double *__restrict__ temp, const double *__restrict__ base,
-                                 double *__restrict__ out, const double *__restrict__ geom, long long gstride,
-                                 const Params *__restrict__ pp, int pitch, int nlat) {
+                                 double *__restrict__ out, const double *__restrict__ geom_sets, long long gstride,
+                                 const Params *__restrict__ p_sets, const int *__restrict__ pset, long long set_stride,
+                                 int pitch, int nlat) {
     const int col = blockIdx.y;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nlat) return;
+    const int set = pset ? pset[col] : 0;
+    const double *const geom = geom_sets + set * set_stride;
+    const Params *const pp = p_sets + set;
     const double *T = temp + (size_t)col * pitch;
     const double tk = T[k], tm = k > 0 ? T[k - 1] : 0.0, tp = k < nlat - 1 ? T[k + 1] : 0.0;
     double term;
@@ -1702,10 +1722,12 @@ __global__ void diffusion_kernel(const double *__restrict__ temp, const double *
     out[(size_t)col * pitch + k] = (base ? base[(size_t)col * pitch + k] : 0.0) + term;
 }
 hipError_t launch_diffusion(const double *temp, const double *base, double *out, const double *geom, long long gstride,
-                            const Params *p, int grid_kind, int pitch, int nlat, int ncol, hipStream_t s) {
+                            const Params *p, const int *pset, long long set_stride, int grid_kind, int pitch, int nlat,
+                            int ncol, hipStream_t s) {
     dim3 grid((nlat + 255) / 256, ncol), block(256);
-    if (grid_kind == 0) diffusion_kernel<0><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pitch, nlat);
-    else diffusion_kernel<1><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pitch, nlat);
+    if (grid_kind == 0)
+        diffusion_kernel<0><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pset, set_stride, pitch, nlat);
+    else diffusion_kernel<1><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pset, set_stride, pitch, nlat);
     return hipGetLastError();
 }
 

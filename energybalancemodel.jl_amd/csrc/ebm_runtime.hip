@@ -11,6 +11,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -53,6 +54,13 @@ struct ebm_ctx {
     ebm::Params *p_dev = nullptr;                  // parameter block in device memory
     double *geom = nullptr;                        // per-latitude tables, G_COUNT x gstride
     long long gstride = 0;
+    // ebm_set_column_params: one parameter block and one geometry slab per distinct row (nsets of them, 0 = no table:
+    // every column steps with p_dev / geom), and the column -> set index (null when every column has set 0)
+    int nsets = 0;
+    ebm::Params *p_sets = nullptr;
+    double *geom_sets = nullptr;                   // nsets x G_COUNT x gstride
+    int *pset_dev = nullptr;
+    std::vector<ebm::Params> sets_host;            // host copies (the zonal operator's D and cw)
     double *state = nullptr;                       // field slab, nslots x fstride
     long long fstride = 0;
     int nslots = 0;
@@ -172,12 +180,12 @@ int check_current(const ebm_ctx *h, int f, const char *who) {
     return fail(EBM_ERR_STALE, msg);
 }
 
-// Per-latitude constants.  Same expressions, in the same order, as the reference:
-// get_diffop (src/infrastructure.jl:480-492), the non-uniform cache (:509-518) and
-// get_statics (src/classic.jl:18-29).
-int build_tables(ebm_ctx *h, const double *x) {
+// Per-latitude constants of parameter block p into the zero-filled host slab `slab` (G_COUNT x h->gstride).  Same
+// expressions, in the same order, as the reference: get_diffop (src/infrastructure.jl:480-492), the non-uniform cache
+// (:509-518) and get_statics (src/classic.jl:18-29).  ebm_create runs it for the handle's vector, ebm_set_column_params
+// for every distinct row.
+void build_tables(const ebm_ctx *h, const ebm::Params &p, const double *x, double *slab) {
     const int nx = h->nlat;
-    const ebm::Params &p = h->p;
     std::vector<double> xv(x, x + nx), g0(nx), g1(nx), g2(nx), g3(nx, 0.0), g4(nx, 0.0), lo(nx), di(nx), up(nx);
     const bool uniform = (h->grid == EBM_GRID_IDENTITY) || (h->model == EBM_MODEL_CLASSIC);
     // classic: get_statics always uses get_diffop, whatever the grid type (src/classic.jl:21)
@@ -223,10 +231,8 @@ int build_tables(ebm_ctx *h, const double *x) {
         }
     }
     // one zero-padded slab: table i at geom + i*gstride
-    h->gstride = h->pitch;
-    std::vector<double> slab((size_t)ebm::G_COUNT * h->gstride, 0.0);
     auto put = [&](int table, const std::vector<double> &v) {
-        std::memcpy(slab.data() + (size_t)table * h->gstride, v.data(), sizeof(double) * v.size());
+        std::memcpy(slab + (size_t)table * h->gstride, v.data(), sizeof(double) * v.size());
     };
     put(ebm::G_X, xv); put(ebm::G_0, g0); put(ebm::G_1, g1); put(ebm::G_2, g2); put(ebm::G_3, g3);
     put(ebm::G_4, g4); put(ebm::G_LO, lo); put(ebm::G_DI, di); put(ebm::G_UP, up);
@@ -244,9 +250,6 @@ int build_tables(ebm_ctx *h, const double *x) {
         put(ebm::G_KSUB, ksub); put(ebm::G_KDIAG, kdiag); put(ebm::G_KSUP, ksup);
         put(ebm::G_AW, aw); put(ebm::G_SB, Sb);
     }
-    HIPCHK(hipMalloc(&h->geom, sizeof(double) * slab.size()));
-    HIPCHK(hipMemcpy(h->geom, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice));
-    return EBM_OK;
 }
 
 void fill_params(ebm::Params &p, const double *v, double dt) {
@@ -309,12 +312,15 @@ void periodic_tables(double a, double B, int n, double *M, double *E, size_t P, 
 // (S = 1): the whole circle's chain with its wrap closure.  S > 1: the chain of ONE segment of m = nlon/S unknowns (open
 // ends), and the reduced periodic system of the S segment ends, (-a'', B'', -a'') with a'' = a ep_{m-2},
 // B'' = B - a cp_{m-2} - a alpha, alpha = sum_i P_i ep_i.  Built on first use and whenever nlon changes.
+// The parameters of the zonal operator: the handle's vector, or the one set ebm_set_column_params installed
+const ebm::Params &zonal_params(const ebm_ctx *h) { return h->nsets ? h->sets_host[0] : h->p; }
 int build_zonal_tables(ebm_ctx *h, int nlon) {
     if (h->ztab && h->nlon == nlon) return EBM_OK;
     const int S = zonal_segments(nlon), m = nlon / S, P = (int)h->pitch, T = h->cfg.threads;
     const int nmember = h->ncol / nlon;
     const double *x = h->xhost.data();
-    const double dl = 2.0 * M_PI / nlon, theta = h->dt / h->p.cw;
+    const double D = zonal_params(h).D;
+    const double dl = 2.0 * M_PI / nlon, theta = h->dt / zonal_params(h).cw;
     const size_t chain_rows = (size_t)(S == 1 ? nlon : m), red_rows = (size_t)(S == 1 ? 0 : S);
     const size_t scratch = S == 1 ? 0 : 3 * (size_t)nmember * S * P;
     std::vector<double> tab(2 * chain_rows * P + 2 * red_rows * P + 3 * (size_t)P, 0.0);
@@ -330,7 +336,7 @@ int build_zonal_tables(ebm_ctx *h, int nlon) {
         if (k < h->nlat) {
             const double mm = (1.0 - x[k]) * (1.0 + x[k]);       // 1 - x^2 without the cancellation near the pole
             if (!(mm > 0.0)) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs |x| < 1 at every cell centre (the zonal coefficient is D/(1-x^2))");
-            a = theta * h->p.D / (mm * (dl * dl));
+            a = theta * D / (mm * (dl * dl));
         }
         const double B = 1.0 + 2.0 * a;
         za[p] = a;
@@ -362,7 +368,7 @@ int build_zonal_tables(ebm_ctx *h, int nlon) {
 }
 hipError_t zonal_sweep(ebm_ctx *h, const double *T, double *outZ, double *outU) {
     const int nmember = h->ncol / h->nlon;
-    const double rtheta = h->p.cw / h->dt;
+    const double rtheta = zonal_params(h).cw / h->dt;
     if (h->zseg == 1)
         return ebm::launch_zonal_sweep(T, outZ, outU, h->zM, h->zE, h->za, h->zW, h->nlon, nmember, (int)h->pitch, rtheta,
                                        main_stream(h));
@@ -374,6 +380,10 @@ ebm::StepArgs base_args(const ebm_ctx *h) {
     ebm::StepArgs a{};
     a.state = h->state; a.fstride = h->fstride; a.geom = h->geom; a.gstride = h->gstride;
     a.fcol = h->fcol; a.fsched = h->fsched; a.p = h->p_dev; a.counters = h->counters; a.amask = h->amask;
+    if (h->nsets) {                  // per-column parameter sets (ebm_set_column_params)
+        a.p = h->p_sets; a.geom = h->geom_sets; a.pset = h->pset_dev;
+        a.set_stride = (long long)ebm::G_COUNT * h->gstride;
+    }
     a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol;
     a.stamps = h->stamps;
     a.prefetch = h->prefetch;
@@ -639,8 +649,14 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     h->pitch = (long long)cfg.threads * cfg.cells;     // >= nlat; padding cells stay zero
     fill_params(h->p, params, dt);
     h->xhost.assign(x, x + nlat);
-    int rc = build_tables(h, x);
-    if (rc) { ebm_destroy(h); return rc; }
+    h->gstride = h->pitch;
+    {
+        std::vector<double> slab((size_t)ebm::G_COUNT * h->gstride, 0.0);
+        build_tables(h, h->p, x, slab.data());
+        hipError_t e = hipMalloc(&h->geom, sizeof(double) * slab.size());
+        if (e == hipSuccess) e = hipMemcpy(h->geom, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { ebm_destroy(h); return fail(EBM_ERR_HIP, std::string("ebm_create: tables: ") + hipGetErrorString(e)); }
+    }
     h->fstride = (long long)ncol * h->pitch;
     h->nslots = (model == EBM_MODEL_MIZ) ? (int)ebm::S_MIZ_COUNT : (int)ebm::C_COUNT;
     const size_t nbytes = sizeof(double) * (size_t)h->nslots * (size_t)h->fstride;
@@ -685,6 +701,9 @@ int ebm_destroy(ebm_handle_t h) {
     for (double *b : {h->scratch, h->ig_sums, h->ig_mean, h->ig_snap, h->ig_stage, h->ig_hm, h->ztab})
         if (b) (void)hipFree(b);
     if (h->geom) (void)hipFree(h->geom);
+    if (h->geom_sets) (void)hipFree(h->geom_sets);
+    if (h->p_sets) (void)hipFree(h->p_sets);
+    if (h->pset_dev) (void)hipFree(h->pset_dev);
     if (h->state) (void)hipFree(h->state);
     if (h->p_dev) (void)hipFree(h->p_dev);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
@@ -844,9 +863,10 @@ int ebm_diffusion(ebm_handle_t h, const double *temp, const double *base, double
     };
     hipError_t e = up(buf, temp);
     if (e == hipSuccess && base) e = up(buf + npitch, base);
+    const ebm::StepArgs a = base_args(h);                // the column's parameter set (ebm_set_column_params)
     if (e == hipSuccess)
-        e = ebm::launch_diffusion(buf, base ? buf + npitch : nullptr, buf + 2 * npitch, h->geom, h->gstride, h->p_dev,
-                                  h->grid, (int)h->pitch, h->nlat, h->ncol, main_stream(h));
+        e = ebm::launch_diffusion(buf, base ? buf + npitch : nullptr, buf + 2 * npitch, a.geom, a.gstride, a.p, a.pset,
+                                  a.set_stride, h->grid, (int)h->pitch, h->nlat, h->ncol, main_stream(h));
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(out, sizeof(double) * h->nlat, buf + 2 * npitch, sizeof(double) * h->pitch,
                              sizeof(double) * h->nlat, h->ncol, hipMemcpyDeviceToHost, main_stream(h));
@@ -860,6 +880,9 @@ int ebm_zonal_diffusion(ebm_handle_t h, int nlon, const double *temp, double *ou
     if (h->model != EBM_MODEL_MIZ) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs a MIZ handle (cw and D are MIZ parameters of this operator)");
     if (nlon < 3) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs nlon >= 3 (longitudes per member)");
     if (h->ncol % nlon) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: the handle's column count must be a multiple of nlon");
+    if (h->nsets > 1)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_zonal_diffusion: needs one parameter set (its tables come from one D and one cw; "
+                                         "ebm_set_column_params installed " + std::to_string(h->nsets) + ")");
     HIPCHK(hipSetDevice(h->device));
     int rc = build_zonal_tables(h, nlon);
     if (rc) return rc;
@@ -933,6 +956,74 @@ int ebm_set_column_schedule(ebm_handle_t h, const double *sched) {
     }
     if (!h->fsched) { HIPCHK(hipMalloc(&h->fsched, nb)); invalidate_graph(h); }
     HIPCHK(hipMemcpy(h->fsched, sched, nb, hipMemcpyHostToDevice));
+    return EBM_OK;
+}
+
+int ebm_set_column_params(ebm_handle_t h, const double *params) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_params: null handle");
+    const int np = EBM_P_COUNT;
+    // the rows ebm_create would refuse as its vector (ebm_create_ex)
+    if (params && h->model == EBM_MODEL_MIZ)
+        for (int c = 0; c < h->ncol; ++c) {
+            const double *r = params + (size_t)np * c;
+            if (r[EBM_P_Tm] < 0.0 && r[EBM_P_m2] != std::floor(r[EBM_P_m2]))
+                return fail(EBM_ERR_ARG, "ebm_set_column_params: column " + std::to_string(c) +
+                                             ": Tm^m2 with Tm < 0 and non-integer m2 (DomainError in the reference, src/miz.jl:71)");
+        }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    // distinct rows by bit pattern, in order of first appearance
+    std::vector<int> col_set((size_t)h->ncol, 0);
+    std::vector<const double *> rows;
+    if (params) {
+        std::map<std::string, int> seen;
+        for (int c = 0; c < h->ncol; ++c) {
+            const double *r = params + (size_t)np * c;
+            auto it = seen.emplace(std::string(reinterpret_cast<const char *>(r), sizeof(double) * np), (int)rows.size());
+            if (it.second) rows.push_back(r);
+            col_set[c] = it.first->second;
+        }
+    }
+    const int nsets = (int)rows.size();
+    const long long set_stride = (long long)ebm::G_COUNT * h->gstride;
+    ebm::Params *p_sets = nullptr;
+    double *geom_sets = nullptr;
+    int *pset_dev = nullptr;
+    std::vector<ebm::Params> ps((size_t)nsets);
+    if (nsets) {
+        // every set built by the code ebm_create runs for its vector: fill_params, build_tables, derive_params_kernel
+        std::vector<double> slab((size_t)nsets * set_stride, 0.0);
+        for (int i = 0; i < nsets; ++i) {
+            fill_params(ps[i], rows[i], h->dt);
+            build_tables(h, ps[i], h->xhost.data(), slab.data() + (size_t)i * set_stride);
+        }
+        hipError_t e = hipMalloc(&p_sets, sizeof(ebm::Params) * (size_t)nsets);
+        if (e == hipSuccess) e = hipMalloc(&geom_sets, sizeof(double) * slab.size());
+        if (e == hipSuccess && nsets > 1) e = hipMalloc(&pset_dev, sizeof(int) * (size_t)h->ncol);
+        if (e == hipSuccess) e = hipMemcpy(p_sets, ps.data(), sizeof(ebm::Params) * (size_t)nsets, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(geom_sets, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && pset_dev)
+            e = hipMemcpy(pset_dev, col_set.data(), sizeof(int) * (size_t)h->ncol, hipMemcpyHostToDevice);
+        for (int i = 0; i < nsets && e == hipSuccess; ++i) e = ebm::launch_derive_params(p_sets + i, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = hipMemcpy(ps.data(), p_sets, sizeof(ebm::Params) * (size_t)nsets, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {                   // the handle keeps the rows it had
+            for (void *b : {(void *)p_sets, (void *)geom_sets, (void *)pset_dev})
+                if (b) (void)hipFree(b);
+            return fail(EBM_ERR_HIP, std::string("ebm_set_column_params: ") + hipGetErrorString(e));
+        }
+    }
+    for (void *b : {(void *)h->p_sets, (void *)h->geom_sets, (void *)h->pset_dev})
+        if (b) (void)hipFree(b);
+    h->nsets = nsets;
+    h->p_sets = p_sets;
+    h->geom_sets = geom_sets;
+    h->pset_dev = pset_dev;
+    h->sets_host = std::move(ps);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    if (h->ztab) (void)hipFree(h->ztab);         // the zonal tables are built again from the parameters now installed
+    h->ztab = nullptr;
+    h->nlon = 0;
     return EBM_OK;
 }
 

@@ -41,6 +41,27 @@ def param_vector(par, defaults) -> np.ndarray:
     return np.array([get(k, defaults[k]) for k in PARAM_ORDER], dtype=np.float64)
 
 
+def param_matrix(rows, base, defaults) -> np.ndarray:
+    """The [len(rows), 25] parameter rows of ebm_set_column_params: row m is ``base`` (a dict / Collection of parameter
+    values, missing names from ``defaults``, as ``param_vector``) with the overrides of ``rows[m]`` — a dict or
+    Collection of parameter name -> value, e.g. ``[{"D": d} for d in Ds]``; None or {} keeps ``base``.  Unknown
+    names raise ValueError."""
+    rows = list(rows)
+    out = np.empty((len(rows), len(PARAM_ORDER)), dtype=np.float64)
+    out[:] = param_vector(base, defaults)
+    index = {k: i for i, k in enumerate(PARAM_ORDER)}
+    for m, row in enumerate(rows):
+        if row is None:
+            continue
+        if not hasattr(row, "items"):
+            raise TypeError(f"member {m}: expected a dict of parameter overrides, got {type(row).__name__}")
+        for k, v in row.items():
+            if k not in index:
+                raise ValueError(f"member {m}: unknown parameter {k!r} (expected one of {', '.join(PARAM_ORDER)})")
+            out[m, index[k]] = float(v)
+    return out
+
+
 def _env_int(name):
     v = os.environ.get(name)
     return None if v in (None, "") else int(v)
@@ -208,6 +229,18 @@ class Engine:
             raise ValueError(f"expected {self.ncol} Forcing objects, got {len(forcings)}")
         a = np.array([schedule_words(f) for f in forcings], dtype=np.float64)
         check(self.lib.ebm_set_column_schedule(self._h, dptr(a)), "ebm_set_column_schedule")
+
+    def set_column_params(self, matrix):
+        """Per-column parameter rows (ebm_set_column_params): ``matrix`` [ncol, 25] in PARAM_ORDER (see
+        ``param_matrix``), or None to return every column to the vector the engine was created with.  Column c then
+        gives the bits of an engine created with row c; distinct rows share nothing but the launch."""
+        if matrix is None:
+            check(self.lib.ebm_set_column_params(self._h, None), "ebm_set_column_params")
+            return
+        a = as_f64(matrix)
+        if a.shape != (self.ncol, len(PARAM_ORDER)):
+            raise ValueError(f"expected parameter rows of shape {(self.ncol, len(PARAM_ORDER))}, got {a.shape}")
+        check(self.lib.ebm_set_column_params(self._h, dptr(a)), "ebm_set_column_params")
 
     def set_step_clock(self, step: int):
         check(self.lib.ebm_set_step_clock(self._h, int(step)), "ebm_set_step_clock")

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import Engine, param_vector
+from .engine import Engine, param_matrix, param_vector
 from .infrastructure import default_parval
 
 
@@ -32,24 +32,49 @@ def hemispheric_mean(vec: np.ndarray, x: np.ndarray) -> np.ndarray:
     return np.cumsum((v[..., :-1] + v[..., 1:]) * (x[1:] - x[:-1]) / 2.0, axis=-1)[..., -1]
 
 
+def member_param_rows(member_params, par, init, fcol=None, forcings=None) -> np.ndarray:
+    """The [members, 25] parameter rows of ``EnsembleRun(..., member_params=...)``, after checking that the per-member
+    inputs agree on the member count: 2-D ``init`` arrays, ``fcol`` and ``forcings``.  Host only (no device call)."""
+    n = len(member_params)
+    if n < 1:
+        raise ValueError("member_params: need at least one member")
+    for k, v in init.items():
+        a = np.asarray(v)
+        if a.ndim != 1 and a.shape[0] != n:
+            raise ValueError(f"member_params has {n} members but init[{k!r}] has {a.shape[0]} columns")
+    if fcol is not None and len(fcol) != n:
+        raise ValueError(f"member_params has {n} members but fcol has {len(fcol)}")
+    if forcings is not None and len(forcings) != n:
+        raise ValueError(f"member_params has {n} members but forcings has {len(forcings)}")
+    return param_matrix(member_params, par, default_parval)
+
+
 class EnsembleRun:
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
     ``init`` maps prognostic names to [ncol, nlat] arrays (or [nlat], broadcast to all
     columns); ``fcol`` is the per-column forcing offset; ``forcings`` a sequence of one Forcing
     per column, evaluated on the device at every step (hysteresis ensembles: every member its own
-    ramp).
+    ramp); ``member_params`` a sequence of one dict of parameter overrides over ``par`` per column
+    (parameter sweeps: ``[{"D": d} for d in Ds]``, ebm_set_column_params) — member m gives the bits of a
+    one-member run with ``par`` updated by ``member_params[m]``.  A sharded run passes ``member_params[mine]`` as it
+    passes ``forcings[mine]``.
 
     A column's results do not depend on how many columns share its handle or on how the ensemble is sharded
     over GPUs: the launch geometry is a function of the latitude count and ``cells_per_thread`` only."""
 
-    def __init__(self, model, st, par, init, fcol=None, device=0, forcings=None, cells_per_thread=None):
+    def __init__(self, model, st, par, init, fcol=None, device=0, forcings=None, cells_per_thread=None,
+                 member_params=None):
         first = np.asarray(next(iter(init.values())))
         self.ncol = 1 if first.ndim == 1 else first.shape[0]
         if fcol is not None:
             self.ncol = len(fcol)
         if forcings is not None:
             self.ncol = len(forcings)
+        rows = None
+        if member_params is not None:
+            rows = member_param_rows(member_params, par, init, fcol, forcings)
+            self.ncol = rows.shape[0]
         self.st = st
         self.device = int(device)
         # cells_per_thread: launch option of ebm_create_ex (None = the library's default of 4).  Every rank of a
@@ -66,6 +91,8 @@ class EnsembleRun:
         self.engine.set_time_table(st.t)
         if forcings is not None:
             self.engine.set_column_schedules(forcings)
+        if rows is not None:
+            self.engine.set_column_params(rows)
         self.step_index = 0
 
     def run(self, nsteps, forcing=None, diag_last=True, steps_per_launch=None):

@@ -233,6 +233,25 @@ int ebm_set_column_forcing(ebm_handle_t h, const double *fcol);
  * forcing = f + fcol[c] + schedule_c(T). */
 int ebm_set_column_schedule(ebm_handle_t h, const double *sched);
 int ebm_set_step_clock(ebm_handle_t h, long long step);
+/* Per-column PARAMETER rows: params[ncol][EBM_P_COUNT] in enum ebm_param order; NULL returns every column to the
+ * vector given to ebm_create.  Column c then steps exactly as a one-column handle created with row c and the same
+ * model, grid, x, dt and options would: the same BITS, in every entry point — ebm_step, ebm_run, ebm_run_fused,
+ * ebm_integrate, ebm_integrate_hemispheric, ebm_diffusion, the hemispheric means and the counters.  This is how a
+ * parameter-sensitivity sweep (D, the albedo contrast, kappa, ...) runs as the members of ONE ensemble, together with
+ * the per-column forcings above.  THIS TEXT IS THE DEFINITION.
+ * Synchronous, like the forcing setters: the handle's stream is synchronised first.  The state, the warm-start pattern
+ * and the validity of the fields (EBM_ERR_STALE) are left as they are; the new rows apply from the next step on.  A
+ * change of Tm reaches the warm-start pattern [T0 < Tm] at the next T0 solve, as in the reference, whose T0 survives a
+ * change of `par`.
+ * A row is refused with EBM_ERR_ARG wherever ebm_create would refuse it as its vector (Tm < 0 with a non-integer m2
+ * for the MIZ models); the message names the column, and the handle keeps the rows it had.  Entries a model does not
+ * use are ignored, as in ebm_create.
+ * Rows are deduplicated by bit pattern into parameter SETS: device memory is one parameter block and one set of
+ * per-latitude tables per DISTINCT row (320 + 112 * pitch bytes per set, pitch = threads * cells_per_thread >= nlat;
+ * at most ncol sets) plus 4 bytes per column for the column -> set index.
+ * ebm_zonal_diffusion returns EBM_ERR_UNSUPPORTED while more than one distinct set is installed (its a_k tables come
+ * from one D and one cw); with one set it uses that set's D and cw. */
+int ebm_set_column_params(ebm_handle_t h, const double *params);
 /* Table of cos(2.0*pi*st.t[i]), i = 1..nt (src/miz.jl:11, src/classic.jl:24), needed by
  * ebm_run/ebm_integrate.  Computed by the caller so that host and device agree bit for bit. */
 int ebm_set_time_table(ebm_handle_t h, int nt, const double *cos2pit);
