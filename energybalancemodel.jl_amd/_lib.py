@@ -28,7 +28,8 @@ EXPORTS = (
     "ebm_field_device_ptr", "ebm_diffusion", "ebm_zonal_diffusion", "ebm_set_column_forcing", "ebm_set_column_schedule",
     "ebm_set_column_params",
     "ebm_set_step_clock", "ebm_set_time_table",
-    "ebm_step", "ebm_run", "ebm_run_fused", "ebm_integrate", "ebm_integrate_hemispheric", "ebm_sync", "ebm_get_counters",
+    "ebm_step", "ebm_run", "ebm_run_fused", "ebm_integrate", "ebm_integrate_hemispheric",
+    "ebm_equilibrate", "ebm_sync", "ebm_get_counters",
     "ebm_reset_counters", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
     "ebm_selftest_divide",
 )
@@ -106,6 +107,8 @@ def load():
                                   C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp]
     lib.ebm_integrate_hemispheric.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_int), _dp, _dp, _dp]
+    lib.ebm_equilibrate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_int), _dp,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
     lib.ebm_sync.argtypes = [C.c_void_p]
     lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_reset_counters.argtypes = [C.c_void_p]

@@ -98,6 +98,8 @@ struct StepArgs {
     long long stage_offset;          // snapshot index * ncol*pitch
     signed char var_of[kMaxQuantities];   // quantity -> saved-variable index, -1 = not saved
     unsigned long long *stamps;      // diagnostic builds only (EBM_STAMPS), else nullptr
+    const int *cols;                 // active columns (ebm_equilibrate): workgroup b steps column cols[col0 + b]; nullptr =
+                                     // identity.  Read by the fused-K kernels and the classic kernel only.
 };
 
 struct LaunchCfg {
@@ -171,6 +173,25 @@ hipError_t launch_zonal_sweep_segmented(const double *T, double *out_Z, double *
                                         const double *rM, const double *rE, const double *za, const double *za2,
                                         const double *rW, double *su, double *sg, double *sy, int nlon, int S, int nmember,
                                         int pitch, double rtheta, hipStream_t s);
+// ebm_equilibrate, one workgroup per active column c = cols[b], b < nactive: for every criterion field v (state slot
+// slot[v]) d = max over k < nlat of |field - snap| (NaN-propagating), snap = field; if `compare`, resid[v][c] = d; then
+// years[c] = year and frozen[c] = (may_freeze && d <= tol[v] for every v)
+struct EquilArgs {
+    const double *state;
+    long long fstride;
+    double *snap;                    // [nvars][ncol][pitch], last year's snapshot
+    double *resid;                   // [nvars][ncol]
+    int *years, *frozen;             // [ncol]
+    const int *cols;                 // [nactive], ascending
+    int pitch, nlat, ncol, nvars;
+    int year, compare, may_freeze;
+    int slot[kMaxQuantities];
+    double tol[kMaxQuantities];
+};
+hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s);
+// the next active list: out = the entries of in[0 .. n) whose column is not frozen, in order; *count = their number
+// (one workgroup)
+hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s);
 // natural <-> pair-split layout of whole fields ([ncol][pitch], 4 cells per thread; a no-op with 2), in place
 hipError_t launch_split_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                hipStream_t s);

@@ -127,6 +127,14 @@ __device__ __forceinline__ int param_set(const StepArgs &a, int col) {
     typedef const __attribute__((address_space(4))) int ConstInt;
     return a.pset ? reinterpret_cast<ConstInt *>(reinterpret_cast<uintptr_t>(a.pset))[col] : 0;
 }
+// The column workgroup blockIdx.x of a launch steps: entry col0 + blockIdx.x of the active list (ebm_equilibrate: frozen
+// columns get no workgroup), one scalar load per workgroup, none without a list (the identity).  The fused-K kernels and
+// the classic kernel only: miz_step_kernel is never launched on a list.
+__device__ __forceinline__ int step_column(const StepArgs &a) {
+    typedef const __attribute__((address_space(4))) int ConstInt;
+    const int b = a.col0 + (int)blockIdx.x;
+    return a.cols ? reinterpret_cast<ConstInt *>(reinterpret_cast<uintptr_t>(a.cols))[b] : b;
+}
 
 // ---- Julia IEEE semantics ----------------------------------------------------------------
 __device__ __forceinline__ double jl_min(double x, double y) {
@@ -1077,7 +1085,7 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     static_assert(C == 2 || C == 4, "cells per thread");
     constexpr int T = TT;
     extern __shared__ double smem[];
-    const int t = threadIdx.x, col = a.col0 + (int)blockIdx.x;
+    const int t = threadIdx.x, col = step_column(a);
     const int nlat = a.nlat;
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
@@ -1240,7 +1248,7 @@ template <int GRID, int TT, bool IMEX, bool SAVE = false>
 __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_kernel(const StepArgs a) {
     constexpr int C = 4, T = TT;
     extern __shared__ double smem[];
-    const int t = threadIdx.x, col = a.col0 + (int)blockIdx.x;
+    const int t = threadIdx.x, col = step_column(a);
     const int nlat = a.nlat;
     const unsigned k0 = (unsigned)t * C;
     double *const PA = smem, *const PB = smem + 3 * T;    // the solve's 3T + T
@@ -1562,7 +1570,7 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
     static_assert(C == 2 || C == 4, "cells per thread");
     constexpr bool LOOP = MODE == OUT_LOOP;
     extern __shared__ double smem[];
-    const int T = blockDim.x, t = threadIdx.x, col = a.col0 + (int)blockIdx.x;
+    const int T = blockDim.x, t = threadIdx.x, col = step_column(a);
     const int nlat = a.nlat;
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
@@ -1691,6 +1699,77 @@ __global__ void hemispheric_mean_kernel(const double *__restrict__ field, const 
         out[blockIdx.x] = acc;
     }
 }
+// ebm_equilibrate's year-end test, one workgroup per active column (EquilArgs): rows k < nlat of this year's fields
+// against last year's snapshot, which takes this year's values in the same pass.  The distance is a max of exact
+// |differences|, NaN-propagating, so its value does not depend on the order of the reduction (lanes, then the waves
+// through LDS); d <= tol is false for NaN.
+__device__ __forceinline__ double max_nan(double x, double y) { return (x != x || x > y) ? x : y; }
+__global__ void __launch_bounds__(256) equilibrium_check_kernel(const EquilArgs e) {
+    __shared__ double part[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int col = e.cols[blockIdx.x];
+    const size_t row = (size_t)col * (size_t)e.pitch;
+    bool ok = true;
+    for (int v = 0; v < e.nvars; ++v) {
+        const double *cur = e.state + (size_t)e.slot[v] * (size_t)e.fstride + row;
+        double *prev = e.snap + (size_t)v * (size_t)e.ncol * (size_t)e.pitch + row;
+        double d = 0.0;
+        for (int k = t; k < e.nlat; k += 256) {
+            const double c = cur[k];
+            d = max_nan(d, fabs(c - prev[k]));
+            prev[k] = c;
+        }
+        for (int off = 32; off > 0; off >>= 1) d = max_nan(d, __shfl_xor(d, off, 64));
+        if (lane == 0) part[wave] = d;
+        __syncthreads();
+        d = max_nan(max_nan(part[0], part[1]), max_nan(part[2], part[3]));
+        __syncthreads();                                  // (part is refilled by the next variable)
+        if (e.compare && t == 0) e.resid[(size_t)v * (size_t)e.ncol + col] = d;
+        ok = ok && d <= e.tol[v];
+    }
+    if (t == 0) {
+        e.years[col] = e.year;
+        e.frozen[col] = (e.may_freeze && ok) ? 1 : 0;
+    }
+}
+hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s) {
+    if (nactive < 1 || nactive > e.ncol || e.nvars < 1 || e.nvars > kMaxQuantities) return hipErrorInvalidValue;
+    equilibrium_check_kernel<<<nactive, 256, 0, s>>>(e);
+    return hipGetLastError();
+}
+
+// The next active list, in one workgroup: a stable stream compaction of in[0 .. n) by !frozen[in[i]], 1024 entries per
+// round — per wave a ballot and a popcount below the lane, across the 16 waves a scan of their counts in LDS.
+__global__ void __launch_bounds__(1024) compact_active_kernel(const int *__restrict__ in, int n, const int *__restrict__ frozen,
+                                                              int *__restrict__ out, int *__restrict__ count) {
+    __shared__ int wave_base[17];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int total = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + t;
+        const int c = i < n ? in[i] : 0;
+        const bool keep = i < n && frozen[c] == 0;
+        const unsigned long long ballot = __ballot(keep);
+        const int below = __popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_base[wave + 1] = __popcll(ballot);
+        __syncthreads();
+        if (t == 0) {
+            wave_base[0] = 0;
+            for (int w = 1; w <= 16; ++w) wave_base[w] += wave_base[w - 1];
+        }
+        __syncthreads();
+        if (keep) out[total + wave_base[wave] + below] = c;
+        total += wave_base[16];
+        __syncthreads();                                  // (wave_base is refilled by the next round)
+    }
+    if (t == 0) *count = total;
+}
+hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s) {
+    if (n < 1) return hipErrorInvalidValue;
+    compact_active_kernel<<<1, 1024, 0, s>>>(in, n, frozen, out, count);
+    return hipGetLastError();
+}
+
 // The diffusion operator on its own: out = base + D d/dx[(1-x^2) d temp/dx], one thread per cell —
 // diffusion!(base, temp, st, par) / diffusion(T, st, par), src/infrastructure.jl:495-533, with the
 // same device functions (and hence the same bits) the step kernels use inside their fused physics.

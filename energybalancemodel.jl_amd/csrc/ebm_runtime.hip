@@ -98,6 +98,10 @@ struct ebm_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int split_col = 0;                             // 0: one chain; else the first column of the second chain
     bool forked = false;
+    // ebm_equilibrate, for the duration of the call only: the launches step the columns active[0 .. nactive) (device list,
+    // ascending) instead of all of them
+    const int *active = nullptr;
+    int nactive = 0;
     // Validity of the fields that only some steps write (diagnostics, the fp64 T0): `epoch` counts every change
     // of the prognostic state (steps taken, prognostic fields overwritten), `state_step` is the global index of
     // the last step taken (-1: none); a field is current iff written_epoch[f] == epoch.
@@ -386,6 +390,7 @@ ebm::StepArgs base_args(const ebm_ctx *h) {
     }
     a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol;
     a.stamps = h->stamps;
+    a.cols = h->active;
     a.prefetch = h->prefetch;
     a.nfused = 1;
     std::memset(a.var_of, -1, sizeof(a.var_of));
@@ -400,16 +405,26 @@ hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, int firs
     return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, first, count, s)
                                        : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
 }
+// The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate), as one
+// chain or split in two halves; a chain with no columns is skipped.
+int chain_count(const ebm_ctx *h, int *first_half) {
+    const int n = h->active ? h->nactive : h->ncol;
+    *first_half = h->split_col ? (h->active ? n / 2 : h->split_col) : n;
+    return (*first_half > 0) + (n - *first_half > 0);
+}
 hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
-    if (!h->split_col) return launch_columns(h, a, mode, 0, h->ncol, main_stream(h));
+    const int n = h->active ? h->nactive : h->ncol;
+    if (!h->split_col) return launch_columns(h, a, mode, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
         hipError_t e = hipEventRecord(h->ev_fork, h->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
         if (e != hipSuccess) return e;
         h->forked = true;
     }
-    hipError_t e = launch_columns(h, a, mode, 0, h->split_col, h->stream);
-    if (e == hipSuccess) e = launch_columns(h, a, mode, h->split_col, h->ncol - h->split_col, h->stream2);
+    int half = 0;
+    (void)chain_count(h, &half);
+    hipError_t e = half > 0 ? launch_columns(h, a, mode, 0, half, h->stream) : hipSuccess;
+    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, half, n - half, h->stream2);
     return e;
 }
 
@@ -1130,7 +1145,8 @@ static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, i
             }
             hipError_t e = launch_step(h, a, save ? ebm::OUT_LOOP_SAVE : ebm::OUT_LOOP);
             if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("fused launch: ") + hipGetErrorString(e));
-            h->n_launches += h->split_col ? 2 : 1;
+            int half = 0;
+            h->n_launches += chain_count(h, &half);
             note_steps(h, a.nfused, first_step + s0 + i + a.nfused - 1, a.write_diag != 0);
             if (a.write_diag && h->model == EBM_MODEL_MIZ) h->diag_split = false;      // the fused kernel stores them in the natural layout
         }
@@ -1349,6 +1365,101 @@ int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_s
     if (!hm_winter && !hm_summer && !hm_avg) return fail(EBM_ERR_ARG, "ebm_integrate_hemispheric: no output requested");
     return integrate_impl(h, nt, dur, f_steps, 1, winter_inx, summer_inx, nvars, fields, nullptr, nullptr, nullptr, nullptr,
                           hm_winter, hm_summer, hm_avg);
+}
+
+// ebm_equilibrate (include/ebm_hip.h).  Every year is one fused_range over the active columns (launches of nactive
+// workgroups, which step cols[b]), then equilibrium_check_kernel compares each active column's year-end fields with the
+// snapshot of the year before and freezes it, compact_active_kernel writes the next list and its length, and the host
+// reads the length: one stream synchronisation per year.  The fused kernels store the diagnostic fields in the natural
+// layout, so the fields of columns frozen in different years share one layout and nothing is un-permuted in between.
+int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const double *f_year, int nvars, const int *fields,
+                    const double *tol, int *years, int *converged, double *resid) {
+    if (!h || nt < 1 || nvars < 1 || !fields || !tol || !years || !converged) return fail(EBM_ERR_ARG, "ebm_equilibrate: bad argument");
+    if (h->fsched)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: per-column forcing schedules are installed (a ramped forcing has no "
+                                         "equilibrium; ebm_set_column_schedule(h, NULL) clears them)");
+    if ((long long)h->ttab.size() != nt) return fail(EBM_ERR_ARG, "ebm_equilibrate: time table length must equal nt");
+    if (max_years < 1) return fail(EBM_ERR_ARG, "ebm_equilibrate: max_years must be >= 1");
+    if (nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_equilibrate: too many fields");
+    ebm::EquilArgs ea{};
+    bool listed[EBM_F_COUNT] = {};
+    for (int v = 0; v < nvars; ++v) {
+        const int f = fields[v];
+        if (!has_field(h, f) || quantity_of(h->model, f) < 0)
+            return fail(EBM_ERR_ARG, "ebm_equilibrate: fields[" + std::to_string(v) + "] is not a solution variable of this model");
+        if (listed[f]) return fail(EBM_ERR_ARG, std::string("ebm_equilibrate: field ") + field_name(f) + " is listed twice");
+        listed[f] = true;
+        if (!(tol[v] >= 0.0))
+            return fail(EBM_ERR_ARG, std::string("ebm_equilibrate: the tolerance of ") + field_name(f) + " must be >= 0 (not NaN)");
+        ea.slot[v] = slot_of(h->model, f);
+        ea.tol[v] = tol[v];
+    }
+    if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: no fused-K kernel for this shape in this build");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = ensure_natural(h);
+    if (rc) return rc;
+    const int ncol = h->ncol;
+    const size_t npitch = (size_t)ncol * h->pitch;
+    // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count; the list is known to
+    // the launches only until the call returns, on every path
+    struct Scope {
+        ebm_ctx *h;
+        double *dbl = nullptr;
+        int *ints = nullptr, *pinned = nullptr;
+        ~Scope() {
+            h->active = nullptr;
+            h->nactive = 0;
+            (void)hipStreamSynchronize(main_stream(h));
+            if (dbl) (void)hipFree(dbl);
+            if (ints) (void)hipFree(ints);
+            if (pinned) (void)hipHostFree(pinned);
+        }
+    } sc{h};
+    HIPCHK(hipMalloc(&sc.dbl, sizeof(double) * ((size_t)nvars * npitch + (size_t)nvars * ncol)));
+    HIPCHK(hipMalloc(&sc.ints, sizeof(int) * (4 * (size_t)ncol + 1)));
+    HIPCHK(hipHostMalloc(&sc.pinned, sizeof(int), hipHostMallocDefault));
+    int *cur = sc.ints, *nxt = cur + ncol, *years_dev = nxt + ncol, *frozen = years_dev + ncol, *count = frozen + ncol;
+    {
+        std::vector<double> nan((size_t)nvars * ncol, std::nan(""));
+        std::vector<int> ident((size_t)ncol);
+        for (int c = 0; c < ncol; ++c) ident[c] = c;
+        HIPCHK(hipMemcpy(sc.dbl + (size_t)nvars * npitch, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(years_dev, 0, sizeof(int) * 2 * (size_t)ncol));
+    }
+    ea.state = h->state; ea.fstride = h->fstride;
+    ea.snap = sc.dbl; ea.resid = sc.dbl + (size_t)nvars * npitch;
+    ea.years = years_dev; ea.frozen = frozen;
+    ea.pitch = (int)h->pitch; ea.nlat = h->nlat; ea.ncol = ncol; ea.nvars = nvars;
+    const long long clock0 = h->clock;
+    const int first_test = std::max(2, min_years);
+    int nactive = ncol;
+    for (int y = 1; y <= max_years; ++y) {
+        h->active = cur;
+        h->nactive = nactive;
+        rc = fused_range(h, 0, clock0 + (long long)(y - 1) * nt, nt, f_year, 1, h->integrate_spl, nullptr);
+        if (rc) return rc;
+        ea.cols = cur;
+        ea.year = y;
+        ea.compare = y >= 2;
+        ea.may_freeze = y >= first_test;
+        hipError_t e = ebm::launch_equilibrium_check(ea, nactive, main_stream(h));
+        if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_equilibrate: check: ") + hipGetErrorString(e));
+        if (y == max_years || !ea.may_freeze) continue;          // (nothing has frozen: the list stays)
+        e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
+        if (e == hipSuccess) e = hipMemcpyAsync(sc.pinned, count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+        if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_equilibrate: active list: ") + hipGetErrorString(e));
+        nactive = *sc.pinned;
+        std::swap(cur, nxt);
+        if (nactive == 0) break;                                 // every column is frozen
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(years, years_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(converged, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    if (resid) HIPCHK(hipMemcpy(resid, ea.resid, sizeof(double) * (size_t)nvars * ncol, hipMemcpyDeviceToHost));
+    return EBM_OK;
 }
 
 int ebm_sync(ebm_handle_t h) {

@@ -315,6 +315,45 @@ class Engine:
               "ebm_integrate_hemispheric")
         return out
 
+    def check_equilibrate_args(self, nt, max_years, tol, min_years=2, f_year=None):
+        """The host-side checks of ``equilibrate`` (no device call): returns (names, field ids, tolerances, f_year)."""
+        if not hasattr(tol, "items") or len(tol) < 1:
+            raise ValueError("tol: expected a dict of field name -> absolute tolerance, e.g. {'T': 1e-3}")
+        names = tuple(tol)
+        allowed = self.prognostic + self.diagnostic
+        for n in names:
+            if n not in allowed:
+                raise ValueError(f"tol: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)})")
+        tols = np.array([float(tol[n]) for n in names], dtype=np.float64)
+        for n, t in zip(names, tols):
+            if not t >= 0.0:
+                raise ValueError(f"tol[{n!r}] = {t}: a tolerance must be >= 0 (and not NaN)")
+        if int(max_years) < 1:
+            raise ValueError(f"max_years = {max_years}: need at least one year")
+        if int(nt) < 1:
+            raise ValueError(f"nt = {nt}: need at least one step per year")
+        f = None if f_year is None else as_f64(f_year, (int(nt),))
+        return names, [FIELD[n] for n in names], tols, f
+
+    def equilibrate(self, nt, max_years, f_year=None, tol=None, min_years=2):
+        """ebm_equilibrate: whole years of ``nt`` steps (forcing ``f_year[i] + fcol[c]``, the same every year) until each
+        column's year-end fields repeat — ``max |S(y) - S(y-1)| <= tol[name]`` for every named field, first tested after
+        year max(2, min_years) — or ``max_years``.  A column stops at its own equilibrium year, its state bit for bit that
+        of plain stepping for that many years.  ``tol``: dict field name -> absolute tolerance (default ``{"T": 1e-3}``).
+        Returns dict(years [ncol] int, converged [ncol] bool, resid {name: [ncol]}: the last distance compared, NaN if
+        none)."""
+        tol = {"T": 1e-3} if tol is None else tol
+        names, ids, tols, f = self.check_equilibrate_args(nt, max_years, tol, min_years, f_year)
+        nv = len(names)
+        fields = (C.c_int * nv)(*ids)
+        years = np.zeros(self.ncol, dtype=np.int32)
+        conv = np.zeros(self.ncol, dtype=np.int32)
+        resid = np.full((nv, self.ncol), np.nan)
+        ip = C.POINTER(C.c_int)
+        check(self.lib.ebm_equilibrate(self._h, int(nt), int(max_years), int(min_years), dptr(f), nv, fields, dptr(tols),
+                                       years.ctypes.data_as(ip), conv.ctypes.data_as(ip), dptr(resid)), "ebm_equilibrate")
+        return dict(years=years.astype(np.int64), converged=conv.astype(bool), resid={n: resid[i] for i, n in enumerate(names)})
+
     def sync(self):
         check(self.lib.ebm_sync(self._h), "ebm_sync")
 

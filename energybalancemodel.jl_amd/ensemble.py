@@ -93,6 +93,7 @@ class EnsembleRun:
             self.engine.set_column_schedules(forcings)
         if rows is not None:
             self.engine.set_column_params(rows)
+        self.has_schedules = forcings is not None
         self.step_index = 0
 
     def run(self, nsteps, forcing=None, diag_last=True, steps_per_launch=None):
@@ -130,6 +131,33 @@ class EnsembleRun:
         self.engine.set_step_clock(self.step_index)
         out = self.engine.integrate_hemispheric(st.nt, years, f, st.winter.inx, st.summer.inx, tuple(names))
         self.step_index += st.nt * years
+        return out
+
+    def equilibrate(self, max_years, tol=None, forcing=None, min_years=2):
+        """Spin this shard's members up until each one's seasonal cycle repeats (ebm_equilibrate): whole years from the
+        current state, member m stopping at the first year y >= max(2, min_years) whose year-end fields named in ``tol``
+        (dict name -> absolute tolerance, default ``{"T": 1e-3}``) differ from the previous year's by at most the
+        tolerance everywhere, or at ``max_years``.  ``forcing``: a constant Forcing (or None) added to every member's
+        ``fcol``; ramps have no equilibrium and are refused, as are ensembles built with ``forcings=``.  Members are
+        independent, so a sharded ensemble gives the bits of an unsharded one.  The call starts a year, like
+        ``seasonal_means``; afterwards ``step_index`` is that of the slowest member.  Returns dict(years, converged,
+        resid) as ``Engine.equilibrate``."""
+        st = self.st
+        if self.has_schedules:
+            raise ValueError("equilibrate: this ensemble was built with forcings= (per-member ramps have no equilibrium)")
+        if forcing is not None and not getattr(forcing, "constant", False):
+            raise ValueError("equilibrate: needs a constant forcing (a Forcing{false} ramp has no equilibrium)")
+        if self.step_index % st.nt:
+            raise ValueError(f"equilibrate starts a year: {self.step_index} steps taken so far is not a multiple of nt = {st.nt}")
+        tol = {"T": 1e-3} if tol is None else tol
+        f = None
+        if forcing is not None:
+            T = (np.arange(self.step_index, self.step_index + st.nt) + 0.5) * st.dt
+            f = np.array([forcing(float(t)) for t in T])
+        self.engine.check_equilibrate_args(st.nt, max_years, tol, min_years, f)
+        self.engine.set_step_clock(self.step_index)
+        out = self.engine.equilibrate(st.nt, max_years, f, tol, min_years)
+        self.step_index += st.nt * int(out["years"].max())
         return out
 
     def state(self, names=None):

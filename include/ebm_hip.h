@@ -313,6 +313,40 @@ int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_s
                               int summer_inx, int nvars, const int *fields, double *hm_winter,
                               double *hm_summer, double *hm_avg);
 
+/* Run whole years until each column's seasonal cycle repeats — the spin-up behind every steady state of the reference
+ * (integrate(...; lastonly=true) run for "enough" years, src/infrastructure.jl:615-636), with a stated criterion and a
+ * stopping year of its own for every column.  THIS TEXT IS THE DEFINITION.
+ *   Year-end snapshot.  S_c,v(y) is field fields[v] of column c after y whole years of this call.  Every year is nt steps
+ *     with time-of-year index 1 .. nt (as ebm_integrate) and the forcing f_year[i] + fcol[c], the same every year
+ *     (f_year[nt]; NULL = 0).
+ *   Distance.  d_c,v(y) = max over k < nlat of |S_c,v(y)[k] - S_c,v(y-1)[k]|, taken for y >= 2 only.
+ *   Equilibrium year.  Y_c is the smallest y with max(2, min_years) <= y <= max_years such that d_c,v(y) <= tol[v] for
+ *     every v.  A NaN anywhere (in a distance, hence in either snapshot) means "not converged" — so Ti and Tw, which hold
+ *     NaN sentinels where there is no ice / no open water (src/miz.jl:193-194), never converge in a column that has one.
+ *   Freezing.  Column c steps exactly Y_c years and then no further step.  Its whole state is bit for bit what
+ *     ebm_run_fused (equivalently ebm_run, ebm_integrate) gives after Y_c * nt steps from the same start: the prognostic
+ *     fields, the warm start T0 and the diagnostic fields, written at the column's own last year end.
+ *   Outputs.  years[c] = Y_c and converged[c] = 1; a column that never meets the criterion steps max_years years and gets
+ *     years[c] = max_years, converged[c] = 0.  resid[v][c] (may be NULL) is d_c,v of the last year compared for the
+ *     column, NaN if none was (max_years = 1).  Host arrays: years, converged [ncol]; resid [nvars][ncol].
+ *   The call returns as soon as every column is frozen.  Afterwards the step clock is at clock0 + nt * max_c years[c]
+ *   (clock0: the clock at entry), counters[0] has counted nt * max_c years[c] steps, and every field is current: each
+ *   column holds the values of its own last step, and the validity bookkeeping (ebm_field_step) records them as written
+ *   by the handle's last step.
+ * fields[nvars] may name any solution variable of the model, prognostic or diagnostic, each at most once; EBM_F_T0 is not
+ * one (as in ebm_integrate).  All models (MIZ, MIZ_IMEX, classic), grids and options; per-column forcings and parameter
+ * rows are honoured.  Columns are independent: a column's result does not depend on the others or on sharding.
+ * Refusals leave the handle as it was: EBM_ERR_UNSUPPORTED while per-column schedules are installed (a ramped forcing has
+ * no equilibrium); EBM_ERR_ARG for a time table whose length is not nt, max_years < 1, a tolerance that is negative or
+ * NaN, a bad or repeated field.
+ * How it runs: each year is the fused stepping of ebm_run_fused (ebm_options.integrate_steps_per_launch steps to a launch,
+ * 1 = one launch per step) over the ACTIVE columns only — a frozen column gets no workgroup and moves no byte — then one
+ * small kernel compares and snapshots the active columns' fields, a second one builds the next active list, and the host
+ * reads its length (one stream synchronisation per year).  Device memory for the call: nvars * ncol * pitch doubles (last
+ * year's snapshot), nvars * ncol doubles (resid) and 4 ints per column, freed before it returns.  Synchronous. */
+int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const double *f_year, int nvars, const int *fields,
+                    const double *tol, int *years, int *converged, double *resid);
+
 int ebm_sync(ebm_handle_t h);
 
 /* ---- measurement / diagnostics ------------------------------------------------------- */
