@@ -27,8 +27,11 @@
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)
 //   finish_mean, hemispheric_mean, mask_from_t0, derive_params, divide: small helpers
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
-// workgroup size as a compile-time constant.  Every one of the 443 instantiations uses 0 bytes of scratch
-// (tests/tools/resource_usage.py).
+// workgroup size as a compile-time constant (the lists of sizes and the lookup are at the end of the file).  Every one of
+// the 445 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
+// (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
+// "pieces of the MIZ step" below; what stays in each kernel is how it holds its state and loads its tables.
 //
 // Arithmetic policy.  Everything outside the tridiagonal solves is a bit-exact restatement of
 // the reference's expressions (IEEE division, no FMA contraction: build with
@@ -483,25 +486,46 @@ __device__ __forceinline__ void partition_solve(const double (&a)[C], const doub
     partition_solve_r<C, second_level_rows(TT != 0 ? TT : 1024), COMPACT>(a, b, c, d, x, t, T, P0, P1);
 }
 
+// Cell i of a thread's chunk has its neighbours in the chunk, or at the chunk's ends in the neighbouring chunks: `halo`
+template <int C>
+__device__ __forceinline__ double left_of(const double (&v)[C], int i, double halo) {
+    return i > 0 ? v[i > 0 ? i - 1 : 0] : halo;
+}
+template <int C>
+__device__ __forceinline__ double right_of(const double (&v)[C], int i, double halo) {
+    return i < C - 1 ? v[i < C - 1 ? i + 1 : i] : halo;
+}
+
 // ---- MIZ pointwise physics (one cell), bit-exact restatement of src/miz.jl:160-194 ----------
 struct MizCellOut {
     double q[Q_MIZ_COUNT];     // indexed by MizQuantity
 };
 
-__device__ __forceinline__ MizCellOut miz_cell_update(ConstParams &p, double f, double S, double xk,
-                                                     double dif, double tb, double Ei, double Ew,
-                                                     double hk, double Dk, double ph, double Tw,
-                                                     double Ti) {
-    const double Tm = p.Tm, Lf = p.Lf, alpha = p.alpha, dt = p.dt;
-    // num, src/miz.jl:83-87
-    double n = ieee_div(ph, alpha * (Dk * Dk));
-    if (Dk == 0.0) n = 0.0;
-    // vert_flux, src/miz.jl:96-101 (called twice in the reference with the same Tbar/diffusion)
+// vert_flux, src/miz.jl:96-101: the vertical fluxes into ice and water (called twice in the reference with the same
+// Tbar / diffusion term)
+struct VertFlux {
+    double Fvi, Fvw;
+};
+__device__ __forceinline__ VertFlux vert_flux(ConstParams &p, double S, double xk, double tb, double dif, double f) {
+    const double Tm = p.Tm;
     const double L = p.A + p.B * (tb - Tm);
     const double sol_i = 0.0 + p.ai * S;
     const double sol_w = 0.0 + (p.a0 - p.a2 * (xk * xk)) * S;
     const double Fvi = sol_i - L + dif + p.Fb + f;
     const double Fvw = sol_w - L + dif + p.Fb + f;
+    return {Fvi, Fvw};
+}
+
+__device__ __forceinline__ MizCellOut miz_cell_update(ConstParams &p, double f, double S, double xk,
+                                                     double dif, double tb, double Ei, double Ew,
+                                                     double hk, double Dk, double ph, double Tw,
+                                                     double Ti) {
+    const double Lf = p.Lf, alpha = p.alpha, dt = p.dt;
+    // num, src/miz.jl:83-87
+    double n = ieee_div(ph, alpha * (Dk * Dk));
+    if (Dk == 0.0) n = 0.0;
+    const VertFlux fv = vert_flux(p, S, xk, tb, dif, f);
+    const double Fvi = fv.Fvi, Fvw = fv.Fvw;
     // wlat :71, lat_flux :103-107
     const double wl = p.m1 * (Tw - p.Tm_pow_m2);
     double Flat = ieee_div(ph * hk * Lf * wl * M_PI, alpha * Dk);
@@ -596,8 +620,36 @@ __device__ __forceinline__ double interface_flux(int kI, int nlat, double xa, do
     return ieee_div((1.0 - xx * xx) * dT, hi_x - lo_x);
 }
 
-// ---- pieces of the T0 system shared by the per-step and the fused-K kernels --------------------
-// (one definition each, so that every kernel forms the rows with the same operations)
+// ---- pieces of the MIZ step shared by miz_step_kernel, miz_fused_kernel and miz_resident_kernel --------------
+// (one definition each, so that every kernel performs the same operations on the same operands: bit-identical steps)
+
+// The Tbar diffusion term D d/dx[(1-x^2) dTbar/dx] of a thread's cells, visited in increasing order: the uniform operator
+// on the identity grid (GRID 0), the non-uniform stencil on any other, which carries the flux and position of the interface
+// left of the current cell from one cell to the next.  The caller passes the diagonals g0/g1/g2 of the identity grid's
+// operator (unused on other grids): each kernel loads them in its own way.
+template <int C, int GRID>
+struct TbarStencil {
+    double Fl = 0.0, xxl = 0.0;                           // flux / position of the interface left of the current cell
+    // the interface left of the chunk: xl, tbl are x and Tbar of the previous chunk's last cell
+    __device__ __forceinline__ void start(unsigned k0, int nlat, double xl, const double (&xk)[C], double tbl,
+                                          const double (&tb)[C]) {
+        if (GRID == 1) Fl = interface_flux((int)k0, nlat, xl, xk[0], tbl, tb[0], xxl);
+    }
+    // cell i of the chunk; xr, tbr: the next chunk's first cell
+    __device__ __forceinline__ double dif(ConstParams &p, int i, unsigned k0, int nlat, const double (&xk)[C], double xr,
+                                          const double (&tb)[C], double tbl, double tbr, double g0, double g1,
+                                          double g2) {
+        const int k = (int)k0 + i;
+        const double tbm = left_of(tb, i, tbl), tbp = right_of(tb, i, tbr);
+        if (GRID == 0) return diffusion_uniform(k, nlat, g0, g1, g2, tbm, tb[i], tbp);
+        double xxr;
+        const double Fr = interface_flux(k + 1, nlat, xk[i], right_of(xk, i, xr), tb[i], tbp, xxr);
+        const double d = 0.0 + ieee_div(p.D * (Fr - Fl), xxr - xxl);             // :524
+        Fl = Fr;
+        xxl = xxr;
+        return d;
+    }
+};
 
 // water_temp (src/miz.jl:30) with the NaN -> 0 of :157
 __device__ __forceinline__ double water_temperature(ConstParams &p, double Ew, double ph) {
@@ -616,6 +668,54 @@ __device__ __forceinline__ double t0_rhs(ConstParams &p, double S, double lo, do
 }
 __device__ __forceinline__ double insolation(ConstParams &p, double xk, double ct) {
     return p.S0 - p.S1 * xk * ct - p.S2 * (xk * xk);                         // src/miz.jl:11
+}
+// The implicit-diffusion extension (IMEX; see miz_step_kernel).  The explicit increment of cell k's total enthalpy,
+// dE = dt*(phi*Fvi + (1-phi)*Fvw).  Padding cells (k >= nlat; on a non-uniform grid their stencil is 0/0) must not reach
+// the solve: their rows are decoupled but a NaN right-hand side would still spread through the elimination.
+__device__ __forceinline__ double enthalpy_increment(ConstParams &p, int k, int nlat, double xk, double ct, double tb,
+                                                     double dif, double f, double ph) {
+    const VertFlux fv = vert_flux(p, insolation(p, xk, ct), xk, tb, dif, f);
+    return k < nlat ? (ph * fv.Fvi + (1.0 - ph) * fv.Fvw) * p.dt : 0.0;
+}
+// the explicit diffusion term and enthalpy increment of every cell of the chunk (xl, tbl / xr, tbr: the neighbouring
+// chunks' cells); on the identity grid the three diagonals are fetched here, not kept across the solve
+template <int C, int GRID>
+__device__ __forceinline__ void imex_increments(const StepArgs &a, ConstParams &p, const double *geom, unsigned k0, int nlat,
+                                                double ct, double f, const double (&xk)[C], double xl, double xr,
+                                                const double (&tb)[C], double tbl, double tbr, const double (&ph)[C],
+                                                double (&dif)[C], double (&dE)[C]) {
+    double g0[GRID == 0 ? C : 1], g1[GRID == 0 ? C : 1], g2[GRID == 0 ? C : 1];
+    if constexpr (GRID == 0) {
+        unsigned kg = k0;
+        asm volatile("" : "+v"(kg));
+        load_chunk<C>(geom + G_LO * a.gstride, kg, g0);
+        load_chunk<C>(geom + G_DI * a.gstride, kg, g1);
+        load_chunk<C>(geom + G_UP * a.gstride, kg, g2);
+    }
+    TbarStencil<C, GRID> stencil;
+    stencil.start(k0, nlat, xl, xk, tbl, tb);
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        dif[i] = stencil.dif(p, i, k0, nlat, xk, xr, tb, tbl, tbr, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
+                             g2[GRID == 0 ? i : 0]);
+        dE[i] = enthalpy_increment(p, (int)k0 + i, nlat, xk[i], ct, tb[i], dif[i], f, ph[i]);
+    }
+}
+// row of I - theta*Dif, theta = dt/cw, from the solver's coefficients lo, up of the cell (padding rows: lo = up = 0,
+// decoupled)
+__device__ __forceinline__ void imex_row(ConstParams &p, double lo, double up, double &ra, double &rb, double &rc) {
+    ra = -(p.theta_imex * lo);
+    rc = -(p.theta_imex * up);
+    rb = 1.0 + p.theta_imex * (lo + up);
+}
+
+// Newton statistics (ebm_newton_stats): thread 0 adds the column's iterations and unconverged steps
+__device__ __forceinline__ void count_newton(const StepArgs &a, int col, int t, int nit, int nfail) {
+    if (t == 0 && a.counters) {
+        unsigned long long *cnt = a.counters + 2 * (col % kCounterShards);
+        atomicAdd(cnt, (unsigned long long)nit);
+        if (nfail) atomicAdd(cnt + 1, (unsigned long long)nfail);
+    }
 }
 
 // One active-set Newton iteration (src/miz.jl:33-68): rows for the active set `smask` (bit i <=>
@@ -638,8 +738,8 @@ __device__ __forceinline__ bool newton_iteration(const double (&lo)[C], const do
     double ra[C], rb[C], rc[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        ra[i] = lo[i] * (i > 0 ? g[i > 0 ? i - 1 : 0] : gl);
-        rc[i] = up[i] * (i < C - 1 ? g[i < C - 1 ? i + 1 : i] : gr);
+        ra[i] = lo[i] * left_of(g, i, gl);
+        rc[i] = up[i] * right_of(g, i, gr);
         rb[i] = -__builtin_fma(lo[i] + up[i], g[i], dd[i]);
     }
     partition_solve<C, TT, COMPACT>(ra, rb, rc, rd, xs, t, T, P0, P1);
@@ -790,12 +890,11 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             double rl, rr;
             halo_exchange(P0, P0 + T, t, T, r[0], r[C - 1], rl, rr);
             EBM_STAMP(2);
+            // (this loop stays in the kernels — the same two lines in all three: moved into a helper, it changes how hipcc
+            // peels the first Newton iteration of this kernel and of miz_resident_kernel, and with it their whole code)
 #pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const double rm = i > 0 ? r[i > 0 ? i - 1 : 0] : rl;
-                const double rp = i < C - 1 ? r[i < C - 1 ? i + 1 : i] : rr;
-                rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], rm, r[i], rp, f);
-            }
+            for (int i = 0; i < C; ++i)
+                rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
             __syncthreads();                                  // r halo reads done before P0 is reused
         } else {
             // second and later iterations (a changed active set): the right-hand side does not depend on the set and
@@ -808,11 +907,7 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         ++it;
         again = newton_iteration<C, TT>(tlo, tup, dd, ph, rd, xs, smask, t, T, k0, nlat, P0, P1);
     } while (again && it < kMaxNewton);
-    if (t == 0 && a.counters) {
-        unsigned long long *cnt = a.counters + 2 * (col % kCounterShards);
-        atomicAdd(cnt, (unsigned long long)it);
-        if (again) atomicAdd(cnt + 1, 1ull);
-    }
+    count_newton(a, col, t, it, again ? 1 : 0);
     {
         // (the lane index is made opaque so that the mask word's per-lane 64-bit address is formed here
         // again instead of being kept — and spilled — across the solve)
@@ -856,64 +951,23 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // twice.  The first pair's new prognostics are parked in LDS words that are dead by then (cells
     // 0,1 of the stash, the idle tail of the cyclic-reduction buffers) and all 32 bytes of a lane go
     // out in two back-to-back 16-B stores once the second pair is done.
-    double Fl = 0.0, xxl = 0.0;                           // flux / position of the interface left of the current cell
-    if (GRID == 1) Fl = interface_flux((int)k0, nlat, xl, xk[0], tbl, tb[0], xxl);
+    TbarStencil<C, GRID> stencil;
+    stencil.start(k0, nlat, xl, xk, tbl, tb);
     double difx[IMEX ? C : 1];                            // IMEX: the corrected diffusion term of every cell
     if constexpr (IMEX) {
-        // explicit D d/dx[(1-x^2) dTbar/dx] of every cell (the expressions of the loop below) and the explicit
-        // increment of its total enthalpy, dE = dt*(phi*Fvi + (1-phi)*Fvw)
-        auto increments = [&](double (&dif)[C], double (&dE)[C], const double hl, const double hr) {
-            double Fl_ = 0.0, xxl_ = 0.0;
-            if constexpr (GRID == 0) {                    // the three diagonals are fetched per use, not kept across the solve
-                unsigned kg = k0;
-                asm volatile("" : "+v"(kg));
-                load_chunk<C>(geom + G_LO * a.gstride, kg, g0);
-                load_chunk<C>(geom + G_DI * a.gstride, kg, g1);
-                load_chunk<C>(geom + G_UP * a.gstride, kg, g2);
-            }
-            if (GRID == 1) Fl_ = interface_flux((int)k0, nlat, xl, xk[0], hl, tb[0], xxl_);
-#pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const int k = (int)k0 + i;
-                const double tbm = i > 0 ? tb[i > 0 ? i - 1 : 0] : hl;
-                const double tbp = i < C - 1 ? tb[i < C - 1 ? i + 1 : i] : hr;
-                const double xp = i < C - 1 ? xk[i < C - 1 ? i + 1 : i] : xr;
-                if (GRID == 0) {
-                    dif[i] = diffusion_uniform(k, nlat, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
-                                               g2[GRID == 0 ? i : 0], tbm, tb[i], tbp);
-                } else {
-                    double xxr;
-                    const double Fr = interface_flux(k + 1, nlat, xk[i], xp, tb[i], tbp, xxr);
-                    dif[i] = 0.0 + ieee_div(p.D * (Fr - Fl_), xxr - xxl_);               // :524
-                    Fl_ = Fr;
-                    xxl_ = xxr;
-                }
-                const double S = insolation(p, xk[i], ct);
-                const double L = p.A + p.B * (tb[i] - Tm);
-                const double sol_i = 0.0 + p.ai * S;
-                const double sol_w = 0.0 + (p.a0 - p.a2 * (xk[i] * xk[i])) * S;
-                const double Fvi = sol_i - L + dif[i] + p.Fb + f;
-                const double Fvw = sol_w - L + dif[i] + p.Fb + f;
-                // padding cells (k >= nlat; on a non-uniform grid their stencil is 0/0) must not reach the solve:
-                // their rows are decoupled but a NaN right-hand side would still spread through the elimination
-                dE[i] = k < nlat ? (ph[i] * Fvi + (1.0 - ph[i]) * Fvw) * p.dt : 0.0;
-            }
-        };
         double sol[C];
         {
-            // rows of I - (dt/cw)*Dif (padding rows: lo = up = 0, decoupled) and the right-hand side
+            // rows of I - (dt/cw)*Dif and the right-hand side, the explicit increments
             double ra[C], rb[C], rc[C], dE[C], dif[C], tlo[C], tup[C];
             load_chunk<C>(geom + G_LO * a.gstride, k0, tlo);
             load_chunk<C>(geom + G_UP * a.gstride, k0, tup);
-            increments(dif, dE, tbl, tbr);
+            imex_increments<C, GRID>(a, p, geom, k0, nlat, ct, f, xk, xl, xr, tb, tbl, tbr, ph, dif, dE);
 #pragma unroll
             for (int i = 0; i < C; ++i) {
                 // the explicit diffusion term waits in the Tw words of the stash (Tw is formed again below from the stashed
                 // Ew and phi — one division — instead of the whole stencil a second time)
                 sTw[i * T] = dif[i];
-                ra[i] = -(p.theta_imex * tlo[i]);
-                rc[i] = -(p.theta_imex * tup[i]);
-                rb[i] = 1.0 + p.theta_imex * (tlo[i] + tup[i]);
+                imex_row(p, tlo[i], tup[i], ra[i], rb[i], rc[i]);
             }
             partition_solve<C, TT>(ra, rb, rc, dE, sol, t, T, P0, P1);
         }
@@ -929,18 +983,11 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             load_chunk<C>(gX, kl, xk);
 #pragma unroll
             for (int i = 0; i < C; ++i) {
-                const int k = (int)k0 + i;
                 const double dif0 = sTw[i * T];
                 const double tw = water_temperature(p, sEw[i * T], ph[i]);
                 sTw[i * T] = tw;                                      // the stash holds Tw again for the cell updates
                 tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * tw;
-                const double S = insolation(p, xk[i], ct);
-                const double L = p.A + p.B * (tb[i] - Tm);
-                const double sol_i = 0.0 + p.ai * S;
-                const double sol_w = 0.0 + (p.a0 - p.a2 * (xk[i] * xk[i])) * S;
-                const double Fvi = sol_i - L + dif0 + p.Fb + f;
-                const double Fvw = sol_w - L + dif0 + p.Fb + f;
-                const double dE = k < nlat ? (ph[i] * Fvi + (1.0 - ph[i]) * Fvw) * p.dt : 0.0;
+                const double dE = enthalpy_increment(p, (int)k0 + i, nlat, xk[i], ct, tb[i], dif0, f, ph[i]);
                 difx[IMEX ? i : 0] = dif0 + div_with_rcp(sol[i] - dE, p.dt, p.rcp_dt);
             }
         }
@@ -955,23 +1002,14 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             __builtin_amdgcn_sched_barrier(0);
-            const int i = 2 * j + q, k = (int)k0 + i;
-            const double tbm = i > 0 ? tb[i > 0 ? i - 1 : 0] : tbl;
-            const double tbp = i < C - 1 ? tb[i < C - 1 ? i + 1 : i] : tbr;
-            const double xp = i < C - 1 ? xk[i < C - 1 ? i + 1 : i] : xr;
+            const int i = 2 * j + q;
             const double S = insolation(p, xk[i], ct);
             double dif;
             if constexpr (IMEX) {
                 dif = difx[IMEX ? i : 0];
-            } else if (GRID == 0) {
-                dif = diffusion_uniform(k, nlat, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
-                                        g2[GRID == 0 ? i : 0], tbm, tb[i], tbp);
             } else {
-                double xxr;
-                const double Fr = interface_flux(k + 1, nlat, xk[i], xp, tb[i], tbp, xxr);
-                dif = 0.0 + ieee_div(p.D * (Fr - Fl), xxr - xxl);         // :524
-                Fl = Fr;
-                xxl = xxr;
+                dif = stencil.dif(p, i, k0, nlat, xk, xr, tb, tbl, tbr, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
+                                  g2[GRID == 0 ? i : 0]);
             }
             o[q] = miz_cell_update(p, f, S, xk[i], dif, tb[i], q ? Ei2.y : Ei2.x, sEw[i * T], sh[i * T],
                                    q ? Dk2.y : Dk2.x, ph[i], sTw[i * T], xs[i]);
@@ -1134,11 +1172,8 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
         double rl, rr;
         halo_exchange(P0, P0 + T, t, T, r[0], r[C - 1], rl, rr);
 #pragma unroll
-        for (int i = 0; i < C; ++i) {
-            const double rm = i > 0 ? r[i > 0 ? i - 1 : 0] : rl;
-            const double rp = i < C - 1 ? r[i < C - 1 ? i + 1 : i] : rr;
-            rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], rm, r[i], rp, f);
-        }
+        for (int i = 0; i < C; ++i)
+            rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
         __syncthreads();
         // phase B
         int it = 0;
@@ -1164,28 +1199,16 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
         }
         double tbl, tbr;
         halo_exchange(P0, P0 + T, t, T, tb[0], tb[C - 1], tbl, tbr);
-        double Fl = 0.0, xxl = 0.0;
-        if (GRID == 1) Fl = interface_flux((int)k0, nlat, xl, xk[0], tbl, tb[0], xxl);
+        TbarStencil<C, GRID> stencil;
+        stencil.start(k0, nlat, xl, xk, tbl, tb);
         [[maybe_unused]] MizCellOut o_even;                            // SAVE: the pair's first cell waits for its second
         [[maybe_unused]] bool v_even = false;
 #pragma unroll
         for (int i = 0; i < C; ++i) {
             __builtin_amdgcn_sched_barrier(0);                         // one cell at a time: bounded live ranges
             const int k = (int)k0 + i;
-            const double tbm = i > 0 ? tb[i > 0 ? i - 1 : 0] : tbl;
-            const double tbp = i < C - 1 ? tb[i < C - 1 ? i + 1 : i] : tbr;
-            const double xp = i < C - 1 ? xk[i < C - 1 ? i + 1 : i] : xr;
             const double S = insolation(p, xk[i], ct);
-            double dif;
-            if (GRID == 0) {
-                dif = diffusion_uniform(k, nlat, tlo[i], g1[GRID == 0 ? i : 0], tup[i], tbm, tb[i], tbp);
-            } else {
-                double xxr;
-                const double Fr = interface_flux(k + 1, nlat, xk[i], xp, tb[i], tbp, xxr);
-                dif = 0.0 + ieee_div(p.D * (Fr - Fl), xxr - xxl);
-                Fl = Fr;
-                xxl = xxr;
-            }
+            const double dif = stencil.dif(p, i, k0, nlat, xk, xr, tb, tbl, tbr, tlo[i], g1[GRID == 0 ? i : 0], tup[i]);
             const MizCellOut o = miz_cell_update(p, f, S, xk[i], dif, tb[i], Ei[i], Ew[i], hk[i], Dk[i], ph[i],
                                                  tw[i], xs[i]);
             const bool valid = k < nlat;                               // padding cells stay zero
@@ -1218,11 +1241,7 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     store_chunk<C>(st + S_D * a.fstride, Dk, k0, nlat);
     store_chunk<C>(st + S_phi * a.fstride, ph, k0, nlat);
     *wmask = (unsigned short)smask;
-    if (t == 0 && a.counters) {
-        unsigned long long *cnt = a.counters + 2 * (col % kCounterShards);
-        atomicAdd(cnt, (unsigned long long)nit);
-        if (nfail) atomicAdd(cnt + 1, (unsigned long long)nfail);
-    }
+    count_newton(a, col, t, nit, nfail);
 }
 
 // Fused-K MIZ stepping for the meridians the register kernel above cannot hold (more than kFusedRegThreads threads
@@ -1344,12 +1363,9 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
                 double rl, rr;
                 halo_exchange_waves(PB, ts, T, r[0], r[C - 1], rl, rr);
 #pragma unroll
-                for (int i = 0; i < C; ++i) {
-                    const double rm = i > 0 ? r[i > 0 ? i - 1 : 0] : rl;
-                    const double rp = i < C - 1 ? r[i < C - 1 ? i + 1 : i] : rr;
-                    rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], rm, r[i], rp, f);
-                }
-                __syncthreads();                                  // the halo words are rewritten by the iteration
+                for (int i = 0; i < C; ++i)
+                    rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
+                __syncthreads();                                 // the halo words are rewritten by the iteration
             } else {
 #pragma unroll
                 for (int i = 0; i < C; ++i) dd[i] = t0_diag_excess(p, sh(i));
@@ -1387,53 +1403,14 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
         if constexpr (IMEX) {
             // the extension's second solve, as in miz_step_kernel; nothing is parked here (no LDS is left): the explicit
             // increment is evaluated a second time after the solve — same operands, same operations, same bits
-            auto increments = [&](double (&dif)[C], double (&dE)[C]) {
-                double Fl_ = 0.0, xxl_ = 0.0;
-                if constexpr (GRID == 0) {
-                    unsigned kg = kl;
-                    asm volatile("" : "+v"(kg));
-                    load_chunk<C>(geom + G_LO * a.gstride, kg, g0);
-                    load_chunk<C>(geom + G_DI * a.gstride, kg, g1);
-                    load_chunk<C>(geom + G_UP * a.gstride, kg, g2);
-                }
-                if (GRID == 1) Fl_ = interface_flux((int)kl, nlat, xl, xk[0], tbl, tb[0], xxl_);
-#pragma unroll
-                for (int i = 0; i < C; ++i) {
-                    const int k = (int)kl + i;
-                    const double tbm = i > 0 ? tb[i > 0 ? i - 1 : 0] : tbl;
-                    const double tbp = i < C - 1 ? tb[i < C - 1 ? i + 1 : i] : tbr;
-                    const double xp = i < C - 1 ? xk[i < C - 1 ? i + 1 : i] : xr;
-                    if (GRID == 0) {
-                        dif[i] = diffusion_uniform(k, nlat, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
-                                                   g2[GRID == 0 ? i : 0], tbm, tb[i], tbp);
-                    } else {
-                        double xxr;
-                        const double Fr = interface_flux(k + 1, nlat, xk[i], xp, tb[i], tbp, xxr);
-                        dif[i] = 0.0 + ieee_div(p.D * (Fr - Fl_), xxr - xxl_);               // :524
-                        Fl_ = Fr;
-                        xxl_ = xxr;
-                    }
-                    const double S = insolation(p, xk[i], ct);
-                    const double L = p.A + p.B * (tb[i] - Tm);
-                    const double sol_i = 0.0 + p.ai * S;
-                    const double sol_w = 0.0 + (p.a0 - p.a2 * (xk[i] * xk[i])) * S;
-                    const double Fvi = sol_i - L + dif[i] + p.Fb + f;
-                    const double Fvw = sol_w - L + dif[i] + p.Fb + f;
-                    dE[i] = k < nlat ? (ph[i] * Fvi + (1.0 - ph[i]) * Fvw) * p.dt : 0.0;     // padding rows stay decoupled
-                }
-            };
             double sol[C];
             {
                 double ra[C], rb[C], rc[C], dE[C], dif[C], qlo[C], qup[C];
                 load_chunk<C>(geom + G_LO * a.gstride, kl, qlo);
                 load_chunk<C>(geom + G_UP * a.gstride, kl, qup);
-                increments(dif, dE);
+                imex_increments<C, GRID>(a, p, geom, kl, nlat, ct, f, xk, xl, xr, tb, tbl, tbr, ph, dif, dE);
 #pragma unroll
-                for (int i = 0; i < C; ++i) {
-                    ra[i] = -(p.theta_imex * qlo[i]);
-                    rc[i] = -(p.theta_imex * qup[i]);
-                    rb[i] = 1.0 + p.theta_imex * (qlo[i] + qup[i]);
-                }
+                for (int i = 0; i < C; ++i) imex_row(p, qlo[i], qup[i], ra[i], rb[i], rc[i]);
                 partition_solve<C, TT, true>(ra, rb, rc, dE, sol, ts, T, PA, PB);
             }
             __syncthreads();                                  // the solve's last LDS reads are done
@@ -1455,30 +1432,27 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
                     tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * tw;
                 }
                 double dif[C], dE[C];
-                increments(dif, dE);
+                imex_increments<C, GRID>(a, p, geom, kl, nlat, ct, f, xk, xl, xr, tb, tbl, tbr, ph, dif, dE);
 #pragma unroll
                 for (int i = 0; i < C; ++i) difx[IMEX ? i : 0] = dif[i] + div_with_rcp(sol[i] - dE[i], p.dt, p.rcp_dt);
             }
         }
-        double Fl = 0.0, xxl = 0.0;
-        if (GRID == 1) Fl = interface_flux((int)kl, nlat, xl, xk[0], tbl, tb[0], xxl);
+        TbarStencil<C, GRID> stencil;
+        stencil.start(kl, nlat, xl, xk, tbl, tb);
         [[maybe_unused]] MizCellOut o_even;                           // SAVE: the pair's first cell waits for its second
         [[maybe_unused]] bool v_even = false;
 #pragma unroll
         for (int i = 0; i < C; ++i) {
             __builtin_amdgcn_sched_barrier(0);                         // one cell at a time: bounded live ranges
             const int k = (int)kl + i;
-            const double tbm = i > 0 ? tb[i > 0 ? i - 1 : 0] : tbl;
-            const double tbp = i < C - 1 ? tb[i < C - 1 ? i + 1 : i] : tbr;
-            const double xp = i < C - 1 ? xk[i < C - 1 ? i + 1 : i] : xr;
             const double S = insolation(p, xk[i], ct);
             double dif;
             if constexpr (IMEX) {
                 dif = difx[IMEX ? i : 0];
-            } else if (GRID == 0) {
+            } else {
                 // the three diagonals of the cell's pair arrive with its first cell (16-byte loads, L2 hits), not all
                 // twelve words before the loop
-                if ((i & 1) == 0) {
+                if (GRID == 0 && (i & 1) == 0) {
                     const double2 q0 = *reinterpret_cast<const double2 *>(geom + G_LO * a.gstride + (kl + i));
                     const double2 q1 = *reinterpret_cast<const double2 *>(geom + G_DI * a.gstride + (kl + i));
                     const double2 q2 = *reinterpret_cast<const double2 *>(geom + G_UP * a.gstride + (kl + i));
@@ -1486,14 +1460,8 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
                     g1[GRID == 0 ? i : 0] = q1.x;  g1[GRID == 0 ? i + 1 : 0] = q1.y;
                     g2[GRID == 0 ? i : 0] = q2.x;  g2[GRID == 0 ? i + 1 : 0] = q2.y;
                 }
-                dif = diffusion_uniform(k, nlat, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0], g2[GRID == 0 ? i : 0],
-                                        tbm, tb[i], tbp);
-            } else {
-                double xxr;
-                const double Fr = interface_flux(k + 1, nlat, xk[i], xp, tb[i], tbp, xxr);
-                dif = 0.0 + ieee_div(p.D * (Fr - Fl), xxr - xxl);         // :524
-                Fl = Fr;
-                xxl = xxr;
+                dif = stencil.dif(p, i, kl, nlat, xk, xr, tb, tbl, tbr, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
+                                  g2[GRID == 0 ? i : 0]);
             }
             const double tw = water_temperature(p, sEw(i), ph[i]);      // and a third time: one division, no register
             const MizCellOut o = miz_cell_update(p, f, S, xk[i], dif, tb[i], sEi(i), sEw(i), sh(i),
@@ -1506,7 +1474,9 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
             ph[i] = valid ? o.q[Q_phi] : 0.0;
             if (diag) {
                 // last step of the run only (wave-uniform base + the per-step opaque 32-bit cell index: no per-lane
-                // 64-bit addresses for the compiler to hoist out of the step loop and keep in registers)
+                // 64-bit addresses for the compiler to hoist out of the step loop and keep in registers; kept out of a
+                // helper shared with miz_fused_kernel: in one, it changes how hipcc peels this kernel's first Newton
+                // iteration)
                 (st + S_n * a.fstride)[kl + i] = valid ? o.q[Q_n] : 0.0;
                 (st + S_E * a.fstride)[kl + i] = valid ? o.q[Q_E] : 0.0;
                 (st + S_T * a.fstride)[kl + i] = valid ? o.q[Q_T] : 0.0;
@@ -1547,11 +1517,7 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
         store_chunk<C>(st + S_phi * a.fstride, ph, ke, nlat);
         cmask[tl] = (unsigned short)smask;
     }
-    if (ts == 0 && a.counters) {
-        unsigned long long *cnt = a.counters + 2 * (col % kCounterShards);
-        atomicAdd(cnt, (unsigned long long)nit);
-        if (nfail) atomicAdd(cnt + 1, (unsigned long long)nfail);
-    }
+    count_newton(a, col, ts, nit, nfail);
 }
 #undef sEi
 #undef sEw
@@ -2151,34 +2117,32 @@ LaunchCfg choose_launch(int nlat, int cells_requested) {
 
 namespace {
 
-// Every workgroup size is compiled as a constant: T = 64 ... 1024 in steps of one wave (two cells per
-// thread: 64 ... 512, and 768 for every meridian of 1025 ... 1536 cells).
+// Every workgroup size is compiled as a constant: T = 64 ... 1024 in steps of one wave (two cells per thread: 64 ... 512,
+// and 768 for every meridian of 1025 ... 1536 cells).  A list of sizes is a type; kernel_for(sizes, threads, pick) returns
+// pick's instantiation for `threads`, nullptr if the list lacks it.
+template <int... TT> struct Sizes {};
+template <int... A, int... B> constexpr Sizes<A..., B...> operator+(Sizes<A...>, Sizes<B...>) { return {}; }
+#ifdef EBM_QUICK   // development builds (tests/tools/resource_usage.py -DEBM_QUICK): four sizes only
+constexpr Sizes<64, 256, 512> kUpTo512;
+constexpr Sizes<1024> kAbove512;
+#else
+constexpr Sizes<64, 128, 192, 256, 320, 384, 448, 512> kUpTo512;
+constexpr Sizes<576, 640, 704, 768, 832, 896, 960, 1024> kAbove512;
+#endif
+constexpr Sizes<768> kTwoCellsAbove512;   // two cells per thread, 1024 < nlat <= kMaxLat2: always 768 threads (choose_launch)
+template <int TT> struct Threads { static constexpr int value = TT; };
+template <typename Pick, int... TT>
+KernelFn kernel_for(Sizes<TT...>, int threads, Pick pick) {
+    KernelFn fn = nullptr;
+    ((fn = threads == TT ? pick(Threads<TT>()) : fn), ...);
+    return fn;
+}
+
 template <int C, int GRID, int OUT, bool IMEX>
-[[maybe_unused]] KernelFn miz_kernel_for(int threads) {
-    switch (threads) {
-#define EBM_CASE(TT) case TT: return miz_step_kernel<C, GRID, OUT, TT, IMEX>;
-#ifdef EBM_QUICK   // development builds (tests/tools/resource_usage.py -DEBM_QUICK): three sizes only
-        EBM_CASE(64) EBM_CASE(256) EBM_CASE(512)
-#else
-        EBM_CASE(64) EBM_CASE(128) EBM_CASE(192) EBM_CASE(256) EBM_CASE(320) EBM_CASE(384) EBM_CASE(448) EBM_CASE(512)
-#endif
-        default: break;
-    }
-    if constexpr (C == 2) {        // 1024 < nlat <= kMaxLat2: always 768 threads (choose_launch)
-        if (threads == 768) return miz_step_kernel<C, GRID, OUT, 768, IMEX>;
-    }
-    if constexpr (C == 4) {
-        switch (threads) {
-#ifdef EBM_QUICK
-            EBM_CASE(1024)
-#else
-            EBM_CASE(576) EBM_CASE(640) EBM_CASE(704) EBM_CASE(768) EBM_CASE(832) EBM_CASE(896) EBM_CASE(960) EBM_CASE(1024)
-#endif
-            default: break;
-        }
-    }
-#undef EBM_CASE
-    return nullptr;
+KernelFn miz_kernel_for(int threads) {
+    auto pick = [](auto tt) -> KernelFn { return miz_step_kernel<C, GRID, OUT, decltype(tt)::value, IMEX>; };
+    if constexpr (C == 4) return kernel_for(kUpTo512 + kAbove512, threads, pick);
+    else return kernel_for(kUpTo512 + kTwoCellsAbove512, threads, pick);
 }
 template <int C, int GRID, bool IMEX>
 [[maybe_unused]] KernelFn miz_step_by_mode(int mode, int threads) {
@@ -2188,6 +2152,22 @@ template <int C, int GRID, bool IMEX>
         case OUT_SAVE: return miz_kernel_for<C, GRID, OUT_SAVE, IMEX>(threads);
         default: return nullptr;
     }
+}
+// every size for both models: the extension has no other fused kernel; the reference's step where the register kernel ends
+// (more than kFusedRegThreads threads) and, below that, where the handle prefers occupancy over latency; integrate (SAVE)
+// has no other fused kernel at four cells per thread
+template <int GRID, bool IMEX, bool SAVE>
+KernelFn miz_resident_for(int threads) {
+    return kernel_for(kUpTo512 + kAbove512, threads,
+                      [](auto tt) -> KernelFn { return miz_resident_kernel<GRID, decltype(tt)::value, IMEX, SAVE>; });
+}
+// the register kernel: 768 threads at two cells per thread (166 VGPRs: three waves per SIMD = kFusedRegThreads2 threads),
+// but not with the sums (SAVE: 144 B of scratch at its three waves per SIMD; ebm_integrate keeps one launch per step there)
+template <int C, int GRID, bool SAVE = false>
+KernelFn miz_fused_for(int threads) {
+    auto pick = [](auto tt) -> KernelFn { return miz_fused_kernel<C, GRID, decltype(tt)::value, SAVE>; };
+    if constexpr (C == 2 && !SAVE) return kernel_for(kUpTo512 + kTwoCellsAbove512, threads, pick);
+    else return kernel_for(kUpTo512, threads, pick);
 }
 
 }  // namespace
@@ -2210,71 +2190,19 @@ KernelFn miz_step_kernels_imex(int grid_kind, int mode, int threads) {        //
 #endif
 
 #ifdef EBM_PART_LOOP
-namespace {
-// every size for both models: the extension has no other fused kernel; the reference's step where the register kernel ends
-// (more than kFusedRegThreads threads) and, below that, where the handle prefers occupancy over latency
-template <int GRID, bool IMEX>
-KernelFn miz_resident_for(int threads) {
-    switch (threads) {
-#define EBM_CASE(TT) case TT: return miz_resident_kernel<GRID, TT, IMEX>;
-#ifdef EBM_QUICK
-        EBM_CASE(64) EBM_CASE(256) EBM_CASE(512) EBM_CASE(1024)
-#else
-        EBM_CASE(64) EBM_CASE(128) EBM_CASE(192) EBM_CASE(256) EBM_CASE(320) EBM_CASE(384) EBM_CASE(448) EBM_CASE(512)
-        EBM_CASE(576) EBM_CASE(640) EBM_CASE(704) EBM_CASE(768) EBM_CASE(832) EBM_CASE(896) EBM_CASE(960) EBM_CASE(1024)
-#endif
-        default: break;
-    }
-#undef EBM_CASE
-    return nullptr;
-}
-}  // namespace
 KernelFn miz_resident_kernels(int grid_kind, int threads, bool imex) {
-    if (imex) return grid_kind == 0 ? miz_resident_for<0, true>(threads) : miz_resident_for<1, true>(threads);
-    return grid_kind == 0 ? miz_resident_for<0, false>(threads) : miz_resident_for<1, false>(threads);
+    if (imex) return grid_kind == 0 ? miz_resident_for<0, true, false>(threads) : miz_resident_for<1, true, false>(threads);
+    return grid_kind == 0 ? miz_resident_for<0, false, false>(threads) : miz_resident_for<1, false, false>(threads);
 }
 #endif
 
 #ifdef EBM_PART_LOOPSAVE
-namespace {
-template <int GRID, bool IMEX>
-KernelFn miz_resident_save_for(int threads) {              // every size: integrate has no other fused kernel
-    switch (threads) {
-#define EBM_CASE(TT) case TT: return miz_resident_kernel<GRID, TT, IMEX, true>;
-#ifdef EBM_QUICK
-        EBM_CASE(64) EBM_CASE(256) EBM_CASE(512) EBM_CASE(1024)
-#else
-        EBM_CASE(64) EBM_CASE(128) EBM_CASE(192) EBM_CASE(256) EBM_CASE(320) EBM_CASE(384) EBM_CASE(448) EBM_CASE(512)
-        EBM_CASE(576) EBM_CASE(640) EBM_CASE(704) EBM_CASE(768) EBM_CASE(832) EBM_CASE(896) EBM_CASE(960) EBM_CASE(1024)
-#endif
-        default: break;
-    }
-#undef EBM_CASE
-    return nullptr;
-}
-}  // namespace
 KernelFn miz_resident_save_kernels(int grid_kind, int threads, bool imex) {
-    if (imex) return grid_kind == 0 ? miz_resident_save_for<0, true>(threads) : miz_resident_save_for<1, true>(threads);
-    return grid_kind == 0 ? miz_resident_save_for<0, false>(threads) : miz_resident_save_for<1, false>(threads);
+    if (imex) return grid_kind == 0 ? miz_resident_for<0, true, true>(threads) : miz_resident_for<1, true, true>(threads);
+    return grid_kind == 0 ? miz_resident_for<0, false, true>(threads) : miz_resident_for<1, false, true>(threads);
 }
-namespace {
-template <int GRID>
-KernelFn miz_fused2_save_for(int threads) {
-    switch (threads) {
-#define EBM_CASE(TT) case TT: return miz_fused_kernel<2, GRID, TT, true>;
-#ifdef EBM_QUICK
-        EBM_CASE(64) EBM_CASE(256) EBM_CASE(512)
-#else
-        EBM_CASE(64) EBM_CASE(128) EBM_CASE(192) EBM_CASE(256) EBM_CASE(320) EBM_CASE(384) EBM_CASE(448) EBM_CASE(512)
-#endif
-        default: break;       // (not 768 threads — meridians of 1025 ... 1536 cells: 144 B of scratch at its three waves per SIMD;
-    }                         //  ebm_integrate keeps one launch per step there)
-#undef EBM_CASE
-    return nullptr;
-}
-}  // namespace
 KernelFn miz_fused2_save_kernels(int grid_kind, int threads) {     // two cells per thread: the register kernel with the sums
-    return grid_kind == 0 ? miz_fused2_save_for<0>(threads) : miz_fused2_save_for<1>(threads);
+    return grid_kind == 0 ? miz_fused_for<2, 0, true>(threads) : miz_fused_for<2, 1, true>(threads);
 }
 #endif
 
@@ -2285,23 +2213,6 @@ namespace {
 // bits, so the choice is free to depend on the column count (LaunchCfg::fused_in_lds, set by the runtime)
 bool fused_state_in_lds(const LaunchCfg &cfg, bool imex) {
     return imex || (cfg.cells == 4 && (cfg.threads > kFusedRegThreads || cfg.fused_in_lds));
-}
-template <int C, int GRID>
-KernelFn miz_fused_for(int threads) {
-    switch (threads) {
-#define EBM_CASE(TT) case TT: return miz_fused_kernel<C, GRID, TT>;
-#ifdef EBM_QUICK
-        EBM_CASE(64) EBM_CASE(256) EBM_CASE(512)
-#else
-        EBM_CASE(64) EBM_CASE(128) EBM_CASE(192) EBM_CASE(256) EBM_CASE(320) EBM_CASE(384) EBM_CASE(448) EBM_CASE(512)
-#endif
-        default: break;
-    }
-    if constexpr (C == 2) {        // 166 VGPRs: three waves per SIMD = kFusedRegThreads2 threads
-        if (threads == 768) return miz_fused_kernel<C, GRID, 768>;
-    }
-#undef EBM_CASE
-    return nullptr;
 }
 KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
     const int cells = cfg.cells, threads = cfg.threads;

@@ -42,7 +42,8 @@ MUTANTS = [
     ("active_set_includes_melting_point", "snew |= (xs[i] < 0.0) ? (1u << i) : 0u;", "snew |= (xs[i] <= 0.0) ? (1u << i) : 0u;"),
     ("active_rows_ignore_concentration", "g[i] = ((smask >> i) & 1u) ? ph[i] : 0.0;", "g[i] = ((smask >> i) & 1u) ? 1.0 : 0.0;"),
     ("classic_ocean_heat_flux_sign", "Ek = Ek + p.dt * (Cc - p.M * Tk + p.Fb);", "Ek = Ek + p.dt * (Cc - p.M * Tk - p.Fb);"),
-    ("extension_matrix_diagonal_sign", "rb[i] = 1.0 + p.theta_imex * (tlo[i] + tup[i]);", "rb[i] = 1.0 - p.theta_imex * (tlo[i] + tup[i]);"),
+    # (merged with resident_extension_matrix_diagonal_sign: the step and the resident kernel share imex_row)
+    ("extension_matrix_diagonal_sign", "rb = 1.0 + p.theta_imex * (lo + up);", "rb = 1.0 - p.theta_imex * (lo + up);"),
     # third batch: the host runtime (tables, time bookkeeping, savesol!) and the small kernels; a 4-tuple names the file
     ("uniform_table_metric_linear", "lam[i - 1] = (1.0 - xb * xb) / (dx * dx);", "lam[i - 1] = (1.0 - xb) / (dx * dx);", "ebm_runtime.hip"),
     ("polar_ghost_cell_misplaced", "double xp = k < nx - 1 ? x[k + 1] : 2.0 - x[nx - 1];", "double xp = k < nx - 1 ? x[k + 1] : 1.0 - x[nx - 1];", "ebm_runtime.hip"),
@@ -62,7 +63,7 @@ MUTANTS = [
     ("running_sum_drops_every_second_cell", "s.y = s.y + x1;", "s.y = s.y + x0;"),
     ("snapshot_ring_ignores_its_offset", "EBM_STORE2(a.stage + (size_t)v * a.stage_var_stride + a.stage_offset + col_off + kp, d);",
      "EBM_STORE2(a.stage + (size_t)v * a.stage_var_stride + col_off + kp, d);"),
-    ("extension_lower_diagonal_sign", "ra[i] = -(p.theta_imex * tlo[i]);", "ra[i] = (p.theta_imex * tlo[i]);"),
+    ("extension_lower_diagonal_sign", "ra = -(p.theta_imex * lo);", "ra = (p.theta_imex * lo);"),
     ("classic_ghost_layer_uses_this_steps_sun", "const double S_ip1 = Sb[i] - (p.S1 * ct_next) * xk[i];", "const double S_ip1 = Sb[i] - (p.S1 * ct) * xk[i];"),
     # fifth batch: the solver's own algebra, the store paths of the two launch geometries, the iteration's control flow
     ("column_offsets_all_take_the_first", "double f = a.fcol ? ft + a.fcol[col] : ft;", "double f = a.fcol ? ft + a.fcol[0] : ft;"),
@@ -104,7 +105,6 @@ MUTANTS = [
     # seventh batch: the LDS-resident fused-K kernel, its compact solve, its halo exchange and its vote
     ("resident_diagnostics_of_the_first_step", "const bool diag = a.write_diag != 0 && step + 1 == nloop;", "const bool diag = a.write_diag != 0 && step == 0;"),
     ("resident_newton_stops_after_one_iteration", "} while (it < kMaxNewton && again);", "} while (false);"),
-    ("resident_extension_matrix_diagonal_sign", "rb[i] = 1.0 + p.theta_imex * (qlo[i] + qup[i]);", "rb[i] = 1.0 - p.theta_imex * (qlo[i] + qup[i]);"),
     ("resident_floe_size_not_written_back", "            sD(i) = valid ? o.q[Q_D] : 0.0;\n", ""),
     ("resident_vote_reads_only_the_first_wave", "for (int w = 0; w < TT / 64; ++w) any |= F[w];", "for (int w = 0; w < 1; ++w) any |= F[w];"),
     ("wave_halo_takes_its_own_edge", "const double pl = E[w > 0 ? w - 1 : 0],", "const double pl = E[w],"),
