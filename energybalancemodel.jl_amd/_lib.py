@@ -26,7 +26,7 @@ EXPORTS = (
     "ebm_create", "ebm_create_ex", "ebm_options_default", "ebm_field_step", "ebm_get_field_as_of", "ebm_destroy", "ebm_last_error", "ebm_version", "ebm_set_field",
     "ebm_get_field", "ebm_hemispheric_mean", "ebm_hemispheric_mean_device", "ebm_get_field_device",
     "ebm_field_device_ptr", "ebm_diffusion", "ebm_zonal_diffusion", "ebm_set_column_forcing", "ebm_set_column_schedule",
-    "ebm_set_column_params",
+    "ebm_set_column_params", "ebm_set_column_noise", "ebm_get_noise_state", "ebm_set_noise_state", "ebm_noise_innovations",
     "ebm_set_step_clock", "ebm_set_time_table",
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_integrate", "ebm_integrate_hemispheric",
     "ebm_equilibrate", "ebm_sync", "ebm_get_counters",
@@ -98,6 +98,10 @@ def load():
     lib.ebm_set_column_forcing.argtypes = [C.c_void_p, _dp]
     lib.ebm_set_column_schedule.argtypes = [C.c_void_p, _dp]
     lib.ebm_set_column_params.argtypes = [C.c_void_p, _dp]
+    lib.ebm_set_column_noise.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_ulonglong), C.c_ulonglong]
+    lib.ebm_get_noise_state.argtypes = [C.c_void_p, _dp]
+    lib.ebm_set_noise_state.argtypes = [C.c_void_p, _dp]
+    lib.ebm_noise_innovations.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp]
     lib.ebm_set_step_clock.argtypes = [C.c_void_p, C.c_longlong]
     lib.ebm_set_time_table.argtypes = [C.c_void_p, C.c_int, _dp]
     lib.ebm_step.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]

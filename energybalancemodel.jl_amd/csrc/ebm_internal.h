@@ -67,6 +67,14 @@ enum GeomTable { G_X = 0, G_0, G_1, G_2, G_3, G_4, G_LO, G_DI, G_UP, G_KSUB, G_K
 // `slot` of a small device table that the host refills before every replay.
 struct StepSched {
     double ct, ct_next, ft, tyear;
+    long long n;                     // 0-based global index of the step (the noise's counter; tyear is year_time(n))
+};
+
+// Per-column AR(1) forcing noise (ebm_set_column_noise, include/ebm_hip.h): s = sigma*sqrt(1 - rho^2), the lag-one
+// autocorrelation rho and the column's stream id.  One record per column, read with scalar loads.
+struct NoiseRec {
+    double s, rho;
+    unsigned long long stream;
 };
 
 struct StepArgs {
@@ -100,6 +108,13 @@ struct StepArgs {
     unsigned long long *stamps;      // diagnostic builds only (EBM_STAMPS), else nullptr
     const int *cols;                 // active columns (ebm_equilibrate): workgroup b steps column cols[col0 + b]; nullptr =
                                      // identity.  Read by the fused-K kernels and the classic kernel only.
+    // forcing noise (ebm_set_column_noise): nullptr = none, and every kernel takes the noise-free path
+    const NoiseRec *noise;           // [ncol]
+    double *nstate;                  // N_c [ncol]: read once per workgroup before its first barrier, written back by one
+                                     // thread after its last
+    double *nseq;                    // [ncol][kNoiseMaxFused]: N_c after each step of a fused launch (ColumnNoise, MEM)
+    unsigned long long seed;
+    long long step;                  // global index of the step of a one-step launch without sched (with sched: sched[slot].n)
 };
 
 struct LaunchCfg {
@@ -114,6 +129,7 @@ struct LaunchCfg {
 };
 
 constexpr int kCounterShards = 64;
+constexpr int kNoiseMaxFused = 64; // with forcing noise, fused launches take at most one wave's lanes of steps (ColumnNoise)
 constexpr int kSchedWords = 9;     // base, peak, cool, rate up, rate down, domain[1..4]
 constexpr int kMaxNewton = 1000;   // the cap of the T0 iteration: NonlinearSolve's default maxiters (src/miz.jl:55-60 passes none)
 
@@ -192,6 +208,10 @@ hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t
 // the next active list: out = the entries of in[0 .. n) whose column is not frozen, in order; *count = their number
 // (one workgroup)
 hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s);
+// ebm_noise_innovations: out[c][i] = xi(seed, noise[c].stream, first + i), c < ncol, i < nsteps, by the function the step
+// kernels call
+hipError_t launch_noise_innovations(const NoiseRec *noise, unsigned long long seed, long long first, int nsteps, int ncol,
+                                    double *out, hipStream_t s);
 // natural <-> pair-split layout of whole fields ([ncol][pitch], 4 cells per thread; a no-op with 2), in place
 hipError_t launch_split_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                hipStream_t s);

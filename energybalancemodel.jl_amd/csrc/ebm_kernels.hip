@@ -223,6 +223,117 @@ __device__ __forceinline__ double column_forcing(const StepArgs &a, int col, dou
     return f;
 }
 
+// ---- forcing noise (ebm_set_column_noise; THE DEFINITION is in include/ebm_hip.h) ----------------------------------
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011; the Random123 constants): ten rounds, the key bumped between rounds.
+// The operands are wave-uniform in the step kernels: scalar integer arithmetic.
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0;
+        c[1] = lo1;
+        c[2] = n2;
+        c[3] = lo0;
+    }
+}
+// xi(seed, stream, n): the standard normal innovation of global step n (two 53-bit uniforms, Box-Muller's first output).
+// The one definition: the step kernels and noise_innovations_kernel (ebm_noise_innovations) call it.
+__device__ __forceinline__ double noise_innovation(unsigned long long seed, unsigned long long stream, long long n) {
+    const unsigned long long un = (unsigned long long)n;
+    unsigned w[4] = {(unsigned)un, (unsigned)(un >> 32), (unsigned)stream, (unsigned)(stream >> 32)};
+    philox4x32_10(w, (unsigned)seed, (unsigned)(seed >> 32));
+    const unsigned long long ia = ((unsigned long long)w[0] << 21) | (w[1] >> 11);
+    const unsigned long long ib = ((unsigned long long)w[2] << 21) | (w[3] >> 11);
+    const double u1 = (double)(ia + 1) * 0x1p-53, u2 = (double)ib * 0x1p-53;     // (0, 1] and [0, 1), exact
+    return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+__device__ __forceinline__ double uniform_double(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// A column's noise inside a step kernel (only touched when a.noise is set).  load() runs before the workgroup's first
+// barrier and store() — thread 0, an ordinary store — after its last: another wave's write-back of N_c can then never
+// overtake this wave's read.  N_c <- rho*N_c + s*xi once per step (two products and a sum, no contraction).
+struct ColumnNoise {
+    double s, rho, N;
+    unsigned long long stream;
+    double Nv;                       // fused launches: lane l holds N_c after step l of the launch
+    __device__ __forceinline__ void load(const StepArgs &a, int col) {
+        typedef const __attribute__((address_space(4))) NoiseRec ConstNoise;     // never written by a kernel
+        ConstNoise &r = *reinterpret_cast<ConstNoise *>(reinterpret_cast<uintptr_t>(a.noise + col));
+        s = r.s;
+        rho = r.rho;
+        stream = r.stream;
+        N = uniform_double(a.nstate[col]);                                        // written by kernels: a plain load
+        Nv = 0.0;
+    }
+    __device__ __forceinline__ double advance(double xi) {
+        N = rho * N + s * xi;
+        return N;
+    }
+    __device__ __forceinline__ void store(const StepArgs &a, int col) const {
+        if (threadIdx.x == 0) a.nstate[col] = N;
+    }
+    // Fused launches (a.nfused <= kNoiseMaxFused, the runtime's cap): the launch's innovations are independent of each
+    // other, so lane l evaluates that of step l — one evaluation's latency per launch instead of one per step — and the
+    // recurrence then runs over the lanes in step order (wave-uniform): lane l ends with N_c after step l.  The step loop
+    // only reads N_c of its step.  Where it is held (MEM, a kernel template argument):
+    //   registers  (miz_fused_kernel up to kFusedRegThreads threads: the latency-bound shapes) every wave of the
+    //              workgroup runs this at the start of the launch, before the state is loaded, and keeps Nv (two VGPRs);
+    //   memory     (every other fused-K kernel: their register budgets are spent) noise_sequence_kernel runs it before the
+    //              launch, into the column's row of a.nseq, and also advances N_c; the step reads entry `step` of the
+    //              row beside the step's other table loads, and the kernel touches no other noise word.
+    // -DEBM_NOISE_SERIAL (A/B timing builds only, profiles/r07_noise_cost.txt): the register kernels evaluate every step's
+    // innovation inside the loop instead, on the scalar path (this spills registers).
+    __device__ __forceinline__ double sequence(const StepArgs &a, int nloop) {
+        const int l = (int)(threadIdx.x & 63u);
+        const double xi = l < nloop ? noise_innovation(a.seed, stream, a.sched[a.slot + l].n) : 0.0;
+        double n = N, nl = 0.0;
+        for (int i = 0; i < nloop; ++i) {
+            n = rho * n + s * __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xi), i),
+                                               __builtin_amdgcn_readlane(__double2loint(xi), i));
+            nl = l == i ? n : nl;
+        }
+        N = n;
+        return nl;
+    }
+    __device__ __forceinline__ void prepare_launch(const StepArgs &a, int nloop) {
+#ifndef EBM_NOISE_SERIAL
+        Nv = sequence(a, nloop);
+#else
+        (void)a;
+        (void)nloop;
+#endif
+    }
+    template <bool MEM>
+    __device__ __forceinline__ double at_step(const StepArgs &a, int col, int step, long long n) {
+        if constexpr (MEM) {
+            // (the column made opaque: the row's address is formed at every step, not kept across the step loop)
+            int c = col;
+            asm volatile("" : "+s"(c));
+            return uniform_double(a.nseq[(size_t)c * kNoiseMaxFused + step]);
+        }
+#ifndef EBM_NOISE_SERIAL
+        (void)n;
+        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(Nv), step),
+                                __builtin_amdgcn_readlane(__double2loint(Nv), step));
+#else
+        (void)step;
+        return advance(noise_innovation(a.seed, stream, n));
+#endif
+    }
+};
+// The forcing of a one-step launch (global step n): column_forcing, plus N_c after its update if the handle has noise
+__device__ __forceinline__ double step_forcing(const StepArgs &a, ColumnNoise &nz, int col, double ft, double tyear, long long n) {
+    const double f = column_forcing(a, col, ft, tyear);
+    return a.noise ? f + nz.advance(noise_innovation(a.seed, nz.stream, n)) : f;
+}
+
 // ---- chunk loads / stores: 8*C contiguous bytes per lane, 16-byte accesses ------------------
 // `f` is a wave-uniform base (kept in SGPRs), `k0` the lane's first cell: the access compiles to
 // the saddr + voffset form, so no per-lane 64-bit pointers are kept alive.
@@ -848,7 +959,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     unsigned short *const cmask = a.amask + (size_t)col * T;            // wave-uniform
     const double ct = a.sched ? a.sched[a.slot].ct : a.ct;              // per-step scalars (scalar loads)
     const double ft = a.sched ? a.sched[a.slot].ft : a.ft;
-    const double f = column_forcing(a, col, ft, a.sched ? a.sched[a.slot].tyear : a.tyear);
+    ColumnNoise nz;
+    if (a.noise) nz.load(a, col);
+    const double f = step_forcing(a, nz, col, ft, a.sched ? a.sched[a.slot].tyear : a.tyear, a.sched ? a.sched[a.slot].n : a.step);
     const bool diag = OUT == OUT_DIAG || (MAYDIAG && a.write_diag);
 
     // ---------------- phase A: loads, water temperature, T0-system coefficients ----------
@@ -1103,6 +1216,7 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         if (j < 2) EBM_STAMP(8 + j);
         if (j == 0) EBM_STAMPW(4);                        // per wave: first pair done
     }
+    if (a.noise) nz.store(a, col);                        // after the step's last barrier
     EBM_STAMP(15);
     EBM_STAMPW(6);                                        // per wave: stores issued
 }
@@ -1122,6 +1236,7 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     static_assert(!SAVE || C == 2, "the savesol! variant of the register kernel exists for two cells per thread");
     static_assert(C == 2 || C == 4, "cells per thread");
     constexpr int T = TT;
+    constexpr bool kNoiseMem = TT > kFusedRegThreads;                 // 168 VGPRs at three waves per SIMD: N_c in memory
     extern __shared__ double smem[];
     const int t = threadIdx.x, col = step_column(a);
     const int nlat = a.nlat;
@@ -1133,6 +1248,11 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;
     const double Tm = p.Tm;
+    ColumnNoise nz;
+    if (!kNoiseMem && a.noise) {                                       // before the state is loaded, and any barrier
+        nz.load(a, col);
+        nz.prepare_launch(a, a.nfused);
+    }
     unsigned short *const wmask = a.amask + (size_t)col * T + t;
     unsigned smask = *wmask;
     double Ei[C], Ew[C], hk[C], Dk[C], ph[C], xk[C], tlo[C], tup[C];
@@ -1159,7 +1279,8 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
             for (int i = 0; i < C; ++i) asm volatile("" : "+v"(xk[i]));
         }
         const double ct = sc.ct;
-        const double f = column_forcing(a, col, sc.ft, sc.tyear);
+        double f = column_forcing(a, col, sc.ft, sc.tyear);
+        if (a.noise) f = f + nz.at_step<kNoiseMem>(a, col, step, sc.n);
         const bool diag = a.write_diag && step == nloop - 1;
         // phase A
         double tw[C], dd[C], r[C], rd[C], xs[C];
@@ -1241,6 +1362,7 @@ __global__ void __launch_bounds__(TT) miz_fused_kernel(const StepArgs a) {
     store_chunk<C>(st + S_D * a.fstride, Dk, k0, nlat);
     store_chunk<C>(st + S_phi * a.fstride, ph, k0, nlat);
     *wmask = (unsigned short)smask;
+    if (!kNoiseMem && a.noise) nz.store(a, col);                        // after the launch's last barrier
     count_newton(a, col, t, nit, nfail);
 }
 
@@ -1297,6 +1419,7 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
     const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;
     const double Tm = p.Tm;
+    ColumnNoise nz;                                                    // N_c in memory (noise_sequence_kernel)
     unsigned short *const cmask = a.amask + (size_t)col * T;           // wave-uniform
     unsigned smask = cmask[t];
     double ph[C];
@@ -1328,7 +1451,8 @@ __global__ void __launch_bounds__(TT, (SAVE || TT <= 512) ? 4 : 1) miz_resident_
         const double ct = sc.ct;
         // (the column's forcing is the same in every lane: moved to SGPRs — the column offset and schedule are read
         // through plain pointers, i.e. by vector loads)
-        const double fv = column_forcing(a, col, sc.ft, sc.tyear);
+        double fv = column_forcing(a, col, sc.ft, sc.tyear);
+        if (a.noise) fv = fv + nz.at_step<true>(a, col, step, sc.n);
         const double f = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(fv)),
                                           __builtin_amdgcn_readfirstlane(__double2loint(fv)));
         const bool diag = a.write_diag != 0 && step + 1 == nloop;
@@ -1544,6 +1668,8 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
     ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
     const double *const geom = a.geom + pset * a.set_stride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;          // wave-uniform
+    ColumnNoise nz;                                                    // LOOP: N_c in memory (noise_sequence_kernel)
+    if (!LOOP && a.noise) nz.load(a, col);                             // before the state is loaded, and any barrier
     double E[C], Tg[C];
     load_chunk<C>(st + C_E * a.fstride, k0, E);
     load_chunk<C>(st + C_Tg * a.fstride, k0, Tg);
@@ -1564,7 +1690,11 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
         const double ct = a.sched ? a.sched[slot].ct : a.ct;
         const double ct_next = a.sched ? a.sched[slot].ct_next : a.ct_next;
         const double ft = a.sched ? a.sched[slot].ft : a.ft;
-        const double f = column_forcing(a, col, ft, a.sched ? a.sched[slot].tyear : a.tyear);
+        double f = column_forcing(a, col, ft, a.sched ? a.sched[slot].tyear : a.tyear);
+        if (a.noise) {
+            if constexpr (LOOP) f = f + nz.at_step<true>(a, col, step, a.sched[slot].n);
+            else f = f + nz.advance(noise_innovation(a.seed, nz.stream, a.sched ? a.sched[slot].n : a.step));
+        }
         double b[C], d[C], oT[C], oh[C], xs[C];
 #pragma unroll
         for (int i = 0; i < C; ++i) {
@@ -1612,6 +1742,7 @@ __global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
         // next solve first writes each thread's own words of P1 — which nobody reads after that last barrier — and passes
         // a barrier of its own before anything is written to P0)
     }
+    if (!LOOP && a.noise) nz.store(a, col);                            // after the solve's last barrier
 }
 
 #ifdef EBM_PART_MAIN
@@ -1624,6 +1755,40 @@ __global__ void mask_from_t0_kernel(const StepArgs a, int C) {
     for (int i = 0; i < C; ++i)
         if (t * C + i < a.nlat && T0[i] < Tm) m |= 1u << i;
     a.amask[(size_t)col * T + t] = (unsigned short)m;
+}
+
+// ebm_noise_innovations: one thread per (column, step), through the step kernels' noise_innovation
+__global__ void __launch_bounds__(256) noise_innovations_kernel(const NoiseRec *__restrict__ noise, unsigned long long seed,
+                                                                long long first, int nsteps, long long total,
+                                                                double *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long c = i / nsteps, k = i - c * nsteps;
+    out[i] = noise_innovation(seed, noise[c].stream, first + k);
+}
+// The N_c sequence of a fused launch for the kernels that read it from memory (ColumnNoise, MEM): one wave per column, lane l
+// -> a.nseq[col][l] = N_c after step l of the launch; N_c advanced by the launch's a.nfused steps
+__global__ void __launch_bounds__(64) noise_sequence_kernel(const StepArgs a) {
+    const int col = step_column(a);
+    ColumnNoise nz;
+    nz.load(a, col);
+    const double nl = nz.sequence(a, a.nfused);
+    if ((int)threadIdx.x < a.nfused) a.nseq[(size_t)col * kNoiseMaxFused + threadIdx.x] = nl;
+    nz.store(a, col);
+}
+hipError_t launch_noise_sequence(const StepArgs &a, int first, int count, hipStream_t s) {
+    if (first < 0 || count < 1 || a.nfused < 1 || a.nfused > kNoiseMaxFused) return hipErrorInvalidValue;
+    StepArgs b = a;
+    b.col0 = first;
+    noise_sequence_kernel<<<dim3(count), 64, 0, s>>>(b);
+    return hipGetLastError();
+}
+hipError_t launch_noise_innovations(const NoiseRec *noise, unsigned long long seed, long long first, int nsteps, int ncol,
+                                    double *out, hipStream_t s) {
+    const long long total = (long long)nsteps * ncol;
+    if (total <= 0) return hipSuccess;
+    noise_innovations_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, s>>>(noise, seed, first, nsteps, total, out);
+    return hipGetLastError();
 }
 
 // rcp_dt / rcp_cdn of the parameter block, with the device's own refinement sequence (see Params)
@@ -2280,6 +2445,14 @@ hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const Lau
                            hipStream_t s) {
     KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex);
     if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
+    // fused launches whose kernel reads N_c from memory: everything but miz_fused_kernel up to kFusedRegThreads threads
+    const bool fused = mode == OUT_LOOP || mode == OUT_LOOP_SAVE;
+    const bool in_registers = !fused_state_in_lds(cfg, imex) && cfg.threads <= kFusedRegThreads &&
+                              !(mode == OUT_LOOP_SAVE && cfg.cells == 4);
+    if (a.noise && fused && !in_registers) {
+        hipError_t e = launch_noise_sequence(a, first, count, s);
+        if (e != hipSuccess) return e;
+    }
     StepArgs b = a;
     b.col0 = first;
     fn<<<dim3(count), dim3(cfg.threads), miz_lds_bytes(cfg, mode, imex), s>>>(b);
@@ -2289,6 +2462,10 @@ hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const Lau
 hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s) {
     KernelFn fn = classic_kernel(cfg.cells, mode);
     if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
+    if (a.noise && mode == OUT_LOOP) {                  // the fused classic kernel reads N_c from memory
+        hipError_t e = launch_noise_sequence(a, first, count, s);
+        if (e != hipSuccess) return e;
+    }
     StepArgs b = a;
     b.col0 = first;
     fn<<<dim3(count), dim3(cfg.threads), sizeof(double) * 6 * (size_t)cfg.threads, s>>>(b);

@@ -67,6 +67,11 @@ struct ebm_ctx {
     double *field[EBM_F_COUNT] = {nullptr};        // views into the slab (null: not in this model)
     double *fcol = nullptr;
     double *fsched = nullptr;                      // per-column Forcing schedules
+    // ebm_set_column_noise: the per-column records, the AR(1) state N_c (null: no noise) and the seed
+    ebm::NoiseRec *noise = nullptr;
+    double *nstate = nullptr;
+    double *nseq = nullptr;                        // [ncol][kNoiseMaxFused], the fused kernels' per-launch N_c sequence
+    unsigned long long seed = 0;
     long long clock = 0;                           // global index of the next step (model time of ebm_step)
     unsigned long long *stamps = nullptr;          // diagnostic builds only
     int num_cus = 0;
@@ -383,7 +388,8 @@ hipError_t zonal_sweep(ebm_ctx *h, const double *T, double *outZ, double *outU) 
 ebm::StepArgs base_args(const ebm_ctx *h) {
     ebm::StepArgs a{};
     a.state = h->state; a.fstride = h->fstride; a.geom = h->geom; a.gstride = h->gstride;
-    a.fcol = h->fcol; a.fsched = h->fsched; a.p = h->p_dev; a.counters = h->counters; a.amask = h->amask;
+    a.fcol = h->fcol; a.fsched = h->fsched; a.p = h->p_dev;
+    a.noise = h->noise; a.nstate = h->nstate; a.nseq = h->nseq; a.seed = h->seed; a.counters = h->counters; a.amask = h->amask;
     if (h->nsets) {                  // per-column parameter sets (ebm_set_column_params)
         a.p = h->p_sets; a.geom = h->geom_sets; a.pset = h->pset_dev;
         a.set_stride = (long long)ebm::G_COUNT * h->gstride;
@@ -480,6 +486,7 @@ int do_step(ebm_ctx *h, double ct, double ct_next, double f, int write_diag, lon
     ebm::StepArgs a = base_args(h);
     a.ct = ct; a.ct_next = ct_next; a.ft = f; a.write_diag = write_diag;
     a.tyear = year_time(h, step);
+    a.step = step;
     int mode = write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE;
     if (save) {
         mode = ebm::OUT_SAVE;
@@ -731,6 +738,9 @@ int ebm_destroy(ebm_handle_t h) {
     if (h->amask) (void)hipFree(h->amask);
     if (h->fcol) (void)hipFree(h->fcol);
     if (h->fsched) (void)hipFree(h->fsched);
+    if (h->noise) (void)hipFree(h->noise);
+    if (h->nstate) (void)hipFree(h->nstate);
+    if (h->nseq) (void)hipFree(h->nseq);
     if (h->counters) (void)hipFree(h->counters);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -974,6 +984,85 @@ int ebm_set_column_schedule(ebm_handle_t h, const double *sched) {
     return EBM_OK;
 }
 
+int ebm_set_column_noise(ebm_handle_t h, const double *sigma, const double *rho, const unsigned long long *stream,
+                         unsigned long long seed) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_noise: null handle");
+    std::vector<ebm::NoiseRec> rec;
+    if (sigma) {
+        if (!rho) return fail(EBM_ERR_ARG, "ebm_set_column_noise: rho is null (pass zeros for white noise)");
+        rec.resize((size_t)h->ncol);
+        for (int c = 0; c < h->ncol; ++c) {
+            if (!(std::isfinite(sigma[c]) && sigma[c] >= 0.0))
+                return fail(EBM_ERR_ARG, "ebm_set_column_noise: sigma[" + std::to_string(c) + "] must be finite and >= 0");
+            if (!(std::isfinite(rho[c]) && rho[c] >= 0.0 && rho[c] < 1.0))
+                return fail(EBM_ERR_ARG, "ebm_set_column_noise: rho[" + std::to_string(c) + "] must lie in [0, 1)");
+            rec[c].s = sigma[c] * std::sqrt(1.0 - rho[c] * rho[c]);
+            rec[c].rho = rho[c];
+            rec[c].stream = stream ? stream[c] : (unsigned long long)c;
+        }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    if (!sigma) {
+        if (h->noise) HIPCHK(hipFree(h->noise));
+        if (h->nstate) HIPCHK(hipFree(h->nstate));
+        if (h->nseq) HIPCHK(hipFree(h->nseq));
+        h->noise = nullptr;
+        h->nstate = nullptr;
+        h->nseq = nullptr;
+        h->seed = 0;
+        return EBM_OK;
+    }
+    if (!h->noise) HIPCHK(hipMalloc(&h->noise, sizeof(ebm::NoiseRec) * (size_t)h->ncol));
+    if (!h->nstate) HIPCHK(hipMalloc(&h->nstate, sizeof(double) * (size_t)h->ncol));
+    if (!h->nseq) HIPCHK(hipMalloc(&h->nseq, sizeof(double) * ebm::kNoiseMaxFused * (size_t)h->ncol));
+    HIPCHK(hipMemcpy(h->noise, rec.data(), sizeof(ebm::NoiseRec) * (size_t)h->ncol, hipMemcpyHostToDevice));
+    const std::vector<double> zeros((size_t)h->ncol, 0.0);
+    HIPCHK(hipMemcpy(h->nstate, zeros.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+    h->seed = seed;
+    return EBM_OK;
+}
+
+int ebm_get_noise_state(ebm_handle_t h, double *N) {
+    if (!h || !N) return fail(EBM_ERR_ARG, "ebm_get_noise_state: bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    if (!h->nstate) {                            // no noise: N_c = 0
+        std::fill(N, N + h->ncol, 0.0);
+        return EBM_OK;
+    }
+    HIPCHK(hipMemcpy(N, h->nstate, sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost));
+    return EBM_OK;
+}
+
+int ebm_set_noise_state(ebm_handle_t h, const double *N) {
+    if (!h || !N) return fail(EBM_ERR_ARG, "ebm_set_noise_state: bad argument");
+    if (!h->nstate) return fail(EBM_ERR_ARG, "ebm_set_noise_state: no noise installed (ebm_set_column_noise)");
+    for (int c = 0; c < h->ncol; ++c)
+        if (!std::isfinite(N[c])) return fail(EBM_ERR_ARG, "ebm_set_noise_state: N[" + std::to_string(c) + "] is not finite");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(h->nstate, N, sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+    return EBM_OK;
+}
+
+int ebm_noise_innovations(ebm_handle_t h, long long first_step, int nsteps, double *out) {
+    if (!h || first_step < 0 || nsteps < 0 || (nsteps > 0 && !out)) return fail(EBM_ERR_ARG, "ebm_noise_innovations: bad argument");
+    if (!h->noise) return fail(EBM_ERR_ARG, "ebm_noise_innovations: no noise installed (ebm_set_column_noise)");
+    if (nsteps == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)h->ncol * (size_t)nsteps;
+    double *dev = nullptr;
+    HIPCHK(hipMalloc(&dev, sizeof(double) * n));
+    hipError_t e = ebm::launch_noise_innovations(h->noise, h->seed, first_step, nsteps, h->ncol, dev, main_stream(h));
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e == hipSuccess) e = hipMemcpy(out, dev, sizeof(double) * n, hipMemcpyDeviceToHost);
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_noise_innovations: ") + hipGetErrorString(e));
+    return EBM_OK;
+}
+
 int ebm_set_column_params(ebm_handle_t h, const double *params) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_params: null handle");
     const int np = EBM_P_COUNT;
@@ -1083,6 +1172,7 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
                 sched[i].ct_next = h->ttab[(ti + 1) % nt];
                 sched[i].ft = f_steps ? f_steps[s + i] : 0.0;
                 sched[i].tyear = year_time(h, first_step + s + i);
+                sched[i].n = first_step + s + i;
             }
             // pageable source: the copy is staged before the call returns, so `sched` can be refilled
             HIPCHK(hipMemcpyAsync(h->sched_dev, sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
@@ -1110,6 +1200,9 @@ static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, i
                        int steps_per_launch, const SaveTarget *save) {
     const long long first_step = clock_first;
     const long long nt = (long long)h->ttab.size();
+    // forcing noise: the kernels draw a launch's innovations one step per lane, so a launch takes at most kNoiseMaxFused
+    // steps (same bits, more launches)
+    if (h->noise) steps_per_launch = std::min(steps_per_launch, ebm::kNoiseMaxFused);
     std::vector<ebm::StepSched> sched;
     for (int s0 = 0; s0 < nsteps; s0 += kFusedTable) {
         const int n = std::min(kFusedTable, nsteps - s0);
@@ -1120,6 +1213,7 @@ static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, i
             sched[i].ct_next = h->ttab[(ti + 1) % nt];
             sched[i].ft = f_steps ? f_steps[s0 + i] : 0.0;
             sched[i].tyear = year_time(h, first_step + s0 + i);
+            sched[i].n = first_step + s0 + i;
         }
         // the table used two batches ago: its launches must have ended before it is refilled (normally long since).  The copy is
         // synchronous for the host but not ordered with the handle's (non-blocking) streams.
@@ -1378,6 +1472,9 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     if (h->fsched)
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: per-column forcing schedules are installed (a ramped forcing has no "
                                          "equilibrium; ebm_set_column_schedule(h, NULL) clears them)");
+    if (h->noise)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: forcing noise is installed (a noisy member has no repeating cycle; "
+                                         "ebm_set_column_noise(h, NULL, ...) clears it)");
     if ((long long)h->ttab.size() != nt) return fail(EBM_ERR_ARG, "ebm_equilibrate: time table length must equal nt");
     if (max_years < 1) return fail(EBM_ERR_ARG, "ebm_equilibrate: max_years must be >= 1");
     if (nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_equilibrate: too many fields");

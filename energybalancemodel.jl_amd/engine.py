@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, noise
 from ._lib import FIELD, GRID, MODEL, PARAM_ORDER, as_f64, check, dptr
 
 MIZ_PROGNOSTIC = ("Ei", "Ew", "h", "D", "phi")
@@ -241,6 +241,45 @@ class Engine:
         if a.shape != (self.ncol, len(PARAM_ORDER)):
             raise ValueError(f"expected parameter rows of shape {(self.ncol, len(PARAM_ORDER))}, got {a.shape}")
         check(self.lib.ebm_set_column_params(self._h, dptr(a)), "ebm_set_column_params")
+
+    def check_noise_args(self, sigma, rho=None, seed=0, streams=None, tau=None):
+        """The host-side checks of ``set_column_noise`` (no device call): see ``noise.check_args``."""
+        return noise.check_args(self.ncol, self.dt, sigma, rho, seed, streams, tau)
+
+    def set_column_noise(self, sigma, rho=None, seed=0, streams=None, tau=None):
+        """Per-column AR(1) forcing noise drawn on the device (ebm_set_column_noise; the definition is in
+        include/ebm_hip.h): ``sigma`` the stationary standard deviation (W m^-2; scalar or [ncol]), ``rho`` the lag-one-step
+        autocorrelation in [0, 1) (default 0: white) or ``tau`` its e-folding time in years (rho = exp(-dt/tau)), ``seed``
+        the handle's seed and ``streams`` the [ncol] stream ids (default 0 .. ncol-1; a shard passes its members' global
+        indices).  Resets the noise state to 0.  ``sigma=None`` clears the noise."""
+        if sigma is None:
+            check(self.lib.ebm_set_column_noise(self._h, None, None, None, 0), "ebm_set_column_noise")
+            return
+        sig, r, st, seed = self.check_noise_args(sigma, rho, seed, streams, tau)
+        sp = None if st is None else st.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        check(self.lib.ebm_set_column_noise(self._h, dptr(sig), dptr(r), sp, C.c_ulonglong(seed)), "ebm_set_column_noise")
+
+    def noise_state(self) -> np.ndarray:
+        """N_c [ncol], the noise added to each column's forcing at the last step (0 without noise)."""
+        out = np.empty(self.ncol)
+        check(self.lib.ebm_get_noise_state(self._h, dptr(out)), "ebm_get_noise_state")
+        return out
+
+    def set_noise_state(self, N):
+        """Restore N_c [ncol] (checkpoint / restart; needs noise installed)."""
+        a = as_f64(N, (self.ncol,))
+        if not np.all(np.isfinite(a)):
+            raise ValueError("noise state: expected finite values")
+        check(self.lib.ebm_set_noise_state(self._h, dptr(a)), "ebm_set_noise_state")
+
+    def noise_innovations(self, first_step: int, nsteps: int) -> np.ndarray:
+        """xi [ncol, nsteps] of global steps first_step .. first_step + nsteps - 1, computed on the device by the function
+        the step kernels use (ebm_noise_innovations)."""
+        if int(first_step) < 0 or int(nsteps) < 0:
+            raise ValueError("noise_innovations: first_step and nsteps must be >= 0")
+        out = np.empty((self.ncol, int(nsteps)))
+        check(self.lib.ebm_noise_innovations(self._h, int(first_step), int(nsteps), dptr(out)), "ebm_noise_innovations")
+        return out
 
     def set_step_clock(self, step: int):
         check(self.lib.ebm_set_step_clock(self._h, int(step)), "ebm_set_step_clock")

@@ -13,6 +13,7 @@ import numpy as np
 
 from .engine import Engine, param_matrix, param_vector
 from .infrastructure import default_parval
+from .noise import check_args as check_noise_args
 
 
 def shard_columns(ncol: int, world_size: int, rank: int) -> slice:
@@ -61,10 +62,17 @@ class EnsembleRun:
     passes ``forcings[mine]``.
 
     A column's results do not depend on how many columns share its handle or on how the ensemble is sharded
-    over GPUs: the launch geometry is a function of the latitude count and ``cells_per_thread`` only."""
+    over GPUs: the launch geometry is a function of the latitude count and ``cells_per_thread`` only.
+
+    ``noise``: per-member AR(1) forcing noise drawn on the device (ebm_set_column_noise), a dict with ``sigma`` (W m^-2,
+    scalar or one per member), ``rho`` (lag-one-step autocorrelation) or ``tau`` (its e-folding time in years), and
+    ``seed``.  Member m draws stream ``noise_streams[m]`` (default: m); a sharded run passes the global member indices
+    of its shard, as it passes ``member_params[mine]``, and then gives the bits of the unsharded run."""
+
+    has_noise = False
 
     def __init__(self, model, st, par, init, fcol=None, device=0, forcings=None, cells_per_thread=None,
-                 member_params=None):
+                 member_params=None, noise=None, noise_streams=None):
         first = np.asarray(next(iter(init.values())))
         self.ncol = 1 if first.ndim == 1 else first.shape[0]
         if fcol is not None:
@@ -75,6 +83,16 @@ class EnsembleRun:
         if member_params is not None:
             rows = member_param_rows(member_params, par, init, fcol, forcings)
             self.ncol = rows.shape[0]
+        noise_args = None
+        if noise is not None:
+            if not hasattr(noise, "items") or "sigma" not in noise or set(noise) - {"sigma", "rho", "tau", "seed"}:
+                raise ValueError("noise: expected dict(sigma=..., rho=... or tau=..., seed=...)")
+            noise_args = dict(sigma=noise["sigma"], rho=noise.get("rho"), tau=noise.get("tau"), seed=noise.get("seed", 0),
+                              streams=None if noise_streams is None else np.asarray(noise_streams))
+        elif noise_streams is not None:
+            raise ValueError("noise_streams without noise")
+        if noise_args is not None:
+            check_noise_args(self.ncol, st.dt, **noise_args)     # before any device call
         self.st = st
         self.device = int(device)
         # cells_per_thread: launch option of ebm_create_ex (None = the library's default of 4).  Every rank of a
@@ -93,7 +111,10 @@ class EnsembleRun:
             self.engine.set_column_schedules(forcings)
         if rows is not None:
             self.engine.set_column_params(rows)
+        if noise_args is not None:
+            self.engine.set_column_noise(**noise_args)
         self.has_schedules = forcings is not None
+        self.has_noise = noise_args is not None
         self.step_index = 0
 
     def run(self, nsteps, forcing=None, diag_last=True, steps_per_launch=None):
@@ -145,6 +166,8 @@ class EnsembleRun:
         st = self.st
         if self.has_schedules:
             raise ValueError("equilibrate: this ensemble was built with forcings= (per-member ramps have no equilibrium)")
+        if self.has_noise:
+            raise ValueError("equilibrate: this ensemble was built with noise= (a noisy member has no repeating cycle)")
         if forcing is not None and not getattr(forcing, "constant", False):
             raise ValueError("equilibrate: needs a constant forcing (a Forcing{false} ramp has no equilibrium)")
         if self.step_index % st.nt:

@@ -1,0 +1,78 @@
+#!/usr/bin/env python
+"""Noise-induced transitions: inside the bistable window of the Wagner & Eisenman (2015) model (examples/
+equilibrium_branches.py finds it), does weather-like variability push a warm climate onto the cold branch, and how
+often?  Every member starts from the warm equilibrium at its forcing F; each member then gets its own realisation of
+AR(1) ("red") noise on the forcing, drawn on the device (ebm_set_column_noise, one stream per member), and the ensemble
+runs `--years` years.  Printed per F and year: the fraction of members whose annual-mean hemispheric temperature has
+fallen below the midpoint between the warm and the cold branch.
+
+    python examples/noise_induced_transitions.py [--nlat 180] [--nt 2000] [--forcings -2,0,2] [--members 64]
+        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import __graft_entry__ as graft  # noqa: E402
+
+PROG = ("Ei", "Ew", "h", "D", "phi", "T0")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nlat", type=int, default=180)
+    ap.add_argument("--nt", type=int, default=2000)
+    ap.add_argument("--forcings", default="-2,0,2", help="forcings F (W m^-2) inside the bistable window")
+    ap.add_argument("--members", type=int, default=64, help="noise realisations per forcing")
+    ap.add_argument("--years", type=int, default=20)
+    ap.add_argument("--sigma", type=float, default=4.0, help="stationary standard deviation of the noise (W m^-2)")
+    ap.add_argument("--tau", type=float, default=0.1, help="e-folding time of the noise (years)")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--max-years", type=int, default=60, help="spin-up limit of the warm and cold equilibria")
+    args = ap.parse_args()
+    pkg = graft.load_package()
+    st = pkg.SpaceTime("sin", args.nlat, args.nt, 1)
+    par = pkg.default_parameters("MIZ")
+    F = np.array([float(v) for v in args.forcings.split(",")])
+    nf = len(F)
+
+    # the warm and the cold equilibrium at every F: started far on the warm and on the cold side, spun up
+    zero = {k: np.zeros(st.nx) for k in PROG[:-1]}
+    far = pkg.EnsembleRun("MIZ", st, par, zero, fcol=np.array([-20.0, 20.0]))
+    far.equilibrate(args.max_years)
+    ends = far.state(PROG)
+    far.close()
+    init = {k: np.concatenate([np.tile(ends[k][0], (nf, 1)), np.tile(ends[k][1], (nf, 1))]) for k in PROG}
+    branches = pkg.EnsembleRun("MIZ", st, par, init, fcol=np.concatenate([F, F]))
+    branches.equilibrate(args.max_years)
+    eq = branches.state(PROG)
+    cold_T, warm_T = np.split(branches.engine.hemispheric_mean("T"), 2)
+    branches.close()
+    print("    F   cold <T>  warm <T>")
+    for i in range(nf):
+        print(f"{F[i]:5.2f}  {cold_T[i]:8.2f}  {warm_T[i]:8.2f}" + ("" if warm_T[i] - cold_T[i] > 0.5 else "   (one branch only)"))
+
+    # the noisy ensemble: member (i, m) starts on the warm branch at F[i] and draws stream i*members + m
+    n = args.members
+    fcol = np.repeat(F, n)
+    init = {k: np.repeat(eq[k][nf:], n, axis=0) for k in PROG}
+    run = pkg.EnsembleRun("MIZ", st, par, init, fcol=fcol,
+                          noise=dict(sigma=args.sigma, tau=args.tau, seed=args.seed), noise_streams=np.arange(nf * n))
+    out = run.seasonal_means(args.years, names=("T",))
+    run.close()
+    avgT = out["avg"][0]                                   # [years, members]
+    threshold = np.repeat(0.5 * (cold_T + warm_T), n)
+    fell = avgT < threshold
+    print(f"\n{nf * n} members ({n} per forcing), noise sigma = {args.sigma} W m^-2, tau = {args.tau} y; "
+          f"fraction of members on the cold side (annual-mean <T> below the branches' midpoint), by year:")
+    print("    F  " + " ".join(f"{y + 1:5d}" for y in range(args.years)))
+    for i in range(nf):
+        frac = fell[:, i * n:(i + 1) * n].mean(axis=1)
+        print(f"{F[i]:5.2f}  " + " ".join(f"{v:5.2f}" for v in frac))
+
+
+if __name__ == "__main__":
+    main()

@@ -252,6 +252,39 @@ int ebm_set_step_clock(ebm_handle_t h, long long step);
  * ebm_zonal_diffusion returns EBM_ERR_UNSUPPORTED while more than one distinct set is installed (its a_k tables come
  * from one D and one cw); with one set it uses that set's D and cw. */
 int ebm_set_column_params(ebm_handle_t h, const double *params);
+/* Per-column STOCHASTIC FORCING: AR(1) ("red") noise N_c added to every column's forcing, one independent realisation per
+ * column, drawn on the device.  THIS TEXT IS THE DEFINITION.  For column c with stream id stream_c, the handle's seed and
+ * the 0-based global index n of the step being taken:
+ *   1. (w0,w1,w2,w3) = Philox4x32-10(counter = (lo32(n), hi32(n), lo32(stream_c), hi32(stream_c)),
+ *                                   key = (lo32(seed), hi32(seed)))
+ *      (Random123's Philox: multipliers 0xD2511F53, 0xCD9E8D57; key bumps 0x9E3779B9, 0xBB67AE85; ten rounds).
+ *   2. a = (w0 << 21) | (w1 >> 11), b = (w2 << 21) | (w3 >> 11) (53-bit integers);
+ *      u1 = (a + 1) * 2^-53 in (0, 1], u2 = b * 2^-53 in [0, 1).
+ *   3. xi = sqrt(-2 log(u1)) * cospi(2 u2) (Box-Muller, first output; the device's own log and cospi).
+ *   4. N_c <- rho_c * N_c + s_c * xi with s_c = sigma_c * sqrt(1 - rho_c^2), computed once on the host at set time; two
+ *      rounded products and one sum (no contraction).  The step uses the updated N_c.
+ *   5. The column's forcing is ((f + fcol[c]) + schedule_c(T)) + N_c (absent terms left out, in this order).
+ * sigma_c is the stationary standard deviation of N_c in the units of f (W m^-2); rho_c in [0, 1) the lag-one-step
+ * autocorrelation (0: white noise).  Because xi is keyed by (seed, stream_c, n), a column's noise does not depend on the
+ * launch geometry, fused K, graph replay or launch chains, on how many columns share the handle or how an ensemble is
+ * sharded (give every member its global index as stream id), nor on how a run is chunked into calls.  N_c is state: it
+ * advances once per step taken, by every stepping entry point (ebm_step, ebm_run, ebm_run_fused, ebm_integrate,
+ * ebm_integrate_hemispheric), for all models; ebm_get_noise_state / ebm_set_noise_state checkpoint it.
+ * sigma, rho, stream: [ncol] each; sigma == NULL clears the noise (every kernel is then exactly the noise-free step);
+ * stream == NULL means stream_c = c.  Every N_c is reset to 0.  EBM_ERR_ARG for a non-finite value, sigma < 0, rho outside
+ * [0, 1) or a NULL rho with a non-NULL sigma; the handle then keeps what it had.  Synchronous, like the other column
+ * setters.  ebm_equilibrate refuses with EBM_ERR_UNSUPPORTED while noise is installed (no repeating cycle).  Device memory:
+ * 544 bytes per column (with 512 for the N_c sequence of a fused launch). */
+int ebm_set_column_noise(ebm_handle_t h, const double *sigma, const double *rho, const unsigned long long *stream,
+                         unsigned long long seed);
+/* N[ncol]: the noise state N_c (all 0 without noise) / restore it (EBM_ERR_ARG without noise or for a non-finite value).
+ * With the fields and the step clock this is a complete checkpoint: restored into a fresh handle with the same noise
+ * settings, a run continues bit for bit.  Synchronous. */
+int ebm_get_noise_state(ebm_handle_t h, double *N);
+int ebm_set_noise_state(ebm_handle_t h, const double *N);
+/* out[ncol][nsteps] = xi(seed, stream_c, first_step + i) of the installed noise, computed on the device by the function
+ * the step kernels call (a test hook: the innovations bit for bit).  EBM_ERR_ARG without noise.  Synchronous. */
+int ebm_noise_innovations(ebm_handle_t h, long long first_step, int nsteps, double *out);
 /* Table of cos(2.0*pi*st.t[i]), i = 1..nt (src/miz.jl:11, src/classic.jl:24), needed by
  * ebm_run/ebm_integrate.  Computed by the caller so that host and device agree bit for bit. */
 int ebm_set_time_table(ebm_handle_t h, int nt, const double *cos2pit);
@@ -336,8 +369,8 @@ int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_s
  * fields[nvars] may name any solution variable of the model, prognostic or diagnostic, each at most once; EBM_F_T0 is not
  * one (as in ebm_integrate).  All models (MIZ, MIZ_IMEX, classic), grids and options; per-column forcings and parameter
  * rows are honoured.  Columns are independent: a column's result does not depend on the others or on sharding.
- * Refusals leave the handle as it was: EBM_ERR_UNSUPPORTED while per-column schedules are installed (a ramped forcing has
- * no equilibrium); EBM_ERR_ARG for a time table whose length is not nt, max_years < 1, a tolerance that is negative or
+ * Refusals leave the handle as it was: EBM_ERR_UNSUPPORTED while per-column schedules or forcing noise are installed (a
+ * ramped or noisy forcing has no equilibrium); EBM_ERR_ARG for a time table whose length is not nt, max_years < 1, a tolerance that is negative or
  * NaN, a bad or repeated field.
  * How it runs: each year is the fused stepping of ebm_run_fused (ebm_options.integrate_steps_per_launch steps to a launch,
  * 1 = one launch per step) over the ACTIVE columns only — a frozen column gets no workgroup and moves no byte — then one
