@@ -1,6 +1,6 @@
-// Host transfers of the runtime behind the C ABI (ebm_runtime.hip): a process-wide pool of host threads and, per handle, a
-// pinned staging ring with a DMA stream and a worker thread for the asynchronous outputs of ebm_integrate.  Header-only,
-// included by ebm_runtime.hip alone; not part of the public interface (include/ebm_hip.h).
+// Host side of the runtime behind the C ABI (ebm_runtime.hip): owners of HIP resources, a process-wide pool of host threads
+// and, per handle, a pinned staging ring with a DMA stream and a worker thread for the asynchronous outputs of ebm_integrate.
+// Header-only, included by ebm_runtime.hip alone; not part of the public interface (include/ebm_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,70 @@
 #include <vector>
 
 namespace ebm_host {
+
+// ---- owners of HIP resources -------------------------------------------------------------------------
+// Owned<T, Release>: move-only, holds one resource (null: none) and releases it when destroyed, reset or assigned over.
+// out() frees what it holds and gives the address a HIP allocate / create call writes the new resource to.
+template <class T, class Release>
+class Owned {
+public:
+    Owned() = default;
+    Owned(Owned &&o) noexcept : v_(o.v_) { o.v_ = T(); }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) {
+            reset();
+            v_ = o.v_;
+            o.v_ = T();
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    T get() const { return v_; }
+    explicit operator bool() const { return v_ != T(); }
+    T *out() {
+        reset();
+        return &v_;
+    }
+    void reset() {
+        if (v_) Release()(v_);
+        v_ = T();
+    }
+
+private:
+    T v_ = T();
+};
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+struct HostFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+struct GraphExecDestroy { void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); } };
+template <class T> using DevBuf = Owned<T *, DevFree>;          // device memory
+template <class T> using PinnedBuf = Owned<T *, HostFree>;      // pinned host memory
+using Event = Owned<hipEvent_t, EventDestroy>;
+using Stream = Owned<hipStream_t, StreamDestroy>;
+using GraphExec = Owned<hipGraphExec_t, GraphExecDestroy>;
+
+// n elements of T into `b` (what b held is freed first)
+template <class T>
+hipError_t dev_alloc(DevBuf<T> &b, size_t n) {
+    return hipMalloc(b.out(), sizeof(T) * n);
+}
+
+// A device array that keeps its capacity between calls: reserve(n) reallocates, without keeping the contents, only when n
+// exceeds it.  The old array is freed before the new one is allocated; after a failure the array is empty.
+template <class T>
+struct DevVec {
+    DevBuf<T> buf;
+    size_t cap = 0;
+    T *get() const { return buf.get(); }
+    hipError_t reserve(size_t n) {
+        if (buf && cap >= n) return hipSuccess;
+        cap = 0;
+        hipError_t e = dev_alloc(buf, n);
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+};
 
 // ---- host transfers: pinned staging ring + a few host threads ---------------------------------------
 // The caller's buffers are pageable.  A device -> pageable copy through the runtime alone runs at 7-8 GB/s
@@ -105,10 +169,10 @@ struct CopyJob {
 // thread that runs the jobs in order while the caller keeps launching steps.
 struct HostCopier {
     int device = 0;
-    char *ring = nullptr;                           // kRingSlots x kSlotBytes, pinned
-    hipStream_t stream = nullptr;                   // DMA stream (ordered after the compute stream by ev_ready)
-    hipEvent_t slot_ev[kRingSlots] = {nullptr};
-    hipEvent_t ev_ready = nullptr;
+    PinnedBuf<char> ring;                           // kRingSlots x kSlotBytes
+    Stream stream;                                  // DMA stream (ordered after the compute stream by ev_ready)
+    Event slot_ev[kRingSlots];
+    Event ev_ready;
     std::thread worker;
     std::mutex m;
     std::condition_variable cv, idle;
@@ -118,13 +182,14 @@ struct HostCopier {
 
     hipError_t init(int dev) {
         device = dev;
-        hipError_t e = hipHostMalloc((void **)&ring, kRingSlots * kSlotBytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-        for (int i = 0; i < kRingSlots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&slot_ev[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming);
+        hipError_t e = hipHostMalloc(ring.out(), kRingSlots * kSlotBytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(stream.out(), hipStreamNonBlocking);
+        for (int i = 0; i < kRingSlots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(slot_ev[i].out(), hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev_ready.out(), hipEventDisableTiming);
         return e;
     }
-    void shutdown() {
+    // the worker finishes the queued jobs and is joined, the DMA stream drains; then the members free themselves
+    ~HostCopier() {
         if (worker.joinable()) {
             {
                 std::lock_guard<std::mutex> lk(m);
@@ -133,21 +198,12 @@ struct HostCopier {
             cv.notify_all();
             worker.join();
         }
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (auto &ev : slot_ev)
-            if (ev) (void)hipEventDestroy(ev);
-        if (ev_ready) (void)hipEventDestroy(ev_ready);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (ring) (void)hipHostFree(ring);
-        ring = nullptr;
-        stream = nullptr;
-        ev_ready = nullptr;
-        for (auto &ev : slot_ev) ev = nullptr;
+        if (stream) (void)hipStreamSynchronize(stream.get());
     }
     // everything the compute stream has been given so far happens before the copies submitted from now on
     hipError_t order_after(hipStream_t compute) {
-        hipError_t e = hipEventRecord(ev_ready, compute);
-        if (e == hipSuccess) e = hipStreamWaitEvent(stream, ev_ready, 0);
+        hipError_t e = hipEventRecord(ev_ready.get(), compute);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream.get(), ev_ready.get(), 0);
         return e;
     }
     // device -> pinned slot -> caller's buffer, the DMA of piece i+1.. in flight while piece i is copied on
@@ -177,24 +233,24 @@ struct HostCopier {
         auto issue = [&](size_t i) -> hipError_t {
             const char *src; char *dst; size_t nr, bpr;
             piece(i, src, dst, nr, bpr);
-            char *slot = ring + (i % kRingSlots) * kSlotBytes;
+            char *slot = ring.get() + (i % kRingSlots) * kSlotBytes;
             hipError_t e = (packed || nr == 1)
-                ? hipMemcpyAsync(slot, src, nr * bpr, hipMemcpyDeviceToHost, stream)
-                : hipMemcpy2DAsync(slot, bpr, src, sizeof(double) * j.src_pitch, bpr, nr, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipEventRecord(slot_ev[i % kRingSlots], stream);
+                ? hipMemcpyAsync(slot, src, nr * bpr, hipMemcpyDeviceToHost, stream.get())
+                : hipMemcpy2DAsync(slot, bpr, src, sizeof(double) * j.src_pitch, bpr, nr, hipMemcpyDeviceToHost, stream.get());
+            if (e == hipSuccess) e = hipEventRecord(slot_ev[i % kRingSlots].get(), stream.get());
             return e;
         };
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < std::min<size_t>(kRingSlots - 1, npieces) && e == hipSuccess; ++i) e = issue(i);
         for (size_t i = 0; i < npieces && e == hipSuccess; ++i) {
             if (i + kRingSlots - 1 < npieces) e = issue(i + kRingSlots - 1);      // its slot was drained at piece i-1
-            if (e == hipSuccess) e = hipEventSynchronize(slot_ev[i % kRingSlots]);
+            if (e == hipSuccess) e = hipEventSynchronize(slot_ev[i % kRingSlots].get());
             if (e != hipSuccess) break;
             const char *src; char *dst; size_t nr, bpr;
             piece(i, src, dst, nr, bpr);
-            parallel_memcpy(dst, ring + (i % kRingSlots) * kSlotBytes, nr * bpr);
+            parallel_memcpy(dst, ring.get() + (i % kRingSlots) * kSlotBytes, nr * bpr);
         }
-        if (e != hipSuccess) (void)hipStreamSynchronize(stream);
+        if (e != hipSuccess) (void)hipStreamSynchronize(stream.get());
         return e;
     }
     // caller's buffer -> pinned slot -> device
@@ -207,17 +263,17 @@ struct HostCopier {
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < npieces && e == hipSuccess; ++i) {
             const size_t r0 = i * rows_per, nr = std::min(rows_per, nrows - r0);
-            char *slot = ring + (i % kRingSlots) * kSlotBytes;
-            if (i >= kRingSlots) e = hipEventSynchronize(slot_ev[i % kRingSlots]);      // the slot's previous DMA has read it
+            char *slot = ring.get() + (i % kRingSlots) * kSlotBytes;
+            if (i >= kRingSlots) e = hipEventSynchronize(slot_ev[i % kRingSlots].get());      // the slot's previous DMA has read it
             if (e != hipSuccess) break;
             parallel_memcpy(slot, src + r0 * row_elems, nr * row_bytes);
             e = (dst_pitch == row_elems)
-                ? hipMemcpyAsync(dst_dev + r0 * dst_pitch, slot, nr * row_bytes, hipMemcpyHostToDevice, stream)
+                ? hipMemcpyAsync(dst_dev + r0 * dst_pitch, slot, nr * row_bytes, hipMemcpyHostToDevice, stream.get())
                 : hipMemcpy2DAsync(dst_dev + r0 * dst_pitch, sizeof(double) * dst_pitch, slot, row_bytes, row_bytes, nr,
-                                   hipMemcpyHostToDevice, stream);
-            if (e == hipSuccess) e = hipEventRecord(slot_ev[i % kRingSlots], stream);
+                                   hipMemcpyHostToDevice, stream.get());
+            if (e == hipSuccess) e = hipEventRecord(slot_ev[i % kRingSlots].get(), stream.get());
         }
-        hipError_t e2 = hipStreamSynchronize(stream);
+        hipError_t e2 = hipStreamSynchronize(stream.get());
         return e != hipSuccess ? e : e2;
     }
     // asynchronous jobs (ebm_integrate): queued, run in order by the worker thread

@@ -3,18 +3,13 @@
 // ebm_kernels.hip.  There is deliberately no CPU fallback: without a GPU every entry point
 // fails with EBM_ERR_NO_DEVICE.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
 #include <map>
-#include <mutex>
+#include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/ebm_hip.h"
@@ -22,7 +17,14 @@
 #include "ebm_internal.h"
 
 using ebm_host::CopyJob;
+using ebm_host::DevBuf;
+using ebm_host::DevVec;
+using ebm_host::Event;
+using ebm_host::GraphExec;
 using ebm_host::HostCopier;
+using ebm_host::PinnedBuf;
+using ebm_host::Stream;
+using ebm_host::dev_alloc;
 
 namespace {
 
@@ -42,67 +44,82 @@ int fail(int code, const std::string &msg) {
             return fail(EBM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+// runs `f` when it goes out of scope, on every path
+template <class F>
+struct Finally {
+    F f;
+    ~Finally() { f(); }
+};
+template <class F>
+Finally<F> finally(F f) { return {std::move(f)}; }
+
 }  // namespace
 
+// Every resource of the handle is held by an owner (ebm_host::Owned, DevVec, unique_ptr) and freed by it; the state of a
+// feature is one member, which a call that installs it replaces with one move after everything new has been built (an
+// install either succeeds or leaves the handle as it was).  Raw pointers here are views.
 struct ebm_ctx {
-    int model = 0, grid = 0, nlat = 0, ncol = 0, device = 0;
-    bool imex = false;                             // EBM_MODEL_MIZ_IMEX: model == EBM_MODEL_MIZ plus the implicit-diffusion extension
-    long long pitch = 0;
-    double dt = 0.0;
-    ebm::Params p{};
-    ebm::LaunchCfg cfg{};
-    ebm::Params *p_dev = nullptr;                  // parameter block in device memory
-    double *geom = nullptr;                        // per-latitude tables, G_COUNT x gstride
-    long long gstride = 0;
-    // ebm_set_column_params: one parameter block and one geometry slab per distinct row (nsets of them, 0 = no table:
-    // every column steps with p_dev / geom), and the column -> set index (null when every column has set 0)
-    int nsets = 0;
-    ebm::Params *p_sets = nullptr;
-    double *geom_sets = nullptr;                   // nsets x G_COUNT x gstride
-    int *pset_dev = nullptr;
-    std::vector<ebm::Params> sets_host;            // host copies (the zonal operator's D and cw)
-    double *state = nullptr;                       // field slab, nslots x fstride
-    long long fstride = 0;
-    int nslots = 0;
-    double *field[EBM_F_COUNT] = {nullptr};        // views into the slab (null: not in this model)
-    double *fcol = nullptr;
-    double *fsched = nullptr;                      // per-column Forcing schedules
-    // ebm_set_column_noise: the per-column records, the AR(1) state N_c (null: no noise) and the seed
-    ebm::NoiseRec *noise = nullptr;
-    double *nstate = nullptr;
-    double *nseq = nullptr;                        // [ncol][kNoiseMaxFused], the fused kernels' per-launch N_c sequence
-    unsigned long long seed = 0;
-    long long clock = 0;                           // global index of the next step (model time of ebm_step)
-    unsigned long long *stamps = nullptr;          // diagnostic builds only
-    int num_cus = 0;
-    int prefetch = 0;                 // L2 prefetch distance of the MIZ kernel, columns (0 = off)
-    double *hm_dev = nullptr;         // ebm_hemispheric_mean: per-column results on the device
-    // per-step scalars of the fused-K launches: two device tables of kFusedTable entries used in turn, each with the event
-    // that marks the end of the launches that read it — a table is refilled only after that event, so consecutive fused
-    // calls neither wait for each other nor synchronise the stream
-    struct SchedTable { ebm::StepSched *dev = nullptr; hipEvent_t done = nullptr; bool in_use = false; } sched_tab[2];
-    int sched_next = 0;
-    int integrate_spl = 64;                  // ebm_options::integrate_steps_per_launch (1 = one launch per step)
-    // hipGraph replay for launch-bound shapes (small grids): kGraphSteps step kernels per replay
-    ebm::StepSched *sched_dev = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    bool use_graph = false;
-    std::vector<double> ttab;                      // cos(2*pi*t_i), host copy
-    unsigned long long *counters = nullptr;        // device, kCounterShards x 2
-    unsigned short *amask = nullptr;               // MIZ warm-start active set, ncol x threads
-    long long n_steps = 0, n_launches = 0;
-    hipStream_t stream = nullptr;                  // THE stream of the handle: everything is ordered on it (see main_stream)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // declared first, destroyed last: the buffers below are freed before the streams and events of their work
+    Stream stream;                                 // THE stream of the handle: everything is ordered on it (see main_stream)
     // Two chains of step launches.  Long meridians leave room for ONE workgroup per CU, so within a launch nothing runs under
     // a workgroup's load, solve and store phases, and a launch cannot start before the slowest workgroup of the previous one
     // has ended.  Columns are independent: the first half of them is stepped on `stream`, the second on `stream2`, each half
     // its own chain of launches; the chains drift apart and fill each other's gaps (measured on 4096 x 2048: 0.1656 ->
     // 0.1594 ms per step, tests/tools/ab_two_handles.py).  `forked` = the chains are running apart; any other use of the
     // handle's stream joins them first (main_stream).
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Stream stream2;
+    Event ev0, ev1, ev_fork, ev_join;
     int split_col = 0;                             // 0: one chain; else the first column of the second chain
     bool forked = false;
+    int model = 0, grid = 0, nlat = 0, ncol = 0, device = 0;
+    bool imex = false;                             // EBM_MODEL_MIZ_IMEX: model == EBM_MODEL_MIZ plus the implicit-diffusion extension
+    long long pitch = 0;
+    double dt = 0.0;
+    ebm::Params p{};
+    ebm::LaunchCfg cfg{};
+    DevBuf<ebm::Params> p_dev;                     // parameter block in device memory
+    DevBuf<double> geom;                           // per-latitude tables, G_COUNT x gstride
+    long long gstride = 0;
+    // ebm_set_column_params: one parameter block and one geometry slab per distinct row (n of them, 0 = no table: every
+    // column steps with p_dev / geom), and the column -> set index (null when every column has set 0)
+    struct ParamSets {
+        int n = 0;
+        DevBuf<ebm::Params> p;
+        DevBuf<double> geom;                       // n x G_COUNT x gstride
+        DevBuf<int> col;
+        std::vector<ebm::Params> host;             // host copies (the zonal operator's D and cw)
+    } sets;
+    DevBuf<double> state;                          // field slab, nslots x fstride
+    long long fstride = 0;
+    int nslots = 0;
+    double *field[EBM_F_COUNT] = {nullptr};        // views into the slab (null: not in this model)
+    DevBuf<double> fcol;
+    DevBuf<double> fsched;                         // per-column Forcing schedules
+    // ebm_set_column_noise: the per-column records, the AR(1) state N_c (null: no noise) and the seed
+    struct Noise {
+        DevBuf<ebm::NoiseRec> rec;
+        DevBuf<double> state;
+        DevBuf<double> seq;                        // [ncol][kNoiseMaxFused], the fused kernels' per-launch N_c sequence
+        unsigned long long seed = 0;
+    } noise;
+    long long clock = 0;                           // global index of the next step (model time of ebm_step)
+    DevBuf<unsigned long long> stamps;             // diagnostic builds only
+    int num_cus = 0;
+    int prefetch = 0;                 // L2 prefetch distance of the MIZ kernel, columns (0 = off)
+    DevBuf<double> hm_dev;            // ebm_hemispheric_mean: per-column results on the device
+    // per-step scalars of the fused-K launches: two device tables of kFusedTable entries used in turn, each with the event
+    // that marks the end of the launches that read it — a table is refilled only after that event, so consecutive fused
+    // calls neither wait for each other nor synchronise the stream
+    struct SchedTable { DevBuf<ebm::StepSched> dev; Event done; bool in_use = false; } sched_tab[2];
+    int sched_next = 0;
+    int integrate_spl = 64;                  // ebm_options::integrate_steps_per_launch (1 = one launch per step)
+    // hipGraph replay for launch-bound shapes (small grids): kGraphSteps step kernels per replay, node i reads sched[i]
+    struct Graph { DevBuf<ebm::StepSched> sched; GraphExec exec; } graph;
+    bool use_graph = false;
+    std::vector<double> ttab;                      // cos(2*pi*t_i), host copy
+    DevBuf<unsigned long long> counters;           // device, kCounterShards x 2
+    DevBuf<unsigned short> amask;                  // MIZ warm-start active set, ncol x threads
+    long long n_steps = 0, n_launches = 0;
     // ebm_equilibrate, for the duration of the call only: the launches step the columns active[0 .. nactive) (device list,
     // ascending) instead of all of them
     const int *active = nullptr;
@@ -117,16 +134,18 @@ struct ebm_ctx {
     // the first reader after such a step runs the in-place un-permutation once.
     bool diag_split = false;
     // ebm_zonal_diffusion: the tables of the last nlon used, kept between calls
-    int nlon = 0, zseg = 1;                        // zseg: segments a circle is cut into (a function of nlon only)
-    double *ztab = nullptr;                        // chain tables | reduced-system tables | per-latitude scalars | scratch (build_zonal_tables)
-    double *zM = nullptr, *zE = nullptr, *zrM = nullptr, *zrE = nullptr, *za = nullptr, *za2 = nullptr, *zW = nullptr,
-           *zsu = nullptr, *zsg = nullptr, *zsy = nullptr;       // views into ztab
+    struct ZonalTables {
+        int nlon = 0, seg = 1;                     // seg: segments a circle is cut into (a function of nlon only)
+        DevBuf<double> tab;                        // chain tables | reduced-system tables | per-latitude scalars | scratch
+        double *M = nullptr, *E = nullptr, *rM = nullptr, *rE = nullptr, *a = nullptr, *a2 = nullptr, *W = nullptr,
+               *su = nullptr, *sg = nullptr, *sy = nullptr;       // views into tab
+    } zonal;
     std::vector<double> xhost;                     // st.x (the zonal tables are built on demand)
-    HostCopier *copier = nullptr;                  // pinned staging ring, lazily created by the first host transfer
-    double *scratch = nullptr;                     // ebm_diffusion: temp | base | out, kept between calls
+    std::unique_ptr<HostCopier> copier;            // pinned staging ring, lazily created by the first host transfer
+    DevBuf<double> scratch;                        // ebm_diffusion / ebm_zonal_diffusion: three fields, kept between calls
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
-    double *ig_sums = nullptr, *ig_mean = nullptr, *ig_snap = nullptr, *ig_stage = nullptr, *ig_hm = nullptr;
-    size_t ig_sums_n = 0, ig_mean_n = 0, ig_snap_n = 0, ig_stage_n = 0, ig_hm_n = 0;
+    DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
+    ~ebm_ctx();
 };
 
 namespace {
@@ -135,12 +154,24 @@ namespace {
 // (ebm_ctx::forked), the second one is joined first: whatever is enqueued next is ordered after all steps of all columns.
 hipStream_t main_stream(ebm_ctx *h) {
     if (h->forked) {
-        (void)hipEventRecord(h->ev_join, h->stream2);
-        (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
+        (void)hipEventRecord(h->ev_join.get(), h->stream2.get());
+        (void)hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0);
         h->forked = false;
     }
-    return h->stream;
+    return h->stream.get();
 }
+
+}  // namespace
+
+// The handle's work ends before anything is freed: the copier's worker finishes its queued jobs (they read the handle's
+// buffers) and is joined; then every member frees what it owns.
+ebm_ctx::~ebm_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(main_stream(this));
+    copier.reset();
+}
+
+namespace {
 
 // slab slot of a public field id for this model, -1 if the model does not have it
 int slot_of(int model, int f) {
@@ -164,17 +195,6 @@ bool is_diagnostic(const ebm_ctx *h, int f) {
 const char *field_name(int f) {
     static const char *names[EBM_F_COUNT] = {"Ei", "Ew", "h", "D", "phi", "T0", "Tw", "Ti", "n", "E", "T", "Tg"};
     return (f >= 0 && f < EBM_F_COUNT) ? names[f] : "?";
-}
-// a step (or a run of steps ending at global index `step`) has been launched
-void note_steps(ebm_ctx *h, long long nsteps, long long last_step, bool wrote_diag) {
-    h->epoch += nsteps;
-    h->state_step = last_step;
-    if (wrote_diag)
-        for (int f = 0; f < EBM_F_COUNT; ++f)
-            if (has_field(h, f) && is_diagnostic(h, f)) {
-                h->written_epoch[f] = h->epoch;
-                h->written_step[f] = last_step;
-            }
 }
 // EBM_OK if `f` may be read now, else EBM_ERR_STALE with the two steps in the message
 int check_current(const ebm_ctx *h, int f, const char *who) {
@@ -322,9 +342,9 @@ void periodic_tables(double a, double B, int n, double *M, double *E, size_t P, 
 // ends), and the reduced periodic system of the S segment ends, (-a'', B'', -a'') with a'' = a ep_{m-2},
 // B'' = B - a cp_{m-2} - a alpha, alpha = sum_i P_i ep_i.  Built on first use and whenever nlon changes.
 // The parameters of the zonal operator: the handle's vector, or the one set ebm_set_column_params installed
-const ebm::Params &zonal_params(const ebm_ctx *h) { return h->nsets ? h->sets_host[0] : h->p; }
+const ebm::Params &zonal_params(const ebm_ctx *h) { return h->sets.n ? h->sets.host[0] : h->p; }
 int build_zonal_tables(ebm_ctx *h, int nlon) {
-    if (h->ztab && h->nlon == nlon) return EBM_OK;
+    if (h->zonal.tab && h->zonal.nlon == nlon) return EBM_OK;
     const int S = zonal_segments(nlon), m = nlon / S, P = (int)h->pitch, T = h->cfg.threads;
     const int nmember = h->ncol / nlon;
     const double *x = h->xhost.data();
@@ -362,40 +382,40 @@ int build_zonal_tables(ebm_ctx *h, int nlon) {
         za2[p] = a2;
         periodic_tables(a2, B2, S, rM + p, rE + p, (size_t)P, &zW[p]);
     }
+    ebm_ctx::ZonalTables z;
+    HIPCHK(dev_alloc(z.tab, tab.size() + scratch));
+    HIPCHK(hipMemcpy(z.tab.get(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    z.M = z.tab.get(); z.E = z.M + chain_rows * P; z.rM = z.E + chain_rows * P; z.rE = z.rM + red_rows * P;
+    z.a = z.rE + red_rows * P; z.a2 = z.a + P; z.W = z.a2 + P;
+    z.su = z.W + P; z.sg = z.su + scratch / 3; z.sy = z.sg + scratch / 3;
+    z.nlon = nlon;
+    z.seg = S;
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    if (h->ztab) (void)hipFree(h->ztab);
-    h->ztab = nullptr;
-    h->nlon = 0;
-    HIPCHK(hipMalloc(&h->ztab, sizeof(double) * (tab.size() + scratch)));
-    HIPCHK(hipMemcpy(h->ztab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    h->zM = h->ztab; h->zE = h->zM + chain_rows * P; h->zrM = h->zE + chain_rows * P; h->zrE = h->zrM + red_rows * P;
-    h->za = h->zrE + red_rows * P; h->za2 = h->za + P; h->zW = h->za2 + P;
-    h->zsu = h->zW + P; h->zsg = h->zsu + scratch / 3; h->zsy = h->zsg + scratch / 3;
-    h->nlon = nlon;
-    h->zseg = S;
+    h->zonal = std::move(z);
     return EBM_OK;
 }
 hipError_t zonal_sweep(ebm_ctx *h, const double *T, double *outZ, double *outU) {
-    const int nmember = h->ncol / h->nlon;
+    const ebm_ctx::ZonalTables &z = h->zonal;
+    const int nmember = h->ncol / z.nlon;
     const double rtheta = zonal_params(h).cw / h->dt;
-    if (h->zseg == 1)
-        return ebm::launch_zonal_sweep(T, outZ, outU, h->zM, h->zE, h->za, h->zW, h->nlon, nmember, (int)h->pitch, rtheta,
-                                       main_stream(h));
-    return ebm::launch_zonal_sweep_segmented(T, outZ, outU, h->zM, h->zE, h->zrM, h->zrE, h->za, h->za2, h->zW, h->zsu, h->zsg,
-                                             h->zsy, h->nlon, h->zseg, nmember, (int)h->pitch, rtheta, main_stream(h));
+    if (z.seg == 1)
+        return ebm::launch_zonal_sweep(T, outZ, outU, z.M, z.E, z.a, z.W, z.nlon, nmember, (int)h->pitch, rtheta, main_stream(h));
+    return ebm::launch_zonal_sweep_segmented(T, outZ, outU, z.M, z.E, z.rM, z.rE, z.a, z.a2, z.W, z.su, z.sg, z.sy, z.nlon,
+                                             z.seg, nmember, (int)h->pitch, rtheta, main_stream(h));
 }
 
 ebm::StepArgs base_args(const ebm_ctx *h) {
     ebm::StepArgs a{};
-    a.state = h->state; a.fstride = h->fstride; a.geom = h->geom; a.gstride = h->gstride;
-    a.fcol = h->fcol; a.fsched = h->fsched; a.p = h->p_dev;
-    a.noise = h->noise; a.nstate = h->nstate; a.nseq = h->nseq; a.seed = h->seed; a.counters = h->counters; a.amask = h->amask;
-    if (h->nsets) {                  // per-column parameter sets (ebm_set_column_params)
-        a.p = h->p_sets; a.geom = h->geom_sets; a.pset = h->pset_dev;
+    a.state = h->state.get(); a.fstride = h->fstride; a.geom = h->geom.get(); a.gstride = h->gstride;
+    a.fcol = h->fcol.get(); a.fsched = h->fsched.get(); a.p = h->p_dev.get();
+    a.noise = h->noise.rec.get(); a.nstate = h->noise.state.get(); a.nseq = h->noise.seq.get(); a.seed = h->noise.seed;
+    a.counters = h->counters.get(); a.amask = h->amask.get();
+    if (h->sets.n) {                 // per-column parameter sets (ebm_set_column_params)
+        a.p = h->sets.p.get(); a.geom = h->sets.geom.get(); a.pset = h->sets.col.get();
         a.set_stride = (long long)ebm::G_COUNT * h->gstride;
     }
     a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol;
-    a.stamps = h->stamps;
+    a.stamps = h->stamps.get();
     a.cols = h->active;
     a.prefetch = h->prefetch;
     a.nfused = 1;
@@ -422,27 +442,28 @@ hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
     const int n = h->active ? h->nactive : h->ncol;
     if (!h->split_col) return launch_columns(h, a, mode, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
-        hipError_t e = hipEventRecord(h->ev_fork, h->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
+        hipError_t e = hipEventRecord(h->ev_fork.get(), h->stream.get());
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);
         if (e != hipSuccess) return e;
         h->forked = true;
     }
     int half = 0;
     (void)chain_count(h, &half);
-    hipError_t e = half > 0 ? launch_columns(h, a, mode, 0, half, h->stream) : hipSuccess;
-    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, half, n - half, h->stream2);
+    hipError_t e = half > 0 ? launch_columns(h, a, mode, 0, half, h->stream.get()) : hipSuccess;
+    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, half, n - half, h->stream2.get());
     return e;
 }
 
-// Capture kGraphSteps step kernels (node i reads sched_dev[i]) into a graph, once per handle.
+// Capture kGraphSteps step kernels (node i reads graph.sched[i]) into a graph, once per handle.
 int build_graph(ebm_ctx *h) {
-    HIPCHK(hipMalloc(&h->sched_dev, sizeof(ebm::StepSched) * kGraphSteps));
+    ebm_ctx::Graph g;
+    HIPCHK(dev_alloc(g.sched, kGraphSteps));
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(main_stream(h), hipStreamCaptureModeThreadLocal));
     hipError_t e = hipSuccess;
     for (int i = 0; i < kGraphSteps && e == hipSuccess; ++i) {
         ebm::StepArgs a = base_args(h);
-        a.sched = h->sched_dev;
+        a.sched = g.sched.get();
         a.slot = i;
         a.write_diag = 0;
         e = launch_step(h, a, ebm::OUT_STATE);
@@ -452,9 +473,10 @@ int build_graph(ebm_ctx *h) {
         if (graph) (void)hipGraphDestroy(graph);
         return fail(EBM_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(e != hipSuccess ? e : e2));
     }
-    e = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(g.exec.out(), graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    h->graph = std::move(g);
     return EBM_OK;
 }
 
@@ -465,11 +487,38 @@ double year_time(const ebm_ctx *h, long long step) {
 }
 
 // drop the captured graph: its kernel nodes hold the argument values of the time of capture
-void invalidate_graph(ebm_ctx *h) {
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    h->graph_exec = nullptr;
-    if (h->sched_dev) (void)hipFree(h->sched_dev);
-    h->sched_dev = nullptr;
+void invalidate_graph(ebm_ctx *h) { h->graph = ebm_ctx::Graph(); }
+
+// per-step scalars of steps i = 0 .. n-1 into out[i]: time-table entry tab_first + i, model-time step clock_first + i and
+// forcing f[i] (f null: 0)
+void fill_sched(const ebm_ctx *h, long long tab_first, long long clock_first, int n, const double *f, ebm::StepSched *out) {
+    const long long nt = (long long)h->ttab.size();
+    for (int i = 0; i < n; ++i) {
+        const long long ti = (tab_first + i) % nt;
+        out[i].ct = h->ttab[ti];
+        out[i].ct_next = h->ttab[(ti + 1) % nt];
+        out[i].ft = f ? f[i] : 0.0;
+        out[i].tyear = year_time(h, clock_first + i);
+        out[i].n = clock_first + i;
+    }
+}
+
+// `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
+// global step `last_step`.  wrote_diag: the last one stored the diagnostic fields, pair-split if `split` (MIZ).
+void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split) {
+    int half = 0;
+    h->n_launches += nlaunch * chain_count(h, &half);
+    h->n_steps += nsteps;
+    h->clock = last_step + 1;
+    h->epoch += nsteps;
+    h->state_step = last_step;
+    if (!wrote_diag) return;
+    for (int f = 0; f < EBM_F_COUNT; ++f)
+        if (has_field(h, f) && is_diagnostic(h, f)) {
+            h->written_epoch[f] = h->epoch;
+            h->written_step[f] = last_step;
+        }
+    if (h->model == EBM_MODEL_MIZ) h->diag_split = split;
 }
 
 // savesol! fused into a step launch (ebm::OUT_SAVE): where the running sums and the raw snapshot go
@@ -479,6 +528,13 @@ struct SaveTarget {
     double *stage = nullptr;
     long long stage_var_stride = 0, stage_offset = 0;
     signed char var_of[ebm::kMaxQuantities];
+    // into a launch's arguments; a fused launch (OUT_LOOP_SAVE) takes the running sums only
+    void put(ebm::StepArgs &a, bool sums_only) const {
+        a.sums = sums; a.sum_stride = sum_stride;
+        std::memcpy(a.var_of, var_of, sizeof(a.var_of));
+        if (sums_only) return;
+        a.stage = stage; a.stage_var_stride = stage_var_stride; a.stage_offset = stage_offset;
+    }
 };
 
 int do_step(ebm_ctx *h, double ct, double ct_next, double f, int write_diag, long long step,
@@ -487,21 +543,11 @@ int do_step(ebm_ctx *h, double ct, double ct_next, double f, int write_diag, lon
     a.ct = ct; a.ct_next = ct_next; a.ft = f; a.write_diag = write_diag;
     a.tyear = year_time(h, step);
     a.step = step;
-    int mode = write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE;
-    if (save) {
-        mode = ebm::OUT_SAVE;
-        a.sums = save->sums; a.sum_stride = save->sum_stride;
-        a.stage = save->stage; a.stage_var_stride = save->stage_var_stride; a.stage_offset = save->stage_offset;
-        std::memcpy(a.var_of, save->var_of, sizeof(a.var_of));
-    }
-    hipError_t e = launch_step(h, a, mode);
+    if (save) save->put(a, false);
+    hipError_t e = launch_step(h, a, save ? ebm::OUT_SAVE : write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE);
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    h->n_steps += 1;
-    h->n_launches += h->split_col ? 2 : 1;
-    h->clock = step + 1;
-    note_steps(h, 1, step, write_diag != 0);
     // the 4-cells-per-thread MIZ step kernels leave the diagnostic fields pair-split (ensure_natural undoes it)
-    if (write_diag && h->model == EBM_MODEL_MIZ) h->diag_split = h->cfg.cells == 4;
+    record_launches(h, 1, 1, step, write_diag != 0, h->cfg.cells == 4);
     return EBM_OK;
 }
 
@@ -519,25 +565,21 @@ bool is_split_field(const ebm_ctx *h, int f) {
 
 int get_copier(ebm_ctx *h) {
     if (h->copier) return EBM_OK;
-    HostCopier *c = new HostCopier();
+    auto c = std::make_unique<HostCopier>();
     hipError_t e = c->init(h->device);
-    if (e != hipSuccess) {
-        c->shutdown();
-        delete c;
-        return fail(EBM_ERR_HIP, std::string("pinned staging ring: ") + hipGetErrorString(e));
-    }
-    h->copier = c;
+    if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("pinned staging ring: ") + hipGetErrorString(e));
+    h->copier = std::move(c);
     return EBM_OK;
 }
-// (re)size one of the handle's kept device buffers
-hipError_t keep_buffer(double **buf, size_t *have, size_t want) {
-    if (*buf && *have >= want) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    hipError_t e = hipMalloc(buf, sizeof(double) * want);
-    if (e == hipSuccess) *have = want;
-    return e;
+// ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
+int get_scratch(ebm_ctx *h) {
+    if (h->scratch) return EBM_OK;
+    const size_t n = 3 * (size_t)h->ncol * h->pitch;
+    DevBuf<double> b;
+    HIPCHK(dev_alloc(b, n));
+    HIPCHK(hipMemsetAsync(b.get(), 0, sizeof(double) * n, main_stream(h)));       // padding cells stay zero
+    h->scratch = std::move(b);
+    return EBM_OK;
 }
 
 // quantity index (ebm::MizQuantity / ClassicQuantity) of a public field id, -1 if the step kernels
@@ -638,7 +680,7 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     HIPCHK(ebm::prepare_kernels(cfg));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
-    ebm_ctx *h = new ebm_ctx();
+    auto h = std::make_unique<ebm_ctx>();
     h->model = model; h->grid = grid; h->nlat = nlat; h->ncol = ncol; h->device = device;
     h->dt = dt; h->cfg = cfg; h->imex = imex;
     h->integrate_spl = opt.integrate_steps_per_launch <= 0 ? 64 : opt.integrate_steps_per_launch;
@@ -674,80 +716,45 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     h->gstride = h->pitch;
     {
         std::vector<double> slab((size_t)ebm::G_COUNT * h->gstride, 0.0);
-        build_tables(h, h->p, x, slab.data());
-        hipError_t e = hipMalloc(&h->geom, sizeof(double) * slab.size());
-        if (e == hipSuccess) e = hipMemcpy(h->geom, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { ebm_destroy(h); return fail(EBM_ERR_HIP, std::string("ebm_create: tables: ") + hipGetErrorString(e)); }
+        build_tables(h.get(), h->p, x, slab.data());
+        hipError_t e = dev_alloc(h->geom, slab.size());
+        if (e == hipSuccess) e = hipMemcpy(h->geom.get(), slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_create: tables: ") + hipGetErrorString(e));
     }
     h->fstride = (long long)ncol * h->pitch;
     h->nslots = (model == EBM_MODEL_MIZ) ? (int)ebm::S_MIZ_COUNT : (int)ebm::C_COUNT;
     const size_t nbytes = sizeof(double) * (size_t)h->nslots * (size_t)h->fstride;
-    hipError_t e = hipMalloc(&h->state, nbytes);
-    if (e == hipSuccess) e = hipMemset(h->state, 0, nbytes);
+    hipError_t e = dev_alloc(h->state, (size_t)h->nslots * (size_t)h->fstride);
+    if (e == hipSuccess) e = hipMemset(h->state.get(), 0, nbytes);
     if (e == hipSuccess && model == EBM_MODEL_MIZ) {
-        const size_t mb = sizeof(unsigned short) * (size_t)ncol * cfg.threads;
-        e = hipMalloc(&h->amask, mb);
-        if (e == hipSuccess) e = hipMemset(h->amask, 0, mb);
+        const size_t mn = (size_t)ncol * cfg.threads;
+        e = dev_alloc(h->amask, mn);
+        if (e == hipSuccess) e = hipMemset(h->amask.get(), 0, sizeof(unsigned short) * mn);
     }
-    if (e == hipSuccess) e = hipMalloc(&h->p_dev, sizeof(ebm::Params));
-    if (e == hipSuccess) e = hipMemcpy(h->p_dev, &h->p, sizeof(ebm::Params), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ebm::launch_derive_params(h->p_dev, nullptr);
+    if (e == hipSuccess) e = dev_alloc(h->p_dev, 1);
+    if (e == hipSuccess) e = hipMemcpy(h->p_dev.get(), &h->p, sizeof(ebm::Params), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ebm::launch_derive_params(h->p_dev.get(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMalloc(&h->hm_dev, sizeof(double) * (size_t)ncol);
-    if (e != hipSuccess) { ebm_destroy(h); return fail(EBM_ERR_HIP, std::string("state allocation: ") + hipGetErrorString(e)); }
+    if (e == hipSuccess) e = dev_alloc(h->hm_dev, ncol);
+    if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("state allocation: ") + hipGetErrorString(e));
     for (int f = 0; f < EBM_F_COUNT; ++f) {
         const int slot = slot_of(model, f);
-        h->field[f] = slot >= 0 ? h->state + (size_t)slot * h->fstride : nullptr;
+        h->field[f] = slot >= 0 ? h->state.get() + (size_t)slot * h->fstride : nullptr;
     }
-    e = hipMalloc(&h->counters, sizeof(unsigned long long) * 2 * ebm::kCounterShards);
-    if (e == hipSuccess) e = hipMemset(h->counters, 0, sizeof(unsigned long long) * 2 * ebm::kCounterShards);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess && h->split_col) e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
-    if (e == hipSuccess && h->split_col) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess && h->split_col) e = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e != hipSuccess) { ebm_destroy(h); return fail(EBM_ERR_HIP, std::string("ebm_create: ") + hipGetErrorString(e)); }
-    *out = h;
+    e = dev_alloc(h->counters, 2 * ebm::kCounterShards);
+    if (e == hipSuccess) e = hipMemset(h->counters.get(), 0, sizeof(unsigned long long) * 2 * ebm::kCounterShards);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking);
+    if (e == hipSuccess && h->split_col) e = hipStreamCreateWithFlags(h->stream2.out(), hipStreamNonBlocking);
+    if (e == hipSuccess && h->split_col) e = hipEventCreateWithFlags(h->ev_fork.out(), hipEventDisableTiming);
+    if (e == hipSuccess && h->split_col) e = hipEventCreateWithFlags(h->ev_join.out(), hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(h->ev0.out());
+    if (e == hipSuccess) e = hipEventCreate(h->ev1.out());
+    if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_create: ") + hipGetErrorString(e));
+    *out = h.release();
     return EBM_OK;
 }
 
 int ebm_destroy(ebm_handle_t h) {
-    if (!h) return EBM_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(main_stream(h));
-    if (h->copier) {
-        h->copier->shutdown();
-        delete h->copier;
-    }
-    for (double *b : {h->scratch, h->ig_sums, h->ig_mean, h->ig_snap, h->ig_stage, h->ig_hm, h->ztab})
-        if (b) (void)hipFree(b);
-    if (h->geom) (void)hipFree(h->geom);
-    if (h->geom_sets) (void)hipFree(h->geom_sets);
-    if (h->p_sets) (void)hipFree(h->p_sets);
-    if (h->pset_dev) (void)hipFree(h->pset_dev);
-    if (h->state) (void)hipFree(h->state);
-    if (h->p_dev) (void)hipFree(h->p_dev);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->sched_dev) (void)hipFree(h->sched_dev);
-    for (auto &tb : h->sched_tab) {
-        if (tb.dev) (void)hipFree(tb.dev);
-        if (tb.done) (void)hipEventDestroy(tb.done);
-    }
-    if (h->hm_dev) (void)hipFree(h->hm_dev);
-    if (h->amask) (void)hipFree(h->amask);
-    if (h->fcol) (void)hipFree(h->fcol);
-    if (h->fsched) (void)hipFree(h->fsched);
-    if (h->noise) (void)hipFree(h->noise);
-    if (h->nstate) (void)hipFree(h->nstate);
-    if (h->nseq) (void)hipFree(h->nseq);
-    if (h->counters) (void)hipFree(h->counters);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return EBM_OK;
 }
@@ -788,7 +795,7 @@ static int download_field(ebm_handle_t h, int field, double *host, const char *w
         rc = ensure_natural(h);
         if (rc) return rc;
     }
-    HostCopier *c = h->copier;
+    HostCopier *c = h->copier.get();
     HIPCHK(c->wait_all());
     HIPCHK(c->order_after(main_stream(h)));
     CopyJob j;
@@ -836,9 +843,9 @@ int ebm_hemispheric_mean(ebm_handle_t h, int field, double *out) {
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     if (is_split_field(h, field) && (rc = ensure_natural(h))) return rc;
-    hipError_t e = ebm::launch_hemispheric_mean(h->field[field], h->geom + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
-                                                h->nlat, h->ncol, h->hm_dev, main_stream(h));
-    if (e == hipSuccess) e = hipMemcpyAsync(out, h->hm_dev, sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost, main_stream(h));
+    hipError_t e = ebm::launch_hemispheric_mean(h->field[field], h->geom.get() + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
+                                                h->nlat, h->ncol, h->hm_dev.get(), main_stream(h));
+    if (e == hipSuccess) e = hipMemcpyAsync(out, h->hm_dev.get(), sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost, main_stream(h));
     if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_hemispheric_mean: ") + hipGetErrorString(e));
     return EBM_OK;
@@ -851,7 +858,7 @@ int ebm_hemispheric_mean_device(ebm_handle_t h, int field, double *dev_out) {
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     if (is_split_field(h, field) && (rc = ensure_natural(h))) return rc;
-    hipError_t e = ebm::launch_hemispheric_mean(h->field[field], h->geom + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
+    hipError_t e = ebm::launch_hemispheric_mean(h->field[field], h->geom.get() + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
                                                 h->nlat, h->ncol, dev_out, main_stream(h));
     if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_hemispheric_mean_device: ") + hipGetErrorString(e));
@@ -877,11 +884,9 @@ int ebm_diffusion(ebm_handle_t h, const double *temp, const double *base, double
         return fail(EBM_ERR_ARG, "ebm_diffusion: needs a MIZ handle (the classic model carries get_diffop unscaled inside kappa, src/classic.jl:21)");
     HIPCHK(hipSetDevice(h->device));
     const size_t npitch = (size_t)h->ncol * h->pitch;
-    if (!h->scratch) {                                   // temp | base | out, [ncol][pitch] each: kept until ebm_destroy
-        HIPCHK(hipMalloc(&h->scratch, sizeof(double) * npitch * 3));
-        HIPCHK(hipMemsetAsync(h->scratch, 0, sizeof(double) * npitch * 3, main_stream(h)));       // padding cells stay zero
-    }
-    double *buf = h->scratch;
+    int rc = get_scratch(h);                             // temp | base | out
+    if (rc) return rc;
+    double *buf = h->scratch.get();
     auto up = [&](double *dst, const double *src) {
         return hipMemcpy2DAsync(dst, sizeof(double) * h->pitch, src, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
                                 h->ncol, hipMemcpyHostToDevice, main_stream(h));
@@ -905,18 +910,15 @@ int ebm_zonal_diffusion(ebm_handle_t h, int nlon, const double *temp, double *ou
     if (h->model != EBM_MODEL_MIZ) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs a MIZ handle (cw and D are MIZ parameters of this operator)");
     if (nlon < 3) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs nlon >= 3 (longitudes per member)");
     if (h->ncol % nlon) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: the handle's column count must be a multiple of nlon");
-    if (h->nsets > 1)
+    if (h->sets.n > 1)
         return fail(EBM_ERR_UNSUPPORTED, "ebm_zonal_diffusion: needs one parameter set (its tables come from one D and one cw; "
-                                         "ebm_set_column_params installed " + std::to_string(h->nsets) + ")");
+                                         "ebm_set_column_params installed " + std::to_string(h->sets.n) + ")");
     HIPCHK(hipSetDevice(h->device));
     int rc = build_zonal_tables(h, nlon);
     if (rc) return rc;
     const size_t npitch = (size_t)h->ncol * h->pitch;
-    if (!h->scratch) {                                   // temp | U | Z, [ncol][pitch] each: kept until ebm_destroy
-        HIPCHK(hipMalloc(&h->scratch, sizeof(double) * npitch * 3));
-        HIPCHK(hipMemsetAsync(h->scratch, 0, sizeof(double) * npitch * 3, main_stream(h)));       // padding cells stay zero
-    }
-    double *buf = h->scratch;
+    if ((rc = get_scratch(h))) return rc;                // temp | U | Z
+    double *buf = h->scratch.get();
     hipError_t e = hipMemsetAsync(buf, 0, sizeof(double) * npitch, main_stream(h));            // (an earlier call left it permuted)
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(buf, sizeof(double) * h->pitch, temp, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
@@ -950,38 +952,34 @@ int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pi
     return EBM_OK;
 }
 
+// ebm_set_column_forcing / _schedule: nwords doubles per column from `src` (null: none) into the handle's `dst`
+int install_columns(ebm_ctx *h, DevBuf<double> &dst, const double *src, size_t nwords) {
+    DevBuf<double> b;
+    if (src) {
+        HIPCHK(dev_alloc(b, nwords * (size_t)h->ncol));
+        HIPCHK(hipMemcpy(b.get(), src, sizeof(double) * nwords * (size_t)h->ncol, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    dst = std::move(b);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    return EBM_OK;
+}
+
 int ebm_set_column_forcing(ebm_handle_t h, const double *fcol) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_forcing: null handle");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
-    if (!fcol) {
-        if (h->fcol) { HIPCHK(hipFree(h->fcol)); invalidate_graph(h); }
-        h->fcol = nullptr;
-        return EBM_OK;
-    }
-    if (!h->fcol) { HIPCHK(hipMalloc(&h->fcol, sizeof(double) * h->ncol)); invalidate_graph(h); }
-    HIPCHK(hipMemcpy(h->fcol, fcol, sizeof(double) * h->ncol, hipMemcpyHostToDevice));
-    return EBM_OK;
+    return install_columns(h, h->fcol, fcol, 1);
 }
 
 int ebm_set_column_schedule(ebm_handle_t h, const double *sched) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_schedule: null handle");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
-    const size_t nb = sizeof(double) * ebm::kSchedWords * (size_t)h->ncol;
-    if (!sched) {
-        if (h->fsched) { HIPCHK(hipFree(h->fsched)); invalidate_graph(h); }
-        h->fsched = nullptr;
-        return EBM_OK;
-    }
-    for (int c = 0; c < h->ncol; ++c) {
+    for (int c = 0; sched && c < h->ncol; ++c) {
         const double *w = sched + (size_t)ebm::kSchedWords * c;
         if (!(w[5] <= w[6] && w[6] <= w[7] && w[7] <= w[8]))
             return fail(EBM_ERR_ARG, "ebm_set_column_schedule: breakpoints must be non-decreasing");
     }
-    if (!h->fsched) { HIPCHK(hipMalloc(&h->fsched, nb)); invalidate_graph(h); }
-    HIPCHK(hipMemcpy(h->fsched, sched, nb, hipMemcpyHostToDevice));
-    return EBM_OK;
+    return install_columns(h, h->fsched, sched, ebm::kSchedWords);
 }
 
 int ebm_set_column_noise(ebm_handle_t h, const double *sigma, const double *rho, const unsigned long long *stream,
@@ -1002,25 +1000,19 @@ int ebm_set_column_noise(ebm_handle_t h, const double *sigma, const double *rho,
         }
     }
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
-    invalidate_graph(h);                         // the captured launches hold the old argument values
-    if (!sigma) {
-        if (h->noise) HIPCHK(hipFree(h->noise));
-        if (h->nstate) HIPCHK(hipFree(h->nstate));
-        if (h->nseq) HIPCHK(hipFree(h->nseq));
-        h->noise = nullptr;
-        h->nstate = nullptr;
-        h->nseq = nullptr;
-        h->seed = 0;
-        return EBM_OK;
+    ebm_ctx::Noise nz;                           // sigma null: no noise
+    if (sigma) {
+        const std::vector<double> zeros((size_t)h->ncol, 0.0);
+        HIPCHK(dev_alloc(nz.rec, (size_t)h->ncol));
+        HIPCHK(dev_alloc(nz.state, (size_t)h->ncol));
+        HIPCHK(dev_alloc(nz.seq, ebm::kNoiseMaxFused * (size_t)h->ncol));
+        HIPCHK(hipMemcpy(nz.rec.get(), rec.data(), sizeof(ebm::NoiseRec) * (size_t)h->ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(nz.state.get(), zeros.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+        nz.seed = seed;
     }
-    if (!h->noise) HIPCHK(hipMalloc(&h->noise, sizeof(ebm::NoiseRec) * (size_t)h->ncol));
-    if (!h->nstate) HIPCHK(hipMalloc(&h->nstate, sizeof(double) * (size_t)h->ncol));
-    if (!h->nseq) HIPCHK(hipMalloc(&h->nseq, sizeof(double) * ebm::kNoiseMaxFused * (size_t)h->ncol));
-    HIPCHK(hipMemcpy(h->noise, rec.data(), sizeof(ebm::NoiseRec) * (size_t)h->ncol, hipMemcpyHostToDevice));
-    const std::vector<double> zeros((size_t)h->ncol, 0.0);
-    HIPCHK(hipMemcpy(h->nstate, zeros.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
-    h->seed = seed;
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    h->noise = std::move(nz);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
     return EBM_OK;
 }
 
@@ -1028,37 +1020,37 @@ int ebm_get_noise_state(ebm_handle_t h, double *N) {
     if (!h || !N) return fail(EBM_ERR_ARG, "ebm_get_noise_state: bad argument");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    if (!h->nstate) {                            // no noise: N_c = 0
+    if (!h->noise.state) {                       // no noise: N_c = 0
         std::fill(N, N + h->ncol, 0.0);
         return EBM_OK;
     }
-    HIPCHK(hipMemcpy(N, h->nstate, sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(N, h->noise.state.get(), sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost));
     return EBM_OK;
 }
 
 int ebm_set_noise_state(ebm_handle_t h, const double *N) {
     if (!h || !N) return fail(EBM_ERR_ARG, "ebm_set_noise_state: bad argument");
-    if (!h->nstate) return fail(EBM_ERR_ARG, "ebm_set_noise_state: no noise installed (ebm_set_column_noise)");
+    if (!h->noise.state) return fail(EBM_ERR_ARG, "ebm_set_noise_state: no noise installed (ebm_set_column_noise)");
     for (int c = 0; c < h->ncol; ++c)
         if (!std::isfinite(N[c])) return fail(EBM_ERR_ARG, "ebm_set_noise_state: N[" + std::to_string(c) + "] is not finite");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    HIPCHK(hipMemcpy(h->nstate, N, sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->noise.state.get(), N, sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
     return EBM_OK;
 }
 
 int ebm_noise_innovations(ebm_handle_t h, long long first_step, int nsteps, double *out) {
     if (!h || first_step < 0 || nsteps < 0 || (nsteps > 0 && !out)) return fail(EBM_ERR_ARG, "ebm_noise_innovations: bad argument");
-    if (!h->noise) return fail(EBM_ERR_ARG, "ebm_noise_innovations: no noise installed (ebm_set_column_noise)");
+    if (!h->noise.rec) return fail(EBM_ERR_ARG, "ebm_noise_innovations: no noise installed (ebm_set_column_noise)");
     if (nsteps == 0) return EBM_OK;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->ncol * (size_t)nsteps;
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, sizeof(double) * n));
-    hipError_t e = ebm::launch_noise_innovations(h->noise, h->seed, first_step, nsteps, h->ncol, dev, main_stream(h));
+    DevBuf<double> dev;
+    HIPCHK(dev_alloc(dev, n));
+    hipError_t e = ebm::launch_noise_innovations(h->noise.rec.get(), h->noise.seed, first_step, nsteps, h->ncol, dev.get(),
+                                                 main_stream(h));
     if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
-    if (e == hipSuccess) e = hipMemcpy(out, dev, sizeof(double) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = hipMemcpy(out, dev.get(), sizeof(double) * n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_noise_innovations: ") + hipGetErrorString(e));
     return EBM_OK;
 }
@@ -1075,7 +1067,6 @@ int ebm_set_column_params(ebm_handle_t h, const double *params) {
                                              ": Tm^m2 with Tm < 0 and non-integer m2 (DomainError in the reference, src/miz.jl:71)");
         }
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
     // distinct rows by bit pattern, in order of first appearance
     std::vector<int> col_set((size_t)h->ncol, 0);
     std::vector<const double *> rows;
@@ -1088,46 +1079,34 @@ int ebm_set_column_params(ebm_handle_t h, const double *params) {
             col_set[c] = it.first->second;
         }
     }
-    const int nsets = (int)rows.size();
-    const long long set_stride = (long long)ebm::G_COUNT * h->gstride;
-    ebm::Params *p_sets = nullptr;
-    double *geom_sets = nullptr;
-    int *pset_dev = nullptr;
-    std::vector<ebm::Params> ps((size_t)nsets);
-    if (nsets) {
+    ebm_ctx::ParamSets sets;
+    sets.n = (int)rows.size();
+    sets.host.resize((size_t)sets.n);
+    if (sets.n) {
         // every set built by the code ebm_create runs for its vector: fill_params, build_tables, derive_params_kernel
-        std::vector<double> slab((size_t)nsets * set_stride, 0.0);
-        for (int i = 0; i < nsets; ++i) {
-            fill_params(ps[i], rows[i], h->dt);
-            build_tables(h, ps[i], h->xhost.data(), slab.data() + (size_t)i * set_stride);
+        const long long set_stride = (long long)ebm::G_COUNT * h->gstride;
+        std::vector<double> slab((size_t)sets.n * set_stride, 0.0);
+        for (int i = 0; i < sets.n; ++i) {
+            fill_params(sets.host[i], rows[i], h->dt);
+            build_tables(h, sets.host[i], h->xhost.data(), slab.data() + (size_t)i * set_stride);
         }
-        hipError_t e = hipMalloc(&p_sets, sizeof(ebm::Params) * (size_t)nsets);
-        if (e == hipSuccess) e = hipMalloc(&geom_sets, sizeof(double) * slab.size());
-        if (e == hipSuccess && nsets > 1) e = hipMalloc(&pset_dev, sizeof(int) * (size_t)h->ncol);
-        if (e == hipSuccess) e = hipMemcpy(p_sets, ps.data(), sizeof(ebm::Params) * (size_t)nsets, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(geom_sets, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && pset_dev)
-            e = hipMemcpy(pset_dev, col_set.data(), sizeof(int) * (size_t)h->ncol, hipMemcpyHostToDevice);
-        for (int i = 0; i < nsets && e == hipSuccess; ++i) e = ebm::launch_derive_params(p_sets + i, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) e = hipMemcpy(ps.data(), p_sets, sizeof(ebm::Params) * (size_t)nsets, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {                   // the handle keeps the rows it had
-            for (void *b : {(void *)p_sets, (void *)geom_sets, (void *)pset_dev})
-                if (b) (void)hipFree(b);
-            return fail(EBM_ERR_HIP, std::string("ebm_set_column_params: ") + hipGetErrorString(e));
-        }
+        hipError_t e = dev_alloc(sets.p, (size_t)sets.n);
+        if (e == hipSuccess) e = dev_alloc(sets.geom, slab.size());
+        if (e == hipSuccess && sets.n > 1) e = dev_alloc(sets.col, (size_t)h->ncol);
+        if (e == hipSuccess) e = hipMemcpy(sets.p.get(), sets.host.data(), sizeof(ebm::Params) * (size_t)sets.n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(sets.geom.get(), slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && sets.col)
+            e = hipMemcpy(sets.col.get(), col_set.data(), sizeof(int) * (size_t)h->ncol, hipMemcpyHostToDevice);
+        for (int i = 0; i < sets.n && e == hipSuccess; ++i) e = ebm::launch_derive_params(sets.p.get() + i, h->stream.get());
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
+        if (e == hipSuccess)
+            e = hipMemcpy(sets.host.data(), sets.p.get(), sizeof(ebm::Params) * (size_t)sets.n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_set_column_params: ") + hipGetErrorString(e));
     }
-    for (void *b : {(void *)h->p_sets, (void *)h->geom_sets, (void *)h->pset_dev})
-        if (b) (void)hipFree(b);
-    h->nsets = nsets;
-    h->p_sets = p_sets;
-    h->geom_sets = geom_sets;
-    h->pset_dev = pset_dev;
-    h->sets_host = std::move(ps);
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    h->sets = std::move(sets);
     invalidate_graph(h);                         // the captured launches hold the old argument values
-    if (h->ztab) (void)hipFree(h->ztab);         // the zonal tables are built again from the parameters now installed
-    h->ztab = nullptr;
-    h->nlon = 0;
+    h->zonal = ebm_ctx::ZonalTables();           // the zonal tables are built again from the parameters now installed
     return EBM_OK;
 }
 
@@ -1159,29 +1138,19 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
     if (h->use_graph && nsteps >= 2 * kGraphSteps) {
         // launch-bound shapes: replay a captured graph of kGraphSteps launches (still one launch
         // per step); the per-step scalars travel through a small device table
-        if (!h->graph_exec) {
+        if (!h->graph.exec) {
             int rc = build_graph(h);
             if (rc) return rc;
         }
         std::vector<ebm::StepSched> sched(kGraphSteps);
         const int last_graph_step = nsteps - (diag_last ? 1 : 0);     // a diagnostic last step is launched directly
         for (; s + kGraphSteps <= last_graph_step; s += kGraphSteps) {
-            for (int i = 0; i < kGraphSteps; ++i) {
-                const long long ti = (first_step + s + i) % nt;
-                sched[i].ct = h->ttab[ti];
-                sched[i].ct_next = h->ttab[(ti + 1) % nt];
-                sched[i].ft = f_steps ? f_steps[s + i] : 0.0;
-                sched[i].tyear = year_time(h, first_step + s + i);
-                sched[i].n = first_step + s + i;
-            }
+            fill_sched(h, first_step + s, first_step + s, kGraphSteps, f_steps ? f_steps + s : nullptr, sched.data());
             // pageable source: the copy is staged before the call returns, so `sched` can be refilled
-            HIPCHK(hipMemcpyAsync(h->sched_dev, sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
+            HIPCHK(hipMemcpyAsync(h->graph.sched.get(), sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
                                   hipMemcpyHostToDevice, main_stream(h)));
-            HIPCHK(hipGraphLaunch(h->graph_exec, main_stream(h)));
-            h->n_steps += kGraphSteps;
-            h->n_launches += kGraphSteps;
-            h->clock = first_step + s + kGraphSteps;
-            note_steps(h, kGraphSteps, first_step + s + kGraphSteps - 1, false);
+            HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
+            record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false);
         }
     }
     for (; s < nsteps; ++s) {
@@ -1198,56 +1167,41 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
 // fused stepping (OUT_LOOP).
 static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, int nsteps, const double *f_steps, int diag_last,
                        int steps_per_launch, const SaveTarget *save) {
-    const long long first_step = clock_first;
-    const long long nt = (long long)h->ttab.size();
     // forcing noise: the kernels draw a launch's innovations one step per lane, so a launch takes at most kNoiseMaxFused
     // steps (same bits, more launches)
-    if (h->noise) steps_per_launch = std::min(steps_per_launch, ebm::kNoiseMaxFused);
+    if (h->noise.rec) steps_per_launch = std::min(steps_per_launch, ebm::kNoiseMaxFused);
     std::vector<ebm::StepSched> sched;
     for (int s0 = 0; s0 < nsteps; s0 += kFusedTable) {
         const int n = std::min(kFusedTable, nsteps - s0);
         sched.resize(n);
-        for (int i = 0; i < n; ++i) {
-            const long long ti = (tab_first + s0 + i) % nt;
-            sched[i].ct = h->ttab[ti];
-            sched[i].ct_next = h->ttab[(ti + 1) % nt];
-            sched[i].ft = f_steps ? f_steps[s0 + i] : 0.0;
-            sched[i].tyear = year_time(h, first_step + s0 + i);
-            sched[i].n = first_step + s0 + i;
-        }
+        fill_sched(h, tab_first + s0, clock_first + s0, n, f_steps ? f_steps + s0 : nullptr, sched.data());
         // the table used two batches ago: its launches must have ended before it is refilled (normally long since).  The copy is
         // synchronous for the host but not ordered with the handle's (non-blocking) streams.
         auto &tb = h->sched_tab[h->sched_next];
         h->sched_next ^= 1;
         if (!tb.dev) {
-            HIPCHK(hipMalloc(&tb.dev, sizeof(ebm::StepSched) * kFusedTable));
-            HIPCHK(hipEventCreateWithFlags(&tb.done, hipEventDisableTiming));
+            ebm_ctx::SchedTable t;
+            HIPCHK(dev_alloc(t.dev, kFusedTable));
+            HIPCHK(hipEventCreateWithFlags(t.done.out(), hipEventDisableTiming));
+            tb = std::move(t);
         }
-        if (tb.in_use) HIPCHK(hipEventSynchronize(tb.done));
-        HIPCHK(hipMemcpy(tb.dev, sched.data(), sizeof(ebm::StepSched) * (size_t)n, hipMemcpyHostToDevice));
+        if (tb.in_use) HIPCHK(hipEventSynchronize(tb.done.get()));
+        HIPCHK(hipMemcpy(tb.dev.get(), sched.data(), sizeof(ebm::StepSched) * (size_t)n, hipMemcpyHostToDevice));
         for (int i = 0; i < n; i += steps_per_launch) {
             ebm::StepArgs a = base_args(h);
-            a.sched = tb.dev;
+            a.sched = tb.dev.get();
             a.slot = i;
             a.nfused = std::min(steps_per_launch, n - i);
             a.prefetch = 0;
             a.write_diag = (diag_last && s0 + i + a.nfused == nsteps) ? 1 : 0;
-            if (save) {
-                a.sums = save->sums; a.sum_stride = save->sum_stride;
-                a.stage = nullptr;
-                std::memcpy(a.var_of, save->var_of, sizeof(a.var_of));
-            }
+            if (save) save->put(a, true);
             hipError_t e = launch_step(h, a, save ? ebm::OUT_LOOP_SAVE : ebm::OUT_LOOP);
             if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("fused launch: ") + hipGetErrorString(e));
-            int half = 0;
-            h->n_launches += chain_count(h, &half);
-            note_steps(h, a.nfused, first_step + s0 + i + a.nfused - 1, a.write_diag != 0);
-            if (a.write_diag && h->model == EBM_MODEL_MIZ) h->diag_split = false;      // the fused kernel stores them in the natural layout
+            // the fused kernels store the diagnostic fields in the natural layout
+            record_launches(h, 1, a.nfused, clock_first + s0 + i + a.nfused - 1, a.write_diag != 0, false);
         }
-        HIPCHK(hipEventRecord(tb.done, main_stream(h)));     // (both launch chains, joined)
+        HIPCHK(hipEventRecord(tb.done.get(), main_stream(h)));     // (both launch chains, joined)
         tb.in_use = true;
-        h->n_steps += n;
-        h->clock = first_step + s0 + n;
     }
     return EBM_OK;
 }
@@ -1290,8 +1244,11 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
     HIPCHK(hipSetDevice(h->device));
     int rc = get_copier(h);
     if (rc) return rc;
-    HostCopier *cp = h->copier;
+    HostCopier *cp = h->copier.get();
     HIPCHK(cp->wait_all());
+    // on every return: let the copier finish what it was given (it reads this call's device buffers and writes the caller's
+    // arrays)
+    const auto drain = finally([cp] { (void)cp->wait_all(); });
     const size_t ncell = (size_t)h->ncol * h->nlat;          // packed cells per snapshot (host side)
     const size_t npitch = (size_t)h->ncol * h->pitch;        // device elements per field
     const long long total = (long long)nt * dur;
@@ -1299,15 +1256,6 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
     const bool want_hm = (hm_winter || hm_summer || hm_avg) && nvars > 0;
     const bool want_sums = (avg || hm_avg) && nvars > 0;
     const bool want_snap = (winter || summer) && nvars > 0;
-    // Any failure: let the copier finish what it was given (it reads this call's device buffers) before returning.
-#define EBM_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (void)cp->wait_all();                                                         \
-            return fail(EBM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-        }                                                                                 \
-    } while (0)
     // Device buffers (kept in the handle between calls): raw snapshots are staged as two halves of
     // [var][chunk][ncol][pitch]; the annual-mean sums are [var][ncol*pitch] (pair-split layout), the means and the
     // seasonal snapshots [var][ncol*pitch] in the natural layout.
@@ -1316,23 +1264,23 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
         chunk = (long long)((128ull << 20) / (sizeof(double) * npitch * (size_t)nvars));
         if (chunk < 1) chunk = 1;
         if (chunk > nraw) chunk = nraw;
-        EBM_TRY(keep_buffer(&h->ig_stage, &h->ig_stage_n, 2 * npitch * (size_t)nvars * (size_t)chunk));
+        HIPCHK(h->ig_stage.reserve(2 * npitch * (size_t)nvars * (size_t)chunk));
     }
-    if (want_hm) EBM_TRY(keep_buffer(&h->ig_hm, &h->ig_hm_n, (size_t)h->ncol * (size_t)nvars));
+    if (want_hm) HIPCHK(h->ig_hm.reserve((size_t)h->ncol * (size_t)nvars));
     if (want_sums) {
-        EBM_TRY(keep_buffer(&h->ig_sums, &h->ig_sums_n, npitch * (size_t)nvars));
-        EBM_TRY(hipMemsetAsync(h->ig_sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));
-        EBM_TRY(keep_buffer(&h->ig_mean, &h->ig_mean_n, npitch * (size_t)nvars));
+        HIPCHK(h->ig_sums.reserve(npitch * (size_t)nvars));
+        HIPCHK(hipMemsetAsync(h->ig_sums.get(), 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));
+        HIPCHK(h->ig_mean.reserve(npitch * (size_t)nvars));
     }
-    if (want_snap) EBM_TRY(keep_buffer(&h->ig_snap, &h->ig_snap_n, npitch * (size_t)nvars));
-    double *const sums = want_sums ? h->ig_sums : nullptr, *const mean = h->ig_mean, *const snap = h->ig_snap;
-    double *const hm = h->ig_hm;
-    double *const stage = (raw && nvars > 0) ? h->ig_stage : nullptr;
+    if (want_snap) HIPCHK(h->ig_snap.reserve(npitch * (size_t)nvars));
+    double *const sums = want_sums ? h->ig_sums.get() : nullptr, *const mean = h->ig_mean.get(), *const snap = h->ig_snap.get();
+    double *const hm = h->ig_hm.get();
+    double *const stage = (raw && nvars > 0) ? h->ig_stage.get() : nullptr;
     // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set,
     // reduced on the device, [nvars][ncol] -> out[v][year][col]
     auto means_to_host = [&](double *out, long long year, auto field_of) -> hipError_t {
         for (int v = 0; v < nvars; ++v) {
-            hipError_t e = ebm::launch_hemispheric_mean(field_of(v), h->geom + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
+            hipError_t e = ebm::launch_hemispheric_mean(field_of(v), h->geom.get() + (size_t)ebm::G_X * h->gstride, (int)h->pitch,
                                                         h->nlat, h->ncol, hm + (size_t)v * h->ncol, main_stream(h));
             if (e != hipSuccess) return e;
         }
@@ -1403,7 +1351,7 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
             while (n < (1 << 30) && plain_step(tinx + n)) ++n;
             rc = fused_range(h, tinx - 1, clock0 + tinx - 1, (int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,
                              sums ? &save : nullptr);
-            if (rc) { (void)cp->wait_all(); return rc; }
+            if (rc) return rc;
             tinx += n - 1;
             continue;
         }
@@ -1419,31 +1367,30 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
         save.stage = want_raw ? stage + (size_t)half * (size_t)nvars * chunk * npitch : nullptr;
         save.stage_offset = staged * (long long)npitch;
         rc = do_step(h, h->ttab[ti - 1], h->ttab[ti % nt], f, diag, clock0 + tinx - 1, (sums || want_raw) ? &save : nullptr);
-        if (rc) { (void)cp->wait_all(); return rc; }
-        if (want_raw && ++staged == chunk) EBM_TRY(flush());
+        if (rc) return rc;
+        if (want_raw && ++staged == chunk) HIPCHK(flush());
         auto state_field = [&](int v) { return (const double *)h->field[fields[v]]; };
-        if (want_season && (rc = ensure_natural(h))) { (void)cp->wait_all(); return rc; }
+        if (want_season && (rc = ensure_natural(h))) return rc;
         if (ti == winter_inx) {
-            if (winter) EBM_TRY(season_to_host(winter, year));
-            if (hm_winter) EBM_TRY(means_to_host(hm_winter, year, state_field));
+            if (winter) HIPCHK(season_to_host(winter, year));
+            if (hm_winter) HIPCHK(means_to_host(hm_winter, year, state_field));
         } else if (ti == summer_inx) {
-            if (summer) EBM_TRY(season_to_host(summer, year));
-            if (hm_summer) EBM_TRY(means_to_host(hm_summer, year, state_field));
+            if (summer) HIPCHK(season_to_host(summer, year));
+            if (hm_summer) HIPCHK(means_to_host(hm_summer, year, state_field));
         } else if (ti == nt) {
             if (sums) {
-                EBM_TRY(cp->wait_all());                                     // last year's means have left `mean`
-                EBM_TRY(ebm::launch_finish_mean(mean, sums, (double)nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h)));
-                if (avg) EBM_TRY(fields_to_host(avg, year, mean));
-                if (hm_avg) EBM_TRY(means_to_host(hm_avg, year, [&](int v) { return (const double *)(mean + (size_t)v * npitch); }));
+                HIPCHK(cp->wait_all());                                      // last year's means have left `mean`
+                HIPCHK(ebm::launch_finish_mean(mean, sums, (double)nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h)));
+                if (avg) HIPCHK(fields_to_host(avg, year, mean));
+                if (hm_avg) HIPCHK(means_to_host(hm_avg, year, [&](int v) { return (const double *)(mean + (size_t)v * npitch); }));
             }
         }
         if (sums && ti == nt && !(ti != winter_inx && ti != summer_inx))   // year ended on a seasonal index:
-            EBM_TRY(hipMemsetAsync(sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));  // no mean is taken, restart sums
+            HIPCHK(hipMemsetAsync(sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));  // no mean is taken, restart sums
     }
-    EBM_TRY(flush());
-    EBM_TRY(hipStreamSynchronize(main_stream(h)));
-    EBM_TRY(cp->wait_all());
-#undef EBM_TRY
+    HIPCHK(flush());
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(cp->wait_all());
     return EBM_OK;
 }
 
@@ -1472,7 +1419,7 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     if (h->fsched)
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: per-column forcing schedules are installed (a ramped forcing has no "
                                          "equilibrium; ebm_set_column_schedule(h, NULL) clears them)");
-    if (h->noise)
+    if (h->noise.rec)
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: forcing noise is installed (a noisy member has no repeating cycle; "
                                          "ebm_set_column_noise(h, NULL, ...) clears it)");
     if ((long long)h->ttab.size() != nt) return fail(EBM_ERR_ARG, "ebm_equilibrate: time table length must equal nt");
@@ -1498,35 +1445,30 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     if (rc) return rc;
     const int ncol = h->ncol;
     const size_t npitch = (size_t)ncol * h->pitch;
-    // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count; the list is known to
-    // the launches only until the call returns, on every path
-    struct Scope {
-        ebm_ctx *h;
-        double *dbl = nullptr;
-        int *ints = nullptr, *pinned = nullptr;
-        ~Scope() {
-            h->active = nullptr;
-            h->nactive = 0;
-            (void)hipStreamSynchronize(main_stream(h));
-            if (dbl) (void)hipFree(dbl);
-            if (ints) (void)hipFree(ints);
-            if (pinned) (void)hipHostFree(pinned);
-        }
-    } sc{h};
-    HIPCHK(hipMalloc(&sc.dbl, sizeof(double) * ((size_t)nvars * npitch + (size_t)nvars * ncol)));
-    HIPCHK(hipMalloc(&sc.ints, sizeof(int) * (4 * (size_t)ncol + 1)));
-    HIPCHK(hipHostMalloc(&sc.pinned, sizeof(int), hipHostMallocDefault));
-    int *cur = sc.ints, *nxt = cur + ncol, *years_dev = nxt + ncol, *frozen = years_dev + ncol, *count = frozen + ncol;
+    // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count
+    DevBuf<double> dbl;
+    DevBuf<int> ints;
+    PinnedBuf<int> pinned;
+    // the list is known to the launches only until the call returns, on every path; they end before the buffers are freed
+    const auto done = finally([h] {
+        (void)hipStreamSynchronize(main_stream(h));
+        h->active = nullptr;
+        h->nactive = 0;
+    });
+    HIPCHK(dev_alloc(dbl, (size_t)nvars * npitch + (size_t)nvars * ncol));
+    HIPCHK(dev_alloc(ints, 4 * (size_t)ncol + 1));
+    HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
+    int *cur = ints.get(), *nxt = cur + ncol, *years_dev = nxt + ncol, *frozen = years_dev + ncol, *count = frozen + ncol;
     {
         std::vector<double> nan((size_t)nvars * ncol, std::nan(""));
         std::vector<int> ident((size_t)ncol);
         for (int c = 0; c < ncol; ++c) ident[c] = c;
-        HIPCHK(hipMemcpy(sc.dbl + (size_t)nvars * npitch, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dbl.get() + (size_t)nvars * npitch, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(years_dev, 0, sizeof(int) * 2 * (size_t)ncol));
     }
-    ea.state = h->state; ea.fstride = h->fstride;
-    ea.snap = sc.dbl; ea.resid = sc.dbl + (size_t)nvars * npitch;
+    ea.state = h->state.get(); ea.fstride = h->fstride;
+    ea.snap = dbl.get(); ea.resid = dbl.get() + (size_t)nvars * npitch;
     ea.years = years_dev; ea.frozen = frozen;
     ea.pitch = (int)h->pitch; ea.nlat = h->nlat; ea.ncol = ncol; ea.nvars = nvars;
     const long long clock0 = h->clock;
@@ -1545,10 +1487,10 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
         if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_equilibrate: check: ") + hipGetErrorString(e));
         if (y == max_years || !ea.may_freeze) continue;          // (nothing has frozen: the list stays)
         e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
-        if (e == hipSuccess) e = hipMemcpyAsync(sc.pinned, count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
         if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
         if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_equilibrate: active list: ") + hipGetErrorString(e));
-        nactive = *sc.pinned;
+        nactive = *pinned.get();
         std::swap(cur, nxt);
         if (nactive == 0) break;                                 // every column is frozen
     }
@@ -1571,7 +1513,7 @@ int ebm_get_counters(ebm_handle_t h, long long *counters) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
     unsigned long long host[2 * ebm::kCounterShards];
-    HIPCHK(hipMemcpy(host, h->counters, sizeof(host), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host, h->counters.get(), sizeof(host), hipMemcpyDeviceToHost));
     long long solves = 0, caps = 0;
     for (int i = 0; i < ebm::kCounterShards; ++i) {
         solves += (long long)host[2 * i];
@@ -1588,7 +1530,7 @@ int ebm_reset_counters(ebm_handle_t h) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_reset_counters: null handle");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    HIPCHK(hipMemset(h->counters, 0, sizeof(unsigned long long) * 2 * ebm::kCounterShards));
+    HIPCHK(hipMemset(h->counters.get(), 0, sizeof(unsigned long long) * 2 * ebm::kCounterShards));
     h->n_steps = 0;
     h->n_launches = 0;
     return EBM_OK;
@@ -1597,16 +1539,16 @@ int ebm_reset_counters(ebm_handle_t h) {
 int ebm_timer_start(ebm_handle_t h) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_timer_start: null handle");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventRecord(h->ev0, main_stream(h)));
+    HIPCHK(hipEventRecord(h->ev0.get(), main_stream(h)));
     return EBM_OK;
 }
 
 int ebm_timer_stop(ebm_handle_t h, float *elapsed_ms) {
     if (!h || !elapsed_ms) return fail(EBM_ERR_ARG, "ebm_timer_stop: null argument");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventRecord(h->ev1, main_stream(h)));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    HIPCHK(hipEventElapsedTime(elapsed_ms, h->ev0, h->ev1));
+    HIPCHK(hipEventRecord(h->ev1.get(), main_stream(h)));
+    HIPCHK(hipEventSynchronize(h->ev1.get()));
+    HIPCHK(hipEventElapsedTime(elapsed_ms, h->ev0.get(), h->ev1.get()));
     return EBM_OK;
 }
 
@@ -1617,13 +1559,16 @@ int ebm_debug_stamps(ebm_handle_t h, unsigned long long *host) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_debug_stamps: null handle");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    const size_t nb = sizeof(unsigned long long) * (16 + 128) * (size_t)h->ncol;
+    const size_t n = (16 + 128) * (size_t)h->ncol;
     if (!h->stamps) {
-        HIPCHK(hipMalloc(&h->stamps, nb));
-        HIPCHK(hipMemset(h->stamps, 0, nb));
+        DevBuf<unsigned long long> b;
+        HIPCHK(dev_alloc(b, n));
+        HIPCHK(hipMemset(b.get(), 0, sizeof(unsigned long long) * n));
+        h->stamps = std::move(b);
+        invalidate_graph(h);                     // the captured launches hold the old argument values
         return EBM_OK;
     }
-    if (host) HIPCHK(hipMemcpy(host, h->stamps, nb, hipMemcpyDeviceToHost));
+    if (host) HIPCHK(hipMemcpy(host, h->stamps.get(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     return EBM_OK;
 }
 #endif
@@ -1634,14 +1579,13 @@ int ebm_selftest_divide(int device, int n, const double *a, const double *b, dou
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(EBM_ERR_NO_DEVICE, "ebm_selftest_divide: no HIP device available");
     HIPCHK(hipSetDevice(device));
-    double *da = nullptr, *db = nullptr, *dq = nullptr;
+    DevBuf<double> da, db, dq;
     const size_t nb = sizeof(double) * (size_t)n;
-    HIPCHK(hipMalloc(&da, nb)); HIPCHK(hipMalloc(&db, nb)); HIPCHK(hipMalloc(&dq, nb));
-    HIPCHK(hipMemcpy(da, a, nb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db, b, nb, hipMemcpyHostToDevice));
-    hipError_t e = ebm::launch_divide(da, db, dq, n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(q, dq, nb, hipMemcpyDeviceToHost);
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dq);
+    HIPCHK(dev_alloc(da, n)); HIPCHK(dev_alloc(db, n)); HIPCHK(dev_alloc(dq, n));
+    HIPCHK(hipMemcpy(da.get(), a, nb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.get(), b, nb, hipMemcpyHostToDevice));
+    hipError_t e = ebm::launch_divide(da.get(), db.get(), dq.get(), n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(q, dq.get(), nb, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_selftest_divide: ") + hipGetErrorString(e));
     return EBM_OK;
 }
