@@ -1,0 +1,187 @@
+// Device-side basics every kernel family may use: the streamed-store and stamp macros, the constant-address-space
+// parameter block, the column lookups, Julia's IEEE semantics, the IEEE division of the bit-exact physics, the solves'
+// reciprocal, a column's forcing, and the 16-byte chunk loads / stores.
+#pragma once
+#include "ebm_internal.h"
+
+namespace ebm {
+
+// Outputs are streamed: written once per step and not read again before the next launch.  With
+// the non-temporal policy they do not allocate in L2 and drain faster (0.238 -> 0.217 ms per step on
+// the 4096 x 2048 workload; the same policy on the loads was slower and is not used).
+#if defined(EBM_TIMING_NO_STORES)
+// Timing-only A/B build (never shipped, results are garbage): the streamed output stores are dropped, what
+// remains is loads + arithmetic — the ceiling a design that hid every store would reach.  The values
+// are kept alive so that the arithmetic is not eliminated.
+#define EBM_STORE2(ptr, v)                                                            \
+    do {                                                                              \
+        asm volatile("" ::"v"((v).x), "v"((v).y), "s"(ptr));                          \
+    } while (0)
+#elif !defined(EBM_PLAIN_STORES)
+typedef double ebm_dvec2 __attribute__((ext_vector_type(2)));
+#define EBM_STORE2(ptr, v)                                                            \
+    do {                                                                              \
+        ebm_dvec2 t_;                                                                 \
+        t_.x = (v).x;                                                                 \
+        t_.y = (v).y;                                                                 \
+        __builtin_nontemporal_store(t_, reinterpret_cast<ebm_dvec2 *>(ptr));          \
+    } while (0)
+#else
+#define EBM_STORE2(ptr, v) (*reinterpret_cast<double2 *>(ptr) = (v))
+#endif
+
+// Diagnostic build only (-DEBM_STAMPS): wave 0 of every workgroup records s_memtime at phase
+// boundaries into a.stamps[col*16 + n].  Never enabled in the shipped library.
+#ifdef EBM_STAMPS
+#define EBM_STAMP(n)                                                                   \
+    do {                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                             \
+        unsigned long long t_;                                                         \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");      \
+        __builtin_amdgcn_sched_barrier(0);                                             \
+        if (threadIdx.x == 0 && a.stamps) a.stamps[(size_t)blockIdx.x * 16 + (n)] = t_; \
+    } while (0)
+// per-wave variant: lane 0 of every wave records into a.stamps[ncol*16 + (col*16 + wave)*8 + n]
+#define EBM_STAMPW(n)                                                                  \
+    do {                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                             \
+        unsigned long long t_;                                                         \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");      \
+        __builtin_amdgcn_sched_barrier(0);                                             \
+        if ((threadIdx.x & 63) == 0 && a.stamps)                                       \
+            a.stamps[(size_t)a.ncol * 16 + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (n)] = t_; \
+    } while (0)
+#else
+#define EBM_STAMP(n) do {} while (0)
+#define EBM_STAMPW(n) do {} while (0)
+#endif
+
+// The parameter block is never written by a kernel: read it through the constant address space so
+// that every access is a scalar load, also after the kernel's own global stores (through a plain
+// pointer hipcc falls back to per-lane vector loads once the kernel has stored anything).
+typedef const __attribute__((address_space(4))) Params ConstParams;
+
+// The parameter set of a column (ebm_set_column_params): one scalar load per workgroup, from the constant address space
+// like the parameter block itself, and none without a table (every column set 0).  The column is the GLOBAL one
+// (col0 + blockIdx.x: launch chains).
+__device__ __forceinline__ int param_set(const StepArgs &a, int col) {
+    typedef const __attribute__((address_space(4))) int ConstInt;
+    return a.pset ? reinterpret_cast<ConstInt *>(reinterpret_cast<uintptr_t>(a.pset))[col] : 0;
+}
+// The column workgroup blockIdx.x of a launch steps: entry col0 + blockIdx.x of the active list (ebm_equilibrate: frozen
+// columns get no workgroup), one scalar load per workgroup, none without a list (the identity).  The fused-K kernels and
+// the classic kernel only: miz_step_kernel is never launched on a list.
+__device__ __forceinline__ int step_column(const StepArgs &a) {
+    typedef const __attribute__((address_space(4))) int ConstInt;
+    const int b = a.col0 + (int)blockIdx.x;
+    return a.cols ? reinterpret_cast<ConstInt *>(reinterpret_cast<uintptr_t>(a.cols))[b] : b;
+}
+
+// ---- Julia IEEE semantics ----------------------------------------------------------------
+__device__ __forceinline__ double jl_min(double x, double y) {
+    // Base.min(::Float64, ::Float64): NaN-propagating, -0.0 < +0.0
+    double diff = x - y;
+    double am = __builtin_signbit(diff) ? x : y;
+    return (__builtin_isnan(x) || __builtin_isnan(y)) ? diff : am;
+}
+__device__ __forceinline__ double jl_clamp(double x, double lo, double hi) {
+    return x > hi ? hi : (x < lo ? lo : x);
+}
+__device__ __forceinline__ double bool_mul(double x, bool b) {
+    return b ? x : __builtin_copysign(0.0, x);   // Bool "strong zero"
+}
+
+// IEEE fp64 division for the bit-exact physics.  hipcc expands a/b to v_div_scale x2, v_rcp_f64,
+// two Newton steps, a residual correction, v_div_fmas and v_div_fixup.  The two scalings and
+// div_fmas only act when an operand or the quotient is near the exponent limits; for every other
+// input the sequence below (the same instructions without the scaling) returns the same bits, and
+// v_div_fixup still produces the IEEE results for zero, infinite and NaN operands.
+// -DEBM_FULL_DIV selects the compiler's expansion instead.
+__device__ __forceinline__ double div_rcp(double b) {     // refined reciprocal of the sequence
+#if defined(EBM_TIMING_NO_TRANS)        // TIMING ONLY (results garbage): what the v_rcp_f64 themselves cost
+    const double r0 = __builtin_bit_cast(double, 0x7FDE6238502484BAll - __builtin_bit_cast(long long, b));   // +-12 %
+#else
+    const double r0 = __builtin_amdgcn_rcp(b);
+#endif
+#if defined(EBM_TIMING_CHEAP_DIV)       // TIMING ONLY (results garbage): what all the refinement work costs
+    return r0;
+#else
+    const double e0 = __builtin_fma(-b, r0, 1.0);
+    const double r1 = __builtin_fma(r0, e0, r0);
+    const double e1 = __builtin_fma(-b, r1, 1.0);
+    return __builtin_fma(r1, e1, r1);
+#endif
+}
+__device__ __forceinline__ double div_with_rcp(double a, double b, double r2) {
+#if defined(EBM_FULL_DIV)
+    return a / b;
+#elif defined(EBM_TIMING_CHEAP_DIV)
+    return a * r2;
+#else
+    const double q0 = a * r2;
+    const double rem = __builtin_fma(-b, q0, a);
+    const double q = __builtin_fma(rem, r2, q0);
+    return __builtin_amdgcn_div_fixup(q, b, a);
+#endif
+}
+__device__ __forceinline__ double ieee_div(double a, double b) {
+#ifdef EBM_FULL_DIV
+    return a / b;
+#else
+    return div_with_rcp(a, b, div_rcp(b));
+#endif
+}
+
+// ---- solver arithmetic (not order-constrained) ---------------------------------------------
+__device__ __forceinline__ double fast_rcp(double x) {
+    double r = __builtin_amdgcn_rcp(x);
+    double e = __builtin_fma(-x, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-x, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    return r;
+}
+
+// Forcing of one column at one step: the step's scalar, plus the column's constant offset, plus the
+// column's own Forcing{false} schedule (src/infrastructure.jl:208-241) evaluated at the model time
+// T of the step exactly as the reference does (:294-307): hold, ramp up, hold, ramp down, hold.
+__device__ __forceinline__ double column_forcing(const StepArgs &a, int col, double ft, double tyear) {
+    double f = a.fcol ? ft + a.fcol[col] : ft;
+    if (a.fsched) {
+        const double *w = a.fsched + (size_t)kSchedWords * col;     // wave-uniform: scalar loads
+        const double base = w[0], peak = w[1], cool = w[2], up = w[3], down = w[4];
+        const double d1 = w[5], d2 = w[6], d3 = w[7], d4 = w[8];
+        double v = cool;
+        if (tyear < d1) v = base;
+        else if (tyear < d2) v = base + up * (tyear - d1);
+        else if (tyear < d3) v = peak;
+        else if (tyear < d4) v = peak + down * (tyear - d3);
+        f = f + v;
+    }
+    return f;
+}
+
+// ---- chunk loads / stores: 8*C contiguous bytes per lane, 16-byte accesses ------------------
+// `f` is a wave-uniform base (kept in SGPRs), `k0` the lane's first cell: the access compiles to
+// the saddr + voffset form, so no per-lane 64-bit pointers are kept alive.
+template <int C>
+__device__ __forceinline__ void load_chunk(const double *__restrict__ f, unsigned k0, double (&v)[C]) {
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        double2 d = *reinterpret_cast<const double2 *>(f + (k0 + 2 * j));
+        v[2 * j] = d.x;
+        v[2 * j + 1] = d.y;
+    }
+}
+template <int C>
+__device__ __forceinline__ void store_chunk(double *__restrict__ f, const double (&v)[C], unsigned k0, int nlat) {
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        double2 d;
+        d.x = ((int)k0 + 2 * j < nlat) ? v[2 * j] : 0.0;           // padding cells stay zero
+        d.y = ((int)k0 + 2 * j + 1 < nlat) ? v[2 * j + 1] : 0.0;
+        EBM_STORE2(f + (k0 + 2 * j), d);
+    }
+}
+
+}  // namespace ebm

@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (ebm_kernels.hip) and the host runtime
+// Internal declarations shared by the HIP kernels (the other .hip files of this directory) and the host runtime
 // behind the C ABI (ebm_runtime.hip).  Not part of the public interface (include/ebm_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,7 +142,7 @@ constexpr int kMaxLat2 = 1536;          // longest meridian stepped with 2 cells
 LaunchCfg choose_launch(int nlat, int cells_requested);
 hipError_t prepare_kernels(const LaunchCfg &cfg);   // raises the dynamic-LDS limit if needed
 // One workgroup per column.  mode: OutMode; OUT_LOOP runs a.nfused steps per launch.
-// The per-step MIZ kernels, one function per build part of ebm_kernels.hip (EBM_PART); nullptr = not compiled
+// The per-step MIZ kernels, one function per translation unit (miz_step_*.hip, miz_resident*.hip); nullptr = not compiled
 using KernelFn = void (*)(const StepArgs);
 KernelFn miz_step_kernels_identity(int cells, int mode, int threads);
 KernelFn miz_step_kernels_nonuniform(int cells, int mode, int threads);

@@ -1,0 +1,543 @@
+// HIP kernels (gfx950 / CDNA4, wave64) for the energy-balance time-stepping hot path.
+//
+// One workgroup of T threads integrates one meridian (column) for one step; thread t owns the
+// C contiguous cells t*C .. t*C+C-1 ("chunk ownership") for the whole step.  A lane reads its
+// 8*C contiguous bytes with 16-byte loads, so a wave covers 64*8*C contiguous bytes of the
+// latitude axis per field.  Everything the reference does in ~60 temporary vectors per step
+// (src/miz.jl:150-196) is fused into one kernel:
+//
+//   phase A  loads; water temperature; right-hand side of the T0 system (3-point stencil: the
+//            chunk interior comes from registers, the two halo cells from the neighbouring
+//            lanes through LDS, zero-flux at equator and pole)
+//   phase B  T0 solve: active-set Newton on the piecewise-linear system of src/miz.jl:33-45.
+//            Each linear system is tridiagonal and is solved per meridian by a chunk
+//            partition (each thread Thomas-eliminates its C rows in registers) followed by
+//            parallel cyclic reduction of the T-row interface system in LDS
+//   phase D  Tbar stencil, radiative + lateral fluxes, enthalpy Euler step, redistribution,
+//            floe size / thickness / concentration update, 16-byte stores
+//
+// Kernels of the library, and where each is defined and instantiated:
+//   miz_step_kernel<C, GRID, OUT, T, IMEX>   one step per launch; OUT: state only / + diagnostics / savesol! from
+//                                       registers (annual-mean sums, raw snapshots); IMEX: the implicit-diffusion
+//                                       extension (one more tridiagonal solve per step, see include/ebm_hip.h)
+//                                       [ebm_miz_step.h; miz_step_identity.hip, miz_step_nonuniform.hip, miz_step_imex.hip]
+//   miz_fused_kernel<C, GRID, T>        K steps per launch, the whole state in registers (<= 512 threads; 768 with C = 2)
+//                                       [ebm_miz_fused.h; this file, with savesol!'s sums miz_resident_save.hip]
+//   miz_resident_kernel<GRID, T, IMEX, SAVE>  K steps per launch, the state resident in LDS (more than 512 threads; the extension;
+//                                       launches of many columns at any size; SAVE: with savesol!'s sums, for ebm_integrate)
+//                                       [ebm_miz_resident.h; miz_resident.hip, SAVE: miz_resident_save.hip]
+//   classic_step_kernel<C, MODE>        WE15 model: single step / savesol! / K steps per launch            [this file]
+//   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
+//   finish_mean, hemispheric_mean, mask_from_t0, derive_params, divide, split / unsplit_fields, noise_innovations,
+//   noise_sequence, equilibrium_check, compact_active: small helpers                                       [this file]
+//   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
+// and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
+// ebm_device.h (stores, parameter block, IEEE division, chunk loads), ebm_noise.h, ebm_solve.h (halo exchanges, the
+// tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
+// C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
+// workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
+// the 447 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
+// (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
+// ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
+//
+// Arithmetic policy.  Everything outside the tridiagonal solves is a bit-exact restatement of
+// the reference's expressions (IEEE division, no FMA contraction: build with
+// -ffp-contract=off; the order of operations is the reference's).  The solves are free to use
+// any arithmetic (explicit FMAs, v_rcp_f64 + Newton): their result is defined by the linear
+// system, not by an operation order.
+//
+// No MFMA: there is no dense contraction on this path; it is HBM-/fp64-VALU-bound.
+#include "ebm_kernel_table.h"
+
+namespace ebm {
+
+// ---- classic (WE15) step, src/classic.jl:37-71 ------------------------------------------------
+// MODE: OUT_STATE (T, h written if write_diag), OUT_SAVE (savesol! from registers) or OUT_LOOP
+// (a.nfused steps per launch, E and Tg in registers between steps).
+struct ClassicCellOut {
+    double q[QC_COUNT];
+};
+template <int C, int MODE>
+__global__ void __launch_bounds__(1024) classic_step_kernel(const StepArgs a) {
+    static_assert(C == 2 || C == 4, "cells per thread");
+    constexpr bool LOOP = MODE == OUT_LOOP;
+    extern __shared__ double smem[];
+    const int T = blockDim.x, t = threadIdx.x, col = step_column(a);
+    const int nlat = a.nlat;
+    const unsigned k0 = (unsigned)t * C;
+    double *P0 = smem, *P1 = smem + 3 * T;
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
+    double *const st = a.state + (size_t)col * (size_t)a.pitch;          // wave-uniform
+    ColumnNoise nz;                                                    // LOOP: N_c in memory (noise_sequence_kernel)
+    if (!LOOP && a.noise) nz.load(a, col);                             // before the state is loaded, and any barrier
+    double E[C], Tg[C];
+    load_chunk<C>(st + C_E * a.fstride, k0, E);
+    load_chunk<C>(st + C_Tg * a.fstride, k0, Tg);
+    const int nloop = LOOP ? a.nfused : 1;
+    for (int step = 0; step < nloop; ++step) {
+        // per-latitude statics (get_statics, src/classic.jl:18-29): re-read every step (L2 hits) rather
+        // than kept in 48 registers across the fused loop
+        const double *ge = geom;
+        if constexpr (LOOP) asm volatile("" : "+s"(ge));
+        double xk[C], aw[C], Sb[C], kd[C], ca[C], cc[C];
+        load_chunk<C>(ge + G_X * a.gstride, k0, xk);
+        load_chunk<C>(ge + G_AW * a.gstride, k0, aw);
+        load_chunk<C>(ge + G_SB * a.gstride, k0, Sb);
+        load_chunk<C>(ge + G_KDIAG * a.gstride, k0, kd);
+        load_chunk<C>(ge + G_KSUB * a.gstride, k0, ca);   // off-diagonals of kappa
+        load_chunk<C>(ge + G_KSUP * a.gstride, k0, cc);
+        const int slot = a.slot + step;
+        const double ct = a.sched ? a.sched[slot].ct : a.ct;
+        const double ct_next = a.sched ? a.sched[slot].ct_next : a.ct_next;
+        const double ft = a.sched ? a.sched[slot].ft : a.ft;
+        double f = column_forcing(a, col, ft, a.sched ? a.sched[slot].tyear : a.tyear);
+        if (a.noise) {
+            if constexpr (LOOP) f = f + nz.at_step<true>(a, col, step, a.sched[slot].n);
+            else f = f + nz.advance(noise_innovation(a.seed, nz.stream, a.sched ? a.sched[slot].n : a.step));
+        }
+        double b[C], d[C], oT[C], oh[C], xs[C];
+#pragma unroll
+        for (int i = 0; i < C; ++i) {
+            const bool valid = (int)k0 + i < nlat;
+            double Ek = E[i];
+            const double S_i = Sb[i] - (p.S1 * ct) * xk[i];                            // :23-24
+            const double S_ip1 = Sb[i] - (p.S1 * ct_next) * xk[i];
+            const double alpha = bool_mul(aw[i], Ek > 0.0) + bool_mul(p.ai, Ek < 0.0); // :47
+            const double Cc = alpha * S_i + p.cg_tau * Tg[i] - p.A + f;                // :48
+            const double T0 = ieee_div(Cc, p.M - ieee_div(p.kLf, Ek));                 // :50
+            const double Tk = bool_mul(ieee_div(Ek, p.cw), Ek >= 0.0) + bool_mul(bool_mul(T0, Ek < 0.0), T0 < 0.0);
+            Ek = Ek + p.dt * (Cc - p.M * Tk + p.Fb);                                   // :53
+            const double den = p.M - ieee_div(p.kLf, Ek);
+            const double q = bool_mul(bool_mul(ieee_div(p.dc, den), T0 < 0.0), Ek < 0.0);       // :56
+            const double rhs = Tg[i] + p.dt_tau * (bool_mul(ieee_div(Ek, p.cw), Ek >= 0.0) +
+                               bool_mul(bool_mul(ieee_div(p.ai * S_ip1 - p.A + f, den), T0 < 0.0), Ek < 0.0));
+            b[i] = valid ? kd[i] - q : 1.0;
+            d[i] = valid ? rhs : 0.0;
+            E[i] = valid ? Ek : 0.0;                                                   // padding cells stay zero
+            oT[i] = Tk;
+            oh[i] = bool_mul(ieee_div(-Ek, p.Lf), Ek < 0.0);                           // :65
+        }
+        const bool last = step == nloop - 1;
+        if (last) store_chunk<C>(st + C_E * a.fstride, E, k0, nlat);
+        if (a.write_diag && last) {
+            store_chunk<C>(st + C_T * a.fstride, oT, k0, nlat);
+            store_chunk<C>(st + C_h * a.fstride, oh, k0, nlat);
+        }
+        partition_solve<C>(ca, b, cc, d, xs, t, T, P0, P1);   // Implicit Euler for Tg, :55-63
+#pragma unroll
+        for (int i = 0; i < C; ++i) Tg[i] = ((int)k0 + i < nlat) ? xs[i] : 0.0;
+        if (last) store_chunk<C>(st + C_Tg * a.fstride, Tg, k0, nlat);
+        if constexpr (MODE == OUT_SAVE) {
+#pragma unroll
+            for (int j = 0; j < C / 2; ++j) {
+                ClassicCellOut c0, c1;
+                c0.q[QC_E] = E[2 * j];  c0.q[QC_Tg] = Tg[2 * j];  c0.q[QC_T] = oT[2 * j];  c0.q[QC_h] = oh[2 * j];
+                c1.q[QC_E] = E[2 * j + 1];  c1.q[QC_Tg] = Tg[2 * j + 1];  c1.q[QC_T] = oT[2 * j + 1];  c1.q[QC_h] = oh[2 * j + 1];
+                const unsigned kp = k0 + 2 * j;
+                save_pair<QC_COUNT>(a, (size_t)col * (size_t)a.pitch, (unsigned)(j * 2 * T + 2 * t), kp, c0, c1,
+                                    (int)kp < nlat, (int)kp + 1 < nlat);
+            }
+        }
+        // (no barrier between the solves of consecutive steps: after a solve's last barrier the threads only READ P0; the
+        // next solve first writes each thread's own words of P1 — which nobody reads after that last barrier — and passes
+        // a barrier of its own before anything is written to P0)
+    }
+    if (!LOOP && a.noise) nz.store(a, col);                            // after the solve's last barrier
+}
+
+// Active set of a T0 field (after ebm_set_field(T0)): bit i of amask[col][t] <=> T0 < Tm in cell t*C+i.
+__global__ void mask_from_t0_kernel(const StepArgs a, int C) {
+    const int T = blockDim.x, t = threadIdx.x, col = blockIdx.x;
+    const double Tm = a.p[param_set(a, col)].Tm;
+    const double *T0 = a.state + S_T0 * a.fstride + (size_t)col * (size_t)a.pitch + (size_t)t * C;
+    unsigned m = 0;
+    for (int i = 0; i < C; ++i)
+        if (t * C + i < a.nlat && T0[i] < Tm) m |= 1u << i;
+    a.amask[(size_t)col * T + t] = (unsigned short)m;
+}
+
+// ebm_noise_innovations: one thread per (column, step), through the step kernels' noise_innovation
+__global__ void __launch_bounds__(256) noise_innovations_kernel(const NoiseRec *__restrict__ noise, unsigned long long seed,
+                                                                long long first, int nsteps, long long total,
+                                                                double *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long c = i / nsteps, k = i - c * nsteps;
+    out[i] = noise_innovation(seed, noise[c].stream, first + k);
+}
+// The N_c sequence of a fused launch for the kernels that read it from memory (ColumnNoise, MEM): one wave per column, lane l
+// -> a.nseq[col][l] = N_c after step l of the launch; N_c advanced by the launch's a.nfused steps
+__global__ void __launch_bounds__(64) noise_sequence_kernel(const StepArgs a) {
+    const int col = step_column(a);
+    ColumnNoise nz;
+    nz.load(a, col);
+    const double nl = nz.sequence(a, a.nfused);
+    if ((int)threadIdx.x < a.nfused) a.nseq[(size_t)col * kNoiseMaxFused + threadIdx.x] = nl;
+    nz.store(a, col);
+}
+hipError_t launch_noise_sequence(const StepArgs &a, int first, int count, hipStream_t s) {
+    if (first < 0 || count < 1 || a.nfused < 1 || a.nfused > kNoiseMaxFused) return hipErrorInvalidValue;
+    StepArgs b = a;
+    b.col0 = first;
+    noise_sequence_kernel<<<dim3(count), 64, 0, s>>>(b);
+    return hipGetLastError();
+}
+hipError_t launch_noise_innovations(const NoiseRec *noise, unsigned long long seed, long long first, int nsteps, int ncol,
+                                    double *out, hipStream_t s) {
+    const long long total = (long long)nsteps * ncol;
+    if (total <= 0) return hipSuccess;
+    noise_innovations_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, s>>>(noise, seed, first, nsteps, total, out);
+    return hipGetLastError();
+}
+
+// rcp_dt / rcp_cdn of the parameter block, with the device's own refinement sequence (see Params)
+__global__ void derive_params_kernel(Params *p) {
+    p->rcp_dt = div_rcp(p->dt);
+    p->rcp_cdn = div_rcp(p->c_dn);
+}
+hipError_t launch_derive_params(Params *p_dev, hipStream_t s) {
+    derive_params_kernel<<<1, 1, 0, s>>>(p_dev);
+    return hipGetLastError();
+}
+
+// Self-test hook (ebm_selftest_divide): q[i] = ieee_div(a[i], b[i]) with the device routine the
+// physics uses, so that tests can compare it bit for bit with host IEEE division.
+__global__ void divide_kernel(const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ q, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) q[i] = ieee_div(a[i], b[i]);
+}
+hipError_t launch_divide(const double *a, const double *b, double *q, int n, hipStream_t s) {
+    divide_kernel<<<(n + 255) / 256, 256, 0, s>>>(a, b, q, n);
+    return hipGetLastError();
+}
+
+// hemispheric_mean (src/utilities.jl:397-403) of one field, one workgroup per column:
+//   int = 0; for i in 1:nx-1: int += (vec[i]+vec[i+1]) * (x[i+1]-x[i]) / 2.0
+// The terms are formed in parallel (elementwise, exact order of operations); the accumulation is
+// the reference's strictly sequential left-to-right sum, done by one lane out of LDS, so the
+// result is bit-identical to the reference's loop.
+__global__ void hemispheric_mean_kernel(const double *__restrict__ field, const double *__restrict__ x,
+                                        int pitch, int nlat, double *__restrict__ out) {
+    extern __shared__ double terms[];
+    const double *v = field + (size_t)blockIdx.x * pitch;
+    for (int i = threadIdx.x; i < nlat - 1; i += blockDim.x)
+        terms[i] = ieee_div((v[i] + v[i + 1]) * (x[i + 1] - x[i]), 2.0);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double acc = 0.0;
+        for (int i = 0; i < nlat - 1; ++i) acc = acc + terms[i];
+        out[blockIdx.x] = acc;
+    }
+}
+// ebm_equilibrate's year-end test, one workgroup per active column (EquilArgs): rows k < nlat of this year's fields
+// against last year's snapshot, which takes this year's values in the same pass.  The distance is a max of exact
+// |differences|, NaN-propagating, so its value does not depend on the order of the reduction (lanes, then the waves
+// through LDS); d <= tol is false for NaN.
+__device__ __forceinline__ double max_nan(double x, double y) { return (x != x || x > y) ? x : y; }
+__global__ void __launch_bounds__(256) equilibrium_check_kernel(const EquilArgs e) {
+    __shared__ double part[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int col = e.cols[blockIdx.x];
+    const size_t row = (size_t)col * (size_t)e.pitch;
+    bool ok = true;
+    for (int v = 0; v < e.nvars; ++v) {
+        const double *cur = e.state + (size_t)e.slot[v] * (size_t)e.fstride + row;
+        double *prev = e.snap + (size_t)v * (size_t)e.ncol * (size_t)e.pitch + row;
+        double d = 0.0;
+        for (int k = t; k < e.nlat; k += 256) {
+            const double c = cur[k];
+            d = max_nan(d, fabs(c - prev[k]));
+            prev[k] = c;
+        }
+        for (int off = 32; off > 0; off >>= 1) d = max_nan(d, __shfl_xor(d, off, 64));
+        if (lane == 0) part[wave] = d;
+        __syncthreads();
+        d = max_nan(max_nan(part[0], part[1]), max_nan(part[2], part[3]));
+        __syncthreads();                                  // (part is refilled by the next variable)
+        if (e.compare && t == 0) e.resid[(size_t)v * (size_t)e.ncol + col] = d;
+        ok = ok && d <= e.tol[v];
+    }
+    if (t == 0) {
+        e.years[col] = e.year;
+        e.frozen[col] = (e.may_freeze && ok) ? 1 : 0;
+    }
+}
+hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s) {
+    if (nactive < 1 || nactive > e.ncol || e.nvars < 1 || e.nvars > kMaxQuantities) return hipErrorInvalidValue;
+    equilibrium_check_kernel<<<nactive, 256, 0, s>>>(e);
+    return hipGetLastError();
+}
+
+// The next active list, in one workgroup: a stable stream compaction of in[0 .. n) by !frozen[in[i]], 1024 entries per
+// round — per wave a ballot and a popcount below the lane, across the 16 waves a scan of their counts in LDS.
+__global__ void __launch_bounds__(1024) compact_active_kernel(const int *__restrict__ in, int n, const int *__restrict__ frozen,
+                                                              int *__restrict__ out, int *__restrict__ count) {
+    __shared__ int wave_base[17];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int total = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + t;
+        const int c = i < n ? in[i] : 0;
+        const bool keep = i < n && frozen[c] == 0;
+        const unsigned long long ballot = __ballot(keep);
+        const int below = __popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_base[wave + 1] = __popcll(ballot);
+        __syncthreads();
+        if (t == 0) {
+            wave_base[0] = 0;
+            for (int w = 1; w <= 16; ++w) wave_base[w] += wave_base[w - 1];
+        }
+        __syncthreads();
+        if (keep) out[total + wave_base[wave] + below] = c;
+        total += wave_base[16];
+        __syncthreads();                                  // (wave_base is refilled by the next round)
+    }
+    if (t == 0) *count = total;
+}
+hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s) {
+    if (n < 1) return hipErrorInvalidValue;
+    compact_active_kernel<<<1, 1024, 0, s>>>(in, n, frozen, out, count);
+    return hipGetLastError();
+}
+
+// The diffusion operator on its own: out = base + D d/dx[(1-x^2) d temp/dx], one thread per cell —
+// diffusion!(base, temp, st, par) / diffusion(T, st, par), src/infrastructure.jl:495-533, with the
+// same device functions (and hence the same bits) the step kernels use inside their fused physics.
+template <int GRID>
+__global__ void diffusion_kernel(const double *__restrict__ temp, const double *__restrict__ base,
+                                 double *__restrict__ out, const double *__restrict__ geom_sets, long long gstride,
+                                 const Params *__restrict__ p_sets, const int *__restrict__ pset, long long set_stride,
+                                 int pitch, int nlat) {
+    const int col = blockIdx.y;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nlat) return;
+    const int set = pset ? pset[col] : 0;
+    const double *const geom = geom_sets + set * set_stride;
+    const Params *const pp = p_sets + set;
+    const double *T = temp + (size_t)col * pitch;
+    const double tk = T[k], tm = k > 0 ? T[k - 1] : 0.0, tp = k < nlat - 1 ? T[k + 1] : 0.0;
+    double term;
+    if (GRID == 0) {
+        term = diffusion_uniform(k, nlat, geom[G_LO * gstride + k], geom[G_DI * gstride + k], geom[G_UP * gstride + k],
+                                 tm, tk, tp);
+    } else {
+        const double *x = geom + G_X * gstride;
+        const double xk = x[k], xm = k > 0 ? x[k - 1] : 0.0, xp = k < nlat - 1 ? x[k + 1] : 0.0;
+        double xxl, xxr;
+        const double Fl = interface_flux(k, nlat, xm, xk, tm, tk, xxl);
+        const double Fr = interface_flux(k + 1, nlat, xk, xp, tk, tp, xxr);
+        term = ieee_div(pp->D * (Fr - Fl), xxr - xxl);                  // :524
+    }
+    out[(size_t)col * pitch + k] = (base ? base[(size_t)col * pitch + k] : 0.0) + term;
+}
+hipError_t launch_diffusion(const double *temp, const double *base, double *out, const double *geom, long long gstride,
+                            const Params *p, const int *pset, long long set_stride, int grid_kind, int pitch, int nlat,
+                            int ncol, hipStream_t s) {
+    dim3 grid((nlat + 255) / 256, ncol), block(256);
+    if (grid_kind == 0)
+        diffusion_kernel<0><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pset, set_stride, pitch, nlat);
+    else diffusion_kernel<1><<<grid, block, 0, s>>>(temp, base, out, geom, gstride, p, pset, set_stride, pitch, nlat);
+    return hipGetLastError();
+}
+
+// annual_mean (src/infrastructure.jl:536-544, crossmean src/utilities.jl:390-395): sum / nt, from
+// the pair-split layout of save_pair to the natural [col][pitch] one; the sum restarts at zero.  blockIdx.y = saved
+// variable (one launch for all of them): dst / sum advance by var_stride per variable.
+__global__ void finish_mean_kernel(double *__restrict__ dst, double *__restrict__ sum, double nt, int threads,
+                                   int cells, long long var_stride) {
+    const int t = threadIdx.x, col = blockIdx.x;
+    const size_t base = (size_t)blockIdx.y * (size_t)var_stride + (size_t)col * (size_t)threads * cells;
+    for (int j = 0; j < cells / 2; ++j) {
+        double2 *sp = reinterpret_cast<double2 *>(sum + base + (size_t)(j * 2 * threads + 2 * t));
+        const double2 s = *sp;
+        double2 m;
+        m.x = s.x / nt;
+        m.y = s.y / nt;
+        *reinterpret_cast<double2 *>(dst + base + (size_t)(t * cells + 2 * j)) = m;
+        double2 z;
+        z.x = 0.0;
+        z.y = 0.0;
+        *sp = z;
+    }
+}
+
+// Pair-split -> natural layout, in place: the diagnostic fields as the 4-cells-per-thread step kernels store them
+// (pair j of thread t at j*2T + 2t) become [col][pitch] with cell k at k.  One workgroup per column holds the whole
+// column in registers across a barrier, so the permutation needs no second buffer.  blockIdx.y = field: `fields`
+// advances by field_stride per field.
+__global__ void unsplit_fields_kernel(double *__restrict__ fields, long long field_stride, int threads) {
+    const int t = threadIdx.x;
+    double *f = fields + (size_t)blockIdx.y * (size_t)field_stride + (size_t)blockIdx.x * (size_t)threads * 4;
+    const double2 p0 = *reinterpret_cast<const double2 *>(f + 2 * t);
+    const double2 p1 = *reinterpret_cast<const double2 *>(f + 2 * threads + 2 * t);
+    __syncthreads();
+    *reinterpret_cast<double2 *>(f + 4 * t) = p0;
+    *reinterpret_cast<double2 *>(f + 4 * t + 2) = p1;
+}
+// natural -> pair-split, the inverse (a field the caller set, about to be read by a kernel that expects the split layout)
+__global__ void split_fields_kernel(double *__restrict__ fields, long long field_stride, int threads) {
+    const int t = threadIdx.x;
+    double *f = fields + (size_t)blockIdx.y * (size_t)field_stride + (size_t)blockIdx.x * (size_t)threads * 4;
+    const double2 p0 = *reinterpret_cast<const double2 *>(f + 4 * t);
+    const double2 p1 = *reinterpret_cast<const double2 *>(f + 4 * t + 2);
+    __syncthreads();
+    *reinterpret_cast<double2 *>(f + 2 * t) = p0;
+    *reinterpret_cast<double2 *>(f + 2 * threads + 2 * t) = p1;
+}
+hipError_t launch_split_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
+                               hipStream_t s) {
+    if (cfg.cells != 4) return hipSuccess;
+    split_fields_kernel<<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
+    return hipGetLastError();
+}
+
+hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
+                                 hipStream_t s) {
+    if (cfg.cells != 4) return hipSuccess;               // two cells per thread: the layouts coincide
+    unsplit_fields_kernel<<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
+    return hipGetLastError();
+}
+
+// ---- host-side launchers ----------------------------------------------------------------------
+// Cells per thread: 4 unless the caller asks for 2 (ebm_options::cells_per_thread; nlat <= kMaxLat2 = 1536: the
+// fused kernel then still fits three waves per SIMD).  4 is the throughput geometry (32 contiguous bytes per lane and
+// field); a run of a FEW short meridians is latency-bound on a handful of waves, and 2 cells per thread put twice as
+// many SIMDs to work on every meridian.  The geometry — and with it the tridiagonal partition, i.e. the rounding of the
+// solves — is a function of (nlat, cells) ONLY, never of the number of columns: a member gives the same bits alone, in
+// a large ensemble and under any sharding.
+LaunchCfg choose_launch(int nlat, int cells_requested) {
+    LaunchCfg cfg{};
+    if (nlat > kMaxLat) {
+        cfg.threads = 0;
+        return cfg;
+    }
+    const int cells = (cells_requested == 2 && nlat <= kMaxLat2) ? 2 : 4;
+    const int chunks = (nlat + cells - 1) / cells;
+    cfg.threads = ((chunks + 63) / 64) * 64;
+    if (cells == 2 && cfg.threads > 512) cfg.threads = 768;     // the one size compiled beyond 512 (padding cells stay zero)
+    cfg.cells = cells;
+    // 2 x 3T cyclic reduction + the MIZ stash of Ew, h, Tw (3 C T)
+    cfg.lds_bytes = sizeof(double) * (size_t)cfg.threads * (6 + 3 * (size_t)cells);
+    return cfg;
+}
+
+namespace {
+
+// which fused-K kernel steps a handle's columns (one rule for the kernel table and the LDS size): the two compute the same
+// bits, so the choice is free to depend on the column count (LaunchCfg::fused_in_lds, set by the runtime)
+bool fused_state_in_lds(const LaunchCfg &cfg, bool imex) {
+    return imex || (cfg.cells == 4 && (cfg.threads > kFusedRegThreads || cfg.fused_in_lds));
+}
+KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
+    const int cells = cfg.cells, threads = cfg.threads;
+    if (mode == OUT_LOOP_SAVE) {
+        if (cells == 4) return miz_resident_save_kernels(grid_kind, threads, imex);
+        return imex ? nullptr : miz_fused2_save_kernels(grid_kind, threads);
+    }
+    if (mode == OUT_LOOP) {        // fused-K: state in registers where it fits, resident in LDS otherwise
+        if (fused_state_in_lds(cfg, imex)) return cells != 4 ? nullptr : miz_resident_kernels(grid_kind, threads, imex);
+        if (cells == 2) return grid_kind == 0 ? miz_fused_for<2, 0>(threads) : miz_fused_for<2, 1>(threads);
+        return grid_kind == 0 ? miz_fused_for<4, 0>(threads) : miz_fused_for<4, 1>(threads);
+    }
+    if (imex) return cells != 4 ? nullptr : miz_step_kernels_imex(grid_kind, mode, threads);
+    return grid_kind == 0 ? miz_step_kernels_identity(cells, mode, threads) : miz_step_kernels_nonuniform(cells, mode, threads);
+}
+template <int C>
+KernelFn classic_kernel_c(int mode) {
+    switch (mode) {
+        case OUT_STATE:
+        case OUT_DIAG: return classic_step_kernel<C, OUT_STATE>;
+        case OUT_SAVE: return classic_step_kernel<C, OUT_SAVE>;
+        case OUT_LOOP: return classic_step_kernel<C, OUT_LOOP>;
+        default: return nullptr;
+    }
+}
+KernelFn classic_kernel(int cells, int mode) { return cells == 2 ? classic_kernel_c<2>(mode) : classic_kernel_c<4>(mode); }
+// LDS of a launch: the fused register kernel only needs the solve's buffers; the resident kernel 4T for the solve and
+// 4 fields x 4 cells x T for the state
+size_t miz_lds_bytes(const LaunchCfg &cfg, int mode, bool imex) {
+    if (mode == OUT_LOOP_SAVE) return sizeof(double) * (cfg.cells == 4 ? 20 : 6) * (size_t)cfg.threads;
+    if (mode == OUT_LOOP) return sizeof(double) * (fused_state_in_lds(cfg, imex) ? 20 : 6) * (size_t)cfg.threads;
+    return cfg.lds_bytes;
+}
+
+}  // namespace
+
+// Dynamic LDS above the 64 KiB default must be requested per kernel.
+hipError_t prepare_kernels(const LaunchCfg &cfg) {
+    auto raise = [](KernelFn fn, size_t bytes) -> hipError_t {
+        if (!fn) return hipErrorInvalidValue;
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    };
+    for (int grid = 0; grid < 2; ++grid)
+        for (int imex = 0; imex < (cfg.cells == 4 ? 2 : 1); ++imex) {
+            if (cfg.lds_bytes > 64 * 1024)
+                for (int mode = OUT_STATE; mode <= OUT_SAVE; ++mode) {   // (the fused register kernel needs 6T doubles <= 24 KiB)
+                    hipError_t e = raise(miz_kernel(cfg, grid, mode, imex != 0), cfg.lds_bytes);
+                    if (e != hipSuccess) return e;
+                }
+            // the resident fused-K kernels and their savesol! variants (four cells per thread): 160 T bytes
+            const size_t bytes = sizeof(double) * 20 * (size_t)cfg.threads;
+            if (cfg.cells != 4 || bytes <= 64 * 1024) continue;
+            hipError_t e = raise(miz_resident_kernels(grid, cfg.threads, imex != 0), bytes);
+            if (e == hipSuccess) e = raise(miz_resident_save_kernels(grid, cfg.threads, imex != 0), bytes);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
+bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
+    return miz_kernel(cfg, grid_kind, mode, imex) != nullptr;
+}
+
+hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, int first, int count,
+                           hipStream_t s) {
+    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex);
+    if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
+    // fused launches whose kernel reads N_c from memory: everything but miz_fused_kernel up to kFusedRegThreads threads
+    const bool fused = mode == OUT_LOOP || mode == OUT_LOOP_SAVE;
+    const bool in_registers = !fused_state_in_lds(cfg, imex) && cfg.threads <= kFusedRegThreads &&
+                              !(mode == OUT_LOOP_SAVE && cfg.cells == 4);
+    if (a.noise && fused && !in_registers) {
+        hipError_t e = launch_noise_sequence(a, first, count, s);
+        if (e != hipSuccess) return e;
+    }
+    StepArgs b = a;
+    b.col0 = first;
+    fn<<<dim3(count), dim3(cfg.threads), miz_lds_bytes(cfg, mode, imex), s>>>(b);
+    return hipGetLastError();
+}
+
+hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s) {
+    KernelFn fn = classic_kernel(cfg.cells, mode);
+    if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
+    if (a.noise && mode == OUT_LOOP) {                  // the fused classic kernel reads N_c from memory
+        hipError_t e = launch_noise_sequence(a, first, count, s);
+        if (e != hipSuccess) return e;
+    }
+    StepArgs b = a;
+    b.col0 = first;
+    fn<<<dim3(count), dim3(cfg.threads), sizeof(double) * 6 * (size_t)cfg.threads, s>>>(b);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_from_t0(const StepArgs &a, int ncol, const LaunchCfg &cfg, hipStream_t s) {
+    mask_from_t0_kernel<<<ncol, cfg.threads, 0, s>>>(a, cfg.cells);
+    return hipGetLastError();
+}
+
+hipError_t launch_hemispheric_mean(const double *field, const double *x, int pitch, int nlat, int ncol, double *out,
+                                   hipStream_t s) {
+    hemispheric_mean_kernel<<<ncol, 256, sizeof(double) * (size_t)nlat, s>>>(field, x, pitch, nlat, out);
+    return hipGetLastError();
+}
+hipError_t launch_finish_mean(double *dst, double *sum, double nt, int ncol, int nvars, long long var_stride,
+                              const LaunchCfg &cfg, hipStream_t s) {
+    finish_mean_kernel<<<dim3(ncol, nvars), cfg.threads, 0, s>>>(dst, sum, nt, cfg.threads, cfg.cells, var_stride);
+    return hipGetLastError();
+}
+
+}  // namespace ebm

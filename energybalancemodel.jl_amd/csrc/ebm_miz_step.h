@@ -1,0 +1,320 @@
+// miz_step_kernel: one MIZ step per launch.
+#pragma once
+#include "ebm_miz_pieces.h"
+
+namespace ebm {
+
+// MIZ step: one workgroup per meridian.
+//
+// Geometry (choose_launch): C = 4 cells per thread, T = ceil(nlat/4 / 64)*64 <= 1024 threads (<= 128
+// VGPRs).  A 4096-cell fp64 meridian fills a CU (512 KiB of VGPRs + 160 KiB of LDS): one workgroup per
+// CU; shorter meridians run several workgroups per CU, which overlap each other.  Longer meridians
+// do not fit one workgroup and are refused (EBM_ERR_UNSUPPORTED).
+//
+// LDS map (doubles; per-cell arrays hold cell i of thread t at i*T + t: lane-consecutive,
+// conflict-free):
+//   P0 = [0,3T), P1 = [3T,6T)    cyclic-reduction ping-pong; idle otherwise, then borrowed for
+//                                the r / g / Tbar halo exchanges
+//   sEw, sh, sTw = [6T, 6T+3CT)  Ew, h, Tw of every cell, parked across the T0 solve so that the
+//                                solve has the register file to itself
+//
+// OUT (OutMode): what is written besides the prognostics (OUT_STATE, OUT_DIAG, OUT_SAVE).
+// TT: workgroup size, a compile-time constant (LDS offsets become immediates).
+//
+// IMEX: the implicit-diffusion EXTENSION (model EBM_MODEL_MIZ_IMEX; not in the reference — defined in
+// include/ebm_hip.h): before the cell updates the explicit increment of
+// every cell's total enthalpy, dE = dt*(phi*Fvi + (1-phi)*Fvw), goes through one more tridiagonal solve per
+// meridian, (I - (dt/cw)*Dif) dE_new = dE — the same partition + cyclic reduction as the T0 system — and the
+// diffusion term of both vertical fluxes is corrected by (dE_new - dE)/dt.  Lifts the explicit limit
+// dt <= cw*dx^2/(2D) of the reference's step.
+// __launch_bounds__(TT, 4): the workgroup size is the compile-time TT, never more; four waves per SIMD keep the
+// 128-VGPR budget that lets a 1024-thread workgroup (and four 256-thread ones) share a CU.
+template <int C, int GRID, int OUT, int TT, bool IMEX>
+__global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
+    static_assert(C == 2 || C == 4, "cells per thread");
+    static_assert(OUT == OUT_STATE || OUT == OUT_DIAG || OUT == OUT_SAVE, "per-step kernel");
+    constexpr bool MAYDIAG = OUT != OUT_STATE;            // diagnostic stores compiled in
+    extern __shared__ double smem[];
+    constexpr int T = TT;
+    const int t = threadIdx.x, col = a.col0 + (int)blockIdx.x;
+    const int nlat = a.nlat;
+    const unsigned k0 = (unsigned)t * C;
+    double *P0 = smem, *P1 = smem + 3 * T;
+    double *sEw = smem + 6 * T + t, *sh = sEw + C * T, *sTw = sh + C * T;
+    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
+    const double *const geom = a.geom + pset * a.set_stride;
+    const double *const gX = geom + G_X * a.gstride;
+    double *const st = a.state + (size_t)col * (size_t)a.pitch;         // wave-uniform
+    const double Tm = p.Tm;
+    EBM_STAMP(0);
+    EBM_STAMPW(0);                                        // per wave: first instruction
+    // Warm start (src/miz.jl:47,52-54,64).  The reference carries T0 itself between steps; the
+    // active-set iteration only uses its sign pattern, so between steps the library carries that
+    // pattern (one bit per cell) and writes the fp64 T0 field on diagnostic launches only.
+    unsigned short *const cmask = a.amask + (size_t)col * T;            // wave-uniform
+    const double ct = a.sched ? a.sched[a.slot].ct : a.ct;              // per-step scalars (scalar loads)
+    const double ft = a.sched ? a.sched[a.slot].ft : a.ft;
+    ColumnNoise nz;
+    if (a.noise) nz.load(a, col);
+    const double f = step_forcing(a, nz, col, ft, a.sched ? a.sched[a.slot].tyear : a.tyear, a.sched ? a.sched[a.slot].n : a.step);
+    const bool diag = OUT == OUT_DIAG || (MAYDIAG && a.write_diag);
+
+    // ---------------- phase A: loads, water temperature, T0-system coefficients ----------
+    // Only phi and the right-hand side stay in registers across the solve; Ew, h, Tw wait in the
+    // LDS stash.  The second and later Newton iterations (a changed active set: < 0.1 % of column-steps at the
+    // reference's time steps, every second one with the extension's long ones) form the rows again from the stashed h
+    // and the two coefficient tables and call the same solve — one copy of the solve in the kernel.
+    double ph[C], rd[C], xs[C];
+    unsigned smask = cmask[t];                            // active set: bit i <=> T0_i < Tm
+    int it = 0;
+    bool again;
+    do {
+        double tlo[C], tup[C], dd[C];
+        // (the lane's cell index is made opaque inside the loop: hoisted out of it, the six addresses
+        // would live as per-lane 64-bit pointers instead of the wave-uniform base + 32-bit offset form)
+        unsigned kl = k0;
+        asm volatile("" : "+v"(kl));
+        load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
+        load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
+        if (it == 0) {
+            double Ew[C], hk[C], xk[C], r[C];
+            load_chunk<C>(st + S_Ew * a.fstride, kl, Ew);
+            load_chunk<C>(st + S_phi * a.fstride, kl, ph);
+            load_chunk<C>(st + S_h * a.fstride, kl, hk);
+            load_chunk<C>(gX, kl, xk);
+            // Padding cells (k >= nlat) need no special case in phases A and B: their state and table
+            // entries are zero, so their rows are decoupled (lo = up = 0, g = phi = 0) and finite.
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const double tw = water_temperature(p, Ew[i], ph[i]);
+                sEw[i * T] = Ew[i];
+                sh[i * T] = hk[i];
+                sTw[i * T] = tw;
+                dd[i] = t0_diag_excess(p, hk[i]);
+                r[i] = (1.0 - ph[i]) * (tw - Tm);
+            }
+            EBM_STAMP(1);
+            EBM_STAMPW(1);                                    // per wave: inputs arrived
+            double rl, rr;
+            halo_exchange(P0, P0 + T, t, T, r[0], r[C - 1], rl, rr);
+            EBM_STAMP(2);
+            // (this loop stays in the kernels — the same two lines in all three: moved into a helper, it changes how hipcc
+            // peels the first Newton iteration of this kernel and of miz_resident_kernel, and with it their whole code)
+#pragma unroll
+            for (int i = 0; i < C; ++i)
+                rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
+            __syncthreads();                                  // r halo reads done before P0 is reused
+        } else {
+            // second and later iterations (a changed active set): the right-hand side does not depend on the set and
+            // is still in registers, like phi; only the rows' ingredients are fetched / formed again — the same values
+#pragma unroll
+            for (int i = 0; i < C; ++i) dd[i] = t0_diag_excess(p, sh[i * T]);
+        }
+        EBM_STAMP(3);
+        // ---------------- phase B: active-set Newton, src/miz.jl:33-68 --------------------
+        ++it;
+        again = newton_iteration<C, TT>(tlo, tup, dd, ph, rd, xs, smask, t, T, k0, nlat, P0, P1);
+    } while (again && it < kMaxNewton);
+    count_newton(a, col, t, it, again ? 1 : 0);
+    {
+        // (the lane index is made opaque so that the mask word's per-lane 64-bit address is formed here
+        // again instead of being kept — and spilled — across the solve)
+        unsigned tl = (unsigned)t;
+        asm volatile("" : "+v"(tl));
+        cmask[tl] = (unsigned short)smask;                // new warm start, src/miz.jl:64
+    }
+    EBM_STAMP(6);
+    EBM_STAMPW(2);                                        // per wave: phase D starts
+
+    // ---------------- phase D: fluxes and state update ---------------------------------------
+    double xk[C];
+    load_chunk<C>(gX, k0, xk);
+    const double xl = gX[k0 > 0 ? k0 - 1 : 0], xr = gX[k0 + C];     // zero-padded table; unused at the ends
+    double g0[GRID == 0 ? C : 1], g1[GRID == 0 ? C : 1], g2[GRID == 0 ? C : 1];
+    if constexpr (GRID == 0 && !IMEX) {
+        // sub-, main and super-diagonal of par.D*get_diffop: on the identity grid the physics stencil
+        // and the solver's plain coefficients are the same three tables (build_tables)
+        load_chunk<C>(geom + G_LO * a.gstride, k0, g0);
+        load_chunk<C>(geom + G_DI * a.gstride, k0, g1);
+        load_chunk<C>(geom + G_UP * a.gstride, k0, g2);
+    }
+    double tb[C];
+    {
+        double T0[C];
+#pragma unroll
+        for (int i = 0; i < C; ++i) {
+            T0[i] = xs[i] + Tm;                                       // new warm start, :64
+            const double ti = jl_min(T0[i], Tm);                      // ice_temp, :31,65
+            xs[i] = (sh[i * T] == 0.0) ? 0.0 : ti;                    // Ti: zeroref!, :66
+            tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * sTw[i * T];       // Tbar, :21-26
+        }
+        if (MAYDIAG && diag) store_chunk<C>(st + S_T0 * a.fstride, T0, k0, nlat);
+    }
+    double tbl, tbr;
+    halo_exchange(P0, P0 + T, t, T, tb[0], tb[C - 1], tbl, tbr);
+    EBM_STAMP(7);
+    EBM_STAMPW(3);                                        // per wave: Tbar halo done
+    // Whole-line stores.  A lane owns 8*C contiguous bytes of every field; written pair by pair,
+    // each 128-B line would reach L2 in two halves ~10^4 cycles apart and be written back to HBM
+    // twice.  The first pair's new prognostics are parked in LDS words that are dead by then (cells
+    // 0,1 of the stash, the idle tail of the cyclic-reduction buffers) and all 32 bytes of a lane go
+    // out in two back-to-back 16-B stores once the second pair is done.
+    TbarStencil<C, GRID> stencil;
+    stencil.start(k0, nlat, xl, xk, tbl, tb);
+    double difx[IMEX ? C : 1];                            // IMEX: the corrected diffusion term of every cell
+    if constexpr (IMEX) {
+        double sol[C];
+        {
+            // rows of I - (dt/cw)*Dif and the right-hand side, the explicit increments
+            double ra[C], rb[C], rc[C], dE[C], dif[C], tlo[C], tup[C];
+            load_chunk<C>(geom + G_LO * a.gstride, k0, tlo);
+            load_chunk<C>(geom + G_UP * a.gstride, k0, tup);
+            imex_increments<C, GRID>(a, p, geom, k0, nlat, ct, f, xk, xl, xr, tb, tbl, tbr, ph, dif, dE);
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                // the explicit diffusion term waits in the Tw words of the stash (Tw is formed again below from the stashed
+                // Ew and phi — one division — instead of the whole stencil a second time)
+                sTw[i * T] = dif[i];
+                imex_row(p, tlo[i], tup[i], ra[i], rb[i], rc[i]);
+            }
+            partition_solve<C, TT>(ra, rb, rc, dE, sol, t, T, P0, P1);
+        }
+        __syncthreads();                                  // the solve's LDS reads are done before P0 is reused
+        {
+            // Only Ti (xs) and the solution crossed the solve in registers: phi and x are fetched again (the lane's cell
+            // index made opaque, so that the reloads are real), Tw and Tbar are formed again, the parked diffusion term comes
+            // back from the stash, and the explicit increment is evaluated a second time from it — same operands, same
+            // operations, same bits — for the correction (dE_new - dE)/dt.
+            unsigned kl = k0;
+            asm volatile("" : "+v"(kl));
+            load_chunk<C>(st + S_phi * a.fstride, kl, ph);
+            load_chunk<C>(gX, kl, xk);
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const double dif0 = sTw[i * T];
+                const double tw = water_temperature(p, sEw[i * T], ph[i]);
+                sTw[i * T] = tw;                                      // the stash holds Tw again for the cell updates
+                tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * tw;
+                const double dE = enthalpy_increment(p, (int)k0 + i, nlat, xk[i], ct, tb[i], dif0, f, ph[i]);
+                difx[IMEX ? i : 0] = dif0 + div_with_rcp(sol[i] - dE, p.dt, p.rcp_dt);
+            }
+        }
+    }
+    double *const park0 = P0 + 2 * T + t;                 // P0[2T..3T), P1[0..3T): clear of the halo words
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        MizCellOut o[2];
+        __builtin_amdgcn_sched_barrier(0);
+        const double2 Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + (k0 + 2 * j));
+        const double2 Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + (k0 + 2 * j));
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            __builtin_amdgcn_sched_barrier(0);
+            const int i = 2 * j + q;
+            const double S = insolation(p, xk[i], ct);
+            double dif;
+            if constexpr (IMEX) {
+                dif = difx[IMEX ? i : 0];
+            } else {
+                dif = stencil.dif(p, i, k0, nlat, xk, xr, tb, tbl, tbr, g0[GRID == 0 ? i : 0], g1[GRID == 0 ? i : 0],
+                                  g2[GRID == 0 ? i : 0]);
+            }
+            o[q] = miz_cell_update(p, f, S, xk[i], dif, tb[i], q ? Ei2.y : Ei2.x, sEw[i * T], sh[i * T],
+                                   q ? Dk2.y : Dk2.x, ph[i], sTw[i * T], xs[i]);
+            if (C == 4 && i == C - 2) {
+                // L2 prefetch for the workgroup that follows this one on the XCD (column + a.prefetch):
+                // one 4-byte LDS-DMA load per 32-B sector of its phase-A inputs, issued once this
+                // thread's own loads have all been consumed and hidden under the last cell's
+                // arithmetic.  The data lands in stash words of cell C-2 that this wave has just
+                // finished with and is never read.
+                // (hipcc waits vmcnt(0) at the first use of any earlier load's result while an LDS-DMA is
+                // in flight: retire the one load not consumed yet before issuing it)
+                asm volatile("" ::"v"(xr), "v"(o[q].q[Q_Ei]), "v"(o[q].q[Q_Ew]), "v"(o[q].q[Q_h]), "v"(o[q].q[Q_D]),
+                             "v"(o[q].q[Q_phi]));
+                __builtin_amdgcn_sched_barrier(0);
+                if (a.prefetch > 0 && col + a.prefetch < a.ncol) {
+                    const double *nxt = a.state + (size_t)(col + a.prefetch) * (size_t)a.pitch +
+                                        ((unsigned)(t >> 6) * 256u + (unsigned)(t & 63) * 4u);
+                    auto *sink = (__attribute__((address_space(3))) void *)(smem + 6 * T + (C - 2) * T + (t & ~63));
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_Ew * a.fstride), sink, 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_phi * a.fstride), sink, 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_h * a.fstride), sink, 4, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned kp = k0 + 2 * j;
+        const bool v0 = (int)kp < nlat, v1 = (int)kp + 1 < nlat;
+#define EBM_PUT(slot_, qi)                                                                         \
+        {                                                                                          \
+            double2 d_;                                                                            \
+            d_.x = v0 ? o[0].q[qi] : 0.0;                                                          \
+            d_.y = v1 ? o[1].q[qi] : 0.0;                                                          \
+            EBM_STORE2(st + (slot_) * a.fstride + kp, d_);                                         \
+        }
+        if constexpr (C == 2) {
+            // two cells per thread (short meridians of latency-bound runs): the lane's 16 bytes are the
+            // pair; a wave's store already covers whole lines
+            EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)
+        } else if (j == 0) {
+            // pair 0 of Ei, Ew -> P words; h, D, phi -> stash words of cells 0, 1 (all read already)
+            park0[0] = v0 ? o[0].q[Q_Ei] : 0.0;  park0[T] = v1 ? o[1].q[Q_Ei] : 0.0;
+            park0[2 * T] = v0 ? o[0].q[Q_Ew] : 0.0;  park0[3 * T] = v1 ? o[1].q[Q_Ew] : 0.0;
+            sEw[0] = v0 ? o[0].q[Q_h] : 0.0;  sEw[T] = v1 ? o[1].q[Q_h] : 0.0;
+            sh[0] = v0 ? o[0].q[Q_D] : 0.0;  sh[T] = v1 ? o[1].q[Q_D] : 0.0;
+            sTw[0] = v0 ? o[0].q[Q_phi] : 0.0;  sTw[T] = v1 ? o[1].q[Q_phi] : 0.0;
+        } else {
+            // the LDS-DMA prefetch must have landed before this wave can end (its LDS is released
+            // with the workgroup); it was issued a whole cell update ago
+            EBM_STAMPW(5);                                // per wave: arithmetic done, before the stores
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#define EBM_PUT4(slot_, qi, w0, w1)                                                                \
+            {                                                                                      \
+                double2 a_, b_;                                                                    \
+                a_.x = (w0);                                                                       \
+                a_.y = (w1);                                                                       \
+                b_.x = v0 ? o[0].q[qi] : 0.0;                                                      \
+                b_.y = v1 ? o[1].q[qi] : 0.0;                                                      \
+                EBM_STORE2(st + (slot_) * a.fstride + k0, a_);                                       \
+                EBM_STORE2(st + (slot_) * a.fstride + kp, b_);                                       \
+            }
+            EBM_PUT4(S_Ei, Q_Ei, park0[0], park0[T])
+            EBM_PUT4(S_Ew, Q_Ew, park0[2 * T], park0[3 * T])
+            EBM_PUT4(S_h, Q_h, sEw[0], sEw[T])
+            EBM_PUT4(S_D, Q_D, sh[0], sh[T])
+            EBM_PUT4(S_phi, Q_phi, sTw[0], sTw[T])
+#undef EBM_PUT4
+        }
+        if (MAYDIAG && diag) {
+            // The diagnostic fields are outputs only: they are stored in the PAIR-SPLIT layout (pair j of thread t at
+            // j*2T + 2t, the layout of the annual-mean sums), in which every store instruction of a wave covers whole
+            // 128-B lines — stored in the natural layout they left pair by pair, i.e. as the two halves of each lane's
+            // 32-byte sector ~10^4 cycles apart (no LDS is left to park five more fields): 0.36 ms for a diagnostic step
+            // of the 4096 x 2048 shape against 0.164 state-only.  The runtime un-permutes in place before the first
+            // read (unsplit_fields_kernel; ebm_ctx::diag_split).  With two cells per thread the pair IS the chunk and
+            // the two layouts coincide.
+            const unsigned ks = (unsigned)(j * 2 * T + 2 * t);
+#define EBM_PUTP(slot_, qi)                                                                        \
+            {                                                                                      \
+                double2 d_;                                                                        \
+                d_.x = v0 ? o[0].q[qi] : 0.0;                                                      \
+                d_.y = v1 ? o[1].q[qi] : 0.0;                                                      \
+                EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                     \
+            }
+            EBM_PUTP(S_n, Q_n) EBM_PUTP(S_E, Q_E) EBM_PUTP(S_T, Q_T) EBM_PUTP(S_Ti, Q_Ti) EBM_PUTP(S_Tw, Q_Tw)
+#undef EBM_PUTP
+        }
+#undef EBM_PUT
+        if constexpr (OUT == OUT_SAVE)
+            save_pair<Q_MIZ_COUNT>(a, (size_t)col * (size_t)a.pitch, (unsigned)(j * 2 * T + 2 * t), kp, o[0], o[1], v0, v1);
+        if (j < 2) EBM_STAMP(8 + j);
+        if (j == 0) EBM_STAMPW(4);                        // per wave: first pair done
+    }
+    if (a.noise) nz.store(a, col);                        // after the step's last barrier
+    EBM_STAMP(15);
+    EBM_STAMPW(6);                                        // per wave: stores issued
+}
+
+}  // namespace ebm

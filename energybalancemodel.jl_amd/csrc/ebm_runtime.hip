@@ -1,6 +1,6 @@
 // Host runtime behind the C ABI of include/ebm_hip.h: handle/state ownership, per-latitude
 // constant tables, the step / run / integrate drivers and HIP-event timing.  Device work is in
-// ebm_kernels.hip.  There is deliberately no CPU fallback: without a GPU every entry point
+// the other .hip files of this directory (ebm_launch.hip lists the kernels).  There is deliberately no CPU fallback: without a GPU every entry point
 // fails with EBM_ERR_NO_DEVICE.
 #include <algorithm>
 #include <cmath>
@@ -130,7 +130,7 @@ struct ebm_ctx {
     long long epoch = 0, state_step = -1;
     long long written_epoch[EBM_F_COUNT], written_step[EBM_F_COUNT];
     // The MIZ step kernels (4 cells per thread) store the five diagnostic fields in the pair-split layout (whole
-    // 128-B lines per store instruction, csrc/ebm_kernels.hip); whoever reads one of them gets the natural layout:
+    // 128-B lines per store instruction, csrc/ebm_miz_step.h); whoever reads one of them gets the natural layout:
     // the first reader after such a step runs the in-place un-permutation once.
     bool diag_split = false;
     // ebm_zonal_diffusion: the tables of the last nlon used, kept between calls

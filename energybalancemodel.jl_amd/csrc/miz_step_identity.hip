@@ -1,0 +1,10 @@
+// miz_step_kernel on the identity grid: every mode and workgroup size, two and four cells per thread.
+#include "ebm_kernel_table.h"
+
+namespace ebm {
+
+KernelFn miz_step_kernels_identity(int cells, int mode, int threads) {
+    return cells == 2 ? miz_step_by_mode<2, 0, false>(mode, threads) : miz_step_by_mode<4, 0, false>(mode, threads);
+}
+
+}  // namespace ebm

@@ -1,0 +1,10 @@
+// miz_step_kernel on every other grid: every mode and workgroup size, two and four cells per thread.
+#include "ebm_kernel_table.h"
+
+namespace ebm {
+
+KernelFn miz_step_kernels_nonuniform(int cells, int mode, int threads) {
+    return cells == 2 ? miz_step_by_mode<2, 1, false>(mode, threads) : miz_step_by_mode<4, 1, false>(mode, threads);
+}
+
+}  // namespace ebm

@@ -1,10 +1,12 @@
 """Mutation check of the GPU test suite: deliberately broken builds of the library must be caught.
 
+    python tests/tools/mutants.py check          (here, CPU: every anchor occurs exactly once; no copy, no build)
     python tests/tools/mutants.py build          (here, CPU: one full build per mutant under build/)
     bash   tests/tools/mutants_run.sh            (GPU box: the -m gpu suite with -x against every mutant)
 
-Each mutant is ONE small textual change of csrc/ebm_kernels.hip (or csrc/ebm_runtime.hip) — a sign, a dropped select, a broken halo — of the
-kind a transcription error would be.  The runner records the first test that fails for each; a mutant that the whole
+Each mutant is ONE small textual change of a file of csrc/ — a sign, a dropped select, a broken halo — of the kind a
+transcription error would be.  A 3-tuple's anchor is looked for in every .hip and .h file of csrc/: it must occur exactly
+once in all of them together, and the file that holds it is the one edited.  A 4-tuple names its file.  The runner records the first test that fails for each; a mutant that the whole
 suite lets pass is a hole in the suite.  Nothing here is product code: the mutants live under build/ only."""
 import os, shutil, subprocess, sys
 
@@ -125,20 +127,46 @@ MUTANTS = [
 ]
 
 
+def sources(csrc):
+    return sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+
+
+def locate(csrc, old, where):
+    """The file of csrc/ that a mutant edits, or a string saying why there is none."""
+    counts = {f: open(os.path.join(csrc, f)).read().count(old) for f in (where or sources(csrc))}
+    hits = {f: n for f, n in counts.items() if n}
+    if sum(hits.values()) != 1:
+        return None, f"anchor occurs {sum(hits.values())} times" + (f" ({hits})" if hits else "")
+    return next(iter(hits)), None
+
+
+def check():
+    csrc = os.path.join(ROOT, "energybalancemodel.jl_amd", "csrc")
+    bad = 0
+    for name, old, new, *where in MUTANTS:
+        f, why = locate(csrc, old, where)
+        if f is None:
+            print(f"{name}: {why}")
+            bad += 1
+    print(f"{len(MUTANTS)} mutants, {bad} whose anchor does not occur exactly once")
+    return 1 if bad else 0
+
+
 def build(only=None):
     src = os.path.join(ROOT, "energybalancemodel.jl_amd", "csrc")
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     for name, old, new, *where in MUTANTS:
         if only and name not in only:
             continue
+        target, why = locate(src, old, where)
+        assert target is not None, (name, why)
         work = f"/tmp/mutant_{name}"
         shutil.rmtree(work, ignore_errors=True)
         os.makedirs(os.path.join(work, "energybalancemodel.jl_amd"))
         shutil.copytree(src, os.path.join(work, "energybalancemodel.jl_amd", "csrc"), ignore=shutil.ignore_patterns("build"))
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(work, "include"))
-        path = os.path.join(work, "energybalancemodel.jl_amd", "csrc", where[0] if where else "ebm_kernels.hip")
+        path = os.path.join(work, "energybalancemodel.jl_amd", "csrc", target)
         text = open(path).read()
-        assert text.count(old) == 1, (name, text.count(old))
         open(path, "w").write(text.replace(old, new))
         out = os.path.join(ROOT, "build", f"libebm_mut_{name}.so")
         subprocess.check_call(["make", "-j8", "-C", os.path.dirname(path), f"OUT={out}", f"BUILD={work}/obj"], stdout=subprocess.DEVNULL)
@@ -148,5 +176,7 @@ def build(only=None):
 if __name__ == "__main__":
     if sys.argv[1:2] == ["build"]:
         build(sys.argv[2:])
+    elif sys.argv[1:2] == ["check"]:
+        sys.exit(check())
     else:
         print("\n".join(m[0] for m in MUTANTS))
