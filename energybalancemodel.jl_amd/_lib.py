@@ -28,7 +28,7 @@ EXPORTS = (
     "ebm_field_device_ptr", "ebm_diffusion", "ebm_zonal_diffusion", "ebm_set_column_forcing", "ebm_set_column_schedule",
     "ebm_set_column_params", "ebm_set_column_noise", "ebm_get_noise_state", "ebm_set_noise_state", "ebm_noise_innovations",
     "ebm_set_step_clock", "ebm_set_time_table",
-    "ebm_step", "ebm_run", "ebm_run_fused", "ebm_integrate", "ebm_integrate_hemispheric",
+    "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
     "ebm_equilibrate", "ebm_sync", "ebm_get_counters",
     "ebm_reset_counters", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
     "ebm_selftest_divide",
@@ -107,6 +107,7 @@ def load():
     lib.ebm_step.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
     lib.ebm_run.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int]
     lib.ebm_run_fused.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int, C.c_int]
+    lib.ebm_run_series.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp]
     lib.ebm_integrate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp]
     lib.ebm_integrate_hemispheric.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,

@@ -166,6 +166,20 @@ hipError_t launch_divide(const double *a, const double *b, double *q, int n, hip
 // out[col] = hemispheric_mean(field[col], x), src/utilities.jl:397-403 (sequential sum, bit-exact)
 hipError_t launch_hemispheric_mean(const double *field, const double *x, int pitch, int nlat, int ncol, double *out,
                                    hipStream_t s);
+// ebm_run_series: one sample of the series.  out[v * var_stride + col] = hemispheric_mean(field in state slot slot[v] of
+// column col, x) for v < nvars, col < ncol, the same bits as launch_hemispheric_mean; one wave per column, one launch.
+constexpr int kSeriesTile = 512;     // terms per LDS tile and variable: at most 12 x 513 doubles = 48 KiB of LDS
+struct SeriesArgs {
+    const double *state;
+    long long fstride;
+    const double *x;
+    double *out;                     // the sample's first word in the device series [nvars][nsamples][ncol]
+    long long var_stride;            // nsamples * ncol
+    int pitch, nlat, nvars;
+    int row;                         // doubles per variable of the LDS tile (odd; set by the launcher)
+    int slot[kMaxQuantities];
+};
+hipError_t launch_hemispheric_series(const SeriesArgs &s, int ncol, hipStream_t st);
 // out = base + D d/dx[(1-x^2) d temp/dx] per column ([ncol][pitch] device arrays; base may be null)
 // (parameter set of column c: pset[c], or 0 if pset is null — see StepArgs)
 hipError_t launch_diffusion(const double *temp, const double *base, double *out, const double *geom, long long gstride,

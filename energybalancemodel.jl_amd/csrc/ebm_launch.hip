@@ -28,15 +28,15 @@
 //                                       [ebm_miz_resident.h; miz_resident.hip, SAVE: miz_resident_save.hip]
 //   classic_step_kernel<C, MODE>        WE15 model: single step / savesol! / K steps per launch            [this file]
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
-//   finish_mean, hemispheric_mean, mask_from_t0, derive_params, divide, split / unsplit_fields, noise_innovations,
-//   noise_sequence, equilibrium_check, compact_active: small helpers                                       [this file]
+//   finish_mean, hemispheric_mean, hemispheric_series, mask_from_t0, derive_params, divide, split / unsplit_fields,
+//   noise_innovations, noise_sequence, equilibrium_check, compact_active: small helpers                    [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
 // and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
 // ebm_device.h (stores, parameter block, IEEE division, chunk loads), ebm_noise.h, ebm_solve.h (halo exchanges, the
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 447 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 448 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -231,6 +231,43 @@ __global__ void hemispheric_mean_kernel(const double *__restrict__ field, const 
         for (int i = 0; i < nlat - 1; ++i) acc = acc + terms[i];
         out[blockIdx.x] = acc;
     }
+}
+// ebm_run_series: the same mean of s.nvars fields of one column by ONE wave, every column in one launch, written straight
+// into slot [v][sample][col] of the device series (SeriesArgs).  The latitudes are walked in tiles of kSeriesTile terms: the
+// 64 lanes form the terms of all variables as hemispheric_mean_kernel does (coalesced row reads, x[i+1]-x[i] once per
+// latitude) into an LDS tile [nvars][row]; then lane v adds row v onto its running sum — the reference's sequential
+// left-to-right sum from 0.0, nvars chains side by side instead of one launch each with one working lane.  `row` is odd, so
+// the lanes' rows start on different banks.
+__global__ void __launch_bounds__(64) hemispheric_series_kernel(const SeriesArgs s) {
+    extern __shared__ double terms[];
+    const int lane = threadIdx.x, col = blockIdx.x, nterms = s.nlat - 1, row = s.row;
+    const double *const column = s.state + (size_t)col * (size_t)s.pitch;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < nterms; k0 += kSeriesTile) {
+        const int n = min(kSeriesTile, nterms - k0);
+        for (int i = lane; i < n; i += 64) {
+            const double dx = s.x[k0 + i + 1] - s.x[k0 + i];
+            for (int v = 0; v < s.nvars; ++v) {
+                const double *f = column + (size_t)s.slot[v] * (size_t)s.fstride + k0;
+                terms[v * row + i] = ieee_div((f[i] + f[i + 1]) * dx, 2.0);
+            }
+        }
+        __syncthreads();
+        if (lane < s.nvars) {
+            const double *t = terms + lane * row;
+#pragma unroll 8
+            for (int i = 0; i < n; ++i) acc = acc + t[i];
+        }
+        __syncthreads();                                  // (the tile is refilled by the next round)
+    }
+    if (lane < s.nvars) s.out[(size_t)lane * (size_t)s.var_stride + col] = acc;
+}
+hipError_t launch_hemispheric_series(const SeriesArgs &s, int ncol, hipStream_t st) {
+    if (ncol < 1 || s.nlat < 2 || s.nvars < 1 || s.nvars > kMaxQuantities) return hipErrorInvalidValue;
+    SeriesArgs b = s;
+    b.row = (s.nlat - 1 < kSeriesTile ? s.nlat - 1 : kSeriesTile) | 1;
+    hemispheric_series_kernel<<<ncol, 64, sizeof(double) * (size_t)b.nvars * (size_t)b.row, st>>>(b);
+    return hipGetLastError();
 }
 // ebm_equilibrate's year-end test, one workgroup per active column (EquilArgs): rows k < nlat of this year's fields
 // against last year's snapshot, which takes this year's values in the same pass.  The distance is a max of exact

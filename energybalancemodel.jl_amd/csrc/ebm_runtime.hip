@@ -1217,6 +1217,66 @@ int ebm_run_fused(ebm_handle_t h, long long first_step, int nsteps, const double
     return fused_range(h, first_step, first_step, nsteps, f_steps, diag_last, steps_per_launch, nullptr);
 }
 
+// ebm_run_series (include/ebm_hip.h).  Every sample is the stepping of ebm_run_fused over `every` steps — so a launch never
+// spans a sample — followed by one launch of hemispheric_series_kernel on the handle's stream, which writes the sample's
+// slot of the device series.  Nothing is synchronised between samples; the series comes down once, at the end.
+int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
+                   int nvars, const int *fields, double *series) {
+    if (!h || !fields || !series) return fail(EBM_ERR_ARG, "ebm_run_series: null argument");
+    if (nsteps < 0 || first_step < 0 || steps_per_launch < 1) return fail(EBM_ERR_ARG, "ebm_run_series: bad argument");
+    if (every < 1) return fail(EBM_ERR_ARG, "ebm_run_series: every must be >= 1");
+    if (nsteps % every) return fail(EBM_ERR_ARG, "ebm_run_series: nsteps must be a multiple of every");
+    if (nvars < 1 || nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_run_series: bad number of fields");
+    ebm::SeriesArgs sa{};
+    bool listed[EBM_F_COUNT] = {};
+    int diag = 0;
+    for (int v = 0; v < nvars; ++v) {
+        const int f = fields[v];
+        if (!has_field(h, f) || quantity_of(h->model, f) < 0)
+            return fail(EBM_ERR_ARG, "ebm_run_series: fields[" + std::to_string(v) + "] is not a solution variable of this model");
+        if (listed[f]) return fail(EBM_ERR_ARG, std::string("ebm_run_series: field ") + field_name(f) + " is listed twice");
+        listed[f] = true;
+        if (is_diagnostic(h, f)) diag = 1;
+        sa.slot[v] = slot_of(h->model, f);
+    }
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_series: call ebm_set_time_table first");
+    const int nsamples = nsteps / every;
+    if (nsamples == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    int rc = get_copier(h);
+    if (rc) return rc;
+    const size_t per_var = (size_t)nsamples * (size_t)h->ncol;
+    DevBuf<double> dev;
+    HIPCHK(dev_alloc(dev, (size_t)nvars * per_var));
+    // the launches that write `dev` end before it is freed, on every path
+    const auto done = finally([h] { (void)hipStreamSynchronize(main_stream(h)); });
+    sa.state = h->state.get(); sa.fstride = h->fstride;
+    sa.x = h->geom.get() + (size_t)ebm::G_X * h->gstride;
+    sa.var_stride = (long long)per_var;
+    sa.pitch = (int)h->pitch; sa.nlat = h->nlat; sa.nvars = nvars;
+    for (int j = 0; j < nsamples; ++j) {
+        const long long first = first_step + (long long)j * every;
+        const double *f = f_steps ? f_steps + (size_t)j * every : nullptr;
+        rc = steps_per_launch == 1 ? ebm_run(h, first, every, f, diag)
+                                   : fused_range(h, first, first, every, f, diag, steps_per_launch, nullptr);
+        if (rc) return rc;
+        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split
+        if (diag && (rc = ensure_natural(h))) return rc;
+        sa.out = dev.get() + (size_t)j * (size_t)h->ncol;
+        hipError_t e = ebm::launch_hemispheric_series(sa, h->ncol, main_stream(h));
+        if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_run_series: reduction: ") + hipGetErrorString(e));
+    }
+    HostCopier *c = h->copier.get();
+    HIPCHK(c->wait_all());
+    HIPCHK(c->order_after(main_stream(h)));
+    CopyJob job;     // [nvars * nsamples] packed rows of ncol doubles
+    job.src = dev.get(); job.src_pitch = (size_t)h->ncol; job.row_elems = (size_t)h->ncol;
+    job.nrows = (size_t)nvars * (size_t)nsamples; job.dst = series;
+    hipError_t e = c->run(job);
+    if (e != hipSuccess) return fail(EBM_ERR_HIP, std::string("ebm_run_series: ") + hipGetErrorString(e));
+    return EBM_OK;
+}
+
 // integrate + savesol! (ebm_integrate) with, optionally, the per-column hemispheric means of the seasonal
 // outputs reduced on the device (ebm_integrate_hemispheric): hm_* are [nvars][dur][ncol] host arrays.
 //

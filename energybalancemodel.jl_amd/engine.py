@@ -308,6 +308,45 @@ class Engine:
             check(self.lib.ebm_run(self._h, int(first_step), int(nsteps), dptr(a), int(diag_last)),
                   "ebm_run")
 
+    def check_series_args(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
+        """The host-side checks of ``run_series`` (no device call): returns (names, field ids, f_steps)."""
+        if isinstance(names, str):
+            names = (names,)
+        names = tuple(names)
+        allowed = self.prognostic + self.diagnostic
+        if not 1 <= len(names) <= len(allowed):
+            raise ValueError(f"names: expected between 1 and {len(allowed)} fields of the {self.model} model")
+        for n in names:
+            if n not in allowed:
+                raise ValueError(f"names: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
+                                 "the warm start T0 is not a solution variable)")
+        if len(set(names)) != len(names):
+            raise ValueError(f"names: a field is listed twice in {names}")
+        if int(first_step) < 0 or int(nsteps) < 0:
+            raise ValueError("run_series: first_step and nsteps must be >= 0")
+        if int(every) < 1:
+            raise ValueError(f"every = {every}: a sample is taken every `every` >= 1 steps")
+        if int(nsteps) % int(every):
+            raise ValueError(f"nsteps = {nsteps} is not a multiple of every = {every}")
+        if int(steps_per_launch) < 1:
+            raise ValueError(f"steps_per_launch = {steps_per_launch}: need at least one step per launch")
+        f = None if f_steps is None else as_f64(f_steps, (int(nsteps),))
+        return names, [FIELD[n] for n in names], f
+
+    def run_series(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
+        """ebm_run_series: ``nsteps`` steps from global step ``first_step`` exactly as ``run`` takes them (``diag_last`` iff
+        one of ``names`` is a diagnostic field), with the per-column hemispheric mean (reference src/utilities.jl:397-403)
+        of every field in ``names`` sampled on the device after every ``every`` steps — ndarray [len(names),
+        nsteps // every, ncol]; sample j is the state after step first_step + (j+1)*every - 1, bit for bit what
+        ``hemispheric_mean`` returns there.  One download at the end; nothing is synchronised between samples."""
+        names, ids, f = self.check_series_args(first_step, nsteps, every, names, f_steps, steps_per_launch)
+        nv, ns = len(names), int(nsteps) // int(every)
+        fields = (C.c_int * nv)(*ids)
+        out = np.full((nv, ns, self.ncol), np.nan)
+        check(self.lib.ebm_run_series(self._h, int(first_step), int(nsteps), dptr(f), int(every), int(steps_per_launch), nv,
+                                      fields, dptr(out)), "ebm_run_series")
+        return out
+
     def integrate(self, nt, dur, f_steps, lastonly, winter_inx, summer_inx, names,
                   want_raw=True, want_seasonal=True, want_avg=True, out=None):
         """ebm_integrate: returns dict(raw, winter, summer, avg), each [nvars, n, ncol, nlat].

@@ -131,6 +131,24 @@ class EnsembleRun:
         self.engine.run(self.step_index, nsteps, f, diag_last, steps_per_launch)
         self.step_index += nsteps
 
+    def series(self, nsteps, every, names=("T", "phi"), forcing=None, steps_per_launch=None):
+        """Advance ``nsteps`` steps like ``run`` (from ``step_index``, which advances; the scalar ``forcing`` evaluated as
+        there) and return the time series of this shard's per-member hemispheric means (reference
+        src/utilities.jl:397-403) of every field in ``names``, sampled on the device after every ``every`` steps
+        (ebm_run_series): [len(names), nsteps // every, ncol].  Sample j is the state after ``every * (j + 1)`` steps of
+        this call — a member's <T>(t) or ice area <phi>(t) at ``every * dt`` resolution, for crossing and residence times.
+        Members are independent, so a sharded ensemble gives the bits of an unsharded one."""
+        if steps_per_launch is None:
+            steps_per_launch = 64
+        self.engine.check_series_args(self.step_index, nsteps, every, names, None, steps_per_launch)    # before any device call
+        f = None
+        if forcing is not None:
+            T = (np.arange(self.step_index, self.step_index + nsteps) + 0.5) * self.st.dt
+            f = np.array([forcing(float(t)) for t in T])
+        out = self.engine.run_series(self.step_index, nsteps, every, names, f, steps_per_launch)
+        self.step_index += nsteps
+        return out
+
     def seasonal_means(self, years, names=("T", "phi"), forcing=None):
         """Integrate ``years`` whole years from the current state and return, per column, the
         hemispheric means (reference src/utilities.jl:397-403) of the winter snapshot, the summer

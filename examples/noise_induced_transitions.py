@@ -4,10 +4,12 @@ equilibrium_branches.py finds it), does weather-like variability push a warm cli
 often?  Every member starts from the warm equilibrium at its forcing F; each member then gets its own realisation of
 AR(1) ("red") noise on the forcing, drawn on the device (ebm_set_column_noise, one stream per member), and the ensemble
 runs `--years` years.  Printed per F and year: the fraction of members whose annual-mean hemispheric temperature has
-fallen below the midpoint between the warm and the cold branch.
+fallen below the midpoint between the warm and the cold branch.  With `--every N` the noisy ensemble runs through
+EnsembleRun.series instead (ebm_run_series: <T> of every member sampled on the device every N steps) and the script prints,
+per F, the quartiles of the FIRST time a member's <T> falls below that midpoint, in years at N * dt resolution.
 
     python examples/noise_induced_transitions.py [--nlat 180] [--nt 2000] [--forcings -2,0,2] [--members 64]
-        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60]
+        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0]
 """
 import argparse
 import os
@@ -32,7 +34,11 @@ def main():
     ap.add_argument("--tau", type=float, default=0.1, help="e-folding time of the noise (years)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-years", type=int, default=60, help="spin-up limit of the warm and cold equilibria")
+    ap.add_argument("--every", type=int, default=0,
+                    help="sample <T> every N steps and print first-passage times (0: the yearly table only)")
     args = ap.parse_args()
+    if args.every < 0 or (args.every and (args.nt * args.years) % args.every):
+        ap.error("--every must be positive and divide nt * years")
     pkg = graft.load_package()
     st = pkg.SpaceTime("sin", args.nlat, args.nt, 1)
     par = pkg.default_parameters("MIZ")
@@ -61,10 +67,24 @@ def main():
     init = {k: np.repeat(eq[k][nf:], n, axis=0) for k in PROG}
     run = pkg.EnsembleRun("MIZ", st, par, init, fcol=fcol,
                           noise=dict(sigma=args.sigma, tau=args.tau, seed=args.seed), noise_streams=np.arange(nf * n))
+    threshold = np.repeat(0.5 * (cold_T + warm_T), n)
+    if args.every:
+        T = run.series(args.nt * args.years, args.every, names=("T",))[0]      # [samples, members]
+        run.close()
+        below = T < threshold
+        first = np.where(below.any(axis=0), (below.argmax(axis=0) + 1) * args.every * st.dt, np.inf)    # years
+        print(f"\n{nf * n} members ({n} per forcing), noise sigma = {args.sigma} W m^-2, tau = {args.tau} y, <T> sampled every "
+              f"{args.every} steps ({args.every * st.dt:.4f} y) for {args.years} years; first time <T> falls below the branches' "
+              "midpoint (years; inf: never):")
+        print("    F   fell   25 %     50 %     75 %")
+        for i in range(nf):
+            t = first[i * n:(i + 1) * n]
+            q = np.quantile(t, [0.25, 0.5, 0.75], method="lower")
+            print(f"{F[i]:5.2f}  {np.isfinite(t).mean():5.2f}  " + "  ".join(f"{v:7.3f}" for v in q))
+        return
     out = run.seasonal_means(args.years, names=("T",))
     run.close()
     avgT = out["avg"][0]                                   # [years, members]
-    threshold = np.repeat(0.5 * (cold_T + warm_T), n)
     fell = avgT < threshold
     print(f"\n{nf * n} members ({n} per forcing), noise sigma = {args.sigma} W m^-2, tau = {args.tau} y; "
           f"fraction of members on the cold side (annual-mean <T> below the branches' midpoint), by year:")

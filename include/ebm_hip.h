@@ -314,6 +314,31 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
 int ebm_run_fused(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps,
                   int diag_last, int steps_per_launch);
 
+/* The same nsteps steps with a TIME SERIES of per-column hemispheric means sampled on the device every `every` steps: a
+ * member's <T>(t) or ice area <phi>(t) at weather resolution — crossing times, residence times, the autocorrelation before
+ * a transition — where ebm_integrate_hemispheric gives three numbers per year.  THIS TEXT IS THE DEFINITION.
+ *   Stepping.  The call takes nsteps steps exactly as ebm_run_fused(h, first_step, nsteps, f_steps, diag, steps_per_launch)
+ *     does, with diag = 1 iff one of fields[] is a diagnostic field of the model (see "Validity"): time table, per-column
+ *     forcings, schedules, parameter rows, noise and launch options as there.
+ *   Samples.  nsamples = nsteps / every; sample j (0-based) is taken after 0-based global step first_step + (j+1)*every - 1.
+ *   Output.  series[nvars][nsamples][ncol] on the host: series[v][j][c] is bit for bit what ebm_hemispheric_mean(h,
+ *     fields[v], out) puts into out[c] after ebm_run_fused(h, first_step, (j+1)*every, f_steps, diag, steps_per_launch) from
+ *     the same start — hemispheric_mean (src/utilities.jl:397-403) in the reference's summation order; a NaN sentinel in
+ *     Ti or Tw gives a NaN mean, as it does there.
+ *   State after the call.  Bit for bit that of the one ebm_run_fused of nsteps steps: prognostic fields and warm start, the
+ *     diagnostic fields if diag, the noise state, counters[0] and the validity bookkeeping (ebm_field_step).
+ *   Launches.  A launch never spans a sample: counters[3] grows by nsamples * ceil(every / K') step launches, K' =
+ *     min(steps_per_launch, 64 if noise is installed), twice that with two launch chains.  The reduction launches (one
+ *     small kernel per sample: one wave per column sums all nvars fields side by side) are not counted.
+ * fields[nvars]: solution variables of the model, prognostic or diagnostic, each at most once; EBM_F_T0 is not one (as in
+ * ebm_integrate).  Refusals leave the handle as it was: EBM_ERR_ARG for every < 1, nsteps not a multiple of every, nvars < 1
+ * or more than 12, a bad or repeated field, a missing time table, a NULL series or fields.  Device memory for the call:
+ * nvars * nsamples * ncol doubles, allocated before the first step (a failure is EBM_ERR_HIP with no step taken) and freed
+ * before it returns.  Nothing is synchronised between samples; the whole series comes down once at the end, through the
+ * handle's pinned ring.  Synchronous.  Thresholds and first-passage times are host arithmetic on the returned series. */
+int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
+                   int nvars, const int *fields, double *series);
+
 /* integrate + savesol! (src/infrastructure.jl:549-591, 615-636) with state resident on the
  * device: runs nt*dur steps from the current state.  `fields[nvars]` selects the saved
  * variables; outputs are host buffers (any may be NULL to skip):

@@ -230,4 +230,23 @@ function set_member_forcings!(h::Handle, forcings::AbstractVector)
                          "ebm_set_column_schedule")
 end
 
+"""
+    run_series!(h, first_step, fsteps, every, names; ncol=1, steps_per_launch=64) -> Array{Float64,3}
+
+`length(fsteps)` steps from 0-based global step `first_step` (time table set beforehand) with the per-column
+`hemispheric_mean` (`src/utilities.jl:397-403`) of every variable in `names` sampled on the device after every `every`
+steps (`ebm_run_series`): `out[c, j, v]` is column `c`, sample `j`, variable `names[v]`.
+"""
+function run_series!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, every::Integer, names::Vector{Symbol};
+                     ncol::Int=1, steps_per_launch::Integer=64)
+    nsteps = length(fsteps)
+    (every >= 1 && nsteps % every == 0) || throw(ArgumentError("the number of steps must be a multiple of every >= 1"))
+    out = Array{Float64,3}(undef, ncol, div(nsteps, every), length(names))        # == C [nvars][nsamples][ncol]
+    GC.@preserve h check(ccall((:ebm_run_series, libebm), Cint,
+                               (Ptr{Cvoid}, Clonglong, Cint, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}),
+                               h.ptr, first_step, nsteps, fsteps, every, steps_per_launch, length(names),
+                               Cint[FIELD[k] for k in names], out), "ebm_run_series")
+    return out
+end
+
 end # module EBMHip
