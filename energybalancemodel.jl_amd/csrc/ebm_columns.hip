@@ -1,0 +1,188 @@
+// Host runtime, per-column inputs (ebm_runtime.h lists the units): forcing offsets, Forcing schedules, AR(1) noise and
+// parameter sets, each installed all-or-nothing; the step clock and the time table.
+#include <cmath>
+#include <map>
+
+#include "ebm_runtime.h"
+#include "ebm_tables.h"
+
+using namespace ebm_rt;
+
+namespace {
+
+// ebm_set_column_forcing / _schedule: nwords doubles per column from `src` (null: none) into the handle's `dst`
+int install_columns(ebm_ctx *h, DevBuf<double> &dst, const double *src, size_t nwords) {
+    DevBuf<double> b;
+    if (src) {
+        HIPCHK(dev_alloc(b, nwords * (size_t)h->ncol));
+        HIPCHK(hipMemcpy(b.get(), src, sizeof(double) * nwords * (size_t)h->ncol, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    dst = std::move(b);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    return EBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ebm_set_column_forcing(ebm_handle_t h, const double *fcol) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_forcing: null handle");
+    HIPCHK(hipSetDevice(h->device));
+    return install_columns(h, h->fcol, fcol, 1);
+}
+
+int ebm_set_column_schedule(ebm_handle_t h, const double *sched) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_schedule: null handle");
+    HIPCHK(hipSetDevice(h->device));
+    for (int c = 0; sched && c < h->ncol; ++c) {
+        const double *w = sched + (size_t)ebm::kSchedWords * c;
+        if (!(w[5] <= w[6] && w[6] <= w[7] && w[7] <= w[8]))
+            return fail(EBM_ERR_ARG, "ebm_set_column_schedule: breakpoints must be non-decreasing");
+    }
+    return install_columns(h, h->fsched, sched, ebm::kSchedWords);
+}
+
+int ebm_set_column_noise(ebm_handle_t h, const double *sigma, const double *rho, const unsigned long long *stream,
+                         unsigned long long seed) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_noise: null handle");
+    std::vector<ebm::NoiseRec> rec;
+    if (sigma) {
+        if (!rho) return fail(EBM_ERR_ARG, "ebm_set_column_noise: rho is null (pass zeros for white noise)");
+        rec.resize((size_t)h->ncol);
+        for (int c = 0; c < h->ncol; ++c) {
+            if (!(std::isfinite(sigma[c]) && sigma[c] >= 0.0))
+                return fail(EBM_ERR_ARG, "ebm_set_column_noise: sigma[" + std::to_string(c) + "] must be finite and >= 0");
+            if (!(std::isfinite(rho[c]) && rho[c] >= 0.0 && rho[c] < 1.0))
+                return fail(EBM_ERR_ARG, "ebm_set_column_noise: rho[" + std::to_string(c) + "] must lie in [0, 1)");
+            rec[c].s = sigma[c] * std::sqrt(1.0 - rho[c] * rho[c]);
+            rec[c].rho = rho[c];
+            rec[c].stream = stream ? stream[c] : (unsigned long long)c;
+        }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    ebm_ctx::Noise nz;                           // sigma null: no noise
+    if (sigma) {
+        const std::vector<double> zeros((size_t)h->ncol, 0.0);
+        HIPCHK(dev_alloc(nz.rec, (size_t)h->ncol));
+        HIPCHK(dev_alloc(nz.state, (size_t)h->ncol));
+        HIPCHK(dev_alloc(nz.seq, ebm::kNoiseMaxFused * (size_t)h->ncol));
+        HIPCHK(hipMemcpy(nz.rec.get(), rec.data(), sizeof(ebm::NoiseRec) * (size_t)h->ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(nz.state.get(), zeros.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+        nz.seed = seed;
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    h->noise = std::move(nz);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    return EBM_OK;
+}
+
+int ebm_get_noise_state(ebm_handle_t h, double *N) {
+    if (!h || !N) return fail(EBM_ERR_ARG, "ebm_get_noise_state: bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    if (!h->noise.state) {                       // no noise: N_c = 0
+        std::fill(N, N + h->ncol, 0.0);
+        return EBM_OK;
+    }
+    HIPCHK(hipMemcpy(N, h->noise.state.get(), sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost));
+    return EBM_OK;
+}
+
+int ebm_set_noise_state(ebm_handle_t h, const double *N) {
+    if (!h || !N) return fail(EBM_ERR_ARG, "ebm_set_noise_state: bad argument");
+    if (!h->noise.state) return fail(EBM_ERR_ARG, "ebm_set_noise_state: no noise installed (ebm_set_column_noise)");
+    for (int c = 0; c < h->ncol; ++c)
+        if (!std::isfinite(N[c])) return fail(EBM_ERR_ARG, "ebm_set_noise_state: N[" + std::to_string(c) + "] is not finite");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(h->noise.state.get(), N, sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice));
+    return EBM_OK;
+}
+
+int ebm_noise_innovations(ebm_handle_t h, long long first_step, int nsteps, double *out) {
+    if (!h || first_step < 0 || nsteps < 0 || (nsteps > 0 && !out)) return fail(EBM_ERR_ARG, "ebm_noise_innovations: bad argument");
+    if (!h->noise.rec) return fail(EBM_ERR_ARG, "ebm_noise_innovations: no noise installed (ebm_set_column_noise)");
+    if (nsteps == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)h->ncol * (size_t)nsteps;
+    DevBuf<double> dev;
+    HIPCHK(dev_alloc(dev, n));
+    hipError_t e = ebm::launch_noise_innovations(h->noise.rec.get(), h->noise.seed, first_step, nsteps, h->ncol, dev.get(),
+                                                 main_stream(h));
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e == hipSuccess) e = hipMemcpy(out, dev.get(), sizeof(double) * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("ebm_noise_innovations", e);
+    return EBM_OK;
+}
+
+int ebm_set_column_params(ebm_handle_t h, const double *params) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_set_column_params: null handle");
+    const int np = EBM_P_COUNT;
+    // the rows ebm_create would refuse as its vector (ebm_create_ex)
+    if (params && h->model == EBM_MODEL_MIZ)
+        for (int c = 0; c < h->ncol; ++c) {
+            const double *r = params + (size_t)np * c;
+            if (r[EBM_P_Tm] < 0.0 && r[EBM_P_m2] != std::floor(r[EBM_P_m2]))
+                return fail(EBM_ERR_ARG, "ebm_set_column_params: column " + std::to_string(c) +
+                                             ": Tm^m2 with Tm < 0 and non-integer m2 (DomainError in the reference, src/miz.jl:71)");
+        }
+    HIPCHK(hipSetDevice(h->device));
+    // distinct rows by bit pattern, in order of first appearance
+    std::vector<int> col_set((size_t)h->ncol, 0);
+    std::vector<const double *> rows;
+    if (params) {
+        std::map<std::string, int> seen;
+        for (int c = 0; c < h->ncol; ++c) {
+            const double *r = params + (size_t)np * c;
+            auto it = seen.emplace(std::string(reinterpret_cast<const char *>(r), sizeof(double) * np), (int)rows.size());
+            if (it.second) rows.push_back(r);
+            col_set[c] = it.first->second;
+        }
+    }
+    ebm_ctx::ParamSets sets;
+    sets.n = (int)rows.size();
+    sets.host.resize((size_t)sets.n);
+    if (sets.n) {
+        // every set built by the code ebm_create runs for its vector: fill_params, build_tables, derive_params_kernel
+        const long long set_stride = (long long)ebm::G_COUNT * h->gstride;
+        std::vector<double> slab((size_t)sets.n * set_stride, 0.0);
+        for (int i = 0; i < sets.n; ++i) {
+            ebm_tables::fill_params(sets.host[i], rows[i], h->dt);
+            ebm_tables::build_tables(h->model, h->grid, h->nlat, h->gstride, h->dt, sets.host[i], h->xhost.data(),
+                                     slab.data() + (size_t)i * set_stride);
+        }
+        hipError_t e = dev_alloc(sets.p, (size_t)sets.n);
+        if (e == hipSuccess) e = dev_alloc(sets.geom, slab.size());
+        if (e == hipSuccess && sets.n > 1) e = dev_alloc(sets.col, (size_t)h->ncol);
+        if (e == hipSuccess) e = hipMemcpy(sets.p.get(), sets.host.data(), sizeof(ebm::Params) * (size_t)sets.n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(sets.geom.get(), slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && sets.col)
+            e = hipMemcpy(sets.col.get(), col_set.data(), sizeof(int) * (size_t)h->ncol, hipMemcpyHostToDevice);
+        for (int i = 0; i < sets.n && e == hipSuccess; ++i) e = ebm::launch_derive_params(sets.p.get() + i, h->stream.get());
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
+        if (e == hipSuccess)
+            e = hipMemcpy(sets.host.data(), sets.p.get(), sizeof(ebm::Params) * (size_t)sets.n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail("ebm_set_column_params", e);
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    h->sets = std::move(sets);
+    invalidate_graph(h);                         // the captured launches hold the old argument values
+    h->zonal = ebm_ctx::ZonalTables();           // the zonal tables are built again from the parameters now installed
+    return EBM_OK;
+}
+
+int ebm_set_step_clock(ebm_handle_t h, long long step) {
+    if (!h || step < 0) return fail(EBM_ERR_ARG, "ebm_set_step_clock: bad argument");
+    h->clock = step;
+    return EBM_OK;
+}
+
+int ebm_set_time_table(ebm_handle_t h, int nt, const double *cos2pit) {
+    if (!h || !cos2pit || nt < 1) return fail(EBM_ERR_ARG, "ebm_set_time_table: bad argument");
+    h->ttab.assign(cos2pit, cos2pit + nt);
+    return EBM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,626 @@
+// Host runtime, the drivers (ebm_runtime.h lists the units): the launches of one step and their two chains, graph replay,
+// fused ranges, and what is built on them: ebm_step, ebm_run, ebm_run_fused, ebm_run_series, ebm_integrate, ebm_equilibrate.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "ebm_runtime.h"
+
+using namespace ebm_rt;
+
+namespace ebm_rt {
+
+ebm::StepArgs base_args(const ebm_ctx *h) {
+    ebm::StepArgs a{};
+    a.state = h->state.get(); a.fstride = h->fstride; a.geom = h->geom.get(); a.gstride = h->gstride;
+    a.fcol = h->fcol.get(); a.fsched = h->fsched.get(); a.p = h->p_dev.get();
+    a.noise = h->noise.rec.get(); a.nstate = h->noise.state.get(); a.nseq = h->noise.seq.get(); a.seed = h->noise.seed;
+    a.counters = h->counters.get(); a.amask = h->amask.get();
+    if (h->sets.n) {                 // per-column parameter sets (ebm_set_column_params)
+        a.p = h->sets.p.get(); a.geom = h->sets.geom.get(); a.pset = h->sets.col.get();
+        a.set_stride = (long long)ebm::G_COUNT * h->gstride;
+    }
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol;
+    a.stamps = h->stamps.get();
+    a.cols = h->active;
+    a.prefetch = h->prefetch;
+    a.nfused = 1;
+    std::memset(a.var_of, -1, sizeof(a.var_of));
+    return a;
+}
+
+// drop the captured graph: its kernel nodes hold the argument values of the time of capture
+void invalidate_graph(ebm_ctx *h) { h->graph = ebm_ctx::Graph(); }
+
+}  // namespace ebm_rt
+
+namespace {
+
+constexpr int kGraphSteps = 64;
+constexpr int kFusedTable = 16384;     // per-step scalars resident on the device at a time (512 KiB)
+
+// mode: ebm::OutMode.  The classic kernel decides about T, h at run time (write_diag).
+hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, int first, int count, hipStream_t s) {
+    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, first, count, s)
+                                       : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
+}
+// The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate), as one
+// chain or split in two halves; a chain with no columns is skipped.
+int chain_count(const ebm_ctx *h, int *first_half) {
+    const int n = h->active ? h->nactive : h->ncol;
+    *first_half = h->split_col ? (h->active ? n / 2 : h->split_col) : n;
+    return (*first_half > 0) + (n - *first_half > 0);
+}
+hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
+    const int n = h->active ? h->nactive : h->ncol;
+    if (!h->split_col) return launch_columns(h, a, mode, 0, n, main_stream(h));
+    if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
+        hipError_t e = hipEventRecord(h->ev_fork.get(), h->stream.get());
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);
+        if (e != hipSuccess) return e;
+        h->forked = true;
+    }
+    int half = 0;
+    (void)chain_count(h, &half);
+    hipError_t e = half > 0 ? launch_columns(h, a, mode, 0, half, h->stream.get()) : hipSuccess;
+    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, half, n - half, h->stream2.get());
+    return e;
+}
+
+// Capture kGraphSteps step kernels (node i reads graph.sched[i]) into a graph, once per handle.
+int build_graph(ebm_ctx *h) {
+    ebm_ctx::Graph g;
+    HIPCHK(dev_alloc(g.sched, kGraphSteps));
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(main_stream(h), hipStreamCaptureModeThreadLocal));
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < kGraphSteps && e == hipSuccess; ++i) {
+        ebm::StepArgs a = base_args(h);
+        a.sched = g.sched.get();
+        a.slot = i;
+        a.write_diag = 0;
+        e = launch_step(h, a, ebm::OUT_STATE);
+    }
+    hipError_t e2 = hipStreamEndCapture(main_stream(h), &graph);
+    if (e != hipSuccess || e2 != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return hip_fail("graph capture", e != hipSuccess ? e : e2);
+    }
+    e = hipGraphInstantiate(g.exec.out(), graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return hip_fail("hipGraphInstantiate", e);
+    h->graph = std::move(g);
+    return EBM_OK;
+}
+
+// model time of 0-based global step `step`: st.T[step+1] = (2 step + 1)/(2 nt), correctly rounded
+double year_time(const ebm_ctx *h, long long step) {
+    const double nt = (double)h->ttab.size();
+    return nt > 0.0 ? (double)(2 * step + 1) / (2.0 * nt) : 0.0;
+}
+
+// per-step scalars of steps i = 0 .. n-1 into out[i]: time-table entry tab_first + i, model-time step clock_first + i and
+// forcing f[i] (f null: 0)
+void fill_sched(const ebm_ctx *h, long long tab_first, long long clock_first, int n, const double *f, ebm::StepSched *out) {
+    const long long nt = (long long)h->ttab.size();
+    for (int i = 0; i < n; ++i) {
+        const long long ti = (tab_first + i) % nt;
+        out[i].ct = h->ttab[ti];
+        out[i].ct_next = h->ttab[(ti + 1) % nt];
+        out[i].ft = f ? f[i] : 0.0;
+        out[i].tyear = year_time(h, clock_first + i);
+        out[i].n = clock_first + i;
+    }
+}
+
+// `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
+// global step `last_step`.  wrote_diag: the last one stored the diagnostic fields, pair-split if `split` (MIZ).
+void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split) {
+    int half = 0;
+    h->n_launches += nlaunch * chain_count(h, &half);
+    h->n_steps += nsteps;
+    h->clock = last_step + 1;
+    h->epoch += nsteps;
+    h->state_step = last_step;
+    if (!wrote_diag) return;
+    for (int f = 0; f < EBM_F_COUNT; ++f)
+        if (has_field(h, f) && is_diagnostic(h, f)) {
+            h->written_epoch[f] = h->epoch;
+            h->written_step[f] = last_step;
+        }
+    if (h->model == EBM_MODEL_MIZ) h->diag_split = split;
+}
+
+// savesol! fused into a step launch (ebm::OUT_SAVE): where the running sums and the raw snapshot go
+struct SaveTarget {
+    double *sums = nullptr;
+    long long sum_stride = 0;
+    double *stage = nullptr;
+    long long stage_var_stride = 0, stage_offset = 0;
+    signed char var_of[ebm::kMaxQuantities];
+    // into a launch's arguments; a fused launch (OUT_LOOP_SAVE) takes the running sums only
+    void put(ebm::StepArgs &a, bool sums_only) const {
+        a.sums = sums; a.sum_stride = sum_stride;
+        std::memcpy(a.var_of, var_of, sizeof(a.var_of));
+        if (sums_only) return;
+        a.stage = stage; a.stage_var_stride = stage_var_stride; a.stage_offset = stage_offset;
+    }
+};
+
+int do_step(ebm_ctx *h, double ct, double ct_next, double f, int write_diag, long long step,
+            const SaveTarget *save = nullptr) {
+    ebm::StepArgs a = base_args(h);
+    a.ct = ct; a.ct_next = ct_next; a.ft = f; a.write_diag = write_diag;
+    a.tyear = year_time(h, step);
+    a.step = step;
+    if (save) save->put(a, false);
+    hipError_t e = launch_step(h, a, save ? ebm::OUT_SAVE : write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE);
+    if (e != hipSuccess) return hip_fail("kernel launch", e);
+    // the 4-cells-per-thread MIZ step kernels leave the diagnostic fields pair-split (ensure_natural undoes it)
+    record_launches(h, 1, 1, step, write_diag != 0, h->cfg.cells == 4);
+    return EBM_OK;
+}
+
+// A caller's list of solution variables (ebm_run_series, ebm_integrate, ebm_equilibrate): each a field of this model, a
+// quantity the step produces, not listed twice.  out[v] for v < nvars.
+struct FieldRef {
+    int field, slot, quantity;       // public id, state slot (slot_of), quantity index (quantity_of)
+    bool diagnostic;
+};
+int resolve_fields(const ebm_ctx *h, const char *who, int nvars, const int *fields, FieldRef *out) {
+    bool listed[EBM_F_COUNT] = {};
+    for (int v = 0; v < nvars; ++v) {
+        const int f = fields[v];
+        if (!has_field(h, f) || quantity_of(h->model, f) < 0)
+            return fail(EBM_ERR_ARG, std::string(who) + ": fields[" + std::to_string(v) + "] is not a solution variable of this model");
+        if (listed[f]) return fail(EBM_ERR_ARG, std::string(who) + ": field " + field_name(f) + " is listed twice");
+        listed[f] = true;
+        out[v] = {f, slot_of(h->model, f), quantity_of(h->model, f), is_diagnostic(h, f)};
+    }
+    return EBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ebm_step(ebm_handle_t h, double cos2pit, double cos2pit_next, double f, int write_diag) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_step: null handle");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->fsched && h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_step: column schedules need the time table (ebm_set_time_table)");
+    return do_step(h, cos2pit, cos2pit_next, f, write_diag, h->clock);
+}
+
+int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int diag_last) {
+    if (!h || nsteps < 0 || first_step < 0) return fail(EBM_ERR_ARG, "ebm_run: bad argument");
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run: call ebm_set_time_table first");
+    HIPCHK(hipSetDevice(h->device));
+    const long long nt = (long long)h->ttab.size();
+    int s = 0;
+    if (h->use_graph && nsteps >= 2 * kGraphSteps) {
+        // launch-bound shapes: replay a captured graph of kGraphSteps launches (still one launch
+        // per step); the per-step scalars travel through a small device table
+        if (!h->graph.exec) {
+            int rc = build_graph(h);
+            if (rc) return rc;
+        }
+        std::vector<ebm::StepSched> sched(kGraphSteps);
+        const int last_graph_step = nsteps - (diag_last ? 1 : 0);     // a diagnostic last step is launched directly
+        for (; s + kGraphSteps <= last_graph_step; s += kGraphSteps) {
+            fill_sched(h, first_step + s, first_step + s, kGraphSteps, f_steps ? f_steps + s : nullptr, sched.data());
+            // pageable source: the copy is staged before the call returns, so `sched` can be refilled
+            HIPCHK(hipMemcpyAsync(h->graph.sched.get(), sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
+                                  hipMemcpyHostToDevice, main_stream(h)));
+            HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
+            record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false);
+        }
+    }
+    for (; s < nsteps; ++s) {
+        const long long ti = (first_step + s) % nt;
+        const double f = f_steps ? f_steps[s] : 0.0;
+        int rc = do_step(h, h->ttab[ti], h->ttab[(ti + 1) % nt], f, diag_last && s == nsteps - 1, first_step + s);
+        if (rc) return rc;
+    }
+    return EBM_OK;
+}
+
+// nsteps steps, steps_per_launch to a launch, the per-step scalars from a device table: time-table entry tab_first + i and
+// model-time step clock_first + i for step i.  save: savesol!'s running sums from every step (OUT_LOOP_SAVE), else plain
+// fused stepping (OUT_LOOP).
+static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, int nsteps, const double *f_steps, int diag_last,
+                       int steps_per_launch, const SaveTarget *save) {
+    // forcing noise: the kernels draw a launch's innovations one step per lane, so a launch takes at most kNoiseMaxFused
+    // steps (same bits, more launches)
+    if (h->noise.rec) steps_per_launch = std::min(steps_per_launch, ebm::kNoiseMaxFused);
+    std::vector<ebm::StepSched> sched;
+    for (int s0 = 0; s0 < nsteps; s0 += kFusedTable) {
+        const int n = std::min(kFusedTable, nsteps - s0);
+        sched.resize(n);
+        fill_sched(h, tab_first + s0, clock_first + s0, n, f_steps ? f_steps + s0 : nullptr, sched.data());
+        // the table used two batches ago: its launches must have ended before it is refilled (normally long since).  The copy is
+        // synchronous for the host but not ordered with the handle's (non-blocking) streams.
+        auto &tb = h->sched_tab[h->sched_next];
+        h->sched_next ^= 1;
+        if (!tb.dev) {
+            ebm_ctx::SchedTable t;
+            HIPCHK(dev_alloc(t.dev, kFusedTable));
+            HIPCHK(hipEventCreateWithFlags(t.done.out(), hipEventDisableTiming));
+            tb = std::move(t);
+        }
+        if (tb.in_use) HIPCHK(hipEventSynchronize(tb.done.get()));
+        HIPCHK(hipMemcpy(tb.dev.get(), sched.data(), sizeof(ebm::StepSched) * (size_t)n, hipMemcpyHostToDevice));
+        for (int i = 0; i < n; i += steps_per_launch) {
+            ebm::StepArgs a = base_args(h);
+            a.sched = tb.dev.get();
+            a.slot = i;
+            a.nfused = std::min(steps_per_launch, n - i);
+            a.prefetch = 0;
+            a.write_diag = (diag_last && s0 + i + a.nfused == nsteps) ? 1 : 0;
+            if (save) save->put(a, true);
+            hipError_t e = launch_step(h, a, save ? ebm::OUT_LOOP_SAVE : ebm::OUT_LOOP);
+            if (e != hipSuccess) return hip_fail("fused launch", e);
+            // the fused kernels store the diagnostic fields in the natural layout
+            record_launches(h, 1, a.nfused, clock_first + s0 + i + a.nfused - 1, a.write_diag != 0, false);
+        }
+        HIPCHK(hipEventRecord(tb.done.get(), main_stream(h)));     // (both launch chains, joined)
+        tb.in_use = true;
+    }
+    return EBM_OK;
+}
+
+int ebm_run_fused(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int diag_last,
+                  int steps_per_launch) {
+    if (!h || nsteps < 0 || first_step < 0 || steps_per_launch < 1) return fail(EBM_ERR_ARG, "ebm_run_fused: bad argument");
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_fused: call ebm_set_time_table first");
+    // every shape has a fused-K kernel: the state in registers up to kFusedRegThreads threads per meridian (2048 cells at
+    // 4 per thread; kFusedRegThreads2 at 2 per thread), resident in LDS for longer meridians and for the extension
+    if (steps_per_launch == 1) return ebm_run(h, first_step, nsteps, f_steps, diag_last);
+    HIPCHK(hipSetDevice(h->device));
+    return fused_range(h, first_step, first_step, nsteps, f_steps, diag_last, steps_per_launch, nullptr);
+}
+
+// ebm_run_series (include/ebm_hip.h).  Every sample is the stepping of ebm_run_fused over `every` steps — so a launch never
+// spans a sample — followed by one launch of hemispheric_series_kernel on the handle's stream, which writes the sample's
+// slot of the device series.  Nothing is synchronised between samples; the series comes down once, at the end.
+int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
+                   int nvars, const int *fields, double *series) {
+    if (!h || !fields || !series) return fail(EBM_ERR_ARG, "ebm_run_series: null argument");
+    if (nsteps < 0 || first_step < 0 || steps_per_launch < 1) return fail(EBM_ERR_ARG, "ebm_run_series: bad argument");
+    if (every < 1) return fail(EBM_ERR_ARG, "ebm_run_series: every must be >= 1");
+    if (nsteps % every) return fail(EBM_ERR_ARG, "ebm_run_series: nsteps must be a multiple of every");
+    if (nvars < 1 || nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_run_series: bad number of fields");
+    FieldRef vars[ebm::kMaxQuantities];
+    int rc = resolve_fields(h, "ebm_run_series", nvars, fields, vars);
+    if (rc) return rc;
+    ebm::SeriesArgs sa{};
+    int diag = 0;
+    for (int v = 0; v < nvars; ++v) {
+        if (vars[v].diagnostic) diag = 1;
+        sa.slot[v] = vars[v].slot;
+    }
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_series: call ebm_set_time_table first");
+    const int nsamples = nsteps / every;
+    if (nsamples == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = get_copier(h))) return rc;
+    const size_t per_var = (size_t)nsamples * (size_t)h->ncol;
+    DevBuf<double> dev;
+    HIPCHK(dev_alloc(dev, (size_t)nvars * per_var));
+    // the launches that write `dev` end before it is freed, on every path
+    const auto done = finally([h] { (void)hipStreamSynchronize(main_stream(h)); });
+    sa.state = h->state.get(); sa.fstride = h->fstride;
+    sa.x = x_table(h);
+    sa.var_stride = (long long)per_var;
+    sa.pitch = (int)h->pitch; sa.nlat = h->nlat; sa.nvars = nvars;
+    for (int j = 0; j < nsamples; ++j) {
+        const long long first = first_step + (long long)j * every;
+        const double *f = f_steps ? f_steps + (size_t)j * every : nullptr;
+        rc = steps_per_launch == 1 ? ebm_run(h, first, every, f, diag)
+                                   : fused_range(h, first, first, every, f, diag, steps_per_launch, nullptr);
+        if (rc) return rc;
+        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split
+        if (diag && (rc = ensure_natural(h))) return rc;
+        sa.out = dev.get() + (size_t)j * (size_t)h->ncol;
+        hipError_t e = ebm::launch_hemispheric_series(sa, h->ncol, main_stream(h));
+        if (e != hipSuccess) return hip_fail("ebm_run_series: reduction", e);
+    }
+    HostCopier *c = h->copier.get();
+    HIPCHK(c->wait_all());
+    HIPCHK(c->order_after(main_stream(h)));
+    CopyJob job;     // [nvars * nsamples] packed rows of ncol doubles
+    job.src = dev.get(); job.src_pitch = (size_t)h->ncol; job.row_elems = (size_t)h->ncol;
+    job.nrows = (size_t)nvars * (size_t)nsamples; job.dst = series;
+    hipError_t e = c->run(job);
+    if (e != hipSuccess) return hip_fail("ebm_run_series", e);
+    return EBM_OK;
+}
+
+// integrate + savesol! (ebm_integrate) with, optionally, the per-column hemispheric means of the seasonal
+// outputs reduced on the device (ebm_integrate_hemispheric): hm_* are [nvars][dur][ncol] host arrays.
+//
+// Host output never stalls the stepping: what has to leave the device is first copied device -> device into a
+// buffer of its own on the compute stream (seasonal snapshots; the annual means come out of ONE finish-mean
+// launch; raw snapshots are written by the step kernel into one half of a two-part staging buffer), then the
+// handle's copier moves it to the caller's arrays — DMA into the pinned ring on its own stream, host threads
+// from there — while the following steps run.  A buffer is reused only after the job that reads it has finished.
+static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps, int lastonly,
+                          int winter_inx, int summer_inx, int nvars, const int *fields, double *raw,
+                          double *winter, double *summer, double *avg, double *hm_winter, double *hm_summer,
+                          double *hm_avg) {
+    if (!h || nt < 1 || dur < 1 || nvars < 0 || nvars > ebm::kMaxQuantities || (nvars > 0 && !fields))
+        return fail(EBM_ERR_ARG, "ebm_integrate: bad argument");
+    if ((hm_winter || hm_summer || hm_avg) && nvars < 1) return fail(EBM_ERR_ARG, "ebm_integrate_hemispheric: no variables");
+    if ((long long)h->ttab.size() != nt) return fail(EBM_ERR_ARG, "ebm_integrate: time table length must equal nt");
+    FieldRef vars[ebm::kMaxQuantities];
+    int rc = resolve_fields(h, "ebm_integrate", nvars, fields, vars);
+    if (rc) return rc;
+    SaveTarget save;
+    std::memset(save.var_of, -1, sizeof(save.var_of));
+    for (int v = 0; v < nvars; ++v) save.var_of[vars[v].quantity] = (signed char)v;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = get_copier(h))) return rc;
+    HostCopier *cp = h->copier.get();
+    HIPCHK(cp->wait_all());
+    // on every return: let the copier finish what it was given (it reads this call's device buffers and writes the caller's
+    // arrays)
+    const auto drain = finally([cp] { (void)cp->wait_all(); });
+    const size_t ncell = (size_t)h->ncol * h->nlat;          // packed cells per snapshot (host side)
+    const size_t npitch = (size_t)h->ncol * h->pitch;        // device elements per field
+    const long long total = (long long)nt * dur;
+    const long long nraw = lastonly ? nt : total;
+    const bool want_hm = (hm_winter || hm_summer || hm_avg) && nvars > 0;
+    const bool want_sums = (avg || hm_avg) && nvars > 0;
+    const bool want_snap = (winter || summer) && nvars > 0;
+    // Device buffers (kept in the handle between calls): raw snapshots are staged as two halves of
+    // [var][chunk][ncol][pitch]; the annual-mean sums are [var][ncol*pitch] (pair-split layout), the means and the
+    // seasonal snapshots [var][ncol*pitch] in the natural layout.
+    long long chunk = 0;
+    if (raw && nvars > 0) {
+        chunk = (long long)((128ull << 20) / (sizeof(double) * npitch * (size_t)nvars));
+        if (chunk < 1) chunk = 1;
+        if (chunk > nraw) chunk = nraw;
+        HIPCHK(h->ig_stage.reserve(2 * npitch * (size_t)nvars * (size_t)chunk));
+    }
+    if (want_hm) HIPCHK(h->ig_hm.reserve((size_t)h->ncol * (size_t)nvars));
+    if (want_sums) {
+        HIPCHK(h->ig_sums.reserve(npitch * (size_t)nvars));
+        HIPCHK(hipMemsetAsync(h->ig_sums.get(), 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));
+        HIPCHK(h->ig_mean.reserve(npitch * (size_t)nvars));
+    }
+    if (want_snap) HIPCHK(h->ig_snap.reserve(npitch * (size_t)nvars));
+    double *const sums = want_sums ? h->ig_sums.get() : nullptr, *const mean = h->ig_mean.get(), *const snap = h->ig_snap.get();
+    double *const hm = h->ig_hm.get();
+    double *const stage = (raw && nvars > 0) ? h->ig_stage.get() : nullptr;
+    // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set,
+    // reduced on the device, [nvars][ncol] -> out[v][year][col]
+    auto means_to_host = [&](double *out, long long year, auto field_of) -> hipError_t {
+        for (int v = 0; v < nvars; ++v) {
+            hipError_t e = ebm::launch_hemispheric_mean(field_of(v), x_table(h), (int)h->pitch, h->nlat, h->ncol,
+                                                        hm + (size_t)v * h->ncol, main_stream(h));
+            if (e != hipSuccess) return e;
+        }
+        hipError_t e = hipStreamSynchronize(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v)
+            e = hipMemcpy(out + ((size_t)v * dur + (size_t)(year - 1)) * h->ncol, hm + (size_t)v * h->ncol,
+                          sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost);
+        return e;
+    };
+    save.sums = sums;
+    save.sum_stride = (long long)npitch;
+    save.stage_var_stride = chunk * (long long)npitch;
+    // one asynchronous job per saved variable: [ncol][pitch] on the device -> packed [ncol][nlat] at dst
+    auto fields_to_host = [&](double *dst_base, long long year, const double *dev_base) -> hipError_t {
+        hipError_t e = cp->order_after(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
+            CopyJob j;
+            j.src = dev_base + (size_t)v * npitch; j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat;
+            j.nrows = (size_t)h->ncol; j.dst = dst_base + ((size_t)v * dur + (size_t)(year - 1)) * ncell;
+            cp->submit(j);
+        }
+        return e;
+    };
+    // seasonal snapshot: the state fields of this step, device -> device, then out
+    auto season_to_host = [&](double *dst_base, long long year) -> hipError_t {
+        hipError_t e = cp->wait_all();                                       // the previous snapshot has left `snap`
+        for (int v = 0; v < nvars && e == hipSuccess; ++v)
+            e = hipMemcpyAsync(snap + (size_t)v * npitch, h->field[fields[v]], sizeof(double) * npitch, hipMemcpyDeviceToDevice, main_stream(h));
+        if (e == hipSuccess) e = fields_to_host(dst_base, year, snap);
+        return e;
+    };
+    long long staged = 0, raw_base = 0;   // snapshots in the current half of the staging buffer; raw index of its first
+    int half = 0;
+    const long long clock0 = h->clock;    // model time continues from the handle's step clock (0 after ebm_create)
+    auto flush = [&]() -> hipError_t {
+        if (!staged) return hipSuccess;
+        // the half just filled goes out while the steps fill the other one — whose previous contents must have left
+        hipError_t e = cp->wait_all();
+        if (e == hipSuccess) e = cp->order_after(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
+            CopyJob j;      // `staged` snapshots of ncol rows each: (staged * ncol) rows of nlat doubles, pitch apart
+            j.src = stage + (size_t)half * (size_t)nvars * chunk * npitch + (size_t)v * chunk * npitch;
+            j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat; j.nrows = (size_t)staged * h->ncol;
+            j.dst = raw + ((size_t)v * nraw + raw_base) * ncell;
+            cp->submit(j);
+        }
+        raw_base += staged;
+        staged = 0;
+        half ^= 1;
+        return e;
+    };
+    // What step tinx (1-based, as the reference; any tinx >= 1) needs besides the running sums: savesol!,
+    // src/infrastructure.jl:549-591.  The loop below reads it, and a stretch may be fused iff none of its steps needs anything.
+    struct StepNeeds {
+        bool raw;            // its raw snapshot is kept
+        int season;          // the seasonal index it falls on: 1 winter, 2 summer (winter first, as savesol!'s chain), 0 neither
+        bool snapshot;       // a seasonal output is taken from it: the step stores the diagnostic fields
+        bool year_end, last; // the last step of a year / of the run (or beyond it)
+        bool plain() const { return !raw && !snapshot && !year_end && !last; }
+    };
+    auto needs = [&](long long tinx) {
+        const long long ti = (tinx - 1) % nt + 1;
+        StepNeeds s;
+        s.raw = stage && (!lastonly || tinx > total - nt);
+        s.season = ti == winter_inx ? 1 : ti == summer_inx ? 2 : 0;
+        s.snapshot = (ti == winter_inx && (winter || hm_winter)) || (ti == summer_inx && (summer || hm_summer));
+        s.year_end = ti == nt;
+        s.last = tinx >= total;
+        return s;
+    };
+    // Stretches that need nothing but the running sums (no raw snapshot, no seasonal snapshot, not a year's last step, not the
+    // run's last step) are fused, integrate_spl steps to a launch, with the state resident on the chip
+    // (miz_resident_kernel<SAVE>, miz_fused_kernel<2, ..., SAVE>; plain fused stepping when no mean is asked for): MIZ and
+    // MIZ_IMEX, every geometry but two cells per thread at 768 threads.
+    const bool may_fuse = h->integrate_spl > 1 && h->model == EBM_MODEL_MIZ &&
+                          (!sums || ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP_SAVE, h->imex));
+    for (long long tinx = 1; tinx <= total; ++tinx) {              // 1-based, as the reference
+        if (may_fuse && needs(tinx).plain() && needs(tinx + 1).plain()) {
+            long long n = 2;
+            while (n < (1 << 30) && needs(tinx + n).plain()) ++n;
+            rc = fused_range(h, tinx - 1, clock0 + tinx - 1, (int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,
+                             sums ? &save : nullptr);
+            if (rc) return rc;
+            tinx += n - 1;
+            continue;
+        }
+        const StepNeeds s = needs(tinx);
+        const long long ti = (tinx - 1) % nt + 1;
+        const long long year = (tinx - 1) / nt + 1;                // ceil(st.T[tinx])
+        const double f = f_steps ? f_steps[tinx - 1] : 0.0;
+        // savesol! from the step kernel's registers: the annual-mean sums on every step, the raw snapshot on the steps that
+        // are kept; the diagnostic FIELDS are only stored on steps whose snapshot is copied out of them (seasons) and on
+        // the last one
+        const int diag = (s.snapshot || s.last) ? 1 : 0;
+        save.stage = s.raw ? stage + (size_t)half * (size_t)nvars * chunk * npitch : nullptr;
+        save.stage_offset = staged * (long long)npitch;
+        rc = do_step(h, h->ttab[ti - 1], h->ttab[ti % nt], f, diag, clock0 + tinx - 1, (sums || s.raw) ? &save : nullptr);
+        if (rc) return rc;
+        if (s.raw && ++staged == chunk) HIPCHK(flush());
+        auto state_field = [&](int v) { return (const double *)h->field[fields[v]]; };
+        if (s.snapshot && (rc = ensure_natural(h))) return rc;
+        if (s.season == 1) {
+            if (winter) HIPCHK(season_to_host(winter, year));
+            if (hm_winter) HIPCHK(means_to_host(hm_winter, year, state_field));
+        } else if (s.season == 2) {
+            if (summer) HIPCHK(season_to_host(summer, year));
+            if (hm_summer) HIPCHK(means_to_host(hm_summer, year, state_field));
+        } else if (s.year_end) {
+            if (sums) {
+                HIPCHK(cp->wait_all());                                      // last year's means have left `mean`
+                HIPCHK(ebm::launch_finish_mean(mean, sums, (double)nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h)));
+                if (avg) HIPCHK(fields_to_host(avg, year, mean));
+                if (hm_avg) HIPCHK(means_to_host(hm_avg, year, [&](int v) { return (const double *)(mean + (size_t)v * npitch); }));
+            }
+        }
+        if (sums && s.year_end && s.season)                                  // year ended on a seasonal index:
+            HIPCHK(hipMemsetAsync(sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));  // no mean is taken, restart sums
+    }
+    HIPCHK(flush());
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(cp->wait_all());
+    return EBM_OK;
+}
+
+int ebm_integrate(ebm_handle_t h, int nt, int dur, const double *f_steps, int lastonly,
+                  int winter_inx, int summer_inx, int nvars, const int *fields, double *raw,
+                  double *winter, double *summer, double *avg) {
+    return integrate_impl(h, nt, dur, f_steps, lastonly, winter_inx, summer_inx, nvars, fields, raw, winter, summer, avg,
+                          nullptr, nullptr, nullptr);
+}
+
+int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_steps, int winter_inx, int summer_inx,
+                              int nvars, const int *fields, double *hm_winter, double *hm_summer, double *hm_avg) {
+    if (!hm_winter && !hm_summer && !hm_avg) return fail(EBM_ERR_ARG, "ebm_integrate_hemispheric: no output requested");
+    return integrate_impl(h, nt, dur, f_steps, 1, winter_inx, summer_inx, nvars, fields, nullptr, nullptr, nullptr, nullptr,
+                          hm_winter, hm_summer, hm_avg);
+}
+
+// ebm_equilibrate (include/ebm_hip.h).  Every year is one fused_range over the active columns (launches of nactive
+// workgroups, which step cols[b]), then equilibrium_check_kernel compares each active column's year-end fields with the
+// snapshot of the year before and freezes it, compact_active_kernel writes the next list and its length, and the host
+// reads the length: one stream synchronisation per year.  The fused kernels store the diagnostic fields in the natural
+// layout, so the fields of columns frozen in different years share one layout and nothing is un-permuted in between.
+int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const double *f_year, int nvars, const int *fields,
+                    const double *tol, int *years, int *converged, double *resid) {
+    if (!h || nt < 1 || nvars < 1 || !fields || !tol || !years || !converged) return fail(EBM_ERR_ARG, "ebm_equilibrate: bad argument");
+    if (h->fsched)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: per-column forcing schedules are installed (a ramped forcing has no "
+                                         "equilibrium; ebm_set_column_schedule(h, NULL) clears them)");
+    if (h->noise.rec)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: forcing noise is installed (a noisy member has no repeating cycle; "
+                                         "ebm_set_column_noise(h, NULL, ...) clears it)");
+    if ((long long)h->ttab.size() != nt) return fail(EBM_ERR_ARG, "ebm_equilibrate: time table length must equal nt");
+    if (max_years < 1) return fail(EBM_ERR_ARG, "ebm_equilibrate: max_years must be >= 1");
+    if (nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_equilibrate: too many fields");
+    FieldRef vars[ebm::kMaxQuantities];
+    int rc = resolve_fields(h, "ebm_equilibrate", nvars, fields, vars);
+    if (rc) return rc;
+    ebm::EquilArgs ea{};
+    for (int v = 0; v < nvars; ++v) {
+        if (!(tol[v] >= 0.0))
+            return fail(EBM_ERR_ARG, std::string("ebm_equilibrate: the tolerance of ") + field_name(vars[v].field) + " must be >= 0 (not NaN)");
+        ea.slot[v] = vars[v].slot;
+        ea.tol[v] = tol[v];
+    }
+    if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: no fused-K kernel for this shape in this build");
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = ensure_natural(h))) return rc;
+    const int ncol = h->ncol;
+    const size_t npitch = (size_t)ncol * h->pitch;
+    // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count
+    DevBuf<double> dbl;
+    DevBuf<int> ints;
+    PinnedBuf<int> pinned;
+    // the list is known to the launches only until the call returns, on every path; they end before the buffers are freed
+    const auto done = finally([h] {
+        (void)hipStreamSynchronize(main_stream(h));
+        h->active = nullptr;
+        h->nactive = 0;
+    });
+    HIPCHK(dev_alloc(dbl, (size_t)nvars * npitch + (size_t)nvars * ncol));
+    HIPCHK(dev_alloc(ints, 4 * (size_t)ncol + 1));
+    HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
+    int *cur = ints.get(), *nxt = cur + ncol, *years_dev = nxt + ncol, *frozen = years_dev + ncol, *count = frozen + ncol;
+    {
+        std::vector<double> nan((size_t)nvars * ncol, std::nan(""));
+        std::vector<int> ident((size_t)ncol);
+        for (int c = 0; c < ncol; ++c) ident[c] = c;
+        HIPCHK(hipMemcpy(dbl.get() + (size_t)nvars * npitch, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(years_dev, 0, sizeof(int) * 2 * (size_t)ncol));
+    }
+    ea.state = h->state.get(); ea.fstride = h->fstride;
+    ea.snap = dbl.get(); ea.resid = dbl.get() + (size_t)nvars * npitch;
+    ea.years = years_dev; ea.frozen = frozen;
+    ea.pitch = (int)h->pitch; ea.nlat = h->nlat; ea.ncol = ncol; ea.nvars = nvars;
+    const long long clock0 = h->clock;
+    const int first_test = std::max(2, min_years);
+    int nactive = ncol;
+    for (int y = 1; y <= max_years; ++y) {
+        h->active = cur;
+        h->nactive = nactive;
+        rc = fused_range(h, 0, clock0 + (long long)(y - 1) * nt, nt, f_year, 1, h->integrate_spl, nullptr);
+        if (rc) return rc;
+        ea.cols = cur;
+        ea.year = y;
+        ea.compare = y >= 2;
+        ea.may_freeze = y >= first_test;
+        hipError_t e = ebm::launch_equilibrium_check(ea, nactive, main_stream(h));
+        if (e != hipSuccess) return hip_fail("ebm_equilibrate: check", e);
+        if (y == max_years || !ea.may_freeze) continue;          // (nothing has frozen: the list stays)
+        e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+        if (e != hipSuccess) return hip_fail("ebm_equilibrate: active list", e);
+        nactive = *pinned.get();
+        std::swap(cur, nxt);
+        if (nactive == 0) break;                                 // every column is frozen
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(years, years_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(converged, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    if (resid) HIPCHK(hipMemcpy(resid, ea.resid, sizeof(double) * (size_t)nvars * ncol, hipMemcpyDeviceToHost));
+    return EBM_OK;
+}
+
+}  // extern "C"

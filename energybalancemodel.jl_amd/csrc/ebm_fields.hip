@@ -1,0 +1,262 @@
+// Host runtime, fields (ebm_runtime.h lists the units): set / get with the validity bookkeeping, device views, hemispheric
+// means, and the two diffusion operators that work on caller-supplied fields (ebm_diffusion, ebm_zonal_diffusion).
+#include "ebm_runtime.h"
+#include "ebm_tables.h"
+
+using namespace ebm_rt;
+
+namespace ebm_rt {
+
+// Readers of a diagnostic field get the natural layout: un-permute in place once after a step that stored them split.
+int ensure_natural(ebm_ctx *h) {
+    if (!h->diag_split) return EBM_OK;
+    hipError_t e = ebm::launch_unsplit_fields(h->field[EBM_F_Tw], h->fstride, 5, h->ncol, h->cfg, main_stream(h));
+    if (e != hipSuccess) return hip_fail("unsplit_fields", e);
+    h->diag_split = false;
+    return EBM_OK;
+}
+
+int get_copier(ebm_ctx *h) {
+    if (h->copier) return EBM_OK;
+    auto c = std::make_unique<HostCopier>();
+    hipError_t e = c->init(h->device);
+    if (e != hipSuccess) return hip_fail("pinned staging ring", e);
+    h->copier = std::move(c);
+    return EBM_OK;
+}
+
+}  // namespace ebm_rt
+
+namespace {
+
+// The preamble of every field reader, in this order: the arguments, the field is one of this model (check_field); it is
+// current (check_current; ebm_get_field_as_of has its own rule here); the handle's device and the natural layout (make_readable).
+int check_field(const ebm_ctx *h, int field, const void *out, const char *who) {
+    if (!h || !out) return fail(EBM_ERR_ARG, std::string(who) + ": null argument");
+    if (!has_field(h, field)) return fail(EBM_ERR_ARG, std::string(who) + ": field not part of this model");
+    return EBM_OK;
+}
+int make_readable(ebm_ctx *h, int field) {
+    HIPCHK(hipSetDevice(h->device));
+    return is_split_field(h, field) ? ensure_natural(h) : EBM_OK;
+}
+int open_field(ebm_ctx *h, int field, const void *out, const char *who) {
+    int rc = check_field(h, field, out, who);
+    if (!rc) rc = check_current(h, field, who);
+    if (!rc) rc = make_readable(h, field);
+    return rc;
+}
+
+// ncol rows of nlat doubles, row pitches in doubles (nlat: packed, h->pitch: a padded device field), on the handle's stream
+hipError_t copy_rows(ebm_ctx *h, double *dst, long long dst_pitch, const double *src, long long src_pitch, hipMemcpyKind kind) {
+    return hipMemcpy2DAsync(dst, sizeof(double) * dst_pitch, src, sizeof(double) * src_pitch, sizeof(double) * h->nlat,
+                            h->ncol, kind, main_stream(h));
+}
+
+// device -> host through the pinned ring (synchronous)
+int download_field(ebm_ctx *h, int field, double *host, const char *who) {
+    int rc = get_copier(h);
+    if (rc) return rc;
+    HostCopier *c = h->copier.get();
+    HIPCHK(c->wait_all());
+    HIPCHK(c->order_after(main_stream(h)));
+    CopyJob j;
+    j.src = h->field[field]; j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat; j.nrows = (size_t)h->ncol; j.dst = host;
+    hipError_t e = c->run(j);
+    if (e != hipSuccess) return hip_fail(who, e);
+    return EBM_OK;
+}
+
+// ebm_hemispheric_mean / _device: the per-column means of a readable field into dev_out
+hipError_t hemispheric_mean(ebm_ctx *h, int field, double *dev_out) {
+    return ebm::launch_hemispheric_mean(h->field[field], x_table(h), (int)h->pitch, h->nlat, h->ncol, dev_out, main_stream(h));
+}
+
+// ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
+int get_scratch(ebm_ctx *h) {
+    if (h->scratch) return EBM_OK;
+    const size_t n = 3 * (size_t)h->ncol * h->pitch;
+    DevBuf<double> b;
+    HIPCHK(dev_alloc(b, n));
+    HIPCHK(hipMemsetAsync(b.get(), 0, sizeof(double) * n, main_stream(h)));       // padding cells stay zero
+    h->scratch = std::move(b);
+    return EBM_OK;
+}
+
+// The parameters of the zonal operator: the handle's vector, or the one set ebm_set_column_params installed
+const ebm::Params &zonal_params(const ebm_ctx *h) { return h->sets.n ? h->sets.host[0] : h->p; }
+// The zonal tables (ebm_tables::build_zonal_tables) on the device, with the segmented sweep's scratch behind them.  Built on
+// first use and whenever nlon changes.
+int build_zonal_tables(ebm_ctx *h, int nlon) {
+    if (h->zonal.tab && h->zonal.nlon == nlon) return EBM_OK;
+    ebm_tables::ZonalHostTables t;
+    const int P = (int)h->pitch;
+    const char *why = ebm_tables::build_zonal_tables(nlon, h->nlat, P, h->cfg.threads, h->cfg.cells, h->dt, h->xhost.data(),
+                                                     zonal_params(h), t);
+    if (why) return fail(EBM_ERR_ARG, why);
+    const int nmember = h->ncol / nlon;
+    const size_t scratch = t.seg == 1 ? 0 : 3 * (size_t)nmember * t.seg * P;
+    ebm_ctx::ZonalTables z;
+    HIPCHK(dev_alloc(z.tab, t.tab.size() + scratch));
+    HIPCHK(hipMemcpy(z.tab.get(), t.tab.data(), sizeof(double) * t.tab.size(), hipMemcpyHostToDevice));
+    z.M = z.tab.get(); z.E = z.M + t.chain_rows * P; z.rM = z.E + t.chain_rows * P; z.rE = z.rM + t.red_rows * P;
+    z.a = z.rE + t.red_rows * P; z.a2 = z.a + P; z.W = z.a2 + P;
+    z.su = z.W + P; z.sg = z.su + scratch / 3; z.sy = z.sg + scratch / 3;
+    z.nlon = nlon;
+    z.seg = t.seg;
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    h->zonal = std::move(z);
+    return EBM_OK;
+}
+hipError_t zonal_sweep(ebm_ctx *h, const double *T, double *outZ, double *outU) {
+    const ebm_ctx::ZonalTables &z = h->zonal;
+    const int nmember = h->ncol / z.nlon;
+    const double rtheta = zonal_params(h).cw / h->dt;
+    if (z.seg == 1)
+        return ebm::launch_zonal_sweep(T, outZ, outU, z.M, z.E, z.a, z.W, z.nlon, nmember, (int)h->pitch, rtheta, main_stream(h));
+    return ebm::launch_zonal_sweep_segmented(T, outZ, outU, z.M, z.E, z.rM, z.rE, z.a, z.a2, z.W, z.su, z.sg, z.sy, z.nlon,
+                                             z.seg, nmember, (int)h->pitch, rtheta, main_stream(h));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ebm_set_field(ebm_handle_t h, int field, const double *host) {
+    int rc = check_field(h, field, host, "ebm_set_field");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = get_copier(h))) return rc;
+    if (is_split_field(h, field)) {
+        rc = ensure_natural(h);                   // the other diagnostic fields keep their values, in the natural layout
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(h->copier->wait_all());
+    HIPCHK(h->copier->upload(h->field[field], (size_t)h->pitch, host, (size_t)h->nlat, (size_t)h->ncol));
+    if (field == EBM_F_T0 && h->model == EBM_MODEL_MIZ) {
+        // the stepping kernels carry the warm start as its active set: rebuild it from the new T0
+        hipError_t e = ebm::launch_mask_from_t0(base_args(h), h->ncol, h->cfg, main_stream(h));
+        if (e != hipSuccess) return hip_fail("mask_from_t0", e);
+        HIPCHK(hipStreamSynchronize(main_stream(h)));
+    }
+    if (is_diagnostic(h, field)) {                // the caller's statement of what the field holds: current as of now
+        h->written_epoch[field] = h->epoch;
+        h->written_step[field] = h->state_step;
+    } else {
+        h->epoch += 1;                            // the prognostic state changed: every diagnostic field is older than it now
+    }
+    return EBM_OK;
+}
+
+int ebm_get_field(ebm_handle_t h, int field, double *host) {
+    int rc = open_field(h, field, host, "ebm_get_field");
+    return rc ? rc : download_field(h, field, host, "ebm_get_field");
+}
+
+int ebm_get_field_as_of(ebm_handle_t h, int field, long long step, double *host) {
+    int rc = check_field(h, field, host, "ebm_get_field_as_of");
+    if (rc) return rc;
+    const long long have = is_diagnostic(h, field) ? (h->written_epoch[field] >= 0 ? h->written_step[field] : -2) : h->state_step;
+    if (have != step)
+        return fail(EBM_ERR_STALE, std::string("ebm_get_field_as_of: field ") + field_name(field) + " is not as of step " +
+                                       std::to_string(step) + (have == -2 ? " (it has never been written)"
+                                                                          : " (it was last written by step " + std::to_string(have) + ")"));
+    if ((rc = make_readable(h, field))) return rc;
+    return download_field(h, field, host, "ebm_get_field_as_of");
+}
+
+int ebm_field_step(ebm_handle_t h, int field, long long *written_step, long long *state_step, int *current) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_field_step: null handle");
+    if (!has_field(h, field)) return fail(EBM_ERR_ARG, "ebm_field_step: field not part of this model");
+    const bool diag = is_diagnostic(h, field);
+    if (written_step) *written_step = diag ? (h->written_epoch[field] >= 0 ? h->written_step[field] : -1) : h->state_step;
+    if (state_step) *state_step = h->state_step;
+    if (current) *current = (!diag || h->written_epoch[field] == h->epoch) ? 1 : 0;
+    return EBM_OK;
+}
+
+int ebm_hemispheric_mean(ebm_handle_t h, int field, double *out) {
+    int rc = open_field(h, field, out, "ebm_hemispheric_mean");
+    if (rc) return rc;
+    hipError_t e = hemispheric_mean(h, field, h->hm_dev.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out, h->hm_dev.get(), sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost, main_stream(h));
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e != hipSuccess) return hip_fail("ebm_hemispheric_mean", e);
+    return EBM_OK;
+}
+
+int ebm_hemispheric_mean_device(ebm_handle_t h, int field, double *dev_out) {
+    int rc = open_field(h, field, dev_out, "ebm_hemispheric_mean_device");
+    if (rc) return rc;
+    hipError_t e = hemispheric_mean(h, field, dev_out);
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e != hipSuccess) return hip_fail("ebm_hemispheric_mean_device", e);
+    return EBM_OK;
+}
+
+int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {
+    int rc = open_field(h, field, dev_out, "ebm_get_field_device");
+    if (rc) return rc;
+    HIPCHK(copy_rows(h, dev_out, h->nlat, h->field[field], h->pitch, hipMemcpyDeviceToDevice));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    return EBM_OK;
+}
+
+int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pitch) {
+    int rc = open_field(h, field, dptr, "ebm_field_device_ptr");
+    if (rc) return rc;
+    if (is_split_field(h, field)) HIPCHK(hipStreamSynchronize(main_stream(h)));   // the view is of the natural layout as of this call
+    *dptr = h->field[field];
+    if (pitch) *pitch = h->pitch;
+    return EBM_OK;
+}
+
+int ebm_diffusion(ebm_handle_t h, const double *temp, const double *base, double *out) {
+    if (!h || !temp || !out) return fail(EBM_ERR_ARG, "ebm_diffusion: null argument");
+    if (h->model != EBM_MODEL_MIZ)
+        return fail(EBM_ERR_ARG, "ebm_diffusion: needs a MIZ handle (the classic model carries get_diffop unscaled inside kappa, src/classic.jl:21)");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t npitch = (size_t)h->ncol * h->pitch;
+    int rc = get_scratch(h);                             // temp | base | out
+    if (rc) return rc;
+    double *buf = h->scratch.get();
+    hipError_t e = copy_rows(h, buf, h->pitch, temp, h->nlat, hipMemcpyHostToDevice);
+    if (e == hipSuccess && base) e = copy_rows(h, buf + npitch, h->pitch, base, h->nlat, hipMemcpyHostToDevice);
+    const ebm::StepArgs a = base_args(h);                // the column's parameter set (ebm_set_column_params)
+    if (e == hipSuccess)
+        e = ebm::launch_diffusion(buf, base ? buf + npitch : nullptr, buf + 2 * npitch, a.geom, a.gstride, a.p, a.pset,
+                                  a.set_stride, h->grid, (int)h->pitch, h->nlat, h->ncol, main_stream(h));
+    if (e == hipSuccess) e = copy_rows(h, out, h->nlat, buf + 2 * npitch, h->pitch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e != hipSuccess) return hip_fail("ebm_diffusion", e);
+    return EBM_OK;
+}
+
+int ebm_zonal_diffusion(ebm_handle_t h, int nlon, const double *temp, double *out_U, double *out_Z) {
+    if (!h || !temp || (!out_U && !out_Z)) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: null argument");
+    if (h->model != EBM_MODEL_MIZ) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs a MIZ handle (cw and D are MIZ parameters of this operator)");
+    if (nlon < 3) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: needs nlon >= 3 (longitudes per member)");
+    if (h->ncol % nlon) return fail(EBM_ERR_ARG, "ebm_zonal_diffusion: the handle's column count must be a multiple of nlon");
+    if (h->sets.n > 1)
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_zonal_diffusion: needs one parameter set (its tables come from one D and one cw; "
+                                         "ebm_set_column_params installed " + std::to_string(h->sets.n) + ")");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = build_zonal_tables(h, nlon);
+    if (rc) return rc;
+    const size_t npitch = (size_t)h->ncol * h->pitch;
+    if ((rc = get_scratch(h))) return rc;                // temp | U | Z
+    double *buf = h->scratch.get();
+    hipError_t e = hipMemsetAsync(buf, 0, sizeof(double) * npitch, main_stream(h));            // (an earlier call left it permuted)
+    if (e == hipSuccess) e = copy_rows(h, buf, h->pitch, temp, h->nlat, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = ebm::launch_split_fields(buf, 0, 1, h->ncol, h->cfg, main_stream(h));
+    if (e == hipSuccess) e = zonal_sweep(h, buf, buf + 2 * npitch, buf + npitch);
+    if (e == hipSuccess) e = ebm::launch_unsplit_fields(buf + npitch, (long long)npitch, 2, h->ncol, h->cfg, main_stream(h));
+    if (e == hipSuccess && out_U) e = copy_rows(h, out_U, h->nlat, buf + npitch, h->pitch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_Z) e = copy_rows(h, out_Z, h->nlat, buf + 2 * npitch, h->pitch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+    if (e != hipSuccess) return hip_fail("ebm_zonal_diffusion", e);
+    return EBM_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
-// Host side of the runtime behind the C ABI (ebm_runtime.hip): owners of HIP resources, a process-wide pool of host threads
+// Host side of the runtime behind the C ABI (ebm_runtime.h): owners of HIP resources, a process-wide pool of host threads
 // and, per handle, a pinned staging ring with a DMA stream and a worker thread for the asynchronous outputs of ebm_integrate.
-// Header-only, included by ebm_runtime.hip alone; not part of the public interface (include/ebm_hip.h).
+// Header-only, included through ebm_runtime.h by the four host units alone; not part of the public interface (include/ebm_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -47,13 +47,13 @@ MUTANTS = [
     # (merged with resident_extension_matrix_diagonal_sign: the step and the resident kernel share imex_row)
     ("extension_matrix_diagonal_sign", "rb = 1.0 + p.theta_imex * (lo + up);", "rb = 1.0 - p.theta_imex * (lo + up);"),
     # third batch: the host runtime (tables, time bookkeeping, savesol!) and the small kernels; a 4-tuple names the file
-    ("uniform_table_metric_linear", "lam[i - 1] = (1.0 - xb * xb) / (dx * dx);", "lam[i - 1] = (1.0 - xb) / (dx * dx);", "ebm_runtime.hip"),
-    ("polar_ghost_cell_misplaced", "double xp = k < nx - 1 ? x[k + 1] : 2.0 - x[nx - 1];", "double xp = k < nx - 1 ? x[k + 1] : 1.0 - x[nx - 1];", "ebm_runtime.hip"),
-    ("solver_table_uses_wrong_spacing", "double l = p.D * g1[k] / (g3[k] * g4[k]);", "double l = p.D * g1[k] / (g2[k] * g4[k]);", "ebm_runtime.hip"),
-    ("classic_ghost_diagonal_sign", "kdiag[k] = one - (dtD * g1[k]) / p.cg;", "kdiag[k] = one + (dtD * g1[k]) / p.cg;", "ebm_runtime.hip"),
-    ("model_time_at_step_start", "return nt > 0.0 ? (double)(2 * step + 1) / (2.0 * nt) : 0.0;", "return nt > 0.0 ? (double)(2 * step) / (2.0 * nt) : 0.0;", "ebm_runtime.hip"),
-    ("lastonly_keeps_one_step_too_many", "const bool want_raw = stage && (!lastonly || tinx > total - nt);", "const bool want_raw = stage && (!lastonly || tinx >= total - nt);", "ebm_runtime.hip"),
-    ("winter_snapshot_one_step_late", "if (ti == winter_inx) {", "if (ti == winter_inx + 1) {", "ebm_runtime.hip"),
+    ("uniform_table_metric_linear", "lam[i - 1] = (1.0 - xb * xb) / (dx * dx);", "lam[i - 1] = (1.0 - xb) / (dx * dx);", "ebm_tables.h"),
+    ("polar_ghost_cell_misplaced", "double xp = k < nx - 1 ? x[k + 1] : 2.0 - x[nx - 1];", "double xp = k < nx - 1 ? x[k + 1] : 1.0 - x[nx - 1];", "ebm_tables.h"),
+    ("solver_table_uses_wrong_spacing", "double l = p.D * g1[k] / (g3[k] * g4[k]);", "double l = p.D * g1[k] / (g2[k] * g4[k]);", "ebm_tables.h"),
+    ("classic_ghost_diagonal_sign", "kdiag[k] = one - (dtD * g1[k]) / p.cg;", "kdiag[k] = one + (dtD * g1[k]) / p.cg;", "ebm_tables.h"),
+    ("model_time_at_step_start", "return nt > 0.0 ? (double)(2 * step + 1) / (2.0 * nt) : 0.0;", "return nt > 0.0 ? (double)(2 * step) / (2.0 * nt) : 0.0;", "ebm_drive.hip"),
+    ("lastonly_keeps_one_step_too_many", "s.raw = stage && (!lastonly || tinx > total - nt);", "s.raw = stage && (!lastonly || tinx >= total - nt);", "ebm_drive.hip"),
+    ("winter_snapshot_one_step_late", "s.season = ti == winter_inx ? 1 :", "s.season = ti == winter_inx + 1 ? 1 :", "ebm_drive.hip"),
     ("annual_mean_divides_by_nt_minus_1", "m.x = s.x / nt;", "m.x = s.x / (nt - 1.0);"),
     ("annual_sum_not_restarted", "z.x = 0.0;", "z.x = s.x;"),
     ("hemispheric_mean_without_the_half", "terms[i] = ieee_div((v[i] + v[i + 1]) * (x[i + 1] - x[i]), 2.0);", "terms[i] = (v[i] + v[i + 1]) * (x[i + 1] - x[i]);"),
@@ -85,26 +85,26 @@ MUTANTS = [
     ("unsplit_writes_the_first_pair_twice", "*reinterpret_cast<double2 *>(f + 4 * t + 2) = p1;", "*reinterpret_cast<double2 *>(f + 4 * t + 2) = p0;"),
     ("diagnostic_pairs_stored_on_top_of_each_other", "const unsigned ks = (unsigned)(j * 2 * T + 2 * t);", "const unsigned ks = (unsigned)(2 * t);"),
     ("diagnostic_layout_flag_never_set", "record_launches(h, 1, 1, step, write_diag != 0, h->cfg.cells == 4);",
-     "record_launches(h, 1, 1, step, write_diag != 0, false);", "ebm_runtime.hip"),
-    ("fields_never_go_stale", "    h->epoch += nsteps;", "    h->epoch += 0;", "ebm_runtime.hip"),
+     "record_launches(h, 1, 1, step, write_diag != 0, false);", "ebm_drive.hip"),
+    ("fields_never_go_stale", "    h->epoch += nsteps;", "    h->epoch += 0;", "ebm_drive.hip"),
     ("classic_kernel_ignores_its_column_offset", "const int T = blockDim.x, t = threadIdx.x, col = a.col0 + (int)blockIdx.x;",
      "const int T = blockDim.x, t = threadIdx.x, col = (int)blockIdx.x;"),
-    ("launch_chains_never_joined", "        (void)hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0);", "", "ebm_runtime.hip"),
+    ("launch_chains_never_joined", "        (void)hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0);", "", "ebm_runtime.h"),
     ("second_chain_does_not_wait_for_earlier_work", "if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);", "",
-     "ebm_runtime.hip"),
+     "ebm_drive.hip"),
     ("zonal_last_row_coefficient_sign", "            f = -a * ee[i];", "            f = a * ee[i];"),
     ("zonal_back_substitution_drops_the_wrap_term", "const double U = __builtin_fma(a * mm[i], Un, __builtin_fma(ee[i], W, dd[i]));",
      "const double U = __builtin_fma(a * mm[i], Un, dd[i]);"),
-    ("zonal_coefficient_linear_in_dlambda", "a = theta * D / (mm * (dl * dl));", "a = theta * D / (mm * dl);", "ebm_runtime.hip"),
+    ("zonal_coefficient_linear_in_dlambda", "a = theta * D / (mm * (dl * dl));", "a = theta * D / (mm * dl);", "ebm_tables.h"),
     ("annual_means_all_from_the_first_variable", "const size_t base = (size_t)blockIdx.y * (size_t)var_stride + (size_t)col * (size_t)threads * cells;",
      "const size_t base = (size_t)col * (size_t)threads * cells;"),
     ("ring_pieces_reuse_the_first_two_offsets", "const size_t r0 = i * rows_per;", "const size_t r0 = (i % 2) * rows_per;", "ebm_hostcopy.h"),
     # (added after the zonal sweep was partitioned along the circle)
     ("zonal_segment_end_takes_the_wrong_neighbour", "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)((s_ + 1) % S) * P], sg[o + (size_t)s_ * P]); };",
      "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)s_ * P], sg[o + (size_t)s_ * P]); };"),
-    ("zonal_reduced_diagonal_without_the_spike_sum", "const double a2 = a * ep_last, B2 = B - a * cp_last - a * alpha;", "const double a2 = a * ep_last, B2 = B - a * cp_last;", "ebm_runtime.hip"),
-    ("integrate_restarts_model_time", "f, diag, clock0 + tinx - 1,", "f, diag, tinx - 1,", "ebm_runtime.hip"),
-    ("as_of_query_inverted", "    if (have != step)", "    if (have == step)", "ebm_runtime.hip"),
+    ("zonal_reduced_diagonal_without_the_spike_sum", "const double a2 = a * ep_last, B2 = B - a * cp_last - a * alpha;", "const double a2 = a * ep_last, B2 = B - a * cp_last;", "ebm_tables.h"),
+    ("integrate_restarts_model_time", "f, diag, clock0 + tinx - 1,", "f, diag, tinx - 1,", "ebm_drive.hip"),
+    ("as_of_query_inverted", "    if (have != step)", "    if (have == step)", "ebm_fields.hip"),
     # seventh batch: the LDS-resident fused-K kernel, its compact solve, its halo exchange and its vote
     ("resident_diagnostics_of_the_first_step", "const bool diag = a.write_diag != 0 && step + 1 == nloop;", "const bool diag = a.write_diag != 0 && step == 0;"),
     ("resident_newton_stops_after_one_iteration", "} while (it < kMaxNewton && again);", "} while (false);"),
@@ -120,10 +120,12 @@ MUTANTS = [
     ("resident_state_words_one_slot_low", "win[((4 + 4 * (F) + (i)) * T) >> 13][((4 + 4 * (F) + (i)) * T) & 8191]", "win[((3 + 4 * (F) + (i)) * T) >> 13][((3 + 4 * (F) + (i)) * T) & 8191]"),
     # eighth batch: ebm_integrate's fused stretches
     ("resident_sums_of_the_second_pair_land_on_the_first", "(unsigned)((i / 2) * 2 * T) + 2u * (unsigned)td,", "2u * (unsigned)td,"),
-    ("integrate_fused_stretch_restarts_its_forcing", "(int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,", "(int)n, f_steps, 0, h->integrate_spl,", "ebm_runtime.hip"),
-    ("integrate_fused_stretch_one_table_entry_late", "rc = fused_range(h, tinx - 1, clock0 + tinx - 1,", "rc = fused_range(h, tinx, clock0 + tinx - 1,", "ebm_runtime.hip"),
-    ("integrate_fuses_through_the_winter_snapshot", "if ((ti_ == winter_inx && (winter || hm_winter)) || (ti_ == summer_inx && (summer || hm_summer))) return false;",
-     "if (ti_ == summer_inx && (summer || hm_summer)) return false;", "ebm_runtime.hip"),
+    ("integrate_fused_stretch_restarts_its_forcing", "(int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,", "(int)n, f_steps, 0, h->integrate_spl,", "ebm_drive.hip"),
+    ("integrate_fused_stretch_one_table_entry_late", "rc = fused_range(h, tinx - 1, clock0 + tinx - 1,", "rc = fused_range(h, tinx, clock0 + tinx - 1,", "ebm_drive.hip"),
+    # (the step plan is one function now: the loop body reads the same result, so the winter step, fused through or
+    # not, is not taken for a snapshot step)
+    ("integrate_fuses_through_the_winter_snapshot", "s.snapshot = (ti == winter_inx && (winter || hm_winter)) || (ti == summer_inx && (summer || hm_summer));",
+     "s.snapshot = ti == summer_inx && (summer || hm_summer);", "ebm_drive.hip"),
 ]
 
 

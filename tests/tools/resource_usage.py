@@ -4,7 +4,7 @@
 
     python tests/tools/resource_usage.py [-D...] > profiles/rNN_resource_usage.txt
 
-Every kernel translation unit of csrc/ (*.hip except ebm_runtime.hip) is compiled with the Makefile's flags; the remarks
+Every kernel translation unit of csrc/ (*.hip except the four host units, HOST_UNITS) is compiled with the Makefile's flags; the remarks
 of all of them go into one sorted table.  EBM_KERNEL_SRC names another directory of sources.
 One line per kernel instantiation: name, VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy.
 Exit status 1 if any kernel of the shipped library uses scratch (register spills), 2 if a translation unit does not
@@ -18,6 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.environ.get("EBM_KERNEL_SRC") or os.path.join(ROOT, "energybalancemodel.jl_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17"]
+HOST_UNITS = ("ebm_runtime.hip", "ebm_fields.hip", "ebm_columns.hip", "ebm_drive.hip")      # no kernels: the host runtime
 
 
 def demangle(names):
@@ -48,7 +49,7 @@ def remarks(unit, extra):
 
 def main():
     extra = [a for a in sys.argv[1:] if a.startswith("-")]
-    units = sorted(f for f in os.listdir(SRC) if f.endswith(".hip") and f != "ebm_runtime.hip")
+    units = sorted(f for f in os.listdir(SRC) if f.endswith(".hip") and f not in HOST_UNITS)
     with ThreadPoolExecutor(max_workers=6) as pool:
         per_unit = list(pool.map(lambda u: remarks(u, extra), units))
     rows, seen = [], {}
