@@ -154,7 +154,8 @@ def choose_tol(d, max_years, min_years):
 
 
 def check_against_reference(setup, names, max_years, min_years=2, snaps=None, tol=None):
-    """ebm_equilibrate on a fresh handle against the oracle; returns (result, snaps, tol)."""
+    """ebm_equilibrate on a fresh handle against the oracle; returns (result, snaps, tol); result["counters"] are the
+    handle's counters after the call."""
     nt = setup.st.nt
     snaps = reference(setup, max_years) if snaps is None else snaps
     d = distances(snaps, names)
@@ -177,7 +178,8 @@ def check_against_reference(setup, names, max_years, min_years=2, snaps=None, to
             field = eng.get_field(k)
             for c in range(setup.ncol):
                 assert np.array_equal(field[c], snaps[k][want_y[c]][c], equal_nan=True), (k, c, want_y[c])
-        assert eng.counters()["steps"] == nt * ymax
+        got["counters"] = eng.counters()
+        assert got["counters"]["steps"] == nt * ymax
     return got, snaps, tol
 
 
