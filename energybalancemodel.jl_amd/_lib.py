@@ -30,8 +30,8 @@ EXPORTS = (
     "ebm_set_step_clock", "ebm_set_time_table",
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
     "ebm_equilibrate", "ebm_sync", "ebm_get_counters",
-    "ebm_reset_counters", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
-    "ebm_selftest_divide",
+    "ebm_reset_counters", "ebm_state_conversions", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
+    "ebm_selftest_divide", "ebm_selftest_permute",
 )
 
 _dp = C.POINTER(C.c_double)
@@ -117,10 +117,12 @@ def load():
     lib.ebm_sync.argtypes = [C.c_void_p]
     lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_reset_counters.argtypes = [C.c_void_p]
+    lib.ebm_state_conversions.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_timer_start.argtypes = [C.c_void_p]
     lib.ebm_timer_stop.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.ebm_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.ebm_selftest_divide.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
+    lib.ebm_selftest_permute.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     _lib = lib
     return lib
 

@@ -173,6 +173,26 @@ __device__ __forceinline__ void load_chunk(const double *__restrict__ f, unsigne
         v[2 * j + 1] = d.y;
     }
 }
+// The fields miz_step_kernel owns between its launches (the prognostics) and the diagnostic fields it stores are in the
+// pair-split layout: where pair j of the lane whose first cell is k0 = 4t lies, split_index(t, j, T), as the sum of a
+// wave-uniform part (the pair's) and the lane's part 2t, formed as k0/2 (C = 2: the natural place).
+template <int C, int T>
+__device__ __forceinline__ constexpr unsigned state_pair_base(int j) {
+    return C == 4 ? split_index(0u, (unsigned)j, (unsigned)T) : 2u * (unsigned)j;
+}
+template <int C>
+__device__ __forceinline__ unsigned state_lane(unsigned k0) { return C == 4 ? k0 / 2u : k0; }
+template <int C, int T>
+__device__ __forceinline__ unsigned state_index(unsigned k0, int j) { return state_pair_base<C, T>(j) + state_lane<C>(k0); }
+template <int C, int T>
+__device__ __forceinline__ void load_state(const double *__restrict__ f, unsigned k0, double (&v)[C]) {
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        double2 d = *reinterpret_cast<const double2 *>(f + state_index<C, T>(k0, j));
+        v[2 * j] = d.x;
+        v[2 * j + 1] = d.y;
+    }
+}
 template <int C>
 __device__ __forceinline__ void store_chunk(double *__restrict__ f, const double (&v)[C], unsigned k0, int nlat) {
 #pragma unroll

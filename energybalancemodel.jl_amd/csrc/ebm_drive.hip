@@ -51,7 +51,12 @@ int chain_count(const ebm_ctx *h, int *first_half) {
     *first_half = h->split_col ? (h->active ? n / 2 : h->split_col) : n;
     return (*first_half > 0) + (n - *first_half > 0);
 }
+// Every step launch of the library goes through here, so the layout rule of the prognostic fields (ebm_ctx::state_split) is
+// applied here: a one-step MIZ launch reads and writes them pair-split, the fused-K and classic kernels the natural layout.
+// A steady run of either kind converts nothing.  Under graph capture the layout is already the one-step one (build_graph).
 hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
+    const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
+    if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
     const int n = h->active ? h->nactive : h->ncol;
     if (!h->split_col) return launch_columns(h, a, mode, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
@@ -72,6 +77,8 @@ int build_graph(ebm_ctx *h) {
     ebm_ctx::Graph g;
     HIPCHK(dev_alloc(g.sched, kGraphSteps));
     hipGraph_t graph = nullptr;
+    int rc = set_state_layout(h, true);                  // never captured: the graph holds one-step launches only
+    if (rc) return rc;
     HIPCHK(hipStreamBeginCapture(main_stream(h), hipStreamCaptureModeThreadLocal));
     hipError_t e = hipSuccess;
     for (int i = 0; i < kGraphSteps && e == hipSuccess; ++i) {
@@ -200,10 +207,8 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
     if (h->use_graph && nsteps >= 2 * kGraphSteps) {
         // launch-bound shapes: replay a captured graph of kGraphSteps launches (still one launch
         // per step); the per-step scalars travel through a small device table
-        if (!h->graph.exec) {
-            int rc = build_graph(h);
-            if (rc) return rc;
-        }
+        int rc = h->graph.exec ? EBM_OK : build_graph(h);
+        if (rc) return rc;
         std::vector<ebm::StepSched> sched(kGraphSteps);
         const int last_graph_step = nsteps - (diag_last ? 1 : 0);     // a diagnostic last step is launched directly
         for (; s + kGraphSteps <= last_graph_step; s += kGraphSteps) {
@@ -211,6 +216,7 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
             // pageable source: the copy is staged before the call returns, so `sched` can be refilled
             HIPCHK(hipMemcpyAsync(h->graph.sched.get(), sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
                                   hipMemcpyHostToDevice, main_stream(h)));
+            if ((rc = set_state_layout(h, true))) return rc;       // the captured launches expect the one-step layout
             HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
             record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false);
         }
@@ -320,6 +326,8 @@ int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const doubl
         if (rc) return rc;
         // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split
         if (diag && (rc = ensure_natural(h))) return rc;
+        // ... and the prognostic ones too: the reduction reads the natural layout (two conversions per sample then)
+        if ((rc = set_state_layout(h, false))) return rc;
         sa.out = dev.get() + (size_t)j * (size_t)h->ncol;
         hipError_t e = ebm::launch_hemispheric_series(sa, h->ncol, main_stream(h));
         if (e != hipSuccess) return hip_fail("ebm_run_series: reduction", e);
@@ -496,7 +504,7 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
         if (rc) return rc;
         if (s.raw && ++staged == chunk) HIPCHK(flush());
         auto state_field = [&](int v) { return (const double *)h->field[fields[v]]; };
-        if (s.snapshot && (rc = ensure_natural(h))) return rc;
+        if (s.snapshot && ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false)))) return rc;
         if (s.season == 1) {
             if (winter) HIPCHK(season_to_host(winter, year));
             if (hm_winter) HIPCHK(means_to_host(hm_winter, year, state_field));
@@ -564,7 +572,7 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
-    if ((rc = ensure_natural(h))) return rc;
+    if ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false))) return rc;
     const int ncol = h->ncol;
     const size_t npitch = (size_t)ncol * h->pitch;
     // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count

@@ -16,6 +16,26 @@ int ensure_natural(ebm_ctx *h) {
     return EBM_OK;
 }
 
+// The prognostic fields in the layout that whoever touches them next expects (ebm_ctx::state_split): pair-split for a
+// one-step launch at four cells per thread, natural for everybody else.  In place, on the handle's stream — which joins the
+// two launch chains first (main_stream), so every column's last step has ended; never inside a graph capture (build_graph
+// and ebm_run convert before they capture / replay).
+hipError_t convert_state(ebm_ctx *h, bool split) {
+    if (h->model != EBM_MODEL_MIZ || h->cfg.cells != 4) split = false;      // no second layout: classic; the pair is the chunk
+    if (h->state_split == split) return hipSuccess;
+    double *first = h->field[EBM_F_Ei];                  // Ei, Ew, h, D, phi: slots 0 .. 4
+    hipError_t e = split ? ebm::launch_split_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h))
+                         : ebm::launch_unsplit_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
+    if (e != hipSuccess) return e;
+    h->state_split = split;
+    h->n_conversions += 1;
+    return hipSuccess;
+}
+int set_state_layout(ebm_ctx *h, bool split) {
+    hipError_t e = convert_state(h, split);
+    return e == hipSuccess ? EBM_OK : hip_fail("state layout conversion", e);
+}
+
 int get_copier(ebm_ctx *h) {
     if (h->copier) return EBM_OK;
     auto c = std::make_unique<HostCopier>();
@@ -38,6 +58,7 @@ int check_field(const ebm_ctx *h, int field, const void *out, const char *who) {
 }
 int make_readable(ebm_ctx *h, int field) {
     HIPCHK(hipSetDevice(h->device));
+    if (is_split_state_field(h, field)) return set_state_layout(h, false);
     return is_split_field(h, field) ? ensure_natural(h) : EBM_OK;
 }
 int open_field(ebm_ctx *h, int field, const void *out, const char *who) {
@@ -131,6 +152,7 @@ int ebm_set_field(ebm_handle_t h, int field, const double *host) {
         rc = ensure_natural(h);                   // the other diagnostic fields keep their values, in the natural layout
         if (rc) return rc;
     }
+    if (is_split_state_field(h, field) && (rc = set_state_layout(h, false))) return rc;     // ... and so do the prognostic ones
     HIPCHK(hipStreamSynchronize(main_stream(h)));
     HIPCHK(h->copier->wait_all());
     HIPCHK(h->copier->upload(h->field[field], (size_t)h->pitch, host, (size_t)h->nlat, (size_t)h->ncol));
@@ -206,7 +228,8 @@ int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {
 int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pitch) {
     int rc = open_field(h, field, dptr, "ebm_field_device_ptr");
     if (rc) return rc;
-    if (is_split_field(h, field)) HIPCHK(hipStreamSynchronize(main_stream(h)));   // the view is of the natural layout as of this call
+    // the view is of the natural layout as of this call
+    if (is_split_field(h, field) || is_split_state_field(h, field)) HIPCHK(hipStreamSynchronize(main_stream(h)));
     *dptr = h->field[field];
     if (pitch) *pitch = h->pitch;
     return EBM_OK;

@@ -73,6 +73,13 @@ struct LaunchCfg {
     bool fused_in_lds;
 };
 
+// THE pair-split permutation of a column at four cells per thread (T threads, pitch 4T): pair j of thread t — the natural
+// cells 4t + 2j and 4t + 2j + 1 — lies at split_index(t, j, T), so that the 16-byte accesses of a wave to one pair cover
+// whole 128-byte lines.  The layout of the annual-mean sums, of the zonal operator's index space, of the diagnostic
+// fields as a one-step launch leaves them and of the prognostic fields between one-step launches.  With two
+// cells per thread the pair is the chunk and the layout is the natural one.
+__host__ __device__ constexpr unsigned split_index(unsigned t, unsigned j, unsigned T) { return j * 2u * T + 2u * t; }
+
 // cells_requested: 2 (honoured for nlat <= kMaxLat2) or anything else = 4.  A function of nlat and the request only.
 LaunchCfg choose_launch(int nlat, int cells_requested);
 hipError_t prepare_kernels(const LaunchCfg &cfg);   // raises the dynamic-LDS limit if needed
@@ -161,10 +168,10 @@ hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *o
 // kernels call
 hipError_t launch_noise_innovations(const NoiseRec *noise, unsigned long long seed, long long first, int nsteps, int ncol,
                                     double *out, hipStream_t s);
-// natural <-> pair-split layout of whole fields ([ncol][pitch], 4 cells per thread; a no-op with 2), in place
+// natural <-> pair-split layout (split_index) of whole fields ([ncol][pitch], 4 cells per thread; a no-op with 2), in
+// place: nfields fields, field_stride apart
 hipError_t launch_split_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                hipStream_t s);
-// the diagnostic fields of a 4-cells-per-thread step launch, pair-split -> natural layout, in place
 hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                  hipStream_t s);
 

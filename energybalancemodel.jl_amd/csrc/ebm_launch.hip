@@ -28,7 +28,7 @@
 //                                       [ebm_miz_resident.h; miz_resident.hip, SAVE: miz_resident_save.hip]
 //   classic_step_kernel<C, MODE>        WE15 model: single step / savesol! / K steps per launch            [this file]
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
-//   finish_mean, hemispheric_mean, hemispheric_series, mask_from_t0, derive_params, divide, split / unsplit_fields,
+//   finish_mean, hemispheric_mean, hemispheric_series, mask_from_t0, derive_params, divide, permute_fields (split / unsplit),
 //   noise_innovations, noise_sequence, equilibrium_check, compact_active: small helpers                    [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
 // and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
@@ -401,40 +401,33 @@ __global__ void finish_mean_kernel(double *__restrict__ dst, double *__restrict_
     }
 }
 
-// Pair-split -> natural layout, in place: the diagnostic fields as the 4-cells-per-thread step kernels store them
-// (pair j of thread t at j*2T + 2t) become [col][pitch] with cell k at k.  One workgroup per column holds the whole
-// column in registers across a barrier, so the permutation needs no second buffer.  blockIdx.y = field: `fields`
-// advances by field_stride per field.
-__global__ void unsplit_fields_kernel(double *__restrict__ fields, long long field_stride, int threads) {
-    const int t = threadIdx.x;
+// Natural <-> pair-split layout (split_index), in place: SPLIT = false turns fields that a 4-cells-per-thread one-step
+// launch left pair-split into [col][pitch] with cell k at k; SPLIT = true is the inverse (the prognostic fields before
+// such a launch; a field the caller set, about to be read by a kernel that expects the split layout).  One workgroup per
+// column holds the whole column in registers across a barrier, so the permutation needs no second buffer.  blockIdx.y =
+// field: `fields` advances by field_stride per field.
+template <bool SPLIT>
+__global__ void permute_fields_kernel(double *__restrict__ fields, long long field_stride, int threads) {
+    const unsigned t = threadIdx.x, T = (unsigned)threads;
     double *f = fields + (size_t)blockIdx.y * (size_t)field_stride + (size_t)blockIdx.x * (size_t)threads * 4;
-    const double2 p0 = *reinterpret_cast<const double2 *>(f + 2 * t);
-    const double2 p1 = *reinterpret_cast<const double2 *>(f + 2 * threads + 2 * t);
+    double2 *const nat0 = reinterpret_cast<double2 *>(f + 4 * t), *const nat1 = reinterpret_cast<double2 *>(f + 4 * t + 2);
+    double2 *const spl0 = reinterpret_cast<double2 *>(f + split_index(t, 0, T));
+    double2 *const spl1 = reinterpret_cast<double2 *>(f + split_index(t, 1, T));
+    const double2 p0 = SPLIT ? *nat0 : *spl0, p1 = SPLIT ? *nat1 : *spl1;
     __syncthreads();
-    *reinterpret_cast<double2 *>(f + 4 * t) = p0;
-    *reinterpret_cast<double2 *>(f + 4 * t + 2) = p1;
-}
-// natural -> pair-split, the inverse (a field the caller set, about to be read by a kernel that expects the split layout)
-__global__ void split_fields_kernel(double *__restrict__ fields, long long field_stride, int threads) {
-    const int t = threadIdx.x;
-    double *f = fields + (size_t)blockIdx.y * (size_t)field_stride + (size_t)blockIdx.x * (size_t)threads * 4;
-    const double2 p0 = *reinterpret_cast<const double2 *>(f + 4 * t);
-    const double2 p1 = *reinterpret_cast<const double2 *>(f + 4 * t + 2);
-    __syncthreads();
-    *reinterpret_cast<double2 *>(f + 2 * t) = p0;
-    *reinterpret_cast<double2 *>(f + 2 * threads + 2 * t) = p1;
+    *(SPLIT ? spl0 : nat0) = p0;
+    *(SPLIT ? spl1 : nat1) = p1;
 }
 hipError_t launch_split_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                hipStream_t s) {
-    if (cfg.cells != 4) return hipSuccess;
-    split_fields_kernel<<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
+    if (cfg.cells != 4) return hipSuccess;               // two cells per thread: the layouts coincide
+    permute_fields_kernel<true><<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
     return hipGetLastError();
 }
-
 hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                  hipStream_t s) {
-    if (cfg.cells != 4) return hipSuccess;               // two cells per thread: the layouts coincide
-    unsplit_fields_kernel<<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
+    if (cfg.cells != 4) return hipSuccess;
+    permute_fields_kernel<false><<<dim3(ncol, nfields), cfg.threads, 0, s>>>(fields, field_stride, cfg.threads);
     return hipGetLastError();
 }
 

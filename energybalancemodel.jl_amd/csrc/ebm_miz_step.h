@@ -79,9 +79,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
         if (it == 0) {
             double Ew[C], hk[C], xk[C], r[C];
-            load_chunk<C>(st + S_Ew * a.fstride, kl, Ew);
-            load_chunk<C>(st + S_phi * a.fstride, kl, ph);
-            load_chunk<C>(st + S_h * a.fstride, kl, hk);
+            load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
+            load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
+            load_state<C, TT>(st + S_h * a.fstride, kl, hk);
             load_chunk<C>(gX, kl, xk);
             // Padding cells (k >= nlat) need no special case in phases A and B: their state and table
             // entries are zero, so their rows are decoupled (lo = up = 0, g = phi = 0) and finite.
@@ -132,13 +132,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     load_chunk<C>(gX, k0, xk);
     const double xl = gX[k0 > 0 ? k0 - 1 : 0], xr = gX[k0 + C];     // zero-padded table; unused at the ends
     double g0[GRID == 0 ? C : 1], g1[GRID == 0 ? C : 1], g2[GRID == 0 ? C : 1];
-    if constexpr (GRID == 0 && !IMEX) {
-        // sub-, main and super-diagonal of par.D*get_diffop: on the identity grid the physics stencil
-        // and the solver's plain coefficients are the same three tables (build_tables)
-        load_chunk<C>(geom + G_LO * a.gstride, k0, g0);
-        load_chunk<C>(geom + G_DI * a.gstride, k0, g1);
-        load_chunk<C>(geom + G_UP * a.gstride, k0, g2);
-    }
+    // (GRID == 0: sub-, main and super-diagonal of par.D*get_diffop — on the identity grid the physics stencil and the
+    // solver's plain coefficients are the same three tables (build_tables) — are loaded pair by pair with Ei and D below:
+    // all four cells' worth at once do not fit the cell updates' register budget at every workgroup size)
     double tb[C];
     {
         double T0[C];
@@ -155,11 +151,10 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     halo_exchange(P0, P0 + T, t, T, tb[0], tb[C - 1], tbl, tbr);
     EBM_STAMP(7);
     EBM_STAMPW(3);                                        // per wave: Tbar halo done
-    // Whole-line stores.  A lane owns 8*C contiguous bytes of every field; written pair by pair,
-    // each 128-B line would reach L2 in two halves ~10^4 cycles apart and be written back to HBM
-    // twice.  The first pair's new prognostics are parked in LDS words that are dead by then (cells
-    // 0,1 of the stash, the idle tail of the cyclic-reduction buffers) and all 32 bytes of a lane go
-    // out in two back-to-back 16-B stores once the second pair is done.
+    // Whole-line stores.  A lane owns 8*C contiguous bytes of every field in the natural layout; written pair by
+    // pair, each 128-B line would reach L2 in two halves ~10^4 cycles apart and be written back to HBM twice.  The
+    // prognostic fields of this kernel are therefore in the pair-split layout (state_index), in which every store
+    // instruction of a wave covers whole lines: each pair's new prognostics leave as soon as the pair is computed.
     TbarStencil<C, GRID> stencil;
     stencil.start(k0, nlat, xl, xk, tbl, tb);
     double difx[IMEX ? C : 1];                            // IMEX: the corrected diffusion term of every cell
@@ -188,7 +183,7 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             // operations, same bits — for the correction (dE_new - dE)/dt.
             unsigned kl = k0;
             asm volatile("" : "+v"(kl));
-            load_chunk<C>(st + S_phi * a.fstride, kl, ph);
+            load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
             load_chunk<C>(gX, kl, xk);
 #pragma unroll
             for (int i = 0; i < C; ++i) {
@@ -201,13 +196,24 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             }
         }
     }
-    double *const park0 = P0 + 2 * T + t;                 // P0[2T..3T), P1[0..3T): clear of the halo words
+    // after the step's last barrier (every wave has used the old N_c), and before the cell updates: their register budget
+    // has no room for a value that only waits for the kernel's last line
+    if (a.noise) nz.store(a, col);
 #pragma unroll
     for (int j = 0; j < C / 2; ++j) {
         MizCellOut o[2];
         __builtin_amdgcn_sched_barrier(0);
-        const double2 Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + (k0 + 2 * j));
-        const double2 Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + (k0 + 2 * j));
+        const unsigned ks = state_index<C, TT>(k0, j);    // the pair's place in every field this kernel stores
+        const double2 Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + ks);
+        const double2 Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + ks);
+        if constexpr (GRID == 0 && !IMEX) {
+            const double2 lo = *reinterpret_cast<const double2 *>(geom + G_LO * a.gstride + (k0 + 2 * j));
+            const double2 di = *reinterpret_cast<const double2 *>(geom + G_DI * a.gstride + (k0 + 2 * j));
+            const double2 up = *reinterpret_cast<const double2 *>(geom + G_UP * a.gstride + (k0 + 2 * j));
+            g0[GRID == 0 ? 2 * j : 0] = lo.x;  g0[GRID == 0 ? 2 * j + 1 : 0] = lo.y;
+            g1[GRID == 0 ? 2 * j : 0] = di.x;  g1[GRID == 0 ? 2 * j + 1 : 0] = di.y;
+            g2[GRID == 0 ? 2 * j : 0] = up.x;  g2[GRID == 0 ? 2 * j + 1 : 0] = up.y;
+        }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             __builtin_amdgcn_sched_barrier(0);
@@ -252,67 +258,25 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             double2 d_;                                                                            \
             d_.x = v0 ? o[0].q[qi] : 0.0;                                                          \
             d_.y = v1 ? o[1].q[qi] : 0.0;                                                          \
-            EBM_STORE2(st + (slot_) * a.fstride + kp, d_);                                         \
+            EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                         \
         }
-        if constexpr (C == 2) {
-            // two cells per thread (short meridians of latency-bound runs): the lane's 16 bytes are the
-            // pair; a wave's store already covers whole lines
-            EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)
-        } else if (j == 0) {
-            // pair 0 of Ei, Ew -> P words; h, D, phi -> stash words of cells 0, 1 (all read already)
-            park0[0] = v0 ? o[0].q[Q_Ei] : 0.0;  park0[T] = v1 ? o[1].q[Q_Ei] : 0.0;
-            park0[2 * T] = v0 ? o[0].q[Q_Ew] : 0.0;  park0[3 * T] = v1 ? o[1].q[Q_Ew] : 0.0;
-            sEw[0] = v0 ? o[0].q[Q_h] : 0.0;  sEw[T] = v1 ? o[1].q[Q_h] : 0.0;
-            sh[0] = v0 ? o[0].q[Q_D] : 0.0;  sh[T] = v1 ? o[1].q[Q_D] : 0.0;
-            sTw[0] = v0 ? o[0].q[Q_phi] : 0.0;  sTw[T] = v1 ? o[1].q[Q_phi] : 0.0;
-        } else {
-            // the LDS-DMA prefetch must have landed before this wave can end (its LDS is released
-            // with the workgroup); it was issued a whole cell update ago
-            EBM_STAMPW(5);                                // per wave: arithmetic done, before the stores
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define EBM_PUT4(slot_, qi, w0, w1)                                                                \
-            {                                                                                      \
-                double2 a_, b_;                                                                    \
-                a_.x = (w0);                                                                       \
-                a_.y = (w1);                                                                       \
-                b_.x = v0 ? o[0].q[qi] : 0.0;                                                      \
-                b_.y = v1 ? o[1].q[qi] : 0.0;                                                      \
-                EBM_STORE2(st + (slot_) * a.fstride + k0, a_);                                       \
-                EBM_STORE2(st + (slot_) * a.fstride + kp, b_);                                       \
-            }
-            EBM_PUT4(S_Ei, Q_Ei, park0[0], park0[T])
-            EBM_PUT4(S_Ew, Q_Ew, park0[2 * T], park0[3 * T])
-            EBM_PUT4(S_h, Q_h, sEw[0], sEw[T])
-            EBM_PUT4(S_D, Q_D, sh[0], sh[T])
-            EBM_PUT4(S_phi, Q_phi, sTw[0], sTw[T])
-#undef EBM_PUT4
-        }
+        if (j == C / 2 - 1) EBM_STAMPW(5);                // per wave: arithmetic done, before the last stores
+        EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)
         if (MAYDIAG && diag) {
-            // The diagnostic fields are outputs only: they are stored in the PAIR-SPLIT layout (pair j of thread t at
-            // j*2T + 2t, the layout of the annual-mean sums), in which every store instruction of a wave covers whole
-            // 128-B lines — stored in the natural layout they left pair by pair, i.e. as the two halves of each lane's
-            // 32-byte sector ~10^4 cycles apart (no LDS is left to park five more fields): 0.36 ms for a diagnostic step
-            // of the 4096 x 2048 shape against 0.164 state-only.  The runtime un-permutes in place before the first
-            // read (unsplit_fields_kernel; ebm_ctx::diag_split).  With two cells per thread the pair IS the chunk and
-            // the two layouts coincide.
-            const unsigned ks = (unsigned)(j * 2 * T + 2 * t);
-#define EBM_PUTP(slot_, qi)                                                                        \
-            {                                                                                      \
-                double2 d_;                                                                        \
-                d_.x = v0 ? o[0].q[qi] : 0.0;                                                      \
-                d_.y = v1 ? o[1].q[qi] : 0.0;                                                      \
-                EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                     \
-            }
-            EBM_PUTP(S_n, Q_n) EBM_PUTP(S_E, Q_E) EBM_PUTP(S_T, Q_T) EBM_PUTP(S_Ti, Q_Ti) EBM_PUTP(S_Tw, Q_Tw)
-#undef EBM_PUTP
+            // The diagnostic fields are outputs only and share the layout of the prognostic ones (stored in the natural
+            // layout they cost 0.36 ms for a diagnostic step of the 4096 x 2048 shape against 0.164 state-only).  The runtime
+            // un-permutes in place before the first read (permute_fields_kernel; ebm_ctx::diag_split).
+            EBM_PUT(S_n, Q_n) EBM_PUT(S_E, Q_E) EBM_PUT(S_T, Q_T) EBM_PUT(S_Ti, Q_Ti) EBM_PUT(S_Tw, Q_Tw)
         }
 #undef EBM_PUT
         if constexpr (OUT == OUT_SAVE)
-            save_pair<Q_MIZ_COUNT>(a, (size_t)col * (size_t)a.pitch, (unsigned)(j * 2 * T + 2 * t), kp, o[0], o[1], v0, v1);
+            save_pair<Q_MIZ_COUNT>(a, (size_t)col * (size_t)a.pitch, ks, kp, o[0], o[1], v0, v1);
         if (j < 2) EBM_STAMP(8 + j);
         if (j == 0) EBM_STAMPW(4);                        // per wave: first pair done
     }
-    if (a.noise) nz.store(a, col);                        // after the step's last barrier
+    // the LDS-DMA prefetch must have landed before this wave can end (its LDS is released with the workgroup); it was
+    // issued a whole cell update ago
+    if constexpr (C == 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     EBM_STAMP(15);
     EBM_STAMPW(6);                                        // per wave: stores issued
 }

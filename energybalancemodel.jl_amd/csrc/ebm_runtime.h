@@ -132,6 +132,13 @@ struct ebm_ctx {
     // 128-B lines per store instruction, csrc/ebm_miz_step.h); whoever reads one of them gets the natural layout:
     // the first reader after such a step runs the in-place un-permutation once.
     bool diag_split = false;
+    // The same layout holds the five prognostic fields BETWEEN one-step launches at 4 cells per thread (miz_step_kernel
+    // reads and writes them pair-split).  One rule (set_state_layout): the one-step launch path splits them first if they
+    // are natural; every other reader or writer of a prognostic field — field I/O and views, the fused and resident
+    // kernels, series, hemispheric means, snapshots — un-splits them first.  A steady ebm_run / ebm_step loop converts
+    // nothing; n_conversions counts the conversions of a handle (ebm_state_conversions).
+    bool state_split = false;
+    long long n_conversions = 0;
     // ebm_zonal_diffusion: the tables of the last nlon used, kept between calls
     struct ZonalTables {
         int nlon = 0, seg = 1;                     // seg: segments a circle is cut into (a function of nlon only)
@@ -186,6 +193,10 @@ inline bool is_diagnostic(const ebm_ctx *h, int f) {
 inline bool is_split_field(const ebm_ctx *h, int f) {
     return h->model == EBM_MODEL_MIZ && (f == EBM_F_Tw || f == EBM_F_Ti || f == EBM_F_n || f == EBM_F_E || f == EBM_F_T);
 }
+// the prognostic fields that a 4-cells-per-thread MIZ one-step launch keeps pair-split (set_state_layout)
+inline bool is_split_state_field(const ebm_ctx *h, int f) {
+    return h->model == EBM_MODEL_MIZ && f >= EBM_F_Ei && f <= EBM_F_phi;
+}
 inline const char *field_name(int f) {
     static const char *names[EBM_F_COUNT] = {"Ei", "Ew", "h", "D", "phi", "T0", "Tw", "Ti", "n", "E", "T", "Tg"};
     return (f >= 0 && f < EBM_F_COUNT) ? names[f] : "?";
@@ -234,6 +245,9 @@ inline int quantity_of(int model, int f) {
 ebm::StepArgs base_args(const ebm_ctx *h);        // ebm_drive.hip: the launch arguments every step launch starts from
 void invalidate_graph(ebm_ctx *h);                // ebm_drive.hip: drop the captured graph (it holds old argument values)
 int ensure_natural(ebm_ctx *h);                   // ebm_fields.hip: un-permute the diagnostic fields if a step left them split
+// ebm_fields.hip: THE rule of ebm_ctx::state_split — the prognostic fields into the layout their next user expects
+hipError_t convert_state(ebm_ctx *h, bool split);
+int set_state_layout(ebm_ctx *h, bool split);     // the same, with the error reported (EBM_ERR_HIP)
 int get_copier(ebm_ctx *h);                       // ebm_fields.hip: the handle's pinned staging ring, created on first use
 
 }  // namespace ebm_rt

@@ -224,6 +224,12 @@ int ebm_reset_counters(ebm_handle_t h) {
     return EBM_OK;
 }
 
+int ebm_state_conversions(ebm_handle_t h, long long *count) {
+    if (!h || !count) return fail(EBM_ERR_ARG, "ebm_state_conversions: null argument");
+    *count = h->n_conversions;
+    return EBM_OK;
+}
+
 int ebm_timer_start(ebm_handle_t h) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_timer_start: null handle");
     HIPCHK(hipSetDevice(h->device));
@@ -275,6 +281,28 @@ int ebm_selftest_divide(int device, int n, const double *a, const double *b, dou
     hipError_t e = ebm::launch_divide(da.get(), db.get(), dq.get(), n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(q, dq.get(), nb, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("ebm_selftest_divide", e);
+    return EBM_OK;
+}
+
+int ebm_selftest_permute(int device, int threads, int ncol, const double *in, double *split, double *back) {
+    if (threads < 64 || threads > 1024 || threads % 64 || ncol < 1 || !in || !split || !back)
+        return fail(EBM_ERR_ARG, "ebm_selftest_permute: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(EBM_ERR_NO_DEVICE, "ebm_selftest_permute: no HIP device available");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)ncol * 4 * (size_t)threads, nb = sizeof(double) * n;
+    DevBuf<double> d;
+    HIPCHK(dev_alloc(d, n));
+    HIPCHK(hipMemcpy(d.get(), in, nb, hipMemcpyHostToDevice));
+    ebm::LaunchCfg cfg{};
+    cfg.threads = threads;
+    cfg.cells = 4;
+    hipError_t e = ebm::launch_split_fields(d.get(), 0, 1, ncol, cfg, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(split, d.get(), nb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = ebm::launch_unsplit_fields(d.get(), 0, 1, ncol, cfg, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(back, d.get(), nb, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("ebm_selftest_permute", e);
     return EBM_OK;
 }
 

@@ -444,6 +444,12 @@ class Engine:
     def reset_counters(self):
         check(self.lib.ebm_reset_counters(self._h), "ebm_reset_counters")
 
+    def state_conversions(self) -> int:
+        """Layout conversions of the prognostic fields so far (ebm_state_conversions)."""
+        n = C.c_longlong()
+        check(self.lib.ebm_state_conversions(self._h, C.byref(n)), "ebm_state_conversions")
+        return int(n.value)
+
     def timer_start(self):
         check(self.lib.ebm_timer_start(self._h), "ebm_timer_start")
 

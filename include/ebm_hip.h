@@ -212,10 +212,11 @@ int ebm_diffusion(ebm_handle_t h, const double *temp, const double *base, double
  * two-dimensional elliptic solve per step — which this library does not contain. */
 int ebm_zonal_diffusion(ebm_handle_t h, int nlon, const double *temp, double *out_U, double *out_Z);
 /* Device pointer of a field and its row pitch in elements (>= nlat), for zero-copy users
- * (e.g. a torch tensor view).  The pointer stays valid until ebm_destroy.  For the MIZ diagnostic fields the view
- * shows the field as of this call: steps that write them afterwards store them in a layout private to the library
- * until the next read through this interface (call again after such a step).  Fails with EBM_ERR_STALE like
- * ebm_get_field. */
+ * (e.g. a torch tensor view).  The pointer stays valid until ebm_destroy.  For the MIZ fields (prognostic and
+ * diagnostic, four cells per thread) the view shows the field as of this call: one-launch-per-step steps taken
+ * afterwards keep the fields they read and write in a layout private to the library until the next access through
+ * this interface (call again after such a step; do not write through the pointer while stepping).  Fails with
+ * EBM_ERR_STALE like ebm_get_field. */
 int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pitch);
 /* Per-column forcing offset added to the per-step scalar forcing (forcing = f + fcol[col];
  * NULL clears it).  This is how ensemble members / longitudes get perturbed forcings — the
@@ -413,6 +414,12 @@ int ebm_sync(ebm_handle_t h);
  * active-set iteration hit its cap, [3] kernel launches.  Synchronises the stream. */
 int ebm_get_counters(ebm_handle_t h, long long *counters);
 int ebm_reset_counters(ebm_handle_t h);
+/* *count: how often the handle has converted its prognostic fields between the natural layout and the layout private to
+ * the one-launch-per-step MIZ kernel at four cells per thread (one in-place pass over the five fields each; see
+ * ebm_field_device_ptr).  A steady loop of ebm_step / ebm_run converts once, at its start; reading or setting a prognostic
+ * field, a fused launch, a series sample or a seasonal snapshot between two such steps costs two.  Since ebm_create (not
+ * reset by ebm_reset_counters).  Does not synchronise. */
+int ebm_state_conversions(ebm_handle_t h, long long *count);
 /* HIP-event timing on the handle's stream (the stream the kernels are launched on). */
 int ebm_timer_start(ebm_handle_t h);
 int ebm_timer_stop(ebm_handle_t h, float *elapsed_ms);
@@ -422,6 +429,10 @@ int ebm_launch_info(ebm_handle_t h, int *info);
 /* Self-test: q[i] = a[i] / b[i] computed on the device with the division routine the physics
  * kernels use (bit-exact IEEE fp64 division is part of the parity contract). */
 int ebm_selftest_divide(int device, int n, const double *a, const double *b, double *q);
+/* Self-test: the in-place layout conversions of the MIZ fields at four cells per thread, on ncol columns of 4*threads
+ * cells (threads: a multiple of 64, <= 1024): split[ncol][4*threads] = `in` taken from the natural layout to the private
+ * one (pair j of thread t, cells 4t+2j and 4t+2j+1, at j*2*threads + 2t), back[...] = that taken back again. */
+int ebm_selftest_permute(int device, int threads, int ncol, const double *in, double *split, double *back);
 
 #ifdef __cplusplus
 }
