@@ -1,5 +1,6 @@
 // Host runtime, the drivers (ebm_runtime.h lists the units): the launches of one step and their two chains, graph replay,
-// fused ranges, and what is built on them: ebm_step, ebm_run, ebm_run_fused, ebm_run_series, ebm_integrate, ebm_equilibrate.
+// fused ranges, and what is built on them: ebm_step, ebm_run, ebm_run_fused, ebm_run_series, ebm_integrate, ebm_equilibrate,
+// ebm_run_until.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -44,8 +45,8 @@ hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, int firs
     return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, first, count, s)
                                        : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
 }
-// The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate), as one
-// chain or split in two halves; a chain with no columns is skipped.
+// The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate,
+// ebm_run_until), as one chain or split in two halves; a chain with no columns is skipped.
 int chain_count(const ebm_ctx *h, int *first_half) {
     const int n = h->active ? h->nactive : h->ncol;
     *first_half = h->split_col ? (h->active ? n / 2 : h->split_col) : n;
@@ -628,6 +629,94 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     HIPCHK(hipMemcpy(years, years_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(converged, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
     if (resid) HIPCHK(hipMemcpy(resid, ea.resid, sizeof(double) * (size_t)nvars * ncol, hipMemcpyDeviceToHost));
+    return EBM_OK;
+}
+
+// ebm_run_until (include/ebm_hip.h).  Every round is one fused_range of `every` steps over the active columns — also with
+// one step per launch: the one-step kernels and a replayed graph know nothing of the list, the fused kernel at K = 1 gives
+// the same bits — then passage_check_kernel takes each active column's mean and compares it with the column's level,
+// compact_active_kernel writes the next list and its length, and the host reads the length: one stream synchronisation
+// per round.  The fused kernels read and write the natural layout, so the fields of columns frozen in different rounds
+// share one layout.
+int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
+                  int field, const double *level, const int *direction, int *samples, int *crossed, double *value) {
+    if (!h || !level || !direction || !samples || !crossed) return fail(EBM_ERR_ARG, "ebm_run_until: null argument");
+    if (every < 1 || max_samples < 1) return fail(EBM_ERR_ARG, "ebm_run_until: every and max_samples must be >= 1");
+    if (steps_per_launch < 1 || first_step < 0) return fail(EBM_ERR_ARG, "ebm_run_until: bad argument");
+    FieldRef var;
+    int rc = resolve_fields(h, "ebm_run_until", 1, &field, &var);
+    if (rc) return rc;
+    const int ncol = h->ncol;
+    for (int c = 0; c < ncol; ++c) {
+        if (level[c] != level[c]) return fail(EBM_ERR_ARG, "ebm_run_until: level[" + std::to_string(c) + "] is NaN");
+        if (direction[c] == 0)
+            return fail(EBM_ERR_ARG, "ebm_run_until: direction[" + std::to_string(c) + "] is 0 (> 0: upward, < 0: downward)");
+    }
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_until: call ebm_set_time_table first");
+    if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_run_until: no fused-K kernel for this shape in this build");
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false))) return rc;
+    const int diag = var.diagnostic ? 1 : 0;
+    // this call's device memory: value | level, and the two active lists | samples | frozen | direction | count
+    DevBuf<double> dbl;
+    DevBuf<int> ints;
+    PinnedBuf<int> pinned;
+    // the list is known to the launches only until the call returns, on every path; they end before the buffers are freed
+    const auto done = finally([h] {
+        (void)hipStreamSynchronize(main_stream(h));
+        h->active = nullptr;
+        h->nactive = 0;
+    });
+    HIPCHK(dev_alloc(dbl, 2 * (size_t)ncol));
+    HIPCHK(dev_alloc(ints, 5 * (size_t)ncol + 1));
+    HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
+    int *cur = ints.get(), *nxt = cur + ncol, *samples_dev = nxt + ncol, *frozen = samples_dev + ncol, *dir_dev = frozen + ncol,
+        *count = dir_dev + ncol;
+    double *value_dev = dbl.get(), *level_dev = value_dev + ncol;
+    {
+        std::vector<int> ident((size_t)ncol);
+        for (int c = 0; c < ncol; ++c) ident[c] = c;
+        // (value needs no initial contents: round 1 tests every column)
+        HIPCHK(hipMemcpy(level_dev, level, sizeof(double) * (size_t)ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(samples_dev, 0, sizeof(int) * 2 * (size_t)ncol));
+        HIPCHK(hipMemcpy(dir_dev, direction, sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
+    }
+    ebm::PassageArgs pa{};
+    pa.field = h->field[var.field];
+    pa.x = x_table(h);
+    pa.level = level_dev; pa.direction = dir_dev;
+    pa.value = value_dev; pa.samples = samples_dev; pa.frozen = frozen;
+    pa.pitch = (int)h->pitch; pa.nlat = h->nlat;
+    int nactive = ncol;
+    for (int j = 1; j <= max_samples; ++j) {
+        h->active = cur;
+        h->nactive = nactive;
+        const long long first = first_step + (long long)(j - 1) * every;
+        rc = fused_range(h, first, first, every, f_steps ? f_steps + (size_t)(j - 1) * (size_t)every : nullptr, diag, steps_per_launch,
+                         nullptr);
+        if (rc) return rc;
+        // (as ebm_run_series before its reduction; after a fused launch both hold already)
+        if (diag && (rc = ensure_natural(h))) return rc;
+        if ((rc = set_state_layout(h, false))) return rc;
+        pa.cols = cur;
+        pa.round = j;
+        hipError_t e = ebm::launch_passage_check(pa, nactive, main_stream(h));
+        if (e != hipSuccess) return hip_fail("ebm_run_until: check", e);
+        if (j == max_samples) break;                             // (no further round: no list is needed)
+        e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+        if (e != hipSuccess) return hip_fail("ebm_run_until: active list", e);
+        nactive = *pinned.get();
+        std::swap(cur, nxt);                                     // (the list just written steps the next round)
+        if (nactive == 0) break;                                 // every column has crossed
+    }
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(samples, samples_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(crossed, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    if (value) HIPCHK(hipMemcpy(value, value_dev, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost));
     return EBM_OK;
 }
 

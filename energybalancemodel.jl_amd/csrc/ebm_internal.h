@@ -51,7 +51,7 @@ struct StepArgs {
     long long stage_offset;          // snapshot index * ncol*pitch
     signed char var_of[kMaxQuantities];   // quantity -> saved-variable index, -1 = not saved
     unsigned long long *stamps;      // diagnostic builds only (EBM_STAMPS), else nullptr
-    const int *cols;                 // active columns (ebm_equilibrate): workgroup b steps column cols[col0 + b]; nullptr =
+    const int *cols;                 // active columns (ebm_equilibrate, ebm_run_until): workgroup b steps column cols[col0 + b]; nullptr =
                                      // identity.  Read by the fused-K kernels and the classic kernel only.
     // forcing noise (ebm_set_column_noise): nullptr = none, and every kernel takes the noise-free path
     const NoiseRec *noise;           // [ncol]
@@ -161,6 +161,19 @@ struct EquilArgs {
     double tol[kMaxQuantities];
 };
 hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s);
+// ebm_run_until, one wave per active column c = cols[b], b < nactive: m = hemispheric_mean(field of column c, x), the bits of
+// launch_hemispheric_mean; value[c] = m, samples[c] = round and frozen[c] = (direction[c] > 0 ? m >= level[c] : m <= level[c])
+struct PassageArgs {
+    const double *field;             // the one field, [ncol][pitch], natural layout
+    const double *x;
+    const double *level;             // [ncol]
+    const int *direction;            // [ncol], never 0
+    const int *cols;                 // [nactive], ascending
+    double *value;                   // [ncol]
+    int *samples, *frozen;           // [ncol]
+    int pitch, nlat, round;
+};
+hipError_t launch_passage_check(const PassageArgs &p, int nactive, hipStream_t s);
 // the next active list: out = the entries of in[0 .. n) whose column is not frozen, in order; *count = their number
 // (one workgroup)
 hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s);

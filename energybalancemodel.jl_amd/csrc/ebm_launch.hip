@@ -29,14 +29,14 @@
 //   classic_step_kernel<C, MODE>        WE15 model: single step / savesol! / K steps per launch            [this file]
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
 //   finish_mean, hemispheric_mean, hemispheric_series, mask_from_t0, derive_params, divide, permute_fields (split / unsplit),
-//   noise_innovations, noise_sequence, equilibrium_check, compact_active: small helpers                    [this file]
+//   noise_innovations, noise_sequence, equilibrium_check, passage_check, compact_active: small helpers     [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
 // and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
 // ebm_device.h (stores, parameter block, IEEE division, chunk loads), ebm_noise.h, ebm_solve.h (halo exchanges, the
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 448 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 449 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -305,6 +305,40 @@ __global__ void __launch_bounds__(256) equilibrium_check_kernel(const EquilArgs 
 hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s) {
     if (nactive < 1 || nactive > e.ncol || e.nvars < 1 || e.nvars > kMaxQuantities) return hipErrorInvalidValue;
     equilibrium_check_kernel<<<nactive, 256, 0, s>>>(e);
+    return hipGetLastError();
+}
+
+// ebm_run_until's test after a round, one wave per active column c = cols[b] (PassageArgs): the hemispheric mean of the one
+// field as hemispheric_series_kernel takes it — the latitudes in tiles of kSeriesTile terms, the 64 lanes form the terms
+// (the expressions of hemispheric_mean_kernel), lane 0 adds them onto the running sum in the reference's order — then the
+// comparison with the column's level.  A NaN mean fails both comparisons: it never crosses.
+__global__ void __launch_bounds__(64) passage_check_kernel(const PassageArgs p) {
+    __shared__ double terms[kSeriesTile];
+    const int lane = threadIdx.x, col = p.cols[blockIdx.x], nterms = p.nlat - 1;
+    const double *const f = p.field + (size_t)col * (size_t)p.pitch;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < nterms; k0 += kSeriesTile) {
+        const int n = min(kSeriesTile, nterms - k0);
+        for (int i = lane; i < n; i += 64)
+            terms[i] = ieee_div((f[k0 + i] + f[k0 + i + 1]) * (p.x[k0 + i + 1] - p.x[k0 + i]), 2.0);
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll 8
+            for (int i = 0; i < n; ++i) acc = acc + terms[i];
+        }
+        __syncthreads();                                  // (the tile is refilled by the next round)
+    }
+    if (lane == 0) {
+        const double level = p.level[col];
+        const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;
+        p.value[col] = acc;
+        p.samples[col] = p.round;
+        p.frozen[col] = crossed ? 1 : 0;
+    }
+}
+hipError_t launch_passage_check(const PassageArgs &p, int nactive, hipStream_t s) {
+    if (nactive < 1 || p.nlat < 1 || p.nlat > p.pitch) return hipErrorInvalidValue;
+    passage_check_kernel<<<nactive, 64, 0, s>>>(p);
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the two diffusion operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table
-//   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate
+//   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate, run-until
 // Not part of the public interface.
 #pragma once
 #include <memory>
@@ -119,7 +119,7 @@ struct ebm_ctx {
     DevBuf<unsigned long long> counters;           // device, kCounterShards x 2
     DevBuf<unsigned short> amask;                  // MIZ warm-start active set, ncol x threads
     long long n_steps = 0, n_launches = 0;
-    // ebm_equilibrate, for the duration of the call only: the launches step the columns active[0 .. nactive) (device list,
+    // ebm_equilibrate and ebm_run_until, for the duration of the call only: the launches step the columns active[0 .. nactive) (device list,
     // ascending) instead of all of them
     const int *active = nullptr;
     int nactive = 0;

@@ -432,6 +432,51 @@ class Engine:
                                        years.ctypes.data_as(ip), conv.ctypes.data_as(ip), dptr(resid)), "ebm_equilibrate")
         return dict(years=years.astype(np.int64), converged=conv.astype(bool), resid={n: resid[i] for i, n in enumerate(names)})
 
+    def check_until_args(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
+        """The host-side checks of ``run_until`` (no device call): returns (field id, level [ncol] float64, direction [ncol]
+        int32, f_steps)."""
+        allowed = self.prognostic + self.diagnostic
+        if not isinstance(name, str) or name not in allowed:
+            raise ValueError(f"name: unknown field {name!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
+                             "the warm start T0 is not a solution variable)")
+        if int(first_step) < 0:
+            raise ValueError("run_until: first_step must be >= 0")
+        if int(max_samples) < 1:
+            raise ValueError(f"max_samples = {max_samples}: need at least one round")
+        if int(every) < 1:
+            raise ValueError(f"every = {every}: the mean is tested every `every` >= 1 steps")
+        if int(steps_per_launch) < 1:
+            raise ValueError(f"steps_per_launch = {steps_per_launch}: need at least one step per launch")
+        lev = as_f64(level, (self.ncol,))
+        if np.isnan(lev).any():
+            raise ValueError("level: NaN (+-inf is legal: never, or at the first sample)")
+        d = np.asarray(direction)
+        if d.shape != (self.ncol,) or d.dtype.kind not in "iu":
+            raise ValueError(f"direction: expected {self.ncol} integers, > 0 upward and < 0 downward")
+        if (d == 0).any():
+            raise ValueError("direction: 0 is neither upward (> 0) nor downward (< 0)")
+        d = np.ascontiguousarray(np.sign(d), dtype=np.int32)
+        f = None if f_steps is None else as_f64(f_steps, (int(max_samples) * int(every),))
+        return FIELD[name], lev, d, f
+
+    def run_until(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
+        """ebm_run_until: rounds of ``every`` steps from global step ``first_step``, at most ``max_samples`` of them; after
+        each the per-column hemispheric mean of field ``name`` is taken on the device and a column whose mean has crossed
+        its ``level`` (``direction`` > 0: mean >= level, < 0: mean <= level; NaN never crosses) takes no further step, its
+        state bit for bit that of ``run`` over its own number of steps.  Returns dict(samples [ncol] int: rounds taken,
+        crossed [ncol] bool, value [ncol]: the last mean, steps: the steps the slowest column took).  One stream
+        synchronisation per round."""
+        fid, lev, d, f = self.check_until_args(first_step, max_samples, every, name, level, direction, f_steps, steps_per_launch)
+        samples = np.zeros(self.ncol, dtype=np.int32)
+        crossed = np.zeros(self.ncol, dtype=np.int32)
+        value = np.full(self.ncol, np.nan)
+        ip = C.POINTER(C.c_int)
+        check(self.lib.ebm_run_until(self._h, int(first_step), int(max_samples), int(every), dptr(f), int(steps_per_launch), fid,
+                                     dptr(lev), d.ctypes.data_as(ip), samples.ctypes.data_as(ip), crossed.ctypes.data_as(ip),
+                                     dptr(value)), "ebm_run_until")
+        samples = samples.astype(np.int64)
+        return dict(samples=samples, crossed=crossed.astype(bool), value=value, steps=int(samples.max()) * int(every))
+
     def sync(self):
         check(self.lib.ebm_sync(self._h), "ebm_sync")
 

@@ -50,6 +50,33 @@ def member_param_rows(member_params, par, init, fcol=None, forcings=None) -> np.
     return param_matrix(member_params, par, default_parval)
 
 
+def passage_levels(ncol: int, level, direction):
+    """The per-member ``level`` [ncol] float64 and ``direction`` [ncol] (+1 upward, -1 downward) of
+    ``EnsembleRun.first_passage``: each a scalar (every member) or one entry per member; a direction is "up", "down" or an
+    integer other than 0.  Host only (no device call)."""
+    lev = np.asarray(level, dtype=np.float64)
+    if lev.ndim > 1 or (lev.ndim == 1 and lev.shape[0] != ncol):
+        raise ValueError(f"level: expected a scalar or {ncol} values, got shape {lev.shape}")
+    lev = np.ascontiguousarray(np.broadcast_to(lev, (ncol,)))
+    if np.isnan(lev).any():
+        raise ValueError("level: NaN (+-inf is legal: never, or at the first sample)")
+    words = {"up": 1, "down": -1}
+    d = [direction] if isinstance(direction, str) or np.ndim(direction) == 0 else list(direction)
+    if len(d) not in (1, ncol):
+        raise ValueError(f"direction: expected a scalar or {ncol} values, got {len(d)}")
+    out = np.empty(len(d), dtype=np.int32)
+    for i, v in enumerate(d):
+        if isinstance(v, str):
+            if v not in words:
+                raise ValueError(f"direction: {v!r} is neither 'up' nor 'down'")
+            out[i] = words[v]
+        elif isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v == 0:
+            raise ValueError(f"direction: {v!r} is neither 'up' / a positive integer nor 'down' / a negative integer")
+        else:
+            out[i] = 1 if v > 0 else -1
+    return lev, np.ascontiguousarray(np.broadcast_to(out, (ncol,)))
+
+
 class EnsembleRun:
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
@@ -148,6 +175,38 @@ class EnsembleRun:
         out = self.engine.run_series(self.step_index, nsteps, every, names, f, steps_per_launch)
         self.step_index += nsteps
         return out
+
+    def first_passage(self, max_steps, every, name="T", level=0.0, direction="up", forcing=None, steps_per_launch=None):
+        """Advance every member of this shard until the hemispheric mean of field ``name`` crosses the member's ``level``
+        (ebm_run_until), tested on the device after every ``every`` steps, for at most ``max_steps`` steps (a multiple of
+        ``every``).  ``direction``: "up" / +1 (mean >= level) or "down" / -1 (mean <= level); ``level`` and ``direction``
+        are scalars or one entry per member; a NaN mean never crosses.  A member that has crossed takes no further step:
+        its state is that of ``run`` over its own number of steps.  The scalar ``forcing`` is evaluated as in ``run``.
+        Returns dict(step [ncol] int: the 0-based global step after which the member had crossed, -1 if it never did;
+        time [ncol]: the model time of that step in years, NaN if never; crossed [ncol] bool; samples [ncol] int: the rounds
+        taken; value [ncol]: the member's last mean).  Members are independent, so a sharded ensemble gives the results of
+        an unsharded one; shards may stop at different rounds (no collective sits inside the call).  ``step_index``
+        advances by the steps of this shard's slowest member; stepping on continues every member from its own state."""
+        if steps_per_launch is None:
+            steps_per_launch = 64
+        if int(every) < 1:
+            raise ValueError(f"every = {every}: the mean is tested every `every` >= 1 steps")
+        if int(max_steps) < int(every) or int(max_steps) % int(every):
+            raise ValueError(f"max_steps = {max_steps} is not a positive multiple of every = {every}")
+        lev, d = passage_levels(self.ncol, level, direction)
+        rounds = int(max_steps) // int(every)
+        self.engine.check_until_args(self.step_index, rounds, every, name, lev, d, None, steps_per_launch)    # before any device call
+        f = None
+        if forcing is not None:
+            T = (np.arange(self.step_index, self.step_index + int(max_steps)) + 0.5) * self.st.dt
+            f = np.array([forcing(float(t)) for t in T])
+        first = self.step_index
+        out = self.engine.run_until(first, rounds, every, name, lev, d, f, steps_per_launch)
+        self.step_index += out["steps"]
+        last = first + out["samples"] * int(every) - 1
+        step = np.where(out["crossed"], last, -1)
+        time = np.where(out["crossed"], (last + 0.5) * self.st.dt, np.nan)
+        return dict(step=step, time=time, crossed=out["crossed"], samples=out["samples"], value=out["value"])
 
     def seasonal_means(self, years, names=("T", "phi"), forcing=None):
         """Integrate ``years`` whole years from the current state and return, per column, the

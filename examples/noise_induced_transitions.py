@@ -6,10 +6,13 @@ AR(1) ("red") noise on the forcing, drawn on the device (ebm_set_column_noise, o
 runs `--years` years.  Printed per F and year: the fraction of members whose annual-mean hemispheric temperature has
 fallen below the midpoint between the warm and the cold branch.  With `--every N` the noisy ensemble runs through
 EnsembleRun.series instead (ebm_run_series: <T> of every member sampled on the device every N steps) and the script prints,
-per F, the quartiles of the FIRST time a member's <T> falls below that midpoint, in years at N * dt resolution.
+per F, the quartiles of the FIRST time a member's <T> falls below that midpoint, in years at N * dt resolution.  With
+`--until` as well, the same table comes from EnsembleRun.first_passage (ebm_run_until): the level is tested on the device
+every N steps and a member that has fallen takes no further step — its state stays that of its crossing — so the table is
+the same and the script also prints the share of column-steps that were not taken.
 
     python examples/noise_induced_transitions.py [--nlat 180] [--nt 2000] [--forcings -2,0,2] [--members 64]
-        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0]
+        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0] [--until]
 """
 import argparse
 import os
@@ -36,7 +39,12 @@ def main():
     ap.add_argument("--max-years", type=int, default=60, help="spin-up limit of the warm and cold equilibria")
     ap.add_argument("--every", type=int, default=0,
                     help="sample <T> every N steps and print first-passage times (0: the yearly table only)")
+    ap.add_argument("--until", action="store_true",
+                    help="with --every: stop each member at its first passage (EnsembleRun.first_passage) instead of "
+                         "thresholding the whole series")
     args = ap.parse_args()
+    if args.until and not args.every:
+        ap.error("--until needs --every N: the level is tested every N steps")
     if args.every < 0 or (args.every and (args.nt * args.years) % args.every):
         ap.error("--every must be positive and divide nt * years")
     pkg = graft.load_package()
@@ -69,10 +77,16 @@ def main():
                           noise=dict(sigma=args.sigma, tau=args.tau, seed=args.seed), noise_streams=np.arange(nf * n))
     threshold = np.repeat(0.5 * (cold_T + warm_T), n)
     if args.every:
-        T = run.series(args.nt * args.years, args.every, names=("T",))[0]      # [samples, members]
+        if args.until:
+            # "<T> < threshold", as the series is thresholded below: at or under the next number down
+            fp = run.first_passage(args.nt * args.years, args.every, "T", level=np.nextafter(threshold, -np.inf), direction="down")
+            first = np.where(fp["crossed"], fp["samples"] * args.every * st.dt, np.inf)                  # years
+            taken = int(fp["samples"].sum()) * args.every
+        else:
+            T = run.series(args.nt * args.years, args.every, names=("T",))[0]      # [samples, members]
+            below = T < threshold
+            first = np.where(below.any(axis=0), (below.argmax(axis=0) + 1) * args.every * st.dt, np.inf)    # years
         run.close()
-        below = T < threshold
-        first = np.where(below.any(axis=0), (below.argmax(axis=0) + 1) * args.every * st.dt, np.inf)    # years
         print(f"\n{nf * n} members ({n} per forcing), noise sigma = {args.sigma} W m^-2, tau = {args.tau} y, <T> sampled every "
               f"{args.every} steps ({args.every * st.dt:.4f} y) for {args.years} years; first time <T> falls below the branches' "
               "midpoint (years; inf: never):")
@@ -81,6 +95,9 @@ def main():
             t = first[i * n:(i + 1) * n]
             q = np.quantile(t, [0.25, 0.5, 0.75], method="lower")
             print(f"{F[i]:5.2f}  {np.isfinite(t).mean():5.2f}  " + "  ".join(f"{v:7.3f}" for v in q))
+        if args.until:
+            total = nf * n * args.nt * args.years
+            print(f"column-steps taken: {taken} of {total} ({100.0 * (1.0 - taken / total):.1f} % not taken)")
         return
     out = run.seasonal_means(args.years, names=("T",))
     run.close()

@@ -406,6 +406,50 @@ int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_s
 int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const double *f_year, int nvars, const int *fields,
                     const double *tol, int *years, int *converged, double *resid);
 
+/* FIRST PASSAGE: step every column until the hemispheric mean of one field crosses the column's level — the tipping step of
+ * a noisy member, the runaway under a forcing ramp, the loss of the summer ice — and keep the column's state at its
+ * crossing.  Where ebm_run_series steps every member over the whole horizon and leaves the thresholding to the host, a member
+ * that has crossed takes no further step here.  THIS TEXT IS THE DEFINITION.
+ *   Rounds.  Round j = 1, 2, ... takes `every` steps, the 0-based global steps first_step + (j-1)*every .. first_step +
+ *     j*every - 1, of the columns still active (all of them in round 1).  A column's stepping over its rounds 1 .. j is
+ *     exactly that of ebm_run_fused(h, first_step, j*every, f_steps, diag, steps_per_launch), with diag = 1 iff `field` is a
+ *     diagnostic field of the model: time table, per-column forcings, schedules, parameter rows, noise and launch options
+ *     as there.  f_steps[max_samples * every] (NULL = 0.0).
+ *   Sample.  After round j, m_c is bit for bit what ebm_hemispheric_mean(h, field, out) would put into out[c] at that point
+ *     (hemispheric_mean, src/utilities.jl:397-403, in the reference's summation order), for every column c active in round j.
+ *   Crossing.  Column c has crossed when direction[c] > 0 ? m_c >= level[c] : m_c <= level[c].  Equality crosses.  A NaN m_c
+ *     never crosses (the NaN sentinels of Ti and Tw, src/miz.jl:193-194).  level[c] = +-inf is legal: "never", or "at the
+ *     first sample", depending on the direction.
+ *   Freezing.  A column that crosses at round j takes no further step: its whole state is bit for bit that of a run of
+ *     j*every steps from the same start — the prognostic fields, the warm start, the noise state N_c and, if diag, the
+ *     diagnostic fields and the fp64 T0, written at the column's own last step.  A column that never crosses takes
+ *     max_samples*every steps.
+ *   Outputs ([ncol] host arrays).  samples[c]: the rounds column c took; crossed[c]: 1 if it crossed (at round samples[c]),
+ *     else 0 (samples[c] = max_samples); value[c] (may be NULL): its last m_c.  The first-passage step of a column that
+ *     crossed is the 0-based global step first_step + samples[c]*every - 1.
+ *   Afterwards.  The call returns as soon as no column is active.  With R = max_c samples[c], the step clock is at
+ *     first_step + R*every and counters[0] has grown by R*every; counters[3] by ceil(every / K') launches per round and
+ *     non-empty launch chain, K' = min(steps_per_launch, 64 if noise is installed) (the two small kernels per round are not
+ *     counted).  Field validity is recorded as for ebm_equilibrate: each column holds the values of its own last step, and
+ *     the bookkeeping (ebm_field_step) records them as written by the handle's last step.  Further stepping of such a handle
+ *     — by any entry point, this one included — continues every member, the frozen ones too, from its own state, under the
+ *     handle's one step clock: a second call tests every column anew, so a column whose mean still satisfies its comparison
+ *     stops again after one round.
+ * Columns are independent: a column's result does not depend on the others or on sharding.  All models, grids and options.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for every < 1, max_samples < 1, steps_per_launch < 1, first_step < 0, a
+ * field that is not a solution variable of the model (EBM_F_T0 is not one), a NaN level, direction[c] == 0, a missing time
+ * table, a NULL level, direction, samples or crossed; EBM_ERR_UNSUPPORTED where the shape has no fused-K kernel in this
+ * build (as ebm_equilibrate).
+ * How it runs: every round is the fused stepping of ebm_run_fused over the ACTIVE columns only — a frozen column gets no
+ * workgroup and moves no byte; also with steps_per_launch = 1, which here is the fused kernel at one step per launch (same
+ * bits), never ebm_run's one-step kernels or its graph replay, which know nothing of the list — then one small kernel takes
+ * the mean of each active column (one wave per column) and compares, a second one builds the next active list, and the
+ * host reads its length: ONE STREAM SYNCHRONISATION PER ROUND (none after the last possible one).  `every` is the caller's
+ * knob for that cost: a crossing is only seen at a multiple of `every` steps.  Device memory for the call: 5 ints and 2
+ * doubles per column (two lists, samples, crossed and direction; value and level), freed before it returns.  Synchronous. */
+int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
+                  int field, const double *level, const int *direction, int *samples, int *crossed, double *value);
+
 int ebm_sync(ebm_handle_t h);
 
 /* ---- measurement / diagnostics ------------------------------------------------------- */

@@ -249,4 +249,30 @@ function run_series!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, ev
     return out
 end
 
+"""
+    run_until!(h, first_step, fsteps, every, name, level, direction; steps_per_launch=64)
+        -> (samples, crossed, value)
+
+First passage (`ebm_run_until`): rounds of `every` steps from 0-based global step `first_step`, at most
+`length(fsteps) ÷ every` of them; after each round the per-column `hemispheric_mean` of field `name` is taken on the
+device, and a column whose mean has crossed `level[c]` (`direction[c] > 0`: mean >= level, `< 0`: mean <= level; a NaN mean
+never crosses) takes no further step.  `samples[c]` rounds were taken by column `c`; its first-passage step is
+`first_step + samples[c]*every - 1` where `crossed[c]`; `value[c]` is its last mean.
+"""
+function run_until!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, every::Integer, name::Symbol,
+                    level::Vector{Float64}, direction::Vector{<:Integer}; steps_per_launch::Integer=64)
+    nsteps = length(fsteps)
+    (every >= 1 && nsteps >= every && nsteps % every == 0) ||
+        throw(ArgumentError("the number of steps must be a positive multiple of every >= 1"))
+    ncol = length(level)
+    length(direction) == ncol || throw(ArgumentError("level and direction must have one entry per column"))
+    samples, crossed, value = zeros(Cint, ncol), zeros(Cint, ncol), fill(NaN, ncol)
+    GC.@preserve h check(ccall((:ebm_run_until, libebm), Cint,
+                               (Ptr{Cvoid}, Clonglong, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cint},
+                                Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+                               h.ptr, first_step, div(nsteps, every), every, fsteps, steps_per_launch, FIELD[name], level,
+                               Cint.(sign.(direction)), samples, crossed, value), "ebm_run_until")
+    return Int.(samples), crossed .!= 0, value
+end
+
 end # module EBMHip

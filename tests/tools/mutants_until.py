@@ -1,0 +1,36 @@
+"""Broken builds of ebm_run_until for the mutation check of tests/tools/mutants.py, whose list, anchor rule and build this
+file uses unchanged: the same commands, restricted to the mutants below.
+
+    python tests/tools/mutants_until.py check        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants_until.py build        (CPU: one full build per mutant under build/)
+    bash   tests/tools/mutants_run.sh                (GPU box: the -m gpu suite against every build/libebm_mut_*.so)
+
+What tests/test_gpu_until.py does with each (profiles/r13_until_mutants.txt):
+  passage_level_must_be_passed_not_met    a measured level is met with equality at the bit, so nobody stops there: every
+                                          case with a measured level fails (25 of 27)
+  passage_nan_mean_counts_as_crossed      the Ti columns stop at round 1: test_nan_mean_never_crosses fails, alone
+  passage_check_reads_the_list_position   from round 2 on the flags of the wrong columns are written: every case with a
+                                          compaction fails (26 of 27)
+  passage_round_steps_the_stale_list      frozen columns are stepped in place of live ones: the same 26"""
+import sys
+
+import mutants
+
+mutants.MUTANTS = [
+    ("passage_level_must_be_passed_not_met", "const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;",
+     "const bool crossed = p.direction[col] > 0 ? acc > level : acc < level;"),
+    ("passage_nan_mean_counts_as_crossed", "const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;",
+     "const bool crossed = p.direction[col] > 0 ? !(acc < level) : !(acc > level);"),
+    ("passage_check_reads_the_list_position", "const int lane = threadIdx.x, col = p.cols[blockIdx.x], nterms = p.nlat - 1;",
+     "const int lane = threadIdx.x, col = (int)blockIdx.x, nterms = p.nlat - 1;"),
+    ("passage_round_steps_the_stale_list", "        std::swap(cur, nxt);                                     // (the list just written steps the next round)\n",
+     "", "ebm_drive.hip"),
+]
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["build"]:
+        mutants.build(sys.argv[2:])
+    elif sys.argv[1:2] == ["check"]:
+        sys.exit(mutants.check())
+    else:
+        print("\n".join(m[0] for m in mutants.MUTANTS))
