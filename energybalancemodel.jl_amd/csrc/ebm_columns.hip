@@ -1,5 +1,5 @@
 // Host runtime, per-column inputs (ebm_runtime.h lists the units): forcing offsets, Forcing schedules, AR(1) noise and
-// parameter sets, each installed all-or-nothing; the step clock and the time table.
+// parameter sets, each installed all-or-nothing; the step clock and the time table; the resampling of whole columns.
 #include <cmath>
 #include <map>
 
@@ -170,6 +170,76 @@ int ebm_set_column_params(ebm_handle_t h, const double *params) {
     h->sets = std::move(sets);
     invalidate_graph(h);                         // the captured launches hold the old argument values
     h->zonal = ebm_ctx::ZonalTables();           // the zonal tables are built again from the parameters now installed
+    return EBM_OK;
+}
+
+// ebm_resample_columns (include/ebm_hip.h).  The host builds the list of moved columns and uploads it; then every array
+// that is part of a column's state goes through the two passes of ebm_resample.hip, one array at a time through ONE
+// staging buffer of `moved` rows: the fields that are current, then the warm-start active set with the noise state.  All
+// on the handle's stream, nothing synchronised but the reuse of the pinned list.
+int ebm_resample_columns(ebm_handle_t h, const int *parent) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_resample_columns: null handle");
+    if (!parent) return fail(EBM_ERR_ARG, "ebm_resample_columns: parent is null");
+    size_t moved = 0;
+    for (int c = 0; c < h->ncol; ++c) {
+        if (parent[c] < 0 || parent[c] >= h->ncol)
+            return fail(EBM_ERR_ARG, "ebm_resample_columns: parent[" + std::to_string(c) + "] = " + std::to_string(parent[c]) +
+                                         " is outside [0, " + std::to_string(h->ncol) + ")");
+        moved += parent[c] != c;
+    }
+    if (moved == 0) return EBM_OK;                       // the identity: nothing is launched
+    HIPCHK(hipSetDevice(h->device));
+    ebm_ctx::Resample &r = h->resample;
+    if (!r.uploaded) HIPCHK(hipEventCreateWithFlags(r.uploaded.out(), hipEventDisableTiming));
+    if (r.in_flight) HIPCHK(hipEventSynchronize(r.uploaded.get()));      // the previous call's upload has read the pinned list
+    r.in_flight = false;
+    if (r.host_cap < moved) {
+        r.host_cap = 0;
+        HIPCHK(hipHostMalloc(r.host.out(), sizeof(int) * 2 * moved, hipHostMallocDefault));
+        r.host_cap = moved;
+    }
+    HIPCHK(r.dev.reserve(2 * moved));
+    // staging rows of pitch doubles each: the scratch of the diffusion operators if the handle has it (three whole fields)
+    const bool borrowed = (bool)h->scratch;
+    if (!borrowed) HIPCHK(r.stage.reserve(moved * (size_t)h->pitch));
+    int *list = r.host.get();
+    for (int c = 0, m = 0; c < h->ncol; ++c)
+        if (parent[c] != c) {
+            list[2 * m] = c;
+            list[2 * m + 1] = parent[c];
+            ++m;
+        }
+    hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
+    HIPCHK(hipMemcpyAsync(r.dev.get(), list, sizeof(int) * 2 * moved, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(r.uploaded.get(), s));
+    r.in_flight = true;
+    ebm::ResampleArgs a{};
+    a.stage = reinterpret_cast<uint4 *>(borrowed ? h->scratch.get() : r.stage.get());
+    a.stage_stride = h->pitch / 2;
+    a.list = reinterpret_cast<const int2 *>(r.dev.get());
+    auto two_passes = [&]() -> hipError_t {
+        hipError_t e = ebm::launch_resample_stage(a, (int)moved, s);
+        return e == hipSuccess ? ebm::launch_resample_scatter(a, (int)moved, s) : e;
+    };
+    // whole rows in whatever layout they are held (state_split, diag_split stay); a stale field is not copied and stays stale
+    a.row_stride = h->pitch / 2;
+    a.units = (int)(h->pitch / 2);
+    for (int f = 0; f < EBM_F_COUNT; ++f) {
+        if (!has_field(h, f) || (is_diagnostic(h, f) && h->written_epoch[f] != h->epoch)) continue;
+        a.rows = reinterpret_cast<uint4 *>(h->field[f]);
+        hipError_t e = two_passes();
+        if (e != hipSuccess) return hip_fail("ebm_resample_columns", e);
+    }
+    // the warm-start active set (rows of `threads` unsigned shorts: threads / 8 units) and N_c
+    if (h->amask || h->noise.state) {
+        a.rows = reinterpret_cast<uint4 *>(h->amask.get());
+        a.row_stride = a.units = h->amask ? h->cfg.threads / 8 : 0;
+        a.nstate = h->noise.state.get();
+        hipError_t e = two_passes();
+        if (e != hipSuccess) return hip_fail("ebm_resample_columns", e);
+    }
+    // the diffusion operators expect their scratch zero in the padding cells
+    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));
     return EBM_OK;
 }
 

@@ -187,5 +187,20 @@ hipError_t launch_split_fields(double *fields, long long field_stride, int nfiel
                                hipStream_t s);
 hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                  hipStream_t s);
+// ebm_resample_columns (ebm_resample.hip), one workgroup per entry m < moved of the list: `stage` copies row list[m].y (the
+// parent) of `rows` to row m of `stage`, `scatter` row m of `stage` to row list[m].x (the destination) of `rows`.  Rows in
+// units of 16 bytes: `units` of them are copied, row_stride / stage_stride apart.  nstate (null: none): N_c goes the same
+// way, through the double behind the units of staging row m — so stage_stride >= units + 1.
+struct ResampleArgs {
+    uint4 *rows;
+    long long row_stride;
+    uint4 *stage;
+    long long stage_stride;
+    const int2 *list;                // [moved] (destination, parent), both < ncol
+    int units;
+    double *nstate;
+};
+hipError_t launch_resample_stage(const ResampleArgs &r, int moved, hipStream_t s);
+hipError_t launch_resample_scatter(const ResampleArgs &r, int moved, hipStream_t s);
 
 }  // namespace ebm

@@ -36,7 +36,7 @@
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 449 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 451 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.

@@ -2,7 +2,7 @@
 // idioms, the handle's stream and the field predicates.
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the two diffusion operators
-//   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table
+//   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling
 //   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate, run-until
 // Not part of the public interface.
 #pragma once
@@ -149,6 +149,17 @@ struct ebm_ctx {
     std::vector<double> xhost;                     // st.x (the zonal tables are built on demand)
     std::unique_ptr<HostCopier> copier;            // pinned staging ring, lazily created by the first host transfer
     DevBuf<double> scratch;                        // ebm_diffusion / ebm_zonal_diffusion: three fields, kept between calls
+    // ebm_resample_columns, kept between calls: the list of moved columns — (destination, parent) pairs — in pinned host
+    // memory and on the device, the event after which the pinned list may be refilled (the upload has read it), and the
+    // staging rows of a handle that has no `scratch`
+    struct Resample {
+        PinnedBuf<int> host;
+        size_t host_cap = 0;                       // pairs
+        DevVec<int> dev;
+        DevVec<double> stage;
+        Event uploaded;
+        bool in_flight = false;
+    } resample;
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
     DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
     ~ebm_ctx();

@@ -477,6 +477,29 @@ class Engine:
         samples = samples.astype(np.int64)
         return dict(samples=samples, crossed=crossed.astype(bool), value=value, steps=int(samples.max()) * int(every))
 
+    def check_resample_args(self, parents):
+        """The host-side checks of ``resample_columns`` (no device call): returns the parents as a contiguous int32 array
+        [ncol]."""
+        p = np.asarray(parents)
+        if p.dtype.kind not in "iu":          # (a bool array is kind "b": a mask is not a list of parents)
+            raise ValueError(f"parents: expected {self.ncol} integers (column indices), got dtype {p.dtype}")
+        if p.shape != (self.ncol,):
+            raise ValueError(f"parents: expected {self.ncol} integers, one per column, got shape {p.shape}")
+        bad = np.flatnonzero((p < 0) | (p >= self.ncol))
+        if bad.size:
+            c = int(bad[0])
+            raise ValueError(f"parents[{c}] = {int(p[c])} is outside [0, {self.ncol})")
+        return np.ascontiguousarray(p, dtype=np.int32)
+
+    def resample_columns(self, parents):
+        """ebm_resample_columns: for every column c at once, the new state of c is the old state of ``parents[c]`` — the
+        prognostic fields, the warm start, the noise state and every field that is current — gathered on the device in
+        whatever layout the handle holds.  Column c keeps its own forcing offset, schedule, parameter row and noise stream,
+        so a clone parts from its parent at the next step.  The step clock, the counters and the validity of the fields
+        are unchanged; ``parents[c] == c`` moves nothing.  Asynchronous."""
+        p = self.check_resample_args(parents)
+        check(self.lib.ebm_resample_columns(self._h, p.ctypes.data_as(C.POINTER(C.c_int))), "ebm_resample_columns")
+
     def sync(self):
         check(self.lib.ebm_sync(self._h), "ebm_sync")
 

@@ -77,6 +77,94 @@ def passage_levels(ncol: int, level, direction):
     return lev, np.ascontiguousarray(np.broadcast_to(out, (ncol,)))
 
 
+def selection_parents(weights, rng) -> np.ndarray:
+    """Systematic resampling: the parents [n] (int32, ascending) of the next generation of ``n = len(weights)`` members,
+    member m getting ``floor(n w_m)`` or ``ceil(n w_m)`` offspring (w: the weights normalised to sum 1).  One uniform
+    draw u from ``rng`` (a ``numpy.random.Generator``), then the n pointers u, u + 1, ..., u + n - 1 through the
+    cumulative weights scaled to n: pointer j falls into member parents[j]'s interval.  The result is ascending, so a
+    survivor stays in its slot, and ``resample`` moves nothing for it, as long as the cumulative weights up to it are
+    within one slot of its index — nearly equal weights; once the relative spread of the weights exceeds about
+    1 / sqrt(n), most members change slot (tests/tools/resample_cost.py prints the share).  Equal weights give the
+    identity (whatever u is) and a member of weight 0 has no offspring.  Host only (no device call).  ValueError for negative or
+    non-finite weights and for an all-zero sum."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] < 1:
+        raise ValueError(f"weights: expected a vector of at least one weight, got shape {w.shape}")
+    if not np.isfinite(w).all():
+        raise ValueError("weights: expected finite values")
+    if (w < 0.0).any():
+        raise ValueError("weights: expected values >= 0")
+    n = w.shape[0]
+    u = rng.random()                                     # drawn in every case: the caller's stream does not depend on w
+    if w.max() == 0.0:
+        raise ValueError("weights: all zero (no member to continue from)")
+    if (w == w[0]).all():
+        return np.arange(n, dtype=np.int32)              # by definition, not up to the rounding of the cumulative sums
+    cum = np.cumsum(w)
+    cum *= n / cum[-1]
+    cum[np.flatnonzero(w > 0.0)[-1]:] = np.inf           # the last pointer cannot fall behind the last live member
+    return np.searchsorted(cum, u + np.arange(n), side="right").astype(np.int32)
+
+
+# ---- genealogical cloning (Giardina-Kurchan-Lecomte-Tailleur), host side ------------------------------------------------------
+# EXPERIMENTAL: the three gklt_* functions are here so that examples/rare_transitions_gklt.py and the host tests share one
+# statement of the estimator; their signatures may change.  selection_parents and EnsembleRun.resample are the supported part.
+# Members are slots 0 .. n-1.  An interval advances every slot and scores it; the selection after it makes slot c continue
+# from slot parents[c].  The functions below are pure NumPy: `advance` and `resample` are the caller's (EnsembleRun.series
+# and EnsembleRun.resample in examples/rare_transitions_gklt.py, a toy process in tests/test_host_resample.py).
+
+def gklt_run(advance, resample, n, nintervals, k, rng):
+    """``nintervals`` rounds of: V = advance(i) — the [n] scores of interval i, the time integral of the tilting observable
+    over the interval for every slot; weights exp(k V); parents = selection_parents(weights, rng); resample(parents).
+    Returns dict(scores [nintervals, n]: V by slot; parents [nintervals, n] int32: the genealogy; log_norm: the log of the
+    product over the intervals of the mean weight).  k = 0 selects nothing: every parents row is the identity."""
+    scores = np.empty((nintervals, n))
+    parents = np.empty((nintervals, n), dtype=np.int32)
+    log_norm = 0.0
+    for i in range(nintervals):
+        v = np.asarray(advance(i), dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError(f"advance({i}) returned shape {v.shape}, expected {(n,)}")
+        e = k * v
+        top = e.max()
+        w = np.exp(e - top)
+        log_norm += float(np.log(w.mean()) + top)
+        parents[i] = selection_parents(w, rng)
+        resample(parents[i])
+        scores[i] = v
+    return dict(scores=scores, parents=parents, log_norm=log_norm)
+
+
+def gklt_lineage(parents, values, reduce=np.add) -> np.ndarray:
+    """``values`` [nintervals, n] were recorded by slot during each interval (before its selection): returns, for every
+    slot after the last selection, ``reduce`` over the intervals of the value of its ANCESTOR in that interval — the sum
+    of the scores along the member's line of descent (np.add), the lowest <T> it has seen (np.minimum)."""
+    parents, values = np.asarray(parents), np.asarray(values)
+    anc = np.arange(parents.shape[1])
+    out = None
+    for i in range(parents.shape[0] - 1, -1, -1):
+        anc = parents[i][anc]                            # the slot that held this line during interval i
+        out = values[i][anc] if out is None else reduce(values[i][anc], out)
+    return out
+
+
+def gklt_estimate(observable, score_sum, k, log_norm=0.0) -> dict:
+    """The re-weighted expectation of ``observable`` [n] (one value per final member, of its whole line) under the
+    UNTILTED dynamics, from a run tilted by exp(k * score): with u_m = exp(-k * score_sum[m]), score_sum the sum of the
+    scores along the member's line (gklt_lineage),
+        raw(O) = exp(log_norm) * mean(O u)     the GKLT estimator; raw(1) is 1 only in expectation, because a member has a
+                                               whole number of offspring
+        estimate = raw(O) / raw(1) = sum(O u) / sum(u)    self-normalised: exactly 1 for O = 1, the plain mean for k = 0.
+    Returns dict(estimate, norm = raw(1), ess = sum(u)^2 / sum(u^2): the effective number of members)."""
+    o = np.asarray(observable, dtype=np.float64)
+    e = -(k * np.asarray(score_sum, dtype=np.float64))
+    top = e.max()
+    u = np.exp(e - top)
+    total = np.sum(u)
+    return dict(estimate=float(np.sum(o * u) / total), norm=float(np.exp(log_norm + top) * (total / u.shape[0])),
+                ess=float(total * total / np.sum(u * u)))
+
+
 class EnsembleRun:
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
@@ -207,6 +295,16 @@ class EnsembleRun:
         step = np.where(out["crossed"], last, -1)
         time = np.where(out["crossed"], (last + 0.5) * self.st.dt, np.nan)
         return dict(step=step, time=time, crossed=out["crossed"], samples=out["samples"], value=out["value"])
+
+    def resample(self, parents):
+        """Selection step of a cloning / splitting / particle-filter algorithm, on the device (ebm_resample_columns):
+        member c of this shard continues from a copy of member ``parents[c]``'s state — fields, warm start, noise state —
+        and keeps its own forcing offset, schedule, parameter row and noise stream, so it draws its own noise from the
+        next step on.  ``parents``: [ncol] integer indices WITHIN THIS SHARD (``selection_parents`` makes them from
+        weights).  ``step_index`` is unchanged; no field becomes stale.  The call is rank-local: a parent on another
+        rank's shard cannot be named — selecting across ranks needs a packed device export / import of whole columns as
+        an RCCL payload, which this library does not have yet."""
+        self.engine.resample_columns(parents)
 
     def seasonal_means(self, years, names=("T", "phi"), forcing=None):
         """Integrate ``years`` whole years from the current state and return, per column, the

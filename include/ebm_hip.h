@@ -450,6 +450,42 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
 int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
                   int field, const double *level, const int *direction, int *samples, int *crossed, double *value);
 
+/* RESAMPLE the members on the device: column c continues from a copy of column parent[c]'s state and draws its own noise
+ * from then on — the selection step of genealogical cloning (Giardina-Kurchan-Lecomte-Tailleur), of adaptive multilevel
+ * splitting, of any particle filter — without the state leaving the device.  THIS TEXT IS THE DEFINITION.
+ *   Gather, all at once.  parent[ncol] is a host array.  For every column c simultaneously, the new state of c is the old
+ *     state of parent[c]: reads happen before writes.  A swap (parent = {1, 0}) exchanges two columns, a shift (parent[c] =
+ *     c - 1) moves every column by one, a fan-out gives many columns one parent.  parent[c] == c leaves c untouched and
+ *     moves no byte of it; the all-identity map launches nothing.
+ *   What moves: the state — everything a checkpoint of the column consists of.  The prognostic fields (MIZ and MIZ_IMEX:
+ *     Ei, Ew, h, D, phi; classic: E, Tg), the warm-start active set, the noise state N_c if noise is installed, and every
+ *     diagnostic field, and the fp64 T0, that is current at the call.  Stale diagnostic fields are not copied and stay stale.
+ *   What stays: the member's identity — everything installed per column stays with the slot: fcol[c], the schedule row,
+ *     the parameter set, the noise record (sigma, rho, stream id).  From the next step on, column c steps exactly as a
+ *     one-column handle created with c's settings and loaded with parent[c]'s state, T0, noise state and the same step
+ *     clock would, bit for bit, in every stepping entry point.  Two clones of one parent keep their own streams, so they
+ *     part at the next step; without noise they stay identical.
+ *   Validity.  The call changes the prognostic state without a step, yet keeps the fields consistent: a field that was
+ *     current before is current after and holds the parent's values; a field that was stale fails with EBM_ERR_STALE
+ *     exactly as before, with the same steps in the message.  written_step and state_step (ebm_field_step) are unchanged,
+ *     and ebm_get_field_as_of keeps answering for the step it answered for.  The step clock and counters[0..3] are
+ *     unchanged: the copy kernels are not counted as launches.
+ *   Layout.  Rows are copied whole — pitch doubles, padding included — in whatever layout the handle holds them (the
+ *     layout private to the one-step MIZ kernel permutes WITHIN a row), so nothing is converted: ebm_state_conversions
+ *     does not grow, and a steady ebm_run loop with a resample between its calls still converts once.
+ *   Ordering.  The work is enqueued on the handle's stream, after every step launched so far (two launch chains are
+ *     joined first).  parent has been consumed when the call returns.  Asynchronous, like ebm_run; a call waits only for
+ *     the list upload of the call before it.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL parent or an entry outside [0, ncol); the message names the
+ * first offending column.
+ * How it runs: the host builds the list of moved columns (destination, parent) and uploads it; every array that moves is
+ * then taken through two passes — the parents' rows into a staging buffer, the staging buffer into the destinations — so
+ * that no swap, cycle or chain reads a row already overwritten; one workgroup per moved column, 16 bytes per lane and
+ * access on whole 128-byte lines.  Device memory for the call, with moved = the number of columns with parent[c] != c:
+ * moved * pitch doubles of staging (one field's worth at most — never a second copy of the state; the scratch of
+ * ebm_diffusion is used instead where the handle has it) and the list, 2 ints per moved column; kept by the handle. */
+int ebm_resample_columns(ebm_handle_t h, const int *parent);
+
 int ebm_sync(ebm_handle_t h);
 
 /* ---- measurement / diagnostics ------------------------------------------------------- */

@@ -275,4 +275,17 @@ function run_until!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, eve
     return Int.(samples), crossed .!= 0, value
 end
 
+"""
+    resample!(h, parents)
+
+Selection step of a cloning / splitting / particle-filter algorithm on the device (`ebm_resample_columns`): for every
+column `c` at once (1-based here), the new state of `c` is the old state of column `parents[c]` — prognostic fields, warm
+start, noise state and every field that is current.  Column `c` keeps its own forcing offset, schedule, parameter row and
+noise stream.  `parents[c] == c` moves nothing; the step clock and the validity of the fields are unchanged.
+"""
+function resample!(h::Handle, parents::Vector{<:Integer})
+    GC.@preserve h check(ccall((:ebm_resample_columns, libebm), Cint, (Ptr{Cvoid}, Ptr{Cint}), h.ptr, Cint.(parents .- 1)),
+                         "ebm_resample_columns")
+end
+
 end # module EBMHip

@@ -1,0 +1,31 @@
+"""Broken builds of ebm_resample_columns for the mutation check of tests/tools/mutants.py, whose anchor rule and build this
+file uses unchanged, restricted to the mutants below.
+
+    python tests/tools/mutants_resample.py check        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants_resample.py build        (CPU: one full build per mutant under build/)
+
+Then tests/test_gpu_resample.py against every build/libebm_mut_*.so (EBM_LIB names the library).  What it does with each is
+recorded in profiles/r14_resample_mutants.txt."""
+import sys
+
+import mutants
+
+mutants.MUTANTS = [
+    # the scatter pass reads the parent's row of the array itself: an in-place gather, no staging
+    ("resample_scatters_in_place", "STAGE ? r.rows + (long long)e.y * r.row_stride : stage;",
+     "r.rows + (long long)e.y * r.row_stride;"),
+    ("resample_leaves_the_active_set", "a.row_stride = a.units = h->amask ? h->cfg.threads / 8 : 0;", "a.row_stride = a.units = 0;"),
+    ("resample_leaves_the_noise_state", "        a.nstate = h->noise.state.get();\n", "        a.nstate = nullptr;\n"),
+    ("resample_copies_stale_fields", "(is_diagnostic(h, f) && h->written_epoch[f] != h->epoch)", "false"),
+    ("resample_marks_the_state_changed", "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n",
+     "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n    h->epoch += 1;\n"),
+    ("resample_keeps_the_scratch_dirty", "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n", ""),
+]
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["build"]:
+        mutants.build(sys.argv[2:])
+    elif sys.argv[1:2] == ["check"]:
+        sys.exit(mutants.check())
+    else:
+        print("\n".join(m[0] for m in mutants.MUTANTS))
