@@ -166,6 +166,8 @@ int ebm_set_column_params(ebm_handle_t h, const double *params) {
             e = hipMemcpy(sets.host.data(), sets.p.get(), sizeof(ebm::Params) * (size_t)sets.n, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail("ebm_set_column_params", e);
     }
+    // phi as the parameters that made it give it, before Lf changes under it
+    if (int rc = state_written_outside(h)) return rc;
     HIPCHK(hipStreamSynchronize(main_stream(h)));
     h->sets = std::move(sets);
     invalidate_graph(h);                         // the captured launches hold the old argument values
@@ -209,6 +211,8 @@ int ebm_resample_columns(ebm_handle_t h, const int *parent) {
             list[2 * m + 1] = parent[c];
             ++m;
         }
+    // phi moves as a field: current first, under the parent's parameters — which the destination need not share
+    if (int rc = state_written_outside(h)) return rc;
     hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
     HIPCHK(hipMemcpyAsync(r.dev.get(), list, sizeof(int) * 2 * moved, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(r.uploaded.get(), s));

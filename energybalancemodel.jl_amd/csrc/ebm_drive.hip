@@ -41,9 +41,15 @@ constexpr int kGraphSteps = 64;
 constexpr int kFusedTable = 16384;     // per-step scalars resident on the device at a time (512 KiB)
 
 // mode: ebm::OutMode.  The classic kernel decides about T, h at run time (write_diag).
-hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, int first, int count, hipStream_t s) {
-    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, first, count, s)
+hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, int first, int count, hipStream_t s) {
+    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, phi_derived, first, count, s)
                                        : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
+}
+// A step launch has been enqueued: what it means for the phi field (ebm_ctx::phi_stored).  Every step kernel leaves Ei, h and
+// the phi it stores — or would have stored — consistent; a launch over a list of active columns says nothing of the others.
+void note_step(ebm_ctx *h, bool phi_derived) {
+    h->phi_stored = !phi_derived;
+    if (!h->active) h->phi_consistent = true;
 }
 // The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate,
 // ebm_run_until), as one chain or split in two halves; a chain with no columns is skipped.
@@ -52,14 +58,10 @@ int chain_count(const ebm_ctx *h, int *first_half) {
     *first_half = h->split_col ? (h->active ? n / 2 : h->split_col) : n;
     return (*first_half > 0) + (n - *first_half > 0);
 }
-// Every step launch of the library goes through here, so the layout rule of the prognostic fields (ebm_ctx::state_split) is
-// applied here: a one-step MIZ launch reads and writes them pair-split, the fused-K and classic kernels the natural layout.
-// A steady run of either kind converts nothing.  Under graph capture the layout is already the one-step one (build_graph).
-hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
-    const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
-    if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
+// ... as one chain of launches or as two (ebm_ctx::stream2)
+hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived) {
     const int n = h->active ? h->nactive : h->ncol;
-    if (!h->split_col) return launch_columns(h, a, mode, 0, n, main_stream(h));
+    if (!h->split_col) return launch_columns(h, a, mode, phi_derived, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
         hipError_t e = hipEventRecord(h->ev_fork.get(), h->stream.get());
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);
@@ -68,8 +70,27 @@ hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode) {
     }
     int half = 0;
     (void)chain_count(h, &half);
-    hipError_t e = half > 0 ? launch_columns(h, a, mode, 0, half, h->stream.get()) : hipSuccess;
-    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, half, n - half, h->stream2.get());
+    hipError_t e = half > 0 ? launch_columns(h, a, mode, phi_derived, 0, half, h->stream.get()) : hipSuccess;
+    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, phi_derived, half, n - half, h->stream2.get());
+    return e;
+}
+// Every step launch of the library goes through here, so the layout rule of the prognostic fields (ebm_ctx::state_split) is
+// applied here: a one-step MIZ launch reads and writes them pair-split, the fused-K and classic kernels the natural layout.
+// A steady run of either kind converts nothing.  Under graph capture the layout is already the one-step one (build_graph).
+// The same place decides about phi: a state-only one-step launch takes the kernel that derives it from Ei and h when the handle
+// has one and the state is consistent; any other one-step launch loads the field, which is restored first if such launches
+// left it stale (the un-split pass before a fused launch does it on the way).  `capturing` (build_graph): nothing but the
+// step launches is enqueued and the handle's bits stay; ebm_run makes the state fit the captured kernels before a replay.
+hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool capturing = false) {
+    const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
+    const bool phi_derived = mode == ebm::OUT_STATE && h->derive_phi && (capturing || h->phi_consistent);
+    if (!capturing) {
+        if (one_step && !phi_derived)
+            if (hipError_t e = restore_phi(h); e != hipSuccess) return e;
+        if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
+    }
+    hipError_t e = launch_chains(h, a, mode, phi_derived);
+    if (e == hipSuccess && !capturing) note_step(h, phi_derived);
     return e;
 }
 
@@ -87,7 +108,7 @@ int build_graph(ebm_ctx *h) {
         a.sched = g.sched.get();
         a.slot = i;
         a.write_diag = 0;
-        e = launch_step(h, a, ebm::OUT_STATE);
+        e = launch_step(h, a, ebm::OUT_STATE, true);     // the deriving kernel where the handle has it
     }
     hipError_t e2 = hipStreamEndCapture(main_stream(h), &graph);
     if (e != hipSuccess || e2 != hipSuccess) {
@@ -210,6 +231,13 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
         // per step); the per-step scalars travel through a small device table
         int rc = h->graph.exec ? EBM_OK : build_graph(h);
         if (rc) return rc;
+        // the captured launches derive phi where the handle can (launch_step): a state somebody else wrote takes the call's
+        // first step directly, with the phi that is stored, and is consistent from then on
+        if (h->derive_phi && !h->phi_consistent && nsteps > (diag_last ? 1 : 0)) {
+            const long long ti = first_step % nt;
+            if ((rc = do_step(h, h->ttab[ti], h->ttab[(ti + 1) % nt], f_steps ? f_steps[0] : 0.0, 0, first_step))) return rc;
+            s = 1;
+        }
         std::vector<ebm::StepSched> sched(kGraphSteps);
         const int last_graph_step = nsteps - (diag_last ? 1 : 0);     // a diagnostic last step is launched directly
         for (; s + kGraphSteps <= last_graph_step; s += kGraphSteps) {
@@ -220,6 +248,7 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
             if ((rc = set_state_layout(h, true))) return rc;       // the captured launches expect the one-step layout
             HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
             record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false);
+            note_step(h, h->derive_phi);
         }
     }
     for (; s < nsteps; ++s) {

@@ -24,9 +24,13 @@ hipError_t convert_state(ebm_ctx *h, bool split) {
     if (h->model != EBM_MODEL_MIZ || h->cfg.cells != 4) split = false;      // no second layout: classic; the pair is the chunk
     if (h->state_split == split) return hipSuccess;
     double *first = h->field[EBM_F_Ei];                  // Ei, Ew, h, D, phi: slots 0 .. 4
-    hipError_t e = split ? ebm::launch_split_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h))
-                         : ebm::launch_unsplit_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
+    hipError_t e;
+    if (split) e = ebm::launch_split_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
+    // (one-step launches that did not store phi: the un-split pass forms it from Ei and h instead of moving it)
+    else if (!h->phi_stored) e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, true, main_stream(h));
+    else e = ebm::launch_unsplit_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
     if (e != hipSuccess) return e;
+    h->phi_stored = true;
     h->state_split = split;
     h->n_conversions += 1;
     return hipSuccess;
@@ -34,6 +38,20 @@ hipError_t convert_state(ebm_ctx *h, bool split) {
 int set_state_layout(ebm_ctx *h, bool split) {
     hipError_t e = convert_state(h, split);
     return e == hipSuccess ? EBM_OK : hip_fail("state layout conversion", e);
+}
+
+hipError_t restore_phi(ebm_ctx *h) {
+    if (h->phi_stored) return hipSuccess;
+    // (stale only between one-step launches: the fields are pair-split)
+    hipError_t e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, false, main_stream(h));
+    if (e == hipSuccess) h->phi_stored = true;
+    return e;
+}
+int state_written_outside(ebm_ctx *h) {
+    hipError_t e = restore_phi(h);
+    if (e != hipSuccess) return hip_fail("phi restore", e);
+    h->phi_consistent = false;
+    return EBM_OK;
 }
 
 int get_copier(ebm_ctx *h) {
@@ -153,6 +171,8 @@ int ebm_set_field(ebm_handle_t h, int field, const double *host) {
         if (rc) return rc;
     }
     if (is_split_state_field(h, field) && (rc = set_state_layout(h, false))) return rc;     // ... and so do the prognostic ones
+    // a caller's Ei, h or phi is honoured as it is: the next step loads phi (any prognostic field counts: when in doubt)
+    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;
     HIPCHK(hipStreamSynchronize(main_stream(h)));
     HIPCHK(h->copier->wait_all());
     HIPCHK(h->copier->upload(h->field[field], (size_t)h->pitch, host, (size_t)h->nlat, (size_t)h->ncol));
@@ -228,6 +248,8 @@ int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {
 int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pitch) {
     int rc = open_field(h, field, dptr, "ebm_field_device_ptr");
     if (rc) return rc;
+    // (the caller may write through the view of a prognostic field)
+    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;
     // the view is of the natural layout as of this call
     if (is_split_field(h, field) || is_split_state_field(h, field)) HIPCHK(hipStreamSynchronize(main_stream(h)));
     *dptr = h->field[field];

@@ -89,6 +89,9 @@ using KernelFn = void (*)(const StepArgs);
 KernelFn miz_step_kernels_identity(int cells, int mode, int threads);
 KernelFn miz_step_kernels_nonuniform(int cells, int mode, int threads);
 KernelFn miz_step_kernels_imex(int grid_kind, int mode, int threads);
+// the state-only step that derives phi from Ei and h (miz_step_kernel, PHI_DERIVED): four cells per thread, the reference's step
+KernelFn miz_step_phi_derived_identity(int threads);
+KernelFn miz_step_phi_derived_nonuniform(int threads);
 // fused-K with the state resident in LDS (miz_resident_kernel): four cells per thread; the reference's step beyond
 // kFusedRegThreads threads, the extension at every size
 KernelFn miz_resident_kernels(int grid_kind, int threads, bool imex);
@@ -96,9 +99,12 @@ KernelFn miz_resident_save_kernels(int grid_kind, int threads, bool imex);   // 
 KernelFn miz_fused2_save_kernels(int grid_kind, int threads);                // two cells per thread: miz_fused_kernel<2, ..., SAVE>
 
 bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex);   // is this (geometry, mode) compiled?
-// `count` workgroups, stepping columns first ... first + count - 1
-hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, int first, int count,
-                           hipStream_t s);
+// may a one-step OUT_STATE launch of this handle take the kernel that derives phi?  (the caller answers for the state)
+bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex);
+// `count` workgroups, stepping columns first ... first + count - 1.  phi_derived (OUT_STATE where has_phi_derived_kernel):
+// the kernel that reads Ei and h for phi and leaves the phi field as it was
+hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
+                           int first, int count, hipStream_t s);
 hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s);
 // rcp_dt / rcp_cdn of the device-resident parameter block (see Params)
 hipError_t launch_derive_params(Params *p_dev, hipStream_t s);
@@ -187,6 +193,11 @@ hipError_t launch_split_fields(double *fields, long long field_stride, int nfiel
                                hipStream_t s);
 hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfields, int ncol, const LaunchCfg &cfg,
                                  hipStream_t s);
+// The phi field of every column written again from the column's Ei and h and its own parameter set (concentration, the
+// step kernels' piece: the bits a step that stores phi would have left), after one-step launches that did not store it;
+// the five prognostic fields pair-split (four cells per thread).  unsplit: in the same pass the five fields go to the
+// natural layout (what launch_unsplit_fields does to them); else in place, only phi is written.
+hipError_t launch_restore_phi(const StepArgs &a, int ncol, const LaunchCfg &cfg, bool unsplit, hipStream_t s);
 // ebm_resample_columns (ebm_resample.hip), one workgroup per entry m < moved of the list: `stage` copies row list[m].y (the
 // parent) of `rows` to row m of `stage`, `scatter` row m of `stage` to row list[m].x (the destination) of `rows`.  Rows in
 // units of 16 bytes: `units` of them are copied, row_stride / stage_stride apart.  nstate (null: none): N_c goes the same

@@ -36,6 +36,13 @@ KernelFn miz_kernel_for(int threads) {
     if constexpr (C == 4) return kernel_for(kUpTo512 + kAbove512, threads, pick);
     else return kernel_for(kUpTo512 + kTwoCellsAbove512, threads, pick);
 }
+// the state-only step that derives phi from Ei and h instead of loading and storing it: four cells per thread, every size
+template <int GRID>
+[[maybe_unused]] KernelFn miz_step_phi_derived_for(int threads) {
+    return kernel_for(kUpTo512 + kAbove512, threads, [](auto tt) -> KernelFn {
+        return miz_step_kernel<4, GRID, OUT_STATE, decltype(tt)::value, false, true>;
+    });
+}
 template <int C, int GRID, bool IMEX>
 [[maybe_unused]] KernelFn miz_step_by_mode(int mode, int threads) {
     switch (mode) {

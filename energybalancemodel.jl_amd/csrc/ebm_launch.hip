@@ -36,7 +36,7 @@
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 451 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 485 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -465,6 +465,49 @@ hipError_t launch_unsplit_fields(double *fields, long long field_stride, int nfi
     return hipGetLastError();
 }
 
+// phi from Ei and h, for the readers of the field after one-step launches that did not store it (miz_step_kernel,
+// PHI_DERIVED): one workgroup of the step's size per column, thread t owns the two pairs of its chunk in the pair-split
+// layout.  UNSPLIT: the un-split pass of permute_fields_kernel over the five prognostic fields (the whole column in
+// registers across a barrier, then the natural layout) with phi formed instead of read; else in place: phi's two pairs
+// are written where they lie.  The column's own parameter set gives Lf, as in the step.
+template <bool UNSPLIT>
+__global__ void restore_phi_kernel(const StepArgs a, int threads) {
+    const unsigned t = threadIdx.x, T = (unsigned)threads;
+    const int col = blockIdx.x;
+    ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + param_set(a, col)));
+    double *const st = a.state + (size_t)col * (size_t)threads * 4;
+    const unsigned s0 = split_index(t, 0, T), s1 = split_index(t, 1, T);
+    double2 v[S_phi + 1][2];
+#pragma unroll
+    for (int f = 0; f < S_phi; ++f) {
+        if (!UNSPLIT && f != S_Ei && f != S_h) continue;
+        v[f][0] = *reinterpret_cast<const double2 *>(st + f * a.fstride + s0);
+        v[f][1] = *reinterpret_cast<const double2 *>(st + f * a.fstride + s1);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        v[S_phi][j].x = concentration(p, v[S_Ei][j].x, v[S_h][j].x);
+        v[S_phi][j].y = concentration(p, v[S_Ei][j].y, v[S_h][j].y);
+    }
+    if constexpr (UNSPLIT) {
+        __syncthreads();                                  // every pair of the column has been read
+#pragma unroll
+        for (int f = 0; f <= S_phi; ++f) {
+            *reinterpret_cast<double2 *>(st + f * a.fstride + 4 * t) = v[f][0];
+            *reinterpret_cast<double2 *>(st + f * a.fstride + 4 * t + 2) = v[f][1];
+        }
+    } else {
+        *reinterpret_cast<double2 *>(st + S_phi * a.fstride + s0) = v[S_phi][0];
+        *reinterpret_cast<double2 *>(st + S_phi * a.fstride + s1) = v[S_phi][1];
+    }
+}
+hipError_t launch_restore_phi(const StepArgs &a, int ncol, const LaunchCfg &cfg, bool unsplit, hipStream_t s) {
+    if (cfg.cells != 4 || a.pitch != 4 * cfg.threads) return hipErrorInvalidValue;     // the variant's only geometry
+    if (unsplit) restore_phi_kernel<true><<<dim3(ncol), cfg.threads, 0, s>>>(a, cfg.threads);
+    else restore_phi_kernel<false><<<dim3(ncol), cfg.threads, 0, s>>>(a, cfg.threads);
+    return hipGetLastError();
+}
+
 // ---- host-side launchers ----------------------------------------------------------------------
 // Cells per thread: 4 unless the caller asks for 2 (ebm_options::cells_per_thread; nlat <= kMaxLat2 = 1536: the
 // fused kernel then still fits three waves per SIMD).  4 is the throughput geometry (32 contiguous bytes per lane and
@@ -495,8 +538,12 @@ namespace {
 bool fused_state_in_lds(const LaunchCfg &cfg, bool imex) {
     return imex || (cfg.cells == 4 && (cfg.threads > kFusedRegThreads || cfg.fused_in_lds));
 }
-KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
+KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex, bool phi_derived = false) {
     const int cells = cfg.cells, threads = cfg.threads;
+    if (phi_derived) {
+        if (mode != OUT_STATE || imex || cells != 4) return nullptr;
+        return grid_kind == 0 ? miz_step_phi_derived_identity(threads) : miz_step_phi_derived_nonuniform(threads);
+    }
     if (mode == OUT_LOOP_SAVE) {
         if (cells == 4) return miz_resident_save_kernels(grid_kind, threads, imex);
         return imex ? nullptr : miz_fused2_save_kernels(grid_kind, threads);
@@ -542,6 +589,9 @@ hipError_t prepare_kernels(const LaunchCfg &cfg) {
                 for (int mode = OUT_STATE; mode <= OUT_SAVE; ++mode) {   // (the fused register kernel needs 6T doubles <= 24 KiB)
                     hipError_t e = raise(miz_kernel(cfg, grid, mode, imex != 0), cfg.lds_bytes);
                     if (e != hipSuccess) return e;
+                    if (mode == OUT_STATE && has_phi_derived_kernel(cfg, grid, imex != 0))
+                        e = raise(miz_kernel(cfg, grid, mode, false, true), cfg.lds_bytes);
+                    if (e != hipSuccess) return e;
                 }
             // the resident fused-K kernels and their savesol! variants (four cells per thread): 160 T bytes
             const size_t bytes = sizeof(double) * 20 * (size_t)cfg.threads;
@@ -557,9 +607,13 @@ bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
     return miz_kernel(cfg, grid_kind, mode, imex) != nullptr;
 }
 
-hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, int first, int count,
-                           hipStream_t s) {
-    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex);
+bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex) {
+    return miz_kernel(cfg, grid_kind, OUT_STATE, imex, true) != nullptr;
+}
+
+hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
+                           int first, int count, hipStream_t s) {
+    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex, phi_derived);
     if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
     // fused launches whose kernel reads N_c from memory: everything but miz_fused_kernel up to kFusedRegThreads threads
     const bool fused = mode == OUT_LOOP || mode == OUT_LOOP_SAVE;

@@ -38,6 +38,17 @@ __device__ __forceinline__ VertFlux vert_flux(ConstParams &p, double S, double x
     return {Fvi, Fvw};
 }
 
+// concentration, src/miz.jl:74-80: the ice cover of a cell from its ice enthalpy and thickness.  miz_cell_update ends with it
+// and stores Ei (zeroed where h == 0, which phi does not see: h == 0 gives 0 first) and h, so after any step phi is this
+// function of the stored Ei and h, bit for bit — what the one-step kernel that does not store phi forms in its phase A
+// (miz_step_kernel, PHI_DERIVED) and restore_phi_kernel writes back.  Padding cells: Ei = h = 0 gives 0.
+__device__ __forceinline__ double concentration(ConstParams &p, double Ei, double h) {
+    double phi_n = ieee_div(-Ei, p.Lf * h);
+    if (h == 0.0) phi_n = 0.0;
+    if (phi_n > 1.0) phi_n = 1.0;
+    return phi_n;
+}
+
 __device__ __forceinline__ MizCellOut miz_cell_update(ConstParams &p, double f, double S, double xk,
                                                      double dif, double tb, double Ei, double Ew,
                                                      double hk, double Dk, double ph, double Tw,
@@ -90,10 +101,7 @@ __device__ __forceinline__ MizCellOut miz_cell_update(ConstParams &p, double f, 
     rh = jl_clamp(rh, 0.0, INFINITY);
     double h_n = div_with_rcp(n * rh + dn * p.hmin, total, rtotal);
     if (total == 0.0) h_n = 0.0;
-    // concentration :74-80
-    double phi_n = ieee_div(-Ei_n, Lf * h_n);
-    if (h_n == 0.0) phi_n = 0.0;
-    if (phi_n > 1.0) phi_n = 1.0;
+    const double phi_n = concentration(p, Ei_n, h_n);
     if (h_n == 0.0) Ei_n = 0.0;   // :185
     MizCellOut o;
     o.q[Q_Ei] = Ei_n;

@@ -29,9 +29,16 @@ namespace ebm {
 // dt <= cw*dx^2/(2D) of the reference's step.
 // __launch_bounds__(TT, 4): the workgroup size is the compile-time TT, never more; four waves per SIMD keep the
 // 128-VGPR budget that lets a 1024-thread workgroup (and four 256-thread ones) share a CU.
-template <int C, int GRID, int OUT, int TT, bool IMEX>
+//
+// PHI_DERIVED (four cells per thread, the reference's step, OUT_STATE): phi is neither loaded nor stored.  After any step
+// phi is concentration(Ei, h) of the stored Ei and h (ebm_miz_pieces.h), so phase A loads Ei instead and forms it, and
+// phase D stores four fields instead of five: a fifth of the store traffic of a launch.  The phi field in HBM goes stale;
+// the runtime launches this variant only on a state that step kernels wrote last and restores the field before anybody
+// else reads it (ebm_ctx::phi_stored).
+template <int C, int GRID, int OUT, int TT, bool IMEX, bool PHI_DERIVED = false>
 __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     static_assert(C == 2 || C == 4, "cells per thread");
+    static_assert(!PHI_DERIVED || (C == 4 && !IMEX && OUT == OUT_STATE), "phi is derived by the state-only kernel of the reference's step");
     static_assert(OUT == OUT_STATE || OUT == OUT_DIAG || OUT == OUT_SAVE, "per-step kernel");
     constexpr bool MAYDIAG = OUT != OUT_STATE;            // diagnostic stores compiled in
     extern __shared__ double smem[];
@@ -80,8 +87,17 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         if (it == 0) {
             double Ew[C], hk[C], xk[C], r[C];
             load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
-            load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
-            load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+            if constexpr (PHI_DERIVED) {
+                // (Ei is not kept: phase D loads its pairs again, as it always has)
+                double Ei[C];
+                load_state<C, TT>(st + S_Ei * a.fstride, kl, Ei);
+                load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+#pragma unroll
+                for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);
+            } else {
+                load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
+                load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+            }
             load_chunk<C>(gX, kl, xk);
             // Padding cells (k >= nlat) need no special case in phases A and B: their state and table
             // entries are zero, so their rows are decoupled (lo = up = 0, g = phi = 0) and finite.
@@ -236,15 +252,18 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
                 // finished with and is never read.
                 // (hipcc waits vmcnt(0) at the first use of any earlier load's result while an LDS-DMA is
                 // in flight: retire the one load not consumed yet before issuing it)
-                asm volatile("" ::"v"(xr), "v"(o[q].q[Q_Ei]), "v"(o[q].q[Q_Ew]), "v"(o[q].q[Q_h]), "v"(o[q].q[Q_D]),
-                             "v"(o[q].q[Q_phi]));
+                if constexpr (PHI_DERIVED)      // (the new phi is not formed at all)
+                    asm volatile("" ::"v"(xr), "v"(o[q].q[Q_Ei]), "v"(o[q].q[Q_Ew]), "v"(o[q].q[Q_h]), "v"(o[q].q[Q_D]));
+                else
+                    asm volatile("" ::"v"(xr), "v"(o[q].q[Q_Ei]), "v"(o[q].q[Q_Ew]), "v"(o[q].q[Q_h]), "v"(o[q].q[Q_D]),
+                                 "v"(o[q].q[Q_phi]));
                 __builtin_amdgcn_sched_barrier(0);
                 if (a.prefetch > 0 && col + a.prefetch < a.ncol) {
                     const double *nxt = a.state + (size_t)(col + a.prefetch) * (size_t)a.pitch +
                                         ((unsigned)(t >> 6) * 256u + (unsigned)(t & 63) * 4u);
                     auto *sink = (__attribute__((address_space(3))) void *)(smem + 6 * T + (C - 2) * T + (t & ~63));
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_Ew * a.fstride), sink, 4, 0, 0);
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_phi * a.fstride), sink, 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + (PHI_DERIVED ? S_Ei : S_phi) * a.fstride), sink, 4, 0, 0);
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_h * a.fstride), sink, 4, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -253,8 +272,9 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         const unsigned kp = k0 + 2 * j;
         const bool v0 = (int)kp < nlat, v1 = (int)kp + 1 < nlat;
+        // (PHI_DERIVED: the phi field is not stored)
 #define EBM_PUT(slot_, qi)                                                                         \
-        {                                                                                          \
+        if constexpr (!PHI_DERIVED || (slot_) != S_phi) {                                          \
             double2 d_;                                                                            \
             d_.x = v0 ? o[0].q[qi] : 0.0;                                                          \
             d_.y = v1 ? o[1].q[qi] : 0.0;                                                          \

@@ -139,6 +139,18 @@ struct ebm_ctx {
     // nothing; n_conversions counts the conversions of a handle (ebm_state_conversions).
     bool state_split = false;
     long long n_conversions = 0;
+    // One more bit of the same rule.  A state-only one-step launch of the reference's step at four cells per thread does not
+    // store phi: after any step phi is concentration(Ei, h) of the stored fields, and the kernel forms it from them
+    // (miz_step_kernel, PHI_DERIVED).
+    //   phi_stored       the phi field in HBM is current.  Cleared by such a launch; false only while state_split.
+    //                    Whoever reads phi otherwise restores it first (restore_phi; convert_state folds it into the
+    //                    un-split pass): a restore with the bit set does nothing, a steady run of launches restores nothing.
+    //   phi_consistent   Ei, h and phi were last written by step kernels of this library, so phi IS that function of Ei and
+    //                    h under the column's parameters.  Cleared by every other writer of one of them and by a change of
+    //                    the parameters (state_written_outside); set again by the next step launch over all columns.  Only
+    //                    then may a launch take the deriving kernel; else it steps with the phi the caller left.
+    bool phi_stored = true, phi_consistent = true;
+    bool derive_phi = false;                       // this handle has the deriving kernel (ebm_create: has_phi_derived_kernel)
     // ebm_zonal_diffusion: the tables of the last nlon used, kept between calls
     struct ZonalTables {
         int nlon = 0, seg = 1;                     // seg: segments a circle is cut into (a function of nlon only)
@@ -259,6 +271,12 @@ int ensure_natural(ebm_ctx *h);                   // ebm_fields.hip: un-permute 
 // ebm_fields.hip: THE rule of ebm_ctx::state_split — the prognostic fields into the layout their next user expects
 hipError_t convert_state(ebm_ctx *h, bool split);
 int set_state_layout(ebm_ctx *h, bool split);     // the same, with the error reported (EBM_ERR_HIP)
+// ebm_fields.hip: the phi field current again in whatever layout the state has (ebm_ctx::phi_stored), for readers that take
+// the fields as they lie — a one-step launch that loads phi, resampling, a change of the parameters
+hipError_t restore_phi(ebm_ctx *h);
+// Ei, h or phi are about to be written by somebody who is not a step kernel, or the parameters they are tied by change:
+// phi is restored under the present ones, then the state no longer counts as consistent (ebm_ctx::phi_consistent)
+int state_written_outside(ebm_ctx *h);
 int get_copier(ebm_ctx *h);                       // ebm_fields.hip: the handle's pinned staging ring, created on first use
 
 }  // namespace ebm_rt

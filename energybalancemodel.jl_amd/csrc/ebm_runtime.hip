@@ -170,6 +170,7 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     auto h = std::make_unique<ebm_ctx>();
     h->model = model; h->grid = grid; h->nlat = nlat; h->ncol = ncol; h->device = device;
     h->dt = dt; h->cfg = cfg; h->imex = imex;
+    h->derive_phi = model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex);
     for (int f = 0; f < EBM_F_COUNT; ++f) {
         h->written_epoch[f] = -1;
         h->written_step[f] = -1;

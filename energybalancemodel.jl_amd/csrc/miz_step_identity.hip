@@ -1,4 +1,5 @@
-// miz_step_kernel on the identity grid: every mode and workgroup size, two and four cells per thread.
+// miz_step_kernel on the identity grid: every mode and workgroup size, two and four cells per thread, and the
+// state-only step that derives phi (four cells per thread).
 #include "ebm_kernel_table.h"
 
 namespace ebm {
@@ -6,5 +7,6 @@ namespace ebm {
 KernelFn miz_step_kernels_identity(int cells, int mode, int threads) {
     return cells == 2 ? miz_step_by_mode<2, 0, false>(mode, threads) : miz_step_by_mode<4, 0, false>(mode, threads);
 }
+KernelFn miz_step_phi_derived_identity(int threads) { return miz_step_phi_derived_for<0>(threads); }
 
 }  // namespace ebm

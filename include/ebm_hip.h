@@ -216,7 +216,12 @@ int ebm_zonal_diffusion(ebm_handle_t h, int nlon, const double *temp, double *ou
  * diagnostic, four cells per thread) the view shows the field as of this call: one-launch-per-step steps taken
  * afterwards keep the fields they read and write in a layout private to the library until the next access through
  * this interface (call again after such a step; do not write through the pointer while stepping).  Fails with
- * EBM_ERR_STALE like ebm_get_field. */
+ * EBM_ERR_STALE like ebm_get_field.
+ * The view of a prognostic MIZ field is writable, so the library takes the call as a possible write of the state: the
+ * next step loads the phi field as it then is, instead of deriving it from Ei and h as the state-only one-launch-per-step
+ * kernel otherwise does (the reference's step at four cells per thread), and a graph-replaying
+ * ebm_run takes its first step directly.  Same results; a caller that takes views between steps only to read pays the
+ * slower kernel for one step after each — ebm_get_field_device and ebm_hemispheric_mean_device read without that cost. */
 int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pitch);
 /* Per-column forcing offset added to the per-step scalar forcing (forcing = f + fcol[col];
  * NULL clears it).  This is how ensemble members / longitudes get perturbed forcings — the

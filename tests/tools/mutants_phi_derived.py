@@ -1,0 +1,41 @@
+"""Broken builds of the one-step kernel that derives phi and of its runtime rule, for the mutation check of
+tests/tools/mutants.py, whose list, anchor rule and build this file uses unchanged: the same commands, restricted to the
+mutants below.
+
+    python tests/tools/mutants_phi_derived.py check        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants_phi_derived.py build        (CPU: one full build per mutant under build/)
+    bash   tests/tools/mutants_run.sh                      (GPU box: the -m gpu suite against every build/libebm_mut_*.so)
+
+What tests/test_gpu_phi_derived.py does with each of its 102 cases (profiles/r14_phi_derived_mutants.txt):
+  phi_restore_skipped                   the un-split pass moves the stale phi field instead of forming it: every case that
+                                        reads phi after a derived step fails (73)
+  set_field_h_leaves_the_state_consistent   after set_field("h") (or Ei, phi) the next step derives phi from the new h
+                                        instead of loading the caller's: test_a_callers_field_is_honoured (all 18), test_interleaved_calls (both)
+  derived_kernel_takes_set_0s_Lf        phi of every column formed with the first parameter set's latent heat:
+                                        test_launch_and_parameter_variants[two_Lf] on the three shapes, alone
+  derived_phi_not_capped_in_phase_A     the cap at 1 dropped where the kernel forms phi for itself only (the shared piece,
+                                        and with it every kernel that stores phi, keeps it): every case whose state has
+                                        cells with -Ei / (Lf h) > 1 and derives at least once (76)"""
+import sys
+
+import mutants
+
+mutants.MUTANTS = [
+    ("phi_restore_skipped", "    else if (!h->phi_stored) e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, true, main_stream(h));\n",
+     "", "ebm_fields.hip"),
+    ("set_field_h_leaves_the_state_consistent",
+     "    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;\n    HIPCHK(hipStreamSynchronize(main_stream(h)));\n    HIPCHK(h->copier->wait_all());",
+     "    HIPCHK(hipStreamSynchronize(main_stream(h)));\n    HIPCHK(h->copier->wait_all());", "ebm_fields.hip"),
+    ("derived_kernel_takes_set_0s_Lf", "for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);",
+     "for (int i = 0; i < C; ++i) ph[i] = concentration(*reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p)), Ei[i], hk[i]);"),
+    ("derived_phi_not_capped_in_phase_A", "for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);",
+     "for (int i = 0; i < C; ++i) ph[i] = (hk[i] == 0.0) ? 0.0 : ieee_div(-Ei[i], p.Lf * hk[i]);"),
+]
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["build"]:
+        mutants.build(sys.argv[2:])
+    elif sys.argv[1:2] == ["check"]:
+        sys.exit(mutants.check())
+    else:
+        print("\n".join(m[0] for m in mutants.MUTANTS))
