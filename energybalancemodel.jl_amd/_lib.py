@@ -29,7 +29,8 @@ EXPORTS = (
     "ebm_set_column_params", "ebm_set_column_noise", "ebm_get_noise_state", "ebm_set_noise_state", "ebm_noise_innovations",
     "ebm_set_step_clock", "ebm_set_time_table",
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
-    "ebm_equilibrate", "ebm_run_until", "ebm_resample_columns", "ebm_sync", "ebm_get_counters",
+    "ebm_equilibrate", "ebm_run_until", "ebm_resample_columns", "ebm_column_record", "ebm_export_columns",
+    "ebm_import_columns", "ebm_sync", "ebm_get_counters",
     "ebm_reset_counters", "ebm_state_conversions", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
     "ebm_selftest_divide", "ebm_selftest_permute",
 )
@@ -117,6 +118,9 @@ def load():
     lib.ebm_run_until.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
     lib.ebm_resample_columns.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.ebm_column_record.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_uint)]
+    lib.ebm_export_columns.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_uint)]
+    lib.ebm_import_columns.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_uint]
     lib.ebm_sync.argtypes = [C.c_void_p]
     lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_reset_counters.argtypes = [C.c_void_p]

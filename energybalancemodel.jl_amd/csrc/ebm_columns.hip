@@ -1,6 +1,9 @@
 // Host runtime, per-column inputs (ebm_runtime.h lists the units): forcing offsets, Forcing schedules, AR(1) noise and
-// parameter sets, each installed all-or-nothing; the step clock and the time table; the resampling of whole columns.
+// parameter sets, each installed all-or-nothing; the step clock and the time table; the resampling of whole columns and
+// their packed export and import.
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <map>
 
 #include "ebm_runtime.h"
@@ -244,6 +247,165 @@ int ebm_resample_columns(ebm_handle_t h, const int *parent) {
     }
     // the diffusion operators expect their scratch zero in the padding cells
     if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));
+    return EBM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The record of ebm_export_columns / ebm_import_columns (include/ebm_hip.h): a function of the model, nlat and
+// cells_per_thread only.  `current` is the mask an export would return now.
+struct RecordShape {
+    int field[ebm::kExchangeSlots];                      // slot -> public field id, in enum order
+    int nfields = 0, rowlen = 0, amask_units = 0;
+    long long doubles = 0;
+    unsigned prognostic = 0, all = 0, current = 0;
+};
+RecordShape record_shape(const ebm_ctx *h) {
+    RecordShape r;
+    for (int f = 0; f < EBM_F_COUNT; ++f) {
+        if (!has_field(h, f)) continue;
+        r.field[r.nfields++] = f;
+        r.all |= 1u << f;
+        if (!is_diagnostic(h, f)) r.prognostic |= 1u << f;
+        if (!is_diagnostic(h, f) || h->written_epoch[f] == h->epoch) r.current |= 1u << f;
+    }
+    r.rowlen = (h->nlat + 15) / 16 * 16;                 // whole 128-byte lines; <= pitch (a multiple of 128 cells)
+    r.amask_units = h->amask ? h->cfg.threads / 8 : 0;   // a row of `threads` unsigned shorts
+    r.doubles = (long long)r.nfields * r.rowlen + 2 * r.amask_units + 2;
+    return r;
+}
+
+// the launch arguments of either direction: the rows of the slots in `moved`, each in the layout the handle holds it in
+ebm::ExchangeArgs exchange_args(ebm_ctx *h, const RecordShape &r, unsigned moved, double *buf) {
+    ebm::ExchangeArgs a{};
+    for (int s = 0; s < r.nfields; ++s) {
+        const int f = r.field[s];
+        if (!(moved >> f & 1u)) continue;
+        a.row[s] = h->field[f];
+        if ((is_split_state_field(h, f) && h->state_split) || (is_split_field(h, f) && h->diag_split)) a.split_mask |= 1u << s;
+    }
+    a.buf = buf;
+    a.record = r.doubles;
+    a.amask = h->amask.get();
+    a.nstate = h->noise.state.get();
+    a.nfields = r.nfields;
+    a.rowlen = r.rowlen;
+    a.pitch = (int)h->pitch;
+    a.threads = h->cfg.threads;
+    a.amask_units = r.amask_units;
+    return a;
+}
+
+// the argument checks the two calls share; the message names the first offending entry
+int check_exchange_args(const ebm_ctx *h, const char *who, int n, const int *cols, const void *dev_buf) {
+    if (n < 0) return fail(EBM_ERR_ARG, std::string(who) + ": n = " + std::to_string(n) + " is negative");
+    if (n == 0) return EBM_OK;
+    if (!cols) return fail(EBM_ERR_ARG, std::string(who) + ": cols is null");
+    if (!dev_buf) return fail(EBM_ERR_ARG, std::string(who) + ": dev_buf is null");
+    if (reinterpret_cast<uintptr_t>(dev_buf) % 16) return fail(EBM_ERR_ARG, std::string(who) + ": dev_buf is not 16-byte aligned");
+    for (int i = 0; i < n; ++i)
+        if (cols[i] < 0 || cols[i] >= h->ncol)
+            return fail(EBM_ERR_ARG, std::string(who) + ": cols[" + std::to_string(i) + "] = " + std::to_string(cols[i]) +
+                                         " is outside [0, " + std::to_string(h->ncol) + ")");
+    return EBM_OK;
+}
+
+// cols, then records if given, through the pinned list of ebm_ctx::Resample to the device, on stream s: the device list
+// (n or 2n ints) is ready for the launch that follows on s, and the host arrays have been consumed on return
+int upload_exchange_list(ebm_ctx *h, int n, const int *cols, const int *records, hipStream_t s) {
+    ebm_ctx::Resample &r = h->resample;
+    if (!r.uploaded) HIPCHK(hipEventCreateWithFlags(r.uploaded.out(), hipEventDisableTiming));
+    if (r.in_flight) HIPCHK(hipEventSynchronize(r.uploaded.get()));      // the previous call's upload has read the pinned list
+    r.in_flight = false;
+    if (r.host_cap < (size_t)n) {
+        r.host_cap = 0;
+        HIPCHK(hipHostMalloc(r.host.out(), sizeof(int) * 2 * (size_t)n, hipHostMallocDefault));
+        r.host_cap = (size_t)n;
+    }
+    HIPCHK(r.dev.reserve(2 * (size_t)n));
+    int *list = r.host.get();
+    std::copy(cols, cols + n, list);
+    if (records) std::copy(records, records + n, list + n);
+    HIPCHK(hipMemcpyAsync(r.dev.get(), list, sizeof(int) * (size_t)n * (records ? 2 : 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(r.uploaded.get(), s));
+    r.in_flight = true;
+    return EBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ebm_column_record(ebm_handle_t h, long long *record_doubles, unsigned *current_mask) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_column_record: null handle");
+    const RecordShape r = record_shape(h);
+    if (record_doubles) *record_doubles = r.doubles;
+    if (current_mask) *current_mask = r.current;
+    return EBM_OK;
+}
+
+int ebm_export_columns(ebm_handle_t h, int n, const int *cols, double *dev_buf, unsigned *mask) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_export_columns: null handle");
+    if (int rc = check_exchange_args(h, "ebm_export_columns", n, cols, dev_buf)) return rc;
+    const RecordShape r = record_shape(h);
+    if (mask) *mask = r.current;
+    if (n == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    // phi travels as a field: current first.  The state stays consistent — nothing is written
+    hipError_t e = restore_phi(h);
+    if (e != hipSuccess) return hip_fail("phi restore", e);
+    hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
+    if (int rc = upload_exchange_list(h, n, cols, nullptr, s)) return rc;
+    ebm::ExchangeArgs a = exchange_args(h, r, r.current, dev_buf);
+    a.cols = h->resample.dev.get();
+    e = ebm::launch_export_columns(a, n, s);
+    if (e != hipSuccess) return hip_fail("ebm_export_columns", e);
+    return EBM_OK;
+}
+
+int ebm_import_columns(ebm_handle_t h, int n, const int *cols, const int *records, const double *dev_buf, unsigned mask) {
+    if (!h) return fail(EBM_ERR_ARG, "ebm_import_columns: null handle");
+    if (int rc = check_exchange_args(h, "ebm_import_columns", n, cols, dev_buf)) return rc;
+    const RecordShape r = record_shape(h);
+    if (n > 0) {
+        std::vector<char> seen((size_t)h->ncol, 0);
+        for (int i = 0; i < n; ++i) {
+            if (seen[cols[i]])
+                return fail(EBM_ERR_ARG, "ebm_import_columns: cols[" + std::to_string(i) + "] = " + std::to_string(cols[i]) +
+                                             " is a repeated destination");
+            seen[cols[i]] = 1;
+        }
+        for (int i = 0; records && i < n; ++i)
+            if (records[i] < 0)
+                return fail(EBM_ERR_ARG, "ebm_import_columns: records[" + std::to_string(i) + "] = " + std::to_string(records[i]) +
+                                             " is negative");
+    }
+    for (int f = 0; f < 32; ++f) {
+        if ((mask >> f & 1u) && !(r.all >> f & 1u))
+            return fail(EBM_ERR_ARG, "ebm_import_columns: mask names field " + std::to_string(f) + ", which this model does not have");
+        if ((r.prognostic >> f & 1u) && !(mask >> f & 1u))
+            return fail(EBM_ERR_ARG, std::string("ebm_import_columns: mask lacks the prognostic field ") + field_name(f));
+    }
+    // a field that is current here and absent from the records would keep its old rows under another member's prognostics
+    for (int s = 0; s < r.nfields; ++s)
+        if ((r.current & ~mask) >> r.field[s] & 1u)
+            return fail(EBM_ERR_STALE, std::string("ebm_import_columns: field ") + field_name(r.field[s]) +
+                                           " is current in this handle but was stale in the exporter (absent from mask): the "
+                                           "imported columns would hold it under another member's state");
+    if (n == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    // Ei, h and phi are written by a non-step writer: phi current first, and the next launch loads it
+    if (int rc = state_written_outside(h)) return rc;
+    hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
+    if (int rc = upload_exchange_list(h, n, cols, records, s)) return rc;
+    // whatever is current here is in the mask; a slot whose field is stale here is ignored, and the field stays stale
+    ebm::ExchangeArgs a = exchange_args(h, r, r.current, const_cast<double *>(dev_buf));
+    a.cols = h->resample.dev.get();
+    a.records = records ? h->resample.dev.get() + n : nullptr;
+    hipError_t e = ebm::launch_import_columns(a, n, s);
+    if (e != hipSuccess) return hip_fail("ebm_import_columns", e);
     return EBM_OK;
 }
 

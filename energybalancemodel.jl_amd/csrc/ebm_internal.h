@@ -213,5 +213,23 @@ struct ResampleArgs {
 };
 hipError_t launch_resample_stage(const ResampleArgs &r, int moved, hipStream_t s);
 hipError_t launch_resample_scatter(const ResampleArgs &r, int moved, hipStream_t s);
+// ebm_export_columns / ebm_import_columns (ebm_exchange.hip), one workgroup per (list entry i < n, slot): export copies the
+// rows of column cols[i] to record i of `buf`, import the rows of record records[i] (null: i) to column cols[i].  A record is
+// `record` doubles: nfields field slots of rowlen doubles in the natural layout, the active-set row, N_c and one reserved
+// double.  row[s] null: slot s does not move; bit s of split_mask: the handle holds the rows of slot s pair-split.
+constexpr int kExchangeSlots = 11;   // fields of the largest model (MIZ: Ei .. T)
+struct ExchangeArgs {
+    double *row[kExchangeSlots];     // the field of slot s, [ncol][pitch], or null
+    unsigned split_mask;
+    const int *cols;                 // [n], all < ncol
+    const int *records;              // [n] or null (import only)
+    double *buf;                     // 16-byte aligned
+    long long record;                // doubles per record (even)
+    unsigned short *amask;           // [ncol][threads] or null (then amask_units = 0)
+    double *nstate;                  // N_c [ncol] or null: export writes 0.0, import leaves the tail unread
+    int nfields, rowlen, pitch, threads, amask_units;
+};
+hipError_t launch_export_columns(const ExchangeArgs &a, int n, hipStream_t s);
+hipError_t launch_import_columns(const ExchangeArgs &a, int n, hipStream_t s);
 
 }  // namespace ebm

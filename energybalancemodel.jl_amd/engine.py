@@ -500,6 +500,69 @@ class Engine:
         p = self.check_resample_args(parents)
         check(self.lib.ebm_resample_columns(self._h, p.ctypes.data_as(C.POINTER(C.c_int))), "ebm_resample_columns")
 
+    def column_record(self):
+        """ebm_column_record: ``(record_doubles, mask)`` — the doubles of one exported column (a function of the model, nlat
+        and cells_per_thread only) and the mask an export would return now (bit f: field f is current)."""
+        n, m = C.c_longlong(), C.c_uint()
+        check(self.lib.ebm_column_record(self._h, C.byref(n), C.byref(m)), "ebm_column_record")
+        return int(n.value), int(m.value)
+
+    def check_exchange_args(self, cols, ptr, records=None, mask=None, distinct=False):
+        """The host-side checks of ``export_columns`` / ``import_columns`` (no device call): returns the columns, and the
+        record indices if given, as contiguous int32 arrays."""
+        c = np.asarray(cols)
+        if c.size == 0:
+            c = c.astype(np.int32)
+        if c.dtype.kind not in "iu" or c.ndim != 1:
+            raise ValueError(f"cols: expected a vector of integers (column indices), got dtype {c.dtype}, shape {c.shape}")
+        bad = np.flatnonzero((c < 0) | (c >= self.ncol))
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError(f"cols[{i}] = {int(c[i])} is outside [0, {self.ncol})")
+        if distinct and np.unique(c).size != c.size:
+            raise ValueError("cols: a destination column is named twice")
+        if not isinstance(ptr, (int, np.integer)) or isinstance(ptr, (bool, np.bool_)):
+            raise ValueError(f"ptr: expected a device address (int), got {type(ptr).__name__}")
+        if c.size and (int(ptr) == 0 or int(ptr) % 16):
+            raise ValueError(f"ptr = {int(ptr):#x}: expected a 16-byte aligned device address")
+        r = None
+        if records is not None:
+            r = np.asarray(records)
+            if r.size == 0:
+                r = r.astype(np.int32)
+            if r.dtype.kind not in "iu" or r.shape != c.shape:
+                raise ValueError(f"records: expected {c.size} integers, one per column, got dtype {r.dtype}, shape {r.shape}")
+            bad = np.flatnonzero(r < 0)
+            if bad.size:
+                raise ValueError(f"records[{int(bad[0])}] = {int(r[bad[0]])} is negative")
+            r = np.ascontiguousarray(r, dtype=np.int32)
+        if mask is not None and (isinstance(mask, (bool, np.bool_)) or not isinstance(mask, (int, np.integer))
+                                 or not 0 <= int(mask) < 1 << len(FIELD)):
+            raise ValueError(f"mask = {mask!r}: expected the integer an export returned (bit f: field f travels)")
+        return np.ascontiguousarray(c, dtype=np.int32), r
+
+    def export_columns(self, cols, ptr):
+        """ebm_export_columns: the state of column ``cols[i]`` into record i of the device buffer at address ``ptr``
+        (``len(cols) * column_record()[0]`` doubles, 16-byte aligned) — every field in the natural layout, the warm start,
+        N_c.  Returns the mask (bit f: the slot of field f was written).  Changes nothing in the handle.  Asynchronous."""
+        c, _ = self.check_exchange_args(cols, ptr)
+        m = C.c_uint()
+        check(self.lib.ebm_export_columns(self._h, len(c), c.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(int(ptr)), C.byref(m)),
+              "ebm_export_columns")
+        return int(m.value)
+
+    def import_columns(self, cols, ptr, mask, records=None):
+        """ebm_import_columns: column ``cols[i]`` (distinct) takes record ``records[i]`` (default i) of the device buffer
+        at ``ptr``, in the layout this handle holds; it keeps its own forcing offset, schedule, parameter row and noise
+        stream.  ``mask`` is the exporter's.  StaleFieldError if a field that is current here is absent from it.  The
+        buffer must be complete before the call and untouched until ``sync``.  Asynchronous."""
+        if mask is None:
+            raise ValueError("mask: expected the integer the export returned")
+        c, r = self.check_exchange_args(cols, ptr, records, mask, distinct=True)
+        ip = C.POINTER(C.c_int)
+        check(self.lib.ebm_import_columns(self._h, len(c), c.ctypes.data_as(ip), None if r is None else r.ctypes.data_as(ip),
+                                          C.c_void_p(int(ptr)), int(mask)), "ebm_import_columns")
+
     def sync(self):
         check(self.lib.ebm_sync(self._h), "ebm_sync")
 

@@ -165,7 +165,131 @@ def gklt_estimate(observable, score_sum, k, log_norm=0.0) -> dict:
                 ess=float(total * total / np.sum(u * u)))
 
 
-class EnsembleRun:
+# ---- selection across shards -------------------------------------------------------------------------------------------------
+# EnsembleRun.resample is rank-local.  With the ensemble sharded by shard_columns, a parent may live on another rank: the plan
+# below splits one global parents vector into, per rank, a rank-local gather and the whole columns that cross ranks, which
+# travel as records of ebm_export_columns / ebm_import_columns.  Pure NumPy.
+
+class ResamplePlan:
+    """Rank ``rank``'s part of one global selection (``resample_plan``).  With n_r the rank's columns:
+    ``send[q]``: the sorted distinct LOCAL columns of this rank that some column of rank q names as parent (empty for q ==
+    rank); ``local`` [n_r] int32: the parents within the shard, ``local[c] = c`` for a column fed from another rank;
+    ``recv_cols`` / ``recv_src`` / ``recv_idx``: for every remotely fed local column its index, its source rank and its index
+    into that rank's send list to this rank; ``recv_counts[q]``: the length of rank q's send list to this rank.  The records a
+    rank receives are those send lists concatenated in rank order, so column recv_cols[i] takes record
+    ``recv_records[i] = sum(recv_counts[:recv_src[i]]) + recv_idx[i]``."""
+
+    def __init__(self, rank, ncol, send, local, recv_cols, recv_src, recv_idx, recv_counts):
+        self.rank, self.ncol, self.send, self.local = rank, ncol, send, local
+        self.recv_cols, self.recv_src, self.recv_idx, self.recv_counts = recv_cols, recv_src, recv_idx, recv_counts
+        self.send_counts = np.array([len(s) for s in send], dtype=np.int64)
+        self.send_cols = np.concatenate(send).astype(np.int32) if send else np.zeros(0, np.int32)
+        offsets = np.concatenate([[0], np.cumsum(recv_counts)[:-1]]).astype(np.int64)
+        self.recv_records = (offsets[recv_src] + recv_idx).astype(np.int32)
+
+
+def resample_plan(parents_global, ncol_total: int, world_size: int) -> list:
+    """The plans of all ranks, ``[ResamplePlan] * world_size``, for the selection "member c continues from member
+    ``parents_global[c]``" over an ensemble of ``ncol_total`` members sharded by ``shard_columns``.  Carried out as: every
+    rank exports ``send`` (old state), then gathers ``local`` within its shard, then imports what it received — the result
+    is the unsharded ``resample(parents_global)``.  Empty shards (``ncol_total < world_size``) are legal.  Host only; ValueError
+    for a wrong length, an out-of-range parent or a non-integer dtype."""
+    ncol_total, world_size = int(ncol_total), int(world_size)
+    if ncol_total < 1 or world_size < 1:
+        raise ValueError(f"resample_plan: need ncol_total >= 1 and world_size >= 1, got {ncol_total} and {world_size}")
+    p = np.asarray(parents_global)
+    if p.dtype.kind not in "iu":
+        raise ValueError(f"parents_global: expected {ncol_total} integers (member indices), got dtype {p.dtype}")
+    if p.shape != (ncol_total,):
+        raise ValueError(f"parents_global: expected {ncol_total} integers, one per member, got shape {p.shape}")
+    bad = np.flatnonzero((p < 0) | (p >= ncol_total))
+    if bad.size:
+        raise ValueError(f"parents_global[{int(bad[0])}] = {int(p[bad[0]])} is outside [0, {ncol_total})")
+    p = p.astype(np.int64)
+    shards = [shard_columns(ncol_total, world_size, r) for r in range(world_size)]
+    starts = np.array([s.start for s in shards] + [ncol_total])
+    owner = np.searchsorted(starts, np.arange(ncol_total), side="right") - 1      # (an empty shard owns nobody)
+    # send[r][q]: the parents on r that the columns of q name, as local columns of r
+    send = [[np.zeros(0, np.int32) for _ in range(world_size)] for _ in range(world_size)]
+    for q in range(world_size):
+        mine = p[shards[q]]
+        src = owner[mine]
+        for r in np.unique(src):
+            if r != q:
+                send[r][q] = (np.unique(mine[src == r]) - shards[r].start).astype(np.int32)
+    plans = []
+    for r in range(world_size):
+        n = shards[r].stop - shards[r].start
+        mine = p[shards[r]]
+        src = owner[mine]
+        remote = np.flatnonzero(src != r)
+        local = np.where(src == r, mine - shards[r].start, np.arange(n)).astype(np.int32)
+        idx = np.array([np.searchsorted(send[src[c]][r], mine[c] - shards[src[c]].start) for c in remote], dtype=np.int32)
+        counts = np.array([len(send[q][r]) for q in range(world_size)], dtype=np.int64)
+        plans.append(ResamplePlan(r, n, send[r], local, remote.astype(np.int32), src[remote].astype(np.int32), idx, counts))
+    return plans
+
+
+class ColumnExchange:
+    """The sharded selection in terms of three methods of the class it is mixed into: ``export_tensor(cols) -> (records
+    [n, R], mask)``, ``import_tensor(cols, records, mask, records_index)`` and ``resample(parents)``.  EnsembleRun is one."""
+
+    def resample_export(self, plan):
+        """First half of a sharded selection: the records of all of ``plan``'s send lists, concatenated in rank order, in
+        one tensor, and their mask.  EVERY rank exports before ANY rank imports: remote parents are read in their old state."""
+        return self.export_tensor(plan.send_cols)
+
+    def resample_import(self, plan, received, mask):
+        """Second half: the rank-local ``resample(plan.local)``, then the import of ``received`` — the send lists of all
+        ranks to this one, concatenated in rank order — into the remotely fed columns."""
+        self.resample(plan.local)
+        if len(plan.recv_cols):
+            self.import_tensor(plan.recv_cols, received, mask, plan.recv_records)
+
+    def resample_global(self, parents_global, ncol_total, dist=None):
+        """``resample`` over the whole sharded ensemble: member c (global index) continues from member
+        ``parents_global[c]``, on whichever rank it lives — export, exchange, import, in that order; the result is the
+        unsharded ``resample(parents_global)`` bit for bit.  Every rank passes the same ``parents_global``.  One small
+        ``all_gather`` checks that all ranks hold the same mask and record size.  With the "nccl" backend (RCCL) the
+        exchange is one ``all_to_all_single`` with the plan's split sizes and the payload stays on the device; with any
+        other backend (gloo has no all-to-all) the records go through the host by ``isend`` / ``irecv``.  With ``dist``
+        absent or a world of one it is ``resample``."""
+        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+            return self.resample(parents_global)
+        import torch
+        ws, rank = dist.get_world_size(), dist.get_rank()
+        plan = resample_plan(parents_global, ncol_total, ws)[rank]
+        buf, mask = self.resample_export(plan)
+        nccl = _backend(dist) == "nccl"
+        mine = torch.tensor([buf.shape[1], mask], dtype=torch.int64, device=buf.device if nccl else "cpu")
+        every = [torch.empty_like(mine) for _ in range(ws)]
+        dist.all_gather(every, mine)
+        for q, t in enumerate(every):
+            if t.tolist() != mine.tolist():
+                raise RuntimeError(f"resample_global: rank {q} exports records of {int(t[0])} doubles with mask {int(t[1]):#x}, "
+                                   f"rank {rank} of {int(mine[0])} with mask {int(mine[1]):#x} (every rank must hold the same "
+                                   "model and shape, and the same fields current)")
+        n_in, n_out = [int(v) for v in plan.send_counts], [int(v) for v in plan.recv_counts]
+        if nccl:
+            received = torch.empty((sum(n_out), buf.shape[1]), dtype=buf.dtype, device=buf.device)
+            dist.all_to_all_single(received, buf.contiguous(), n_out, n_in)
+        else:
+            host = buf.cpu().contiguous()
+            got = torch.empty((sum(n_out), buf.shape[1]), dtype=buf.dtype)
+            work, a, b = [], 0, 0
+            for q in range(ws):
+                if n_out[q]:
+                    work.append(dist.irecv(got[b:b + n_out[q]], src=q))
+                if n_in[q]:
+                    work.append(dist.isend(host[a:a + n_in[q]], dst=q))
+                a, b = a + n_in[q], b + n_out[q]
+            for w in work:
+                w.wait()
+            received = got.to(buf.device)
+        self.resample_import(plan, received, mask)
+
+
+class EnsembleRun(ColumnExchange):
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
     ``init`` maps prognostic names to [ncol, nlat] arrays (or [nlat], broadcast to all
@@ -302,9 +426,46 @@ class EnsembleRun:
         and keeps its own forcing offset, schedule, parameter row and noise stream, so it draws its own noise from the
         next step on.  ``parents``: [ncol] integer indices WITHIN THIS SHARD (``selection_parents`` makes them from
         weights).  ``step_index`` is unchanged; no field becomes stale.  The call is rank-local: a parent on another
-        rank's shard cannot be named — selecting across ranks needs a packed device export / import of whole columns as
-        an RCCL payload, which this library does not have yet."""
+        rank's shard cannot be named here — ``resample_global`` selects across ranks, by the packed device export and
+        import of whole columns (``export_tensor`` / ``import_tensor``: ebm_export_columns / ebm_import_columns) as the
+        payload of an all-to-all between the shards."""
         self.engine.resample_columns(parents)
+
+    def export_tensor(self, cols):
+        """The state of the members ``cols`` of this shard (indices may repeat) as ``(records, mask)``: a float64 device
+        tensor [len(cols), R], record i the packed state of member cols[i] (ebm_export_columns: every field in the natural
+        layout, the warm start, N_c), and the mask of the fields that travel.  Nothing in the run changes.  The handle is
+        synchronised before the tensor is returned: it is complete and any stream may read it."""
+        import torch
+        c, _ = self.engine.check_exchange_args(cols, 16)
+        R, _ = self.engine.column_record()
+        out = torch.empty((len(c), R), dtype=torch.float64, device=torch.device("cuda", self.device))
+        mask = self.engine.export_columns(c, out.data_ptr() if len(c) else 0)
+        self.engine.sync()
+        return out, mask
+
+    def import_tensor(self, cols, tensor, mask, records=None):
+        """Member ``cols[i]`` of this shard (distinct) continues from record ``records[i]`` (default i) of ``tensor``, a
+        float64 tensor [m, R] on this run's device as ``export_tensor`` of a run of the same model and shape returns it,
+        with that export's ``mask`` (ebm_import_columns).  The member keeps its own settings and noise stream;
+        ``step_index`` is unchanged.  torch's current stream is synchronised before the call (whatever filled the tensor has
+        ended) and the handle after it (the tensor may be reused)."""
+        import torch
+        R, _ = self.engine.column_record()
+        if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float64 or tensor.dim() != 2 or tensor.shape[1] != R:
+            raise ValueError(f"tensor: expected a float64 tensor [m, {R}], got {getattr(tensor, 'dtype', type(tensor).__name__)} "
+                             f"{tuple(getattr(tensor, 'shape', ()))}")
+        if tensor.device != torch.device("cuda", self.device) or not tensor.is_contiguous():
+            raise ValueError(f"tensor: expected a contiguous tensor on cuda:{self.device}, got one on {tensor.device}")
+        c, r = self.engine.check_exchange_args(cols, 16, records, mask, distinct=True)
+        top = int(r.max()) + 1 if r is not None and len(r) else (len(c) if r is None else 0)
+        if top > tensor.shape[0]:
+            raise ValueError(f"tensor holds {tensor.shape[0]} records, but record {top - 1} is asked for")
+        if len(c) == 0:
+            return
+        torch.cuda.current_stream(self.device).synchronize()
+        self.engine.import_columns(c, tensor.data_ptr(), mask, r)
+        self.engine.sync()
 
     def seasonal_means(self, years, names=("T", "phi"), forcing=None):
         """Integrate ``years`` whole years from the current state and return, per column, the

@@ -491,6 +491,58 @@ int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int eve
  * ebm_diffusion is used instead where the handle has it) and the list, 2 ints per moved column; kept by the handle. */
 int ebm_resample_columns(ebm_handle_t h, const int *parent);
 
+/* EXPORT and IMPORT whole columns on the device: the state of a list of columns into one contiguous device buffer of
+ * records and back — between two handles without the host, and as the payload of an all-to-all (RCCL) between the shards
+ * of an ensemble, which makes the selection above possible across ranks.  THIS TEXT IS THE DEFINITION.
+ *   The record.  One exported column is R doubles (ebm_column_record), a function of the model, nlat and cells_per_thread
+ *     only — not of which fields are current, of the layout the handle holds, or of whether noise is installed.  With
+ *     rowlen = nlat rounded up to a multiple of 16 doubles (whole 128-byte lines; rowlen <= pitch always), in this order:
+ *       one slot of rowlen doubles per field the model has, in enum ebm_field order (MIZ and MIZ_IMEX: 11 slots, Ei ... T
+ *         with T0 among them; classic: h, E, T, Tg);
+ *       the warm-start active-set row as it lies in memory: `threads` unsigned shorts = threads/4 doubles (classic: none,
+ *         zero length);
+ *       a 16-byte tail: N_c (0.0 when no noise is installed), then one reserved double written as 0.0.
+ *     Field slots are in the NATURAL layout: cell k of the column is double k of its slot, whatever layout the handle
+ *     holds the row in (the layout private to the one-step MIZ kernel is un-permuted on the way out and permuted on the
+ *     way in).  Cells between nlat and rowlen travel as the row holds them; no stepping entry point reads them.  The record
+ *     is a transport format between handles of the same model, nlat and cells_per_thread.  It is not a file format.
+ *   mask.  Bit f (enum ebm_field) is set when the slot of field f holds field f.  Export always sets the prognostic bits,
+ *     and the bit of a diagnostic field, and of the fp64 T0, exactly when that field is current at the call — the rule by
+ *     which ebm_resample_columns decides what moves.  Slots of fields that are not current are not written.  The mask
+ *     travels on the host: an out-parameter of export, an argument of import.  Nothing in the device buffer is validated,
+ *     so neither call synchronises to check it.  ebm_column_record returns R and the mask an export would return now.
+ *   Export.  Record i of dev_buf (n * R doubles) is the state of column cols[i]; cols may repeat.  phi is made current
+ *     first, as resampling does.  Nothing in the handle changes: no conversion, no validity change, no counter.
+ *   Import.  Column cols[i] takes record records[i] of dev_buf; records == NULL means records[i] = i.  One record may seed
+ *     many columns (the clones of one parent: the payload holds the distinct parents only).  cols must be distinct.  Written,
+ *     all in the layout the handle holds at the call, ebm_state_conversions unchanged: the prognostic fields; the active-set
+ *     row; N_c if noise is installed on the destination; every diagnostic field, and T0, that is current in the destination
+ *     and present in mask.  A slot whose field is stale in the destination is ignored: the field stays stale, with the same
+ *     steps in its message.  A field that is current in the destination but absent from mask refuses the call with
+ *     EBM_ERR_STALE and nothing is written (the column would hold another member's prognostics under its own old
+ *     diagnostics, flagged current).  Like resampling, import writes Ei, h and phi without a step: the next launch loads
+ *     phi, which is not derived under the destination's parameters.  What stays with the slot: fcol, the schedule row, the
+ *     parameter set, the noise record.  The step clock, counters[0..3] and ebm_field_step are unchanged.  From the next step
+ *     on the column steps as a one-column handle with its settings, loaded with the source's state, T0, noise state and
+ *     clock, would: bit for bit, in every stepping entry point.
+ *   Ordering.  Both calls are asynchronous on the handle's stream, the two launch chains joined first.  An export followed
+ *     by an import on the same handle through one buffer is ordered by the stream: for cols = the moved columns c and the
+ *     records of parent[c] the pair IS ebm_resample_columns(parent), all reads before all writes.  Across handles or streams
+ *     the caller orders the work: ebm_sync of the exporter before anyone else reads the buffer; the buffer complete before
+ *     import is called; the buffer untouched until the importer's ebm_sync.  cols and records have been consumed when the
+ *     call returns.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle, n < 0, NULL cols or dev_buf with n > 0, a dev_buf
+ * that is not 16-byte aligned, a column outside [0, ncol), a repeated destination, a record index < 0, a mask without every
+ * prognostic bit or with a bit of a field the model lacks — the message names the first offending entry; EBM_ERR_STALE as
+ * above.  n == 0 launches nothing.
+ * How it runs: ONE launch per call over (entries x slots), one workgroup of 256 lanes per row, the row pointers of all slots
+ * in one argument struct; 16 bytes per lane and access in both layouts (the unit of the permutation is the pair of cells:
+ * natural unit u lies at split unit (u & 1) * threads + (u >> 1)); plain loads and stores.  Device memory: the list, kept by
+ * the handle.  The buffer is the caller's. */
+int ebm_column_record(ebm_handle_t h, long long *record_doubles, unsigned *current_mask);
+int ebm_export_columns(ebm_handle_t h, int n, const int *cols, double *dev_buf, unsigned *mask);
+int ebm_import_columns(ebm_handle_t h, int n, const int *cols, const int *records, const double *dev_buf, unsigned mask);
+
 int ebm_sync(ebm_handle_t h);
 
 /* ---- measurement / diagnostics ------------------------------------------------------- */

@@ -288,4 +288,42 @@ function resample!(h::Handle, parents::Vector{<:Integer})
                          "ebm_resample_columns")
 end
 
+"""
+    column_record(h) -> (record_doubles, mask)
+
+The doubles of one exported column (`ebm_column_record`: a function of the model, `nlat` and `cells_per_thread` only) and
+the mask an export would return now (bit `f`: field `f` is current).
+"""
+function column_record(h::Handle)
+    n, m = Ref{Clonglong}(0), Ref{Cuint}(0)
+    GC.@preserve h check(@ccall(libebm.ebm_column_record(h.ptr::Ptr{Cvoid}, n::Ref{Clonglong}, m::Ref{Cuint})::Cint),
+                         "ebm_column_record")
+    return Int(n[]), m[]
+end
+
+"""
+    export_columns!(h, cols, devbuf) -> mask
+    import_columns!(h, cols, devbuf, mask; records=nothing)
+
+Whole columns (1-based here) into a packed device buffer of records and back (`ebm_export_columns`,
+`ebm_import_columns`): record `i` of `devbuf` — a device pointer to `length(cols) * column_record(h)[1]` doubles, 16-byte
+aligned — is the state of column `cols[i]`, every field in the natural layout, with the warm start and the noise state;
+on import column `cols[i]` (distinct) takes record `records[i]` (default `i`) and keeps its own settings and noise
+stream.  Both are asynchronous on the handle's stream; across handles the caller orders the work (see the header).
+"""
+function export_columns!(h::Handle, cols::Vector{<:Integer}, devbuf::Ptr{Cdouble})
+    m = Ref{Cuint}(0)
+    c = Cint.(cols .- 1)
+    GC.@preserve h check(@ccall(libebm.ebm_export_columns(h.ptr::Ptr{Cvoid}, length(c)::Cint, c::Ptr{Cint}, devbuf::Ptr{Cdouble},
+                                                          m::Ref{Cuint})::Cint), "ebm_export_columns")
+    return m[]
+end
+
+function import_columns!(h::Handle, cols::Vector{<:Integer}, devbuf::Ptr{Cdouble}, mask::Integer; records=nothing)
+    c = Cint.(cols .- 1)
+    r = records === nothing ? Ptr{Cint}(C_NULL) : Cint.(records .- 1)
+    GC.@preserve h check(@ccall(libebm.ebm_import_columns(h.ptr::Ptr{Cvoid}, length(c)::Cint, c::Ptr{Cint}, r::Ptr{Cint},
+                                                          devbuf::Ptr{Cdouble}, Cuint(mask)::Cuint)::Cint), "ebm_import_columns")
+end
+
 end # module EBMHip
