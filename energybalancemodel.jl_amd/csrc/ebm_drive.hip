@@ -209,6 +209,64 @@ int resolve_fields(const ebm_ctx *h, const char *who, int nvars, const int *fiel
     return EBM_OK;
 }
 
+// The active list of ebm_equilibrate and ebm_run_until: the columns that are still stepped, and the rounds that shorten it.
+// A round is: activate, a fused_range over the list, the caller's check kernel — which writes round_of[c] and frozen[c] of
+// every active column c — and, where the caller's rule says the list may have changed, advance.  The list is known to the
+// launches only until the owner goes out of scope, on every path; they end before its buffers are freed (and before those
+// that the caller declared before it).
+struct ActiveRounds {
+    int *cur = nullptr, *nxt = nullptr;      // [ncol] each: this round's list, ascending, and the one advance writes
+    int *round_of = nullptr, *frozen = nullptr;   // [ncol]: the round that last tested the column (0: none); it froze it
+    int *extra = nullptr;                    // [extra_ints_per_column][ncol], the caller's
+    int nactive = 0;
+    ~ActiveRounds() {
+        if (!h) return;
+        (void)hipStreamSynchronize(main_stream(h));
+        h->active = nullptr;
+        h->nactive = 0;
+    }
+    // every column active, none tested or frozen
+    int begin(ebm_ctx *handle, int extra_ints_per_column) {
+        h = handle;
+        const size_t n = (size_t)(nactive = h->ncol);
+        HIPCHK(dev_alloc(ints, (4 + (size_t)extra_ints_per_column) * n + 1));
+        HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
+        cur = ints.get(); nxt = cur + n; round_of = nxt + n; frozen = round_of + n; extra = frozen + n;
+        count = extra + (size_t)extra_ints_per_column * n;
+        std::vector<int> ident(n);
+        for (size_t c = 0; c < n; ++c) ident[c] = (int)c;
+        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(round_of, 0, sizeof(int) * n));
+        HIPCHK(hipMemset(frozen, 0, sizeof(int) * n));
+        return EBM_OK;
+    }
+    // the coming fused_range steps this round's list
+    void activate() const { h->active = cur; h->nactive = nactive; }
+    // The next list: compact_active_kernel drops the frozen columns, the host reads the new length (the round's one stream
+    // synchronisation), and the list just written steps the next round.  Returns the new nactive, or an error (< 0).
+    int advance(const char *who) {
+        hipError_t e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+        if (e != hipSuccess) return hip_fail(std::string(who) + ": active list", e);
+        std::swap(cur, nxt);
+        return nactive = *pinned.get();
+    }
+    // after the last round: round_of and frozen of every column
+    int download(int *round_out, int *frozen_out) const {
+        HIPCHK(hipStreamSynchronize(main_stream(h)));
+        HIPCHK(hipMemcpy(round_out, round_of, sizeof(int) * (size_t)h->ncol, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(frozen_out, frozen, sizeof(int) * (size_t)h->ncol, hipMemcpyDeviceToHost));
+        return EBM_OK;
+    }
+
+private:
+    ebm_ctx *h = nullptr;
+    DevBuf<int> ints;
+    PinnedBuf<int> pinned;
+    int *count = nullptr;
+};
+
 }  // namespace
 
 extern "C" {
@@ -316,7 +374,7 @@ int ebm_run_fused(ebm_handle_t h, long long first_step, int nsteps, const double
 }
 
 // ebm_run_series (include/ebm_hip.h).  Every sample is the stepping of ebm_run_fused over `every` steps — so a launch never
-// spans a sample — followed by one launch of hemispheric_series_kernel on the handle's stream, which writes the sample's
+// spans a sample — followed by one launch of hemispheric_means_kernel on the handle's stream, which writes the sample's
 // slot of the device series.  Nothing is synchronised between samples; the series comes down once, at the end.
 int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
                    int nvars, const int *fields, double *series) {
@@ -328,7 +386,7 @@ int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const doubl
     FieldRef vars[ebm::kMaxQuantities];
     int rc = resolve_fields(h, "ebm_run_series", nvars, fields, vars);
     if (rc) return rc;
-    ebm::SeriesArgs sa{};
+    ebm::MeansArgs sa{};
     int diag = 0;
     for (int v = 0; v < nvars; ++v) {
         if (vars[v].diagnostic) diag = 1;
@@ -354,12 +412,11 @@ int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const doubl
         rc = steps_per_launch == 1 ? ebm_run(h, first, every, f, diag)
                                    : fused_range(h, first, first, every, f, diag, steps_per_launch, nullptr);
         if (rc) return rc;
-        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split
-        if (diag && (rc = ensure_natural(h))) return rc;
-        // ... and the prognostic ones too: the reduction reads the natural layout (two conversions per sample then)
-        if ((rc = set_state_layout(h, false))) return rc;
+        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split, and the
+        // prognostic ones too: the reduction reads the natural layout (two conversions per sample then)
+        if ((rc = natural_layout(h, diag != 0))) return rc;
         sa.out = dev.get() + (size_t)j * (size_t)h->ncol;
-        hipError_t e = ebm::launch_hemispheric_series(sa, h->ncol, main_stream(h));
+        hipError_t e = ebm::launch_hemispheric_means(sa, h->ncol, main_stream(h));
         if (e != hipSuccess) return hip_fail("ebm_run_series: reduction", e);
     }
     HostCopier *c = h->copier.get();
@@ -429,15 +486,21 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
     double *const sums = want_sums ? h->ig_sums.get() : nullptr, *const mean = h->ig_mean.get(), *const snap = h->ig_snap.get();
     double *const hm = h->ig_hm.get();
     double *const stage = (raw && nvars > 0) ? h->ig_stage.get() : nullptr;
-    // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set,
-    // reduced on the device, [nvars][ncol] -> out[v][year][col]
-    auto means_to_host = [&](double *out, long long year, auto field_of) -> hipError_t {
-        for (int v = 0; v < nvars; ++v) {
-            hipError_t e = ebm::launch_hemispheric_mean(field_of(v), x_table(h), (int)h->pitch, h->nlat, h->ncol,
-                                                        hm + (size_t)v * h->ncol, main_stream(h));
-            if (e != hipSuccess) return e;
-        }
-        hipError_t e = hipStreamSynchronize(main_stream(h));
+    // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set — the state fields
+    // through their slots, or the [nvars][ncol*pitch] buffer of annual means — reduced on the device in one launch,
+    // [nvars][ncol] -> out[v][year][col]
+    ebm::MeansArgs of_state{}, of_mean{};
+    of_state.state = h->state.get(); of_state.fstride = h->fstride;
+    of_mean.state = h->ig_mean.get(); of_mean.fstride = (long long)npitch;
+    for (int v = 0; v < nvars; ++v) {
+        of_state.slot[v] = vars[v].slot;
+        of_mean.slot[v] = v;
+    }
+    auto means_to_host = [&](double *out, long long year, ebm::MeansArgs m) -> hipError_t {
+        m.x = x_table(h); m.out = hm; m.var_stride = h->ncol;
+        m.pitch = (int)h->pitch; m.nlat = h->nlat; m.nvars = nvars;
+        hipError_t e = ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
         for (int v = 0; v < nvars && e == hipSuccess; ++v)
             e = hipMemcpy(out + ((size_t)v * dur + (size_t)(year - 1)) * h->ncol, hm + (size_t)v * h->ncol,
                           sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost);
@@ -533,20 +596,19 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
         rc = do_step(h, h->ttab[ti - 1], h->ttab[ti % nt], f, diag, clock0 + tinx - 1, (sums || s.raw) ? &save : nullptr);
         if (rc) return rc;
         if (s.raw && ++staged == chunk) HIPCHK(flush());
-        auto state_field = [&](int v) { return (const double *)h->field[fields[v]]; };
-        if (s.snapshot && ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false)))) return rc;
+        if (s.snapshot && (rc = natural_layout(h, true))) return rc;
         if (s.season == 1) {
             if (winter) HIPCHK(season_to_host(winter, year));
-            if (hm_winter) HIPCHK(means_to_host(hm_winter, year, state_field));
+            if (hm_winter) HIPCHK(means_to_host(hm_winter, year, of_state));
         } else if (s.season == 2) {
             if (summer) HIPCHK(season_to_host(summer, year));
-            if (hm_summer) HIPCHK(means_to_host(hm_summer, year, state_field));
+            if (hm_summer) HIPCHK(means_to_host(hm_summer, year, of_state));
         } else if (s.year_end) {
             if (sums) {
                 HIPCHK(cp->wait_all());                                      // last year's means have left `mean`
                 HIPCHK(ebm::launch_finish_mean(mean, sums, (double)nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h)));
                 if (avg) HIPCHK(fields_to_host(avg, year, mean));
-                if (hm_avg) HIPCHK(means_to_host(hm_avg, year, [&](int v) { return (const double *)(mean + (size_t)v * npitch); }));
+                if (hm_avg) HIPCHK(means_to_host(hm_avg, year, of_mean));
             }
         }
         if (sums && s.year_end && s.season)                                  // year ended on a seasonal index:
@@ -574,8 +636,7 @@ int ebm_integrate_hemispheric(ebm_handle_t h, int nt, int dur, const double *f_s
 
 // ebm_equilibrate (include/ebm_hip.h).  Every year is one fused_range over the active columns (launches of nactive
 // workgroups, which step cols[b]), then equilibrium_check_kernel compares each active column's year-end fields with the
-// snapshot of the year before and freezes it, compact_active_kernel writes the next list and its length, and the host
-// reads the length: one stream synchronisation per year.  The fused kernels store the diagnostic fields in the natural
+// snapshot of the year before and freezes it, and the list advances (ActiveRounds): one stream synchronisation per year.  The fused kernels store the diagnostic fields in the natural
 // layout, so the fields of columns frozen in different years share one layout and nothing is un-permuted in between.
 int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const double *f_year, int nvars, const int *fields,
                     const double *tol, int *years, int *converged, double *resid) {
@@ -602,70 +663,47 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
     if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
-    if ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false))) return rc;
+    if ((rc = natural_layout(h, true))) return rc;
     const int ncol = h->ncol;
     const size_t npitch = (size_t)ncol * h->pitch;
-    // this call's device memory: snapshot | resid, and the two active lists | years | frozen | count
+    // this call's device memory: snapshot | resid, and the active list with the year each column was last tested in
     DevBuf<double> dbl;
-    DevBuf<int> ints;
-    PinnedBuf<int> pinned;
-    // the list is known to the launches only until the call returns, on every path; they end before the buffers are freed
-    const auto done = finally([h] {
-        (void)hipStreamSynchronize(main_stream(h));
-        h->active = nullptr;
-        h->nactive = 0;
-    });
+    ActiveRounds rounds;
     HIPCHK(dev_alloc(dbl, (size_t)nvars * npitch + (size_t)nvars * ncol));
-    HIPCHK(dev_alloc(ints, 4 * (size_t)ncol + 1));
-    HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
-    int *cur = ints.get(), *nxt = cur + ncol, *years_dev = nxt + ncol, *frozen = years_dev + ncol, *count = frozen + ncol;
+    if ((rc = rounds.begin(h, 0))) return rc;
     {
         std::vector<double> nan((size_t)nvars * ncol, std::nan(""));
-        std::vector<int> ident((size_t)ncol);
-        for (int c = 0; c < ncol; ++c) ident[c] = c;
         HIPCHK(hipMemcpy(dbl.get() + (size_t)nvars * npitch, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(years_dev, 0, sizeof(int) * 2 * (size_t)ncol));
     }
     ea.state = h->state.get(); ea.fstride = h->fstride;
     ea.snap = dbl.get(); ea.resid = dbl.get() + (size_t)nvars * npitch;
-    ea.years = years_dev; ea.frozen = frozen;
+    ea.years = rounds.round_of; ea.frozen = rounds.frozen;
     ea.pitch = (int)h->pitch; ea.nlat = h->nlat; ea.ncol = ncol; ea.nvars = nvars;
     const long long clock0 = h->clock;
     const int first_test = std::max(2, min_years);
-    int nactive = ncol;
     for (int y = 1; y <= max_years; ++y) {
-        h->active = cur;
-        h->nactive = nactive;
+        rounds.activate();
         rc = fused_range(h, 0, clock0 + (long long)(y - 1) * nt, nt, f_year, 1, h->integrate_spl, nullptr);
         if (rc) return rc;
-        ea.cols = cur;
+        ea.cols = rounds.cur;
         ea.year = y;
         ea.compare = y >= 2;
         ea.may_freeze = y >= first_test;
-        hipError_t e = ebm::launch_equilibrium_check(ea, nactive, main_stream(h));
+        hipError_t e = ebm::launch_equilibrium_check(ea, rounds.nactive, main_stream(h));
         if (e != hipSuccess) return hip_fail("ebm_equilibrate: check", e);
         if (y == max_years || !ea.may_freeze) continue;          // (nothing has frozen: the list stays)
-        e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
-        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
-        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
-        if (e != hipSuccess) return hip_fail("ebm_equilibrate: active list", e);
-        nactive = *pinned.get();
-        std::swap(cur, nxt);
-        if (nactive == 0) break;                                 // every column is frozen
+        if ((rc = rounds.advance("ebm_equilibrate")) < 0) return rc;
+        if (rc == 0) break;                                      // every column is frozen
     }
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
-    HIPCHK(hipMemcpy(years, years_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(converged, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    if ((rc = rounds.download(years, converged))) return rc;
     if (resid) HIPCHK(hipMemcpy(resid, ea.resid, sizeof(double) * (size_t)nvars * ncol, hipMemcpyDeviceToHost));
     return EBM_OK;
 }
 
 // ebm_run_until (include/ebm_hip.h).  Every round is one fused_range of `every` steps over the active columns — also with
 // one step per launch: the one-step kernels and a replayed graph know nothing of the list, the fused kernel at K = 1 gives
-// the same bits — then passage_check_kernel takes each active column's mean and compares it with the column's level,
-// compact_active_kernel writes the next list and its length, and the host reads the length: one stream synchronisation
-// per round.  The fused kernels read and write the natural layout, so the fields of columns frozen in different rounds
+// the same bits — then passage_check_kernel takes each active column's mean and compares it with the column's level, and
+// the list advances (ActiveRounds): one stream synchronisation per round.  The fused kernels read and write the natural layout, so the fields of columns frozen in different rounds
 // share one layout.
 int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
                   int field, const double *level, const int *direction, int *samples, int *crossed, double *value) {
@@ -685,66 +723,41 @@ int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int eve
     if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
         return fail(EBM_ERR_UNSUPPORTED, "ebm_run_until: no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
-    if ((rc = ensure_natural(h)) || (rc = set_state_layout(h, false))) return rc;
+    if ((rc = natural_layout(h, true))) return rc;
     const int diag = var.diagnostic ? 1 : 0;
-    // this call's device memory: value | level, and the two active lists | samples | frozen | direction | count
+    // this call's device memory: value | level, and the active list with the round each column was last tested in and, as
+    // its extra array, the directions
     DevBuf<double> dbl;
-    DevBuf<int> ints;
-    PinnedBuf<int> pinned;
-    // the list is known to the launches only until the call returns, on every path; they end before the buffers are freed
-    const auto done = finally([h] {
-        (void)hipStreamSynchronize(main_stream(h));
-        h->active = nullptr;
-        h->nactive = 0;
-    });
+    ActiveRounds rounds;
     HIPCHK(dev_alloc(dbl, 2 * (size_t)ncol));
-    HIPCHK(dev_alloc(ints, 5 * (size_t)ncol + 1));
-    HIPCHK(hipHostMalloc(pinned.out(), sizeof(int), hipHostMallocDefault));
-    int *cur = ints.get(), *nxt = cur + ncol, *samples_dev = nxt + ncol, *frozen = samples_dev + ncol, *dir_dev = frozen + ncol,
-        *count = dir_dev + ncol;
+    if ((rc = rounds.begin(h, 1))) return rc;
     double *value_dev = dbl.get(), *level_dev = value_dev + ncol;
-    {
-        std::vector<int> ident((size_t)ncol);
-        for (int c = 0; c < ncol; ++c) ident[c] = c;
-        // (value needs no initial contents: round 1 tests every column)
-        HIPCHK(hipMemcpy(level_dev, level, sizeof(double) * (size_t)ncol, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(cur, ident.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(samples_dev, 0, sizeof(int) * 2 * (size_t)ncol));
-        HIPCHK(hipMemcpy(dir_dev, direction, sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
-    }
+    // (value needs no initial contents: round 1 tests every column)
+    HIPCHK(hipMemcpy(level_dev, level, sizeof(double) * (size_t)ncol, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rounds.extra, direction, sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
     ebm::PassageArgs pa{};
     pa.field = h->field[var.field];
     pa.x = x_table(h);
-    pa.level = level_dev; pa.direction = dir_dev;
-    pa.value = value_dev; pa.samples = samples_dev; pa.frozen = frozen;
+    pa.level = level_dev; pa.direction = rounds.extra;
+    pa.value = value_dev; pa.samples = rounds.round_of; pa.frozen = rounds.frozen;
     pa.pitch = (int)h->pitch; pa.nlat = h->nlat;
-    int nactive = ncol;
     for (int j = 1; j <= max_samples; ++j) {
-        h->active = cur;
-        h->nactive = nactive;
+        rounds.activate();
         const long long first = first_step + (long long)(j - 1) * every;
         rc = fused_range(h, first, first, every, f_steps ? f_steps + (size_t)(j - 1) * (size_t)every : nullptr, diag, steps_per_launch,
                          nullptr);
         if (rc) return rc;
         // (as ebm_run_series before its reduction; after a fused launch both hold already)
-        if (diag && (rc = ensure_natural(h))) return rc;
-        if ((rc = set_state_layout(h, false))) return rc;
-        pa.cols = cur;
+        if ((rc = natural_layout(h, diag != 0))) return rc;
+        pa.cols = rounds.cur;
         pa.round = j;
-        hipError_t e = ebm::launch_passage_check(pa, nactive, main_stream(h));
+        hipError_t e = ebm::launch_passage_check(pa, rounds.nactive, main_stream(h));
         if (e != hipSuccess) return hip_fail("ebm_run_until: check", e);
         if (j == max_samples) break;                             // (no further round: no list is needed)
-        e = ebm::launch_compact_active(cur, nactive, frozen, nxt, count, main_stream(h));
-        if (e == hipSuccess) e = hipMemcpyAsync(pinned.get(), count, sizeof(int), hipMemcpyDeviceToHost, main_stream(h));
-        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
-        if (e != hipSuccess) return hip_fail("ebm_run_until: active list", e);
-        nactive = *pinned.get();
-        std::swap(cur, nxt);                                     // (the list just written steps the next round)
-        if (nactive == 0) break;                                 // every column has crossed
+        if ((rc = rounds.advance("ebm_run_until")) < 0) return rc;
+        if (rc == 0) break;                                      // every column has crossed
     }
-    HIPCHK(hipStreamSynchronize(main_stream(h)));
-    HIPCHK(hipMemcpy(samples, samples_dev, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(crossed, frozen, sizeof(int) * (size_t)ncol, hipMemcpyDeviceToHost));
+    if ((rc = rounds.download(samples, crossed))) return rc;
     if (value) HIPCHK(hipMemcpy(value, value_dev, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost));
     return EBM_OK;
 }

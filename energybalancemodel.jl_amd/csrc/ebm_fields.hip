@@ -39,6 +39,13 @@ int set_state_layout(ebm_ctx *h, bool split) {
     hipError_t e = convert_state(h, split);
     return e == hipSuccess ? EBM_OK : hip_fail("state layout conversion", e);
 }
+// What a kernel that reads whole fields where they lie needs first (the mean kernels, snapshots, the fused kernels over an
+// active list): the prognostic fields natural and, if the caller reads them too, the diagnostic ones.
+int natural_layout(ebm_ctx *h, bool diagnostics_too) {
+    if (diagnostics_too)
+        if (int rc = ensure_natural(h)) return rc;
+    return set_state_layout(h, false);
+}
 
 hipError_t restore_phi(ebm_ctx *h) {
     if (h->phi_stored) return hipSuccess;
@@ -108,7 +115,10 @@ int download_field(ebm_ctx *h, int field, double *host, const char *who) {
 
 // ebm_hemispheric_mean / _device: the per-column means of a readable field into dev_out
 hipError_t hemispheric_mean(ebm_ctx *h, int field, double *dev_out) {
-    return ebm::launch_hemispheric_mean(h->field[field], x_table(h), (int)h->pitch, h->nlat, h->ncol, dev_out, main_stream(h));
+    ebm::MeansArgs m{};              // one field: slot[0] = 0
+    m.state = h->field[field]; m.x = x_table(h); m.out = dev_out;
+    m.pitch = (int)h->pitch; m.nlat = h->nlat; m.nvars = 1;
+    return ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
 }
 
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed

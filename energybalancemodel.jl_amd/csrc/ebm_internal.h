@@ -111,23 +111,23 @@ hipError_t launch_derive_params(Params *p_dev, hipStream_t s);
 // active set from the T0 field (after ebm_set_field(T0))
 hipError_t launch_mask_from_t0(const StepArgs &a, int ncol, const LaunchCfg &cfg, hipStream_t s);
 hipError_t launch_divide(const double *a, const double *b, double *q, int n, hipStream_t s);
-// out[col] = hemispheric_mean(field[col], x), src/utilities.jl:397-403 (sequential sum, bit-exact)
-hipError_t launch_hemispheric_mean(const double *field, const double *x, int pitch, int nlat, int ncol, double *out,
-                                   hipStream_t s);
-// ebm_run_series: one sample of the series.  out[v * var_stride + col] = hemispheric_mean(field in state slot slot[v] of
-// column col, x) for v < nvars, col < ncol, the same bits as launch_hemispheric_mean; one wave per column, one launch.
-constexpr int kSeriesTile = 512;     // terms per LDS tile and variable: at most 12 x 513 doubles = 48 KiB of LDS
-struct SeriesArgs {
+// out[v * var_stride + col] = hemispheric_mean(field in slot slot[v] of column col, x), src/utilities.jl:397-403, for
+// v < nvars, col < ncol: the sequential sum, bit-exact, by hemispheric_means_of_column (ebm_launch.hip) — the one definition
+// of the mean in the library.  One wave per column, one launch.  Field v of column col starts at
+// state + slot[v] * fstride + col * pitch, natural layout: a handle's slab with its slots, or any [nvars][ncol][pitch]
+// buffer with slot[v] = v; one field is nvars = 1, slot[0] = 0.
+constexpr int kMeanTile = 512;       // terms per LDS tile and variable: at most 12 x 513 doubles = 48 KiB of LDS
+struct MeansArgs {
     const double *state;
     long long fstride;
     const double *x;
-    double *out;                     // the sample's first word in the device series [nvars][nsamples][ncol]
-    long long var_stride;            // nsamples * ncol
+    double *out;                     // ebm_run_series: the sample's first word in the device series [nvars][nsamples][ncol]
+    long long var_stride;            // ... and nsamples * ncol
     int pitch, nlat, nvars;
     int row;                         // doubles per variable of the LDS tile (odd; set by the launcher)
     int slot[kMaxQuantities];
 };
-hipError_t launch_hemispheric_series(const SeriesArgs &s, int ncol, hipStream_t st);
+hipError_t launch_hemispheric_means(const MeansArgs &s, int ncol, hipStream_t st);
 // out = base + D d/dx[(1-x^2) d temp/dx] per column ([ncol][pitch] device arrays; base may be null)
 // (parameter set of column c: pset[c], or 0 if pset is null — see StepArgs)
 hipError_t launch_diffusion(const double *temp, const double *base, double *out, const double *geom, long long gstride,
@@ -168,7 +168,7 @@ struct EquilArgs {
 };
 hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t s);
 // ebm_run_until, one wave per active column c = cols[b], b < nactive: m = hemispheric_mean(field of column c, x), the bits of
-// launch_hemispheric_mean; value[c] = m, samples[c] = round and frozen[c] = (direction[c] > 0 ? m >= level[c] : m <= level[c])
+// hemispheric_means_of_column; value[c] = m, samples[c] = round and frozen[c] = (direction[c] > 0 ? m >= level[c] : m <= level[c])
 struct PassageArgs {
     const double *field;             // the one field, [ncol][pitch], natural layout
     const double *x;

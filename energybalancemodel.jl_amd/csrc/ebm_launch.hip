@@ -28,7 +28,7 @@
 //                                       [ebm_miz_resident.h; miz_resident.hip, SAVE: miz_resident_save.hip]
 //   classic_step_kernel<C, MODE>        WE15 model: single step / savesol! / K steps per launch            [this file]
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
-//   finish_mean, hemispheric_mean, hemispheric_series, mask_from_t0, derive_params, divide, permute_fields (split / unsplit),
+//   finish_mean, hemispheric_means, mask_from_t0, derive_params, divide, permute_fields (split / unsplit), restore_phi,
 //   noise_innovations, noise_sequence, equilibrium_check, passage_check, compact_active: small helpers     [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
 // and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
@@ -36,7 +36,7 @@
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 485 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 487 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -214,59 +214,59 @@ hipError_t launch_divide(const double *a, const double *b, double *q, int n, hip
     return hipGetLastError();
 }
 
-// hemispheric_mean (src/utilities.jl:397-403) of one field, one workgroup per column:
+// hemispheric_mean (src/utilities.jl:397-403) of nvars fields of one column, by a workgroup of LANES lanes:
 //   int = 0; for i in 1:nx-1: int += (vec[i]+vec[i+1]) * (x[i+1]-x[i]) / 2.0
-// The terms are formed in parallel (elementwise, exact order of operations); the accumulation is
-// the reference's strictly sequential left-to-right sum, done by one lane out of LDS, so the
-// result is bit-identical to the reference's loop.
-__global__ void hemispheric_mean_kernel(const double *__restrict__ field, const double *__restrict__ x,
-                                        int pitch, int nlat, double *__restrict__ out) {
-    extern __shared__ double terms[];
-    const double *v = field + (size_t)blockIdx.x * pitch;
-    for (int i = threadIdx.x; i < nlat - 1; i += blockDim.x)
-        terms[i] = ieee_div((v[i] + v[i + 1]) * (x[i + 1] - x[i]), 2.0);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double acc = 0.0;
-        for (int i = 0; i < nlat - 1; ++i) acc = acc + terms[i];
-        out[blockIdx.x] = acc;
-    }
-}
-// ebm_run_series: the same mean of s.nvars fields of one column by ONE wave, every column in one launch, written straight
-// into slot [v][sample][col] of the device series (SeriesArgs).  The latitudes are walked in tiles of kSeriesTile terms: the
-// 64 lanes form the terms of all variables as hemispheric_mean_kernel does (coalesced row reads, x[i+1]-x[i] once per
-// latitude) into an LDS tile [nvars][row]; then lane v adds row v onto its running sum — the reference's sequential
-// left-to-right sum from 0.0, nvars chains side by side instead of one launch each with one working lane.  `row` is odd, so
-// the lanes' rows start on different banks.
-__global__ void __launch_bounds__(64) hemispheric_series_kernel(const SeriesArgs s) {
-    extern __shared__ double terms[];
-    const int lane = threadIdx.x, col = blockIdx.x, nterms = s.nlat - 1, row = s.row;
-    const double *const column = s.state + (size_t)col * (size_t)s.pitch;
+// THE definition of the mean in this library: every kernel that needs one calls this function, so they agree to the bit.
+// The latitudes are walked in tiles of kMeanTile terms: the lanes form the terms of all fields (elementwise, exact order
+// of operations; coalesced row reads, x[i+1]-x[i] once per latitude) into the LDS tile terms[nvars][row]; then lane v adds row
+// v onto its running sum — the reference's strictly sequential left-to-right sum from 0.0, nvars chains side by side — so
+// the result is bit-identical to the reference's loop.  field_of(v): field v of the column, natural layout.  Returns, in lane
+// v < nvars, the mean of field v.  With several fields an odd `row` starts the lanes' rows on different banks.
+template <int LANES, class FieldOf>
+__device__ __forceinline__ double hemispheric_means_of_column(FieldOf field_of, const double *__restrict__ x, int nlat, int nvars,
+                                                              double *terms, int row) {
+    const int lane = threadIdx.x, nterms = nlat - 1;
     double acc = 0.0;
-    for (int k0 = 0; k0 < nterms; k0 += kSeriesTile) {
-        const int n = min(kSeriesTile, nterms - k0);
-        for (int i = lane; i < n; i += 64) {
-            const double dx = s.x[k0 + i + 1] - s.x[k0 + i];
-            for (int v = 0; v < s.nvars; ++v) {
-                const double *f = column + (size_t)s.slot[v] * (size_t)s.fstride + k0;
-                terms[v * row + i] = ieee_div((f[i] + f[i + 1]) * dx, 2.0);
+    for (int k0 = 0; k0 < nterms; k0 += kMeanTile) {
+        const int n = min(kMeanTile, nterms - k0);
+        for (int i = lane; i < n; i += LANES) {
+            const double dx = x[k0 + i + 1] - x[k0 + i];
+            for (int v = 0; v < nvars; ++v) {
+                const double *f = field_of(v);
+                terms[v * row + i] = ieee_div((f[k0 + i] + f[k0 + i + 1]) * dx, 2.0);
             }
         }
         __syncthreads();
-        if (lane < s.nvars) {
+        if (lane < nvars) {
             const double *t = terms + lane * row;
 #pragma unroll 8
             for (int i = 0; i < n; ++i) acc = acc + t[i];
         }
         __syncthreads();                                  // (the tile is refilled by the next round)
     }
+    return acc;
+}
+// The mean kernel of the library (MeansArgs): one workgroup per column, every column and every field in one launch; lane v
+// writes the mean of field v to out[v][col] — ebm_hemispheric_mean (one field), ebm_integrate_hemispheric, and
+// ebm_run_series, whose `out` is the sample's slot of the device series.  LANES: 64 (one wave, its barriers free), or 256
+// for one field of a long meridian, where the one chain waits for the term loads of a tile and four waves issue them at
+// once (the launcher's rule; measured, profiles/r16_means_ab.txt).  Same bits.
+template <int LANES>
+__global__ void __launch_bounds__(LANES) hemispheric_means_kernel(const MeansArgs s) {
+    extern __shared__ double terms[];
+    const int lane = threadIdx.x, col = blockIdx.x;
+    const double *const column = s.state + (size_t)col * (size_t)s.pitch;
+    const double acc = hemispheric_means_of_column<LANES>([&](int v) { return column + (size_t)s.slot[v] * (size_t)s.fstride; }, s.x,
+                                                   s.nlat, s.nvars, terms, s.row);
     if (lane < s.nvars) s.out[(size_t)lane * (size_t)s.var_stride + col] = acc;
 }
-hipError_t launch_hemispheric_series(const SeriesArgs &s, int ncol, hipStream_t st) {
+hipError_t launch_hemispheric_means(const MeansArgs &s, int ncol, hipStream_t st) {
     if (ncol < 1 || s.nlat < 2 || s.nvars < 1 || s.nvars > kMaxQuantities) return hipErrorInvalidValue;
-    SeriesArgs b = s;
-    b.row = (s.nlat - 1 < kSeriesTile ? s.nlat - 1 : kSeriesTile) | 1;
-    hemispheric_series_kernel<<<ncol, 64, sizeof(double) * (size_t)b.nvars * (size_t)b.row, st>>>(b);
+    MeansArgs b = s;
+    b.row = (s.nlat - 1 < kMeanTile ? s.nlat - 1 : kMeanTile) | 1;
+    const size_t lds = sizeof(double) * (size_t)b.nvars * (size_t)b.row;
+    if (b.nvars == 1 && s.nlat - 1 > 256) hemispheric_means_kernel<256><<<ncol, 256, lds, st>>>(b);
+    else hemispheric_means_kernel<64><<<ncol, 64, lds, st>>>(b);
     return hipGetLastError();
 }
 // ebm_equilibrate's year-end test, one workgroup per active column (EquilArgs): rows k < nlat of this year's fields
@@ -309,25 +309,13 @@ hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t
 }
 
 // ebm_run_until's test after a round, one wave per active column c = cols[b] (PassageArgs): the hemispheric mean of the one
-// field as hemispheric_series_kernel takes it — the latitudes in tiles of kSeriesTile terms, the 64 lanes form the terms
-// (the expressions of hemispheric_mean_kernel), lane 0 adds them onto the running sum in the reference's order — then the
-// comparison with the column's level.  A NaN mean fails both comparisons: it never crosses.
+// field (hemispheric_means_of_column: lane 0 holds it), then the comparison with the column's level.  A NaN mean fails both
+// comparisons: it never crosses.
 __global__ void __launch_bounds__(64) passage_check_kernel(const PassageArgs p) {
-    __shared__ double terms[kSeriesTile];
-    const int lane = threadIdx.x, col = p.cols[blockIdx.x], nterms = p.nlat - 1;
+    __shared__ double terms[kMeanTile];
+    const int lane = threadIdx.x, col = p.cols[blockIdx.x];
     const double *const f = p.field + (size_t)col * (size_t)p.pitch;
-    double acc = 0.0;
-    for (int k0 = 0; k0 < nterms; k0 += kSeriesTile) {
-        const int n = min(kSeriesTile, nterms - k0);
-        for (int i = lane; i < n; i += 64)
-            terms[i] = ieee_div((f[k0 + i] + f[k0 + i + 1]) * (p.x[k0 + i + 1] - p.x[k0 + i]), 2.0);
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll 8
-            for (int i = 0; i < n; ++i) acc = acc + terms[i];
-        }
-        __syncthreads();                                  // (the tile is refilled by the next round)
-    }
+    const double acc = hemispheric_means_of_column<64>([&](int) { return f; }, p.x, p.nlat, 1, terms, kMeanTile);
     if (lane == 0) {
         const double level = p.level[col];
         const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;
@@ -647,11 +635,6 @@ hipError_t launch_mask_from_t0(const StepArgs &a, int ncol, const LaunchCfg &cfg
     return hipGetLastError();
 }
 
-hipError_t launch_hemispheric_mean(const double *field, const double *x, int pitch, int nlat, int ncol, double *out,
-                                   hipStream_t s) {
-    hemispheric_mean_kernel<<<ncol, 256, sizeof(double) * (size_t)nlat, s>>>(field, x, pitch, nlat, out);
-    return hipGetLastError();
-}
 hipError_t launch_finish_mean(double *dst, double *sum, double nt, int ncol, int nvars, long long var_stride,
                               const LaunchCfg &cfg, hipStream_t s) {
     finish_mean_kernel<<<dim3(ncol, nvars), cfg.threads, 0, s>>>(dst, sum, nt, cfg.threads, cfg.cells, var_stride);

@@ -271,6 +271,8 @@ int ensure_natural(ebm_ctx *h);                   // ebm_fields.hip: un-permute 
 // ebm_fields.hip: THE rule of ebm_ctx::state_split — the prognostic fields into the layout their next user expects
 hipError_t convert_state(ebm_ctx *h, bool split);
 int set_state_layout(ebm_ctx *h, bool split);     // the same, with the error reported (EBM_ERR_HIP)
+// ebm_fields.hip: the prognostic fields natural (set_state_layout(h, false)), after the diagnostic ones if asked (ensure_natural)
+int natural_layout(ebm_ctx *h, bool diagnostics_too);
 // ebm_fields.hip: the phi field current again in whatever layout the state has (ebm_ctx::phi_stored), for readers that take
 // the fields as they lie — a one-step launch that loads phi, resampling, a change of the parameters
 hipError_t restore_phi(ebm_ctx *h);

@@ -214,6 +214,36 @@ def test_two_calls_compose(pkg, case):
     assert_same_snapshot(after, r["after"], case)
 
 
+# ---- the one-field entry points walk the same tiles -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("nlat", [2, 3, 65, 513, 514, 1025, 1026])
+def test_hemispheric_mean_at_tile_boundaries(pkg, nlat):
+    """ebm_hemispheric_mean and ebm_hemispheric_mean_device go through the mean kernel of the series, which walks the
+    nlat - 1 terms in tiles of 512: 1, 2 and 64 terms, exactly one tile, one tile plus one term, exactly two tiles, two
+    tiles plus one term.  Fields the caller set — T, a diagnostic field, and Ei, a prognostic one (the un-split path) — of
+    seeded normal values, with a NaN in column 1 at cell 512 where it exists (it enters the last term of tile 1 and the
+    first of tile 2) and +inf in column 2 at cell 0; against the host's sequential loop, bit for bit."""
+    import torch
+    ncol = 3
+    st = pkg.SpaceTime("sin", nlat, 2000, 1)
+    vec = pkg.engine.param_vector(pkg.default_parameters("MIZ"), pkg.default_parval)
+    rng = np.random.default_rng(nlat)
+    with pkg.Engine("MIZ", st.grid_kind, st.x, vec, st.dt, ncol, device=0) as eng:
+        for name in ("T", "Ei"):
+            field = rng.standard_normal((ncol, nlat))
+            if nlat > 512:
+                field[1, 512] = np.nan
+            field[2, 0] = np.inf
+            eng.set_field(name, field)
+            want = pkg.hemispheric_mean(field, st.x)
+            assert np.isfinite(want[0]) and np.isnan(want[1]) == (nlat > 512) and want[2] == np.inf
+            assert np.array_equal(eng.hemispheric_mean(name), want, equal_nan=True), (nlat, name)
+            out = torch.empty(ncol, dtype=torch.float64, device="cuda:0")
+            eng.hemispheric_mean_device(name, out.data_ptr())
+            torch.cuda.synchronize()
+            assert np.array_equal(out.cpu().numpy(), want, equal_nan=True), (nlat, name, "device output")
+
+
 # ---- options and per-column settings -------------------------------------------------------------------------------------
 
 def install_members(pkg, model, ncol_total):

@@ -56,7 +56,8 @@ MUTANTS = [
     ("winter_snapshot_one_step_late", "s.season = ti == winter_inx ? 1 :", "s.season = ti == winter_inx + 1 ? 1 :", "ebm_drive.hip"),
     ("annual_mean_divides_by_nt_minus_1", "m.x = s.x / nt;", "m.x = s.x / (nt - 1.0);"),
     ("annual_sum_not_restarted", "z.x = 0.0;", "z.x = s.x;"),
-    ("hemispheric_mean_without_the_half", "terms[i] = ieee_div((v[i] + v[i + 1]) * (x[i + 1] - x[i]), 2.0);", "terms[i] = (v[i] + v[i + 1]) * (x[i + 1] - x[i]);"),
+    # (the one term expression of the library: hemispheric_means_of_column, which every mean of every entry point goes through)
+    ("hemispheric_mean_without_the_half", "terms[v * row + i] = ieee_div((f[k0 + i] + f[k0 + i + 1]) * dx, 2.0);", "terms[v * row + i] = (f[k0 + i] + f[k0 + i + 1]) * dx;"),
     # fourth batch: code that only the fused-K kernels, savesol!-in-the-step, the extension and the classic solve run
     # (a seventh mutant of this batch removed the barrier that closed the classic kernel's K-step loop and SURVIVED: the
     # barrier was redundant — see the comment there — and is gone)

@@ -11,7 +11,12 @@ What tests/test_gpu_until.py does with each (profiles/r13_until_mutants.txt):
   passage_nan_mean_counts_as_crossed      the Ti columns stop at round 1: test_nan_mean_never_crosses fails, alone
   passage_check_reads_the_list_position   from round 2 on the flags of the wrong columns are written: every case with a
                                           compaction fails (26 of 27)
-  passage_round_steps_the_stale_list      frozen columns are stepped in place of live ones: the same 26"""
+  passage_round_steps_the_stale_list      frozen columns are stepped in place of live ones: the same 26.  The line is the
+                                          round driver's (ActiveRounds::advance), which ebm_equilibrate shares: the mutant
+                                          breaks it the same way — from the first compaction on converged columns are
+                                          stepped and live ones left behind, so the cases of tests/test_gpu_equilibrate.py
+                                          and tests/test_gpu_equilibrate_lists.py in which a column freezes before the last
+                                          year fail too"""
 import sys
 
 import mutants
@@ -21,10 +26,9 @@ mutants.MUTANTS = [
      "const bool crossed = p.direction[col] > 0 ? acc > level : acc < level;"),
     ("passage_nan_mean_counts_as_crossed", "const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;",
      "const bool crossed = p.direction[col] > 0 ? !(acc < level) : !(acc > level);"),
-    ("passage_check_reads_the_list_position", "const int lane = threadIdx.x, col = p.cols[blockIdx.x], nterms = p.nlat - 1;",
-     "const int lane = threadIdx.x, col = (int)blockIdx.x, nterms = p.nlat - 1;"),
-    ("passage_round_steps_the_stale_list", "        std::swap(cur, nxt);                                     // (the list just written steps the next round)\n",
-     "", "ebm_drive.hip"),
+    ("passage_check_reads_the_list_position", "const int lane = threadIdx.x, col = p.cols[blockIdx.x];",
+     "const int lane = threadIdx.x, col = (int)blockIdx.x;"),
+    ("passage_round_steps_the_stale_list", "        std::swap(cur, nxt);\n", "", "ebm_drive.hip"),
 ]
 
 if __name__ == "__main__":
