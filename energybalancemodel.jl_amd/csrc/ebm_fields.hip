@@ -1,5 +1,7 @@
 // Host runtime, fields (ebm_runtime.h lists the units): set / get with the validity bookkeeping, device views, hemispheric
 // means, and the two diffusion operators that work on caller-supplied fields (ebm_diffusion, ebm_zonal_diffusion).
+#include <cmath>
+
 #include "ebm_runtime.h"
 #include "ebm_tables.h"
 
@@ -119,6 +121,70 @@ hipError_t hemispheric_mean(ebm_ctx *h, int field, double *dev_out) {
     m.state = h->field[field]; m.x = x_table(h); m.out = dev_out;
     m.pitch = (int)h->pitch; m.nlat = h->nlat; m.nvars = 1;
     return ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
+}
+
+// ebm_ensemble_sums / _device (include/ebm_hip.h): the checks, then the two launches of ebm_ensemble.hip into dev_out (the
+// caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
+int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, const double *center, double *host_out,
+                  double *dev_out, const char *who) {
+    const std::string me(who);
+    if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
+    if (!fields || (!host_out && !dev_out)) return fail(EBM_ERR_ARG, me + ": null argument");
+    if (nvars < 1 || nvars > ebm::kMaxQuantities)
+        return fail(EBM_ERR_ARG, me + ": nvars = " + std::to_string(nvars) + " is outside 1 ... " + std::to_string(ebm::kMaxQuantities));
+    for (int v = 0; v < nvars; ++v) {
+        if (!has_field(h, fields[v]) || quantity_of(h->model, fields[v]) < 0)
+            return fail(EBM_ERR_ARG, me + ": fields[" + std::to_string(v) + "] is not a solution variable of this model");
+        for (int u = 0; u < v; ++u)
+            if (fields[u] == fields[v]) return fail(EBM_ERR_ARG, me + ": field " + field_name(fields[v]) + " is listed twice");
+    }
+    for (int c = 0; w && c < h->ncol; ++c)
+        if (!std::isfinite(w[c])) return fail(EBM_ERR_ARG, me + ": w[" + std::to_string(c) + "] is not finite (column " + std::to_string(c) + ")");
+    for (long long i = 0; center && i < (long long)nvars * h->nlat; ++i)
+        if (!std::isfinite(center[i]))
+            return fail(EBM_ERR_ARG, me + ": center[" + std::to_string(i / h->nlat) + "][" + std::to_string(i % h->nlat) + "] is not finite");
+    for (int v = 0; v < nvars; ++v)
+        if (int rc = check_current(h, fields[v], who)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    ebm_ctx::EnsembleSums &b = h->sums;
+    const int nblocks = (h->ncol + ebm::kSumsBlock - 1) / ebm::kSumsBlock;
+    const size_t npitch = (size_t)h->pitch;
+    HIPCHK(b.partial.reserve((size_t)nblocks * 3 * (size_t)nvars * npitch));
+    HIPCHK(b.w.reserve((size_t)h->ncol));
+    if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * 3 * (size_t)h->nlat));
+    // phi is read as a field: current first, in the layout the state has.  Nothing else of the handle changes
+    for (int v = 0; v < nvars; ++v)
+        if (fields[v] == EBM_F_phi && h->model == EBM_MODEL_MIZ) {
+            hipError_t e = restore_phi(h);
+            if (e != hipSuccess) return hip_fail("phi restore", e);
+        }
+    hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
+    if (center && !b.center.get()) {                     // all twelve rows once; the padding cells stay zero
+        HIPCHK(b.center.reserve((size_t)ebm::kMaxQuantities * npitch));
+        HIPCHK(hipMemsetAsync(b.center.get(), 0, sizeof(double) * ebm::kMaxQuantities * npitch, s));
+    }
+    const std::vector<double> ones(w ? 0 : (size_t)h->ncol, 1.0);
+    hipError_t e = hipMemcpyAsync(b.w.get(), w ? w : ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && center)
+        e = hipMemcpy2DAsync(b.center.get(), sizeof(double) * npitch, center, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
+                             (size_t)nvars, hipMemcpyHostToDevice, s);
+    ebm::EnsembleSumsArgs a{};
+    for (int v = 0; v < nvars; ++v) {
+        const int f = fields[v];
+        a.row[v] = h->field[f];                          // where it lies: no field is converted
+        if ((is_split_state_field(h, f) && h->state_split) || (is_split_field(h, f) && h->diag_split)) a.split_mask |= 1u << v;
+    }
+    a.w = b.w.get();
+    a.center = center ? b.center.get() : nullptr;
+    a.partial = b.partial.get();
+    a.out = dev_out ? dev_out : b.out.get();
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.nblocks = nblocks; a.threads = h->cfg.threads;
+    if (e == hipSuccess) e = ebm::launch_ensemble_sums(a, s);
+    if (e == hipSuccess && !dev_out)
+        e = hipMemcpyAsync(host_out, b.out.get(), sizeof(double) * 3 * (size_t)nvars * (size_t)h->nlat, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(who, e);
+    return EBM_OK;
 }
 
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
@@ -245,6 +311,14 @@ int ebm_hemispheric_mean_device(ebm_handle_t h, int field, double *dev_out) {
     if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
     if (e != hipSuccess) return hip_fail("ebm_hemispheric_mean_device", e);
     return EBM_OK;
+}
+
+int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *out) {
+    return ensemble_sums(h, nvars, fields, w, center, out, nullptr, "ebm_ensemble_sums");
+}
+
+int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *dev_out) {
+    return ensemble_sums(h, nvars, fields, w, center, nullptr, dev_out, "ebm_ensemble_sums_device");
 }
 
 int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {

@@ -231,5 +231,20 @@ struct ExchangeArgs {
 };
 hipError_t launch_export_columns(const ExchangeArgs &a, int n, hipStream_t s);
 hipError_t launch_import_columns(const ExchangeArgs &a, int n, hipStream_t s);
+// ebm_ensemble_sums (ebm_ensemble.hip): out[v][q][k] = S_q of variable v at latitude k < nlat, summed over the columns in
+// the order of the definition — blocks of kSumsBlock columns in ascending column order into partial[block][v][q][pitch], then
+// the blocks in ascending order.  Two launches.  row[v]: the field of variable v, [ncol][pitch], read where it lies; bit v of
+// split_mask: the handle holds it pair-split (then partial is in that layout too; center and out never are).
+constexpr int kSumsBlock = 32;       // columns per block: part of the definition (include/ebm_hip.h)
+struct EnsembleSumsArgs {
+    const double *row[kMaxQuantities];
+    unsigned split_mask;
+    const double *w;                 // [ncol], finite; never written by a kernel
+    const double *center;            // [nvars][pitch], natural layout, or null: nothing is subtracted
+    double *partial;                 // [nblocks][nvars][3][pitch]
+    double *out;                     // [nvars][3][nlat], natural
+    int pitch, nlat, ncol, nvars, nblocks, threads;
+};
+hipError_t launch_ensemble_sums(const EnsembleSumsArgs &a, hipStream_t s);
 
 }  // namespace ebm

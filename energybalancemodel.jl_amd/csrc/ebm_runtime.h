@@ -172,6 +172,11 @@ struct ebm_ctx {
         Event uploaded;
         bool in_flight = false;
     } resample;
+    // ebm_ensemble_sums, kept between calls: the block partials, the uploaded weights and centers ([nvars][pitch], padding
+    // zero) and the result of the host variant
+    struct EnsembleSums {
+        DevVec<double> partial, w, center, out;
+    } sums;
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
     DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
     ~ebm_ctx();

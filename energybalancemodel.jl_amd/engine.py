@@ -185,6 +185,54 @@ class Engine:
         check(self.lib.ebm_hemispheric_mean_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),
               "ebm_hemispheric_mean_device")
 
+    def _check_sums_args(self, names, weights=None, center=None):
+        """The host-side checks of ``ensemble_sums`` (no device call): returns (names, field ids, weights [ncol] or None,
+        center [nvars, nlat] or None) as contiguous float64 arrays."""
+        if isinstance(names, str):
+            names = (names,)
+        names = tuple(names)
+        allowed = self.prognostic + self.diagnostic
+        if not 1 <= len(names) <= 12:
+            raise ValueError(f"names: expected between 1 and 12 fields of the {self.model} model")
+        for n in names:
+            if n not in allowed:
+                raise ValueError(f"names: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
+                                 "the warm start T0 is not a solution variable)")
+        if len(set(names)) != len(names):
+            raise ValueError(f"names: a field is listed twice in {names}")
+        w = None if weights is None else as_f64(weights, (self.ncol,))
+        if w is not None and not np.isfinite(w).all():
+            c = int(np.flatnonzero(~np.isfinite(w))[0])
+            raise ValueError(f"weights[{c}] = {w[c]} is not finite (negative and zero weights are legal)")
+        ctr = None if center is None else as_f64(center, (len(names), self.nlat))
+        if ctr is not None and not np.isfinite(ctr).all():
+            raise ValueError("center: expected finite values")
+        return names, [FIELD[n] for n in names], w, ctr
+
+    def ensemble_sums(self, names, weights=None, center=None) -> np.ndarray:
+        """ebm_ensemble_sums (the definition is in include/ebm_hip.h): the weighted sums ACROSS the columns, per latitude,
+        reduced on the device — ndarray [len(names), 3, nlat] of S0 = sum w_c, S1 = sum w_c d and S2 = sum (w_c d) d with
+        d = x - center[v, k] (d = x without ``center``), over the columns with w_c != 0 whose cell is not NaN (the sentinels
+        of Ti and Tw; a zero weight removes the member; +-Inf propagates).  ``weights`` [ncol] (None: all 1.0; negative ones
+        are legal), ``center`` [len(names), nlat].  Every product and sum is rounded once, in a fixed order — blocks of 32
+        columns in ascending column order, then the block partials in ascending order — so the bits do not depend on the run,
+        the launch geometry or the layout the handle holds the rows in; no field is converted.  StaleFieldError for a stale
+        diagnostic field, as ``hemispheric_mean``.  The step clock, the counters and ``field_step`` are unchanged."""
+        names, ids, w, ctr = self._check_sums_args(names, weights, center)
+        out = np.full((len(names), 3, self.nlat), np.nan)
+        check(self.lib.ebm_ensemble_sums(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), dptr(out)),
+              "ebm_ensemble_sums")
+        return out
+
+    def ensemble_sums_device(self, names, dev_ptr: int, weights=None, center=None):
+        """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()``
+        of a torch tensor on this engine's device: the payload of an all-reduce between shards)."""
+        names, ids, w, ctr = self._check_sums_args(names, weights, center)
+        if not isinstance(dev_ptr, (int, np.integer)) or isinstance(dev_ptr, (bool, np.bool_)) or int(dev_ptr) == 0:
+            raise ValueError(f"dev_ptr: expected a device address (int), got {dev_ptr!r}")
+        check(self.lib.ebm_ensemble_sums_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr),
+                                                C.c_void_p(int(dev_ptr))), "ebm_ensemble_sums_device")
+
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""
         check(self.lib.ebm_get_field_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),

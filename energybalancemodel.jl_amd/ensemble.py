@@ -289,7 +289,86 @@ class ColumnExchange:
         self.resample_import(plan, received, mask)
 
 
-class EnsembleRun(ColumnExchange):
+# ---- moments across the members ------------------------------------------------------------------------------------------------
+# ebm_ensemble_sums reduces across the columns on the device: S0 = sum w, S1 = sum w d, S2 = sum (w d) d per latitude, d = x -
+# center.  The arithmetic from sums to moments is host NumPy on O(nlat) numbers.
+
+def moments_from_sums(sums1, sums2=None) -> dict:
+    """Mean and variance from the packed sums [..., 3, nlat] of ebm_ensemble_sums, in two passes: ``sums1`` taken with
+    ``center=None`` gives ``weight = S0`` and ``mean = S1 / S0``; ``sums2`` taken with ``center = mean`` (``moments_center``)
+    gives ``var = S2 / S0 - (S1 / S0) ** 2``, whose second term is of rounding size by construction (S1 is then the sum of the
+    deviations from the mean).  A latitude with S0 == 0 — no contributing member — gives NaN mean and variance.  Without
+    ``sums2`` the variance is left out.  Pure NumPy (no device call)."""
+    a = np.asarray(sums1, dtype=np.float64)
+    if a.ndim < 2 or a.shape[-2] != 3:
+        raise ValueError(f"sums1: expected [..., 3, nlat] (S0, S1, S2), got shape {a.shape}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s0 = a[..., 0, :]
+        out = dict(weight=s0.copy(), mean=np.where(s0 == 0.0, np.nan, a[..., 1, :] / s0))
+        if sums2 is not None:
+            b = np.asarray(sums2, dtype=np.float64)
+            if b.shape != a.shape:
+                raise ValueError(f"sums2: expected the shape of sums1 {a.shape}, got {b.shape}")
+            t0 = b[..., 0, :]
+            m1 = b[..., 1, :] / t0
+            out["var"] = np.where(t0 == 0.0, np.nan, b[..., 2, :] / t0 - m1 * m1)
+    return out
+
+
+def moments_center(mean) -> np.ndarray:
+    """The ``center`` of the second pass: ``mean`` with 0.0 where it is not finite (a latitude without a contributor has no
+    mean, and a center must be finite; that latitude's variance is NaN whatever is subtracted)."""
+    m = np.asarray(mean, dtype=np.float64)
+    return np.ascontiguousarray(np.where(np.isfinite(m), m, 0.0))
+
+
+class EnsembleMoments:
+    """Moments across the members in terms of two methods of the class it is mixed into: ``ensemble_sums(names, weights,
+    center) -> ndarray [nvars, 3, nlat]`` and ``ensemble_sums_tensor(names, weights, center)``, the same as a device tensor.
+    EnsembleRun is one."""
+
+    def reduced_sums(self, names, weights=None, center=None, dist=None) -> np.ndarray:
+        """This shard's packed sums, all-reduced (SUM) over the ranks of ``dist``: with the "nccl" backend (RCCL) the payload
+        is the device tensor the reduction wrote and comes to the host once, afterwards; with any other backend (gloo) it is
+        staged on the CPU, as ``gather_columns`` does.  With ``dist`` absent or a world of one: the shard's own sums."""
+        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+            return self.ensemble_sums(names, weights, center)
+        import torch
+        if _backend(dist) == "nccl":
+            t = self.ensemble_sums_tensor(names, weights, center)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            return t.cpu().numpy()
+        t = torch.from_numpy(np.ascontiguousarray(self.ensemble_sums(names, weights, center)))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.numpy()
+
+    def moments(self, names=("T", "phi"), weights=None, dist=None) -> dict:
+        """Weighted mean and variance ACROSS the members, per latitude, of every field in ``names``: ``{name: {"weight": S0,
+        "mean": ..., "var": ...}}``, each [nlat].  Two passes of ebm_ensemble_sums, reduced on the device — O(nlat) numbers
+        leave it, never the fields: pass 1 without a center gives ``mean = S1 / S0``; pass 2 centered on that mean gives
+        ``var = S2 / S0 - (S1 / S0) ** 2`` (``moments_from_sums``).  ``weights`` [ncol of this shard]: None for the plain
+        ensemble mean, zeros to leave members out (the mean ice profile of the members that tipped), importance weights
+        such as ``gklt_estimate``'s exp(-k * score_sum) for the mean under the untilted dynamics; negative weights are
+        legal.  A member contributes at a latitude iff its weight is not 0 and its cell is not NaN (the "no ice / no water
+        here" sentinels of Ti and Tw); a latitude with S0 == 0 has NaN mean and variance.
+        With ``dist`` the packed sums of the shards are all-reduced (SUM) between and after the passes (``reduced_sums``), so
+        every rank returns the moments of the whole ensemble.  Each shard's own sums are defined to the bit (blocks of 32
+        members in ascending order, then the blocks in ascending order).  Across shards the sums are added in another order
+        than the unsharded call adds them, so they are not equal bit for bit: a term of a call over m members passes through
+        at most D(m) = min(m, 32) + ceil(m / 32) - 2 rounded adds and the combination of n shards adds n - 1 more, so the
+        combined sums agree with the unsharded ones to within (D(ncol) + max_r D(ncol_r) + n - 1) * 2^-53 * sum|terms| per
+        latitude, ncol_r the members of shard r."""
+        if isinstance(names, str):
+            names = (names,)
+        names = tuple(names)
+        s1 = np.asarray(self.reduced_sums(names, weights, None, dist))
+        center = moments_center(moments_from_sums(s1)["mean"])
+        s2 = np.asarray(self.reduced_sums(names, weights, center, dist))
+        m = moments_from_sums(s1, s2)
+        return {n: {k: m[k][i] for k in ("weight", "mean", "var")} for i, n in enumerate(names)}
+
+
+class EnsembleRun(ColumnExchange, EnsembleMoments):
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
     ``init`` maps prognostic names to [ncol, nlat] arrays (or [nlat], broadcast to all
@@ -529,6 +608,20 @@ class EnsembleRun(ColumnExchange):
         import torch
         out = torch.empty(self.ncol, dtype=torch.float64, device=torch.device("cuda", self.device))
         self.engine.hemispheric_mean_device(name, out.data_ptr())
+        return out
+
+    def ensemble_sums(self, names, weights=None, center=None):
+        """This shard's weighted sums across its members, per latitude (ebm_ensemble_sums): ndarray [len(names), 3, nlat] of
+        S0, S1, S2, reduced on the device.  See ``Engine.ensemble_sums``; ``moments`` turns them into mean and variance."""
+        return self.engine.ensemble_sums(names, weights, center)
+
+    def ensemble_sums_tensor(self, names, weights=None, center=None):
+        """The same sums as a float64 torch tensor [len(names), 3, nlat] ON THE DEVICE — written there by
+        ebm_ensemble_sums_device, never staged through the host — ready to be all-reduced over RCCL (``reduced_sums``)."""
+        import torch
+        nv = 1 if isinstance(names, str) else len(tuple(names))
+        out = torch.empty((nv, 3, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        self.engine.ensemble_sums_device(names, out.data_ptr(), weights, center)
         return out
 
     def field_tensor(self, name):

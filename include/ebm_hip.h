@@ -157,7 +157,7 @@ const char *ebm_version(void);
  * T, h) and the fp64 warm start EBM_F_T0 are written only by steps that were asked to (ebm_step with
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
- * ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
+ * ebm_ensemble_sums*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
  * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
@@ -542,6 +542,57 @@ int ebm_resample_columns(ebm_handle_t h, const int *parent);
 int ebm_column_record(ebm_handle_t h, long long *record_doubles, unsigned *current_mask);
 int ebm_export_columns(ebm_handle_t h, int n, const int *cols, double *dev_buf, unsigned *mask);
 int ebm_import_columns(ebm_handle_t h, int n, const int *cols, const int *records, const double *dev_buf, unsigned mask);
+
+/* WEIGHTED SUMS ACROSS THE MEMBERS, per latitude: the column-wise partner of ebm_hemispheric_mean — the ensemble mean T(x)
+ * and its spread, the mean ice profile of the members that tipped, a mean under importance weights — reduced on the device,
+ * so that O(nlat) doubles cross the bus, or enter an all-reduce between shards, instead of O(state).  THIS TEXT IS THE
+ * DEFINITION.
+ *   Arguments.  fields[nvars]: solution variables of the model, prognostic or diagnostic, each at most once; EBM_F_T0 is not
+ *     one; 1 <= nvars <= 12 (the rules of ebm_run_series).  w[ncol]: host array of member weights, NULL = every w_c = 1.0.
+ *     center[nvars][nlat]: host array in natural latitude order, NULL = nothing is subtracted.  out[nvars][3][nlat]: S0, S1
+ *     and S2 in natural latitude order, on the host; the _device variant writes the same packed array into the caller's
+ *     device buffer dev_out (the payload of an all-reduce).
+ *   Terms.  For variable v, latitude k < nlat and column c, with x the value of field fields[v] of column c at k: the column
+ *     CONTRIBUTES at k iff w_c != 0.0 and x is not NaN.  The NaN sentinels of Ti and Tw (src/miz.jl:193-194) mean "no ice / no
+ *     water here"; a zero weight removes the member altogether, which is how a conditional mean over a sub-ensemble is taken
+ *     (its cells may hold anything, Inf included); +-Inf in a contributing cell is data and propagates.  d = x - center[v][k],
+ *     or d = x when center is NULL.  The three terms are t0 = w_c, t1 = w_c * d and t2 = (w_c * d) * d: every product and every
+ *     sum is rounded once, nothing is contracted into a fused multiply-add.
+ *   Order.  Block b holds the columns 32 b ... min(32 b + 31, ncol - 1).  The block partial of each of S0, S1, S2 starts at
+ *     0.0 and adds the terms of the contributing columns of the block in ascending column order.  The result starts at 0.0
+ *     and adds the block partials in ascending b; a block without a contributor adds its 0.0.  The order is part of the
+ *     definition: the same call gives the same bits on every run, under either launch geometry (cells_per_thread) and in
+ *     either stored layout, and no floating-point atomic is involved.  A latitude without a contributor gives S0 = S1 = S2 =
+ *     0.0.  Mean and variance are the caller's arithmetic: with center NULL, mean = S1 / S0; with center = that mean,
+ *     var = S2 / S0 - (S1 / S0)^2, whose second term is then of rounding size.
+ *   Across shards.  Each shard's sums are defined to the bit.  Adding the sums of n shards adds the same terms in another
+ *     order than the unsharded call does, so the two are not equal bit for bit.  A term of a call over m columns passes
+ *     through at most D(m) = min(m, 32) + ceil(m / 32) - 2 rounded adds (inside its block, then over the blocks; an add to
+ *     0.0 is exact), and the combination of n shards adds n - 1 more: per latitude the two agree to within
+ *     (D(ncol) + max_r D(ncol_r) + n - 1) * 2^-53 * (sum of |terms|), to first order in 2^-53, ncol_r the columns of shard r.
+ *   Validity.  A diagnostic field that is older than the state fails with EBM_ERR_STALE exactly as ebm_hemispheric_mean does
+ *     (the same message).  If phi is among the fields and state-only one-step launches have left it underived, it is made
+ *     current first, as ebm_export_columns does.
+ *   Layout.  The reduction is elementwise along latitude, so rows are read in whatever layout the handle holds them (the
+ *     layout private to the one-step MIZ kernel at four cells per thread, the natural one otherwise); only the indexing of
+ *     center and of the output is un-permuted.  No field is converted: ebm_state_conversions does not grow, and a steady ebm_run
+ *     loop with this call between its calls still converts once.  Cells between nlat and the row pitch are never read into
+ *     a result (for odd nlat the last 16-byte pair is loaded with its padding cell, whose sums are never used).
+ *   Bookkeeping.  The step clock, counters[0..3] and ebm_field_step are unchanged; the two reduction launches are not
+ *     counted.  Both calls are synchronous on the handle's stream, the two launch chains joined first.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle, fields or out, nvars outside 1 ... 12, a field that is
+ * not a solution variable of the model or is listed twice, a non-finite w[c] (the message names the column), a non-finite
+ * center entry; EBM_ERR_STALE as above.  Negative weights are legal (differences of estimators).
+ * How it runs: one kernel forms the block partials — grid (latitude tiles) x (column blocks) x (variables); a lane owns one
+ * 16-byte pair of cells, the unit of the layout permutation, and walks the 32 columns of its block with the loads issued
+ * ahead of the dependent adds, a wave reading whole 128-byte lines; w_c is read once per column through the scalar cache —
+ * and a second one adds the block partials per latitude in ascending order and writes the natural index.  Plain loads and
+ * stores, no LDS, no scratch.  Device memory, kept by the handle and reused: ceil(ncol / 32) * 3 * nvars * pitch doubles of
+ * block partials, the uploaded weights (ncol doubles) and centers (12 * pitch doubles), and 36 * nlat doubles for the host
+ * variant's result. */
+int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *out);
+int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center,
+                             double *dev_out);
 
 int ebm_sync(ebm_handle_t h);
 

@@ -326,4 +326,36 @@ function import_columns!(h::Handle, cols::Vector{<:Integer}, devbuf::Ptr{Cdouble
                                                           devbuf::Ptr{Cdouble}, Cuint(mask)::Cuint)::Cint), "ebm_import_columns")
 end
 
+"""
+    ensemble_sums(h, names; ncol, nlat, weights=nothing, center=nothing) -> Array{Float64,3}
+    ensemble_sums_device!(h, names, devout; weights=nothing, center=nothing)
+
+Weighted sums across the columns, per latitude, reduced on the device (`ebm_ensemble_sums`; the definition is in the
+header): `out[k, q, v]` is `S_(q-1)` of variable `names[v]` at latitude `k` — `S0 = sum w`, `S1 = sum w d`,
+`S2 = sum (w d) d` with `d = x - center[k, v]` (`d = x` without `center`) over the columns whose weight is not 0 and whose
+cell is not NaN.  `weights`: `ncol` values (`nothing`: all 1.0); `center`: `nlat x length(names)`.  The order of the sums is
+fixed (blocks of 32 columns), so the bits do not depend on the run, the launch geometry or the layout the handle holds.
+The `_device!` form writes the packed array to the device pointer `devout` (the payload of an all-reduce between shards).
+"""
+function ensemble_sums(h::Handle, names::Vector{Symbol}; ncol::Integer, nlat::Integer, weights=nothing, center=nothing)
+    out = Array{Float64,3}(undef, nlat, 3, length(names))
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    c = center === nothing ? Ptr{Cdouble}(C_NULL) : Matrix{Float64}(center)
+    weights === nothing || length(weights) == ncol || error("weights: expected $ncol values")
+    center === nothing || size(center) == (nlat, length(names)) || error("center: expected $nlat x $(length(names)) values")
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_sums(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, w::Ptr{Cdouble},
+                                                         c::Ptr{Cdouble}, out::Ptr{Cdouble})::Cint), "ebm_ensemble_sums")
+    return out
+end
+
+function ensemble_sums_device!(h::Handle, names::Vector{Symbol}, devout::Ptr{Cdouble}; weights=nothing, center=nothing)
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    c = center === nothing ? Ptr{Cdouble}(C_NULL) : Matrix{Float64}(center)
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_sums_device(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, w::Ptr{Cdouble},
+                                                                c::Ptr{Cdouble}, devout::Ptr{Cdouble})::Cint),
+                         "ebm_ensemble_sums_device")
+end
+
 end # module EBMHip
