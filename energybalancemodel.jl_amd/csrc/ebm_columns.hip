@@ -228,11 +228,11 @@ int ebm_resample_columns(ebm_handle_t h, const int *parent) {
         hipError_t e = ebm::launch_resample_stage(a, (int)moved, s);
         return e == hipSuccess ? ebm::launch_resample_scatter(a, (int)moved, s) : e;
     };
-    // whole rows in whatever layout they are held (state_split, diag_split stay); a stale field is not copied and stays stale
+    // whole rows in whatever layout they are held (the book hears nothing); a stale field is not copied and stays stale
     a.row_stride = h->pitch / 2;
     a.units = (int)(h->pitch / 2);
     for (int f = 0; f < EBM_F_COUNT; ++f) {
-        if (!has_field(h, f) || (is_diagnostic(h, f) && h->written_epoch[f] != h->epoch)) continue;
+        if (!(h->book.current_mask() >> f & 1u)) continue;
         a.rows = reinterpret_cast<uint4 *>(h->field[f]);
         hipError_t e = two_passes();
         if (e != hipSuccess) return hip_fail("ebm_resample_columns", e);
@@ -265,12 +265,12 @@ struct RecordShape {
 RecordShape record_shape(const ebm_ctx *h) {
     RecordShape r;
     for (int f = 0; f < EBM_F_COUNT; ++f) {
-        if (!has_field(h, f)) continue;
+        if (!h->book.has(f)) continue;
         r.field[r.nfields++] = f;
         r.all |= 1u << f;
-        if (!is_diagnostic(h, f)) r.prognostic |= 1u << f;
-        if (!is_diagnostic(h, f) || h->written_epoch[f] == h->epoch) r.current |= 1u << f;
+        if (!h->book.is_diagnostic(f)) r.prognostic |= 1u << f;
     }
+    r.current = h->book.current_mask();
     r.rowlen = (h->nlat + 15) / 16 * 16;                 // whole 128-byte lines; <= pitch (a multiple of 128 cells)
     r.amask_units = h->amask ? h->cfg.threads / 8 : 0;   // a row of `threads` unsigned shorts
     r.doubles = (long long)r.nfields * r.rowlen + 2 * r.amask_units + 2;
@@ -284,7 +284,7 @@ ebm::ExchangeArgs exchange_args(ebm_ctx *h, const RecordShape &r, unsigned moved
         const int f = r.field[s];
         if (!(moved >> f & 1u)) continue;
         a.row[s] = h->field[f];
-        if ((is_split_state_field(h, f) && h->state_split) || (is_split_field(h, f) && h->diag_split)) a.split_mask |= 1u << s;
+        if (h->book.held_split(f)) a.split_mask |= 1u << s;
     }
     a.buf = buf;
     a.record = r.doubles;

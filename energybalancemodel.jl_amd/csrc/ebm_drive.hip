@@ -45,12 +45,6 @@ hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi
     return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, phi_derived, first, count, s)
                                        : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
 }
-// A step launch has been enqueued: what it means for the phi field (ebm_ctx::phi_stored).  Every step kernel leaves Ei, h and
-// the phi it stores — or would have stored — consistent; a launch over a list of active columns says nothing of the others.
-void note_step(ebm_ctx *h, bool phi_derived) {
-    h->phi_stored = !phi_derived;
-    if (!h->active) h->phi_consistent = true;
-}
 // The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate,
 // ebm_run_until), as one chain or split in two halves; a chain with no columns is skipped.
 int chain_count(const ebm_ctx *h, int *first_half) {
@@ -74,23 +68,32 @@ hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_
     if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, phi_derived, half, n - half, h->stream2.get());
     return e;
 }
-// Every step launch of the library goes through here, so the layout rule of the prognostic fields (ebm_ctx::state_split) is
-// applied here: a one-step MIZ launch reads and writes them pair-split, the fused-K and classic kernels the natural layout.
-// A steady run of either kind converts nothing.  Under graph capture the layout is already the one-step one (build_graph).
-// The same place decides about phi: a state-only one-step launch takes the kernel that derives it from Ei and h when the handle
-// has one and the state is consistent; any other one-step launch loads the field, which is restored first if such launches
-// left it stale (the un-split pass before a fused launch does it on the way).  `capturing` (build_graph): nothing but the
-// step launches is enqueued and the handle's bits stay; ebm_run makes the state fit the captured kernels before a replay.
-hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool capturing = false) {
+// `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
+// global step `last_step`; the other arguments are FieldBook::steps'.
+void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived) {
+    int half = 0;
+    h->n_launches += nlaunch * chain_count(h, &half);
+    h->n_steps += nsteps;
+    h->clock = last_step + 1;
+    h->book.steps(nsteps, last_step, wrote_diag, split, phi_derived, !h->active);
+}
+// Every step launch of the library goes through here — a.nfused steps, the last of them global step `last_step` — so here the
+// book is asked (ebm_fieldbook.h): a one-step MIZ launch reads and writes the prognostic fields pair-split, the fused-K and
+// classic kernels the natural layout; a one-step launch that does not derive phi loads the field.  `capturing` (build_graph):
+// nothing but the step launches is enqueued and the book hears nothing; ebm_run makes the state fit the captured kernels
+// before a replay.
+hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode, long long last_step, bool capturing = false) {
     const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
-    const bool phi_derived = mode == ebm::OUT_STATE && h->derive_phi && (capturing || h->phi_consistent);
+    const bool phi_derived = h->book.step_derives_phi(mode, capturing);
     if (!capturing) {
         if (one_step && !phi_derived)
             if (hipError_t e = restore_phi(h); e != hipSuccess) return e;
         if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
     }
     hipError_t e = launch_chains(h, a, mode, phi_derived);
-    if (e == hipSuccess && !capturing) note_step(h, phi_derived);
+    // the 4-cells-per-thread MIZ one-step kernels leave the diagnostic fields pair-split, the fused kernels natural
+    if (e == hipSuccess && !capturing)
+        record_launches(h, 1, a.nfused, last_step, a.write_diag != 0, one_step && h->cfg.cells == 4, phi_derived);
     return e;
 }
 
@@ -108,7 +111,7 @@ int build_graph(ebm_ctx *h) {
         a.sched = g.sched.get();
         a.slot = i;
         a.write_diag = 0;
-        e = launch_step(h, a, ebm::OUT_STATE, true);     // the deriving kernel where the handle has it
+        e = launch_step(h, a, ebm::OUT_STATE, 0, true);  // the deriving kernel where the handle has it
     }
     hipError_t e2 = hipStreamEndCapture(main_stream(h), &graph);
     if (e != hipSuccess || e2 != hipSuccess) {
@@ -142,24 +145,6 @@ void fill_sched(const ebm_ctx *h, long long tab_first, long long clock_first, in
     }
 }
 
-// `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
-// global step `last_step`.  wrote_diag: the last one stored the diagnostic fields, pair-split if `split` (MIZ).
-void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split) {
-    int half = 0;
-    h->n_launches += nlaunch * chain_count(h, &half);
-    h->n_steps += nsteps;
-    h->clock = last_step + 1;
-    h->epoch += nsteps;
-    h->state_step = last_step;
-    if (!wrote_diag) return;
-    for (int f = 0; f < EBM_F_COUNT; ++f)
-        if (has_field(h, f) && is_diagnostic(h, f)) {
-            h->written_epoch[f] = h->epoch;
-            h->written_step[f] = last_step;
-        }
-    if (h->model == EBM_MODEL_MIZ) h->diag_split = split;
-}
-
 // savesol! fused into a step launch (ebm::OUT_SAVE): where the running sums and the raw snapshot go
 struct SaveTarget {
     double *sums = nullptr;
@@ -183,11 +168,8 @@ int do_step(ebm_ctx *h, double ct, double ct_next, double f, int write_diag, lon
     a.tyear = year_time(h, step);
     a.step = step;
     if (save) save->put(a, false);
-    hipError_t e = launch_step(h, a, save ? ebm::OUT_SAVE : write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE);
-    if (e != hipSuccess) return hip_fail("kernel launch", e);
-    // the 4-cells-per-thread MIZ step kernels leave the diagnostic fields pair-split (ensure_natural undoes it)
-    record_launches(h, 1, 1, step, write_diag != 0, h->cfg.cells == 4);
-    return EBM_OK;
+    hipError_t e = launch_step(h, a, save ? ebm::OUT_SAVE : write_diag ? ebm::OUT_DIAG : ebm::OUT_STATE, step);
+    return e == hipSuccess ? EBM_OK : hip_fail("kernel launch", e);
 }
 
 // A caller's list of solution variables (ebm_run_series, ebm_integrate, ebm_equilibrate): each a field of this model, a
@@ -200,11 +182,11 @@ int resolve_fields(const ebm_ctx *h, const char *who, int nvars, const int *fiel
     bool listed[EBM_F_COUNT] = {};
     for (int v = 0; v < nvars; ++v) {
         const int f = fields[v];
-        if (!has_field(h, f) || quantity_of(h->model, f) < 0)
+        if (!h->book.has(f) || quantity_of(h->model, f) < 0)
             return fail(EBM_ERR_ARG, std::string(who) + ": fields[" + std::to_string(v) + "] is not a solution variable of this model");
         if (listed[f]) return fail(EBM_ERR_ARG, std::string(who) + ": field " + field_name(f) + " is listed twice");
         listed[f] = true;
-        out[v] = {f, slot_of(h->model, f), quantity_of(h->model, f), is_diagnostic(h, f)};
+        out[v] = {f, slot_of(h->model, f), quantity_of(h->model, f), h->book.is_diagnostic(f)};
     }
     return EBM_OK;
 }
@@ -289,9 +271,7 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
         // per step); the per-step scalars travel through a small device table
         int rc = h->graph.exec ? EBM_OK : build_graph(h);
         if (rc) return rc;
-        // the captured launches derive phi where the handle can (launch_step): a state somebody else wrote takes the call's
-        // first step directly, with the phi that is stored, and is consistent from then on
-        if (h->derive_phi && !h->phi_consistent && nsteps > (diag_last ? 1 : 0)) {
+        if (h->book.replay_needs_a_direct_step() && nsteps > (diag_last ? 1 : 0)) {
             const long long ti = first_step % nt;
             if ((rc = do_step(h, h->ttab[ti], h->ttab[(ti + 1) % nt], f_steps ? f_steps[0] : 0.0, 0, first_step))) return rc;
             s = 1;
@@ -305,8 +285,8 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
                                   hipMemcpyHostToDevice, main_stream(h)));
             if ((rc = set_state_layout(h, true))) return rc;       // the captured launches expect the one-step layout
             HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
-            record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false);
-            note_step(h, h->derive_phi);
+            record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false,
+                            h->book.step_derives_phi(ebm::OUT_STATE, true));
         }
     }
     for (; s < nsteps; ++s) {
@@ -351,10 +331,8 @@ static int fused_range(ebm_ctx *h, long long tab_first, long long clock_first, i
             a.prefetch = 0;
             a.write_diag = (diag_last && s0 + i + a.nfused == nsteps) ? 1 : 0;
             if (save) save->put(a, true);
-            hipError_t e = launch_step(h, a, save ? ebm::OUT_LOOP_SAVE : ebm::OUT_LOOP);
+            hipError_t e = launch_step(h, a, save ? ebm::OUT_LOOP_SAVE : ebm::OUT_LOOP, clock_first + s0 + i + a.nfused - 1);
             if (e != hipSuccess) return hip_fail("fused launch", e);
-            // the fused kernels store the diagnostic fields in the natural layout
-            record_launches(h, 1, a.nfused, clock_first + s0 + i + a.nfused - 1, a.write_diag != 0, false);
         }
         HIPCHK(hipEventRecord(tb.done.get(), main_stream(h)));     // (both launch chains, joined)
         tb.in_use = true;

@@ -9,34 +9,29 @@ using namespace ebm_rt;
 
 namespace ebm_rt {
 
-// Readers of a diagnostic field get the natural layout: un-permute in place once after a step that stored them split.
-int ensure_natural(ebm_ctx *h) {
-    if (!h->diag_split) return EBM_OK;
-    hipError_t e = ebm::launch_unsplit_fields(h->field[EBM_F_Tw], h->fstride, 5, h->ncol, h->cfg, main_stream(h));
-    if (e != hipSuccess) return hip_fail("unsplit_fields", e);
-    h->diag_split = false;
-    return EBM_OK;
+// The one executor of the book's passes (Pass, ebm_fieldbook.h): in place, on the handle's stream — which joins the two launch
+// chains first (main_stream), so every column's last step has ended; never inside a graph capture (build_graph and ebm_run
+// convert before they capture / replay).  The book hears of the pass only if it was enqueued.
+static hipError_t exec_pass(ebm_ctx *h, Pass p) {
+    double *const prog = h->field[EBM_F_Ei], *const diag = h->field[EBM_F_Tw];     // Ei .. phi: slots 0 .. 4; Tw .. T: 6 .. 10
+    hipError_t e = hipSuccess;
+    switch (p) {
+        case Pass::NONE: return hipSuccess;
+        case Pass::SPLIT_STATE: e = ebm::launch_split_fields(prog, h->fstride, 5, h->ncol, h->cfg, main_stream(h)); break;
+        case Pass::UNSPLIT_STATE: e = ebm::launch_unsplit_fields(prog, h->fstride, 5, h->ncol, h->cfg, main_stream(h)); break;
+        case Pass::UNSPLIT_STATE_FORM_PHI: e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, true, main_stream(h)); break;
+        case Pass::RESTORE_PHI: e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, false, main_stream(h)); break;
+        case Pass::UNSPLIT_DIAG: e = ebm::launch_unsplit_fields(diag, h->fstride, 5, h->ncol, h->cfg, main_stream(h)); break;
+    }
+    if (e == hipSuccess) h->book.done(p);
+    return e;
 }
 
-// The prognostic fields in the layout that whoever touches them next expects (ebm_ctx::state_split): pair-split for a
-// one-step launch at four cells per thread, natural for everybody else.  In place, on the handle's stream — which joins the
-// two launch chains first (main_stream), so every column's last step has ended; never inside a graph capture (build_graph
-// and ebm_run convert before they capture / replay).
-hipError_t convert_state(ebm_ctx *h, bool split) {
-    if (h->model != EBM_MODEL_MIZ || h->cfg.cells != 4) split = false;      // no second layout: classic; the pair is the chunk
-    if (h->state_split == split) return hipSuccess;
-    double *first = h->field[EBM_F_Ei];                  // Ei, Ew, h, D, phi: slots 0 .. 4
-    hipError_t e;
-    if (split) e = ebm::launch_split_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
-    // (one-step launches that did not store phi: the un-split pass forms it from Ei and h instead of moving it)
-    else if (!h->phi_stored) e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, true, main_stream(h));
-    else e = ebm::launch_unsplit_fields(first, h->fstride, 5, h->ncol, h->cfg, main_stream(h));
-    if (e != hipSuccess) return e;
-    h->phi_stored = true;
-    h->state_split = split;
-    h->n_conversions += 1;
-    return hipSuccess;
+int ensure_natural(ebm_ctx *h) {
+    hipError_t e = exec_pass(h, h->book.diag_layout_natural());
+    return e == hipSuccess ? EBM_OK : hip_fail("unsplit_fields", e);
 }
+hipError_t convert_state(ebm_ctx *h, bool split) { return exec_pass(h, h->book.state_layout(split)); }
 int set_state_layout(ebm_ctx *h, bool split) {
     hipError_t e = convert_state(h, split);
     return e == hipSuccess ? EBM_OK : hip_fail("state layout conversion", e);
@@ -48,18 +43,11 @@ int natural_layout(ebm_ctx *h, bool diagnostics_too) {
         if (int rc = ensure_natural(h)) return rc;
     return set_state_layout(h, false);
 }
-
-hipError_t restore_phi(ebm_ctx *h) {
-    if (h->phi_stored) return hipSuccess;
-    // (stale only between one-step launches: the fields are pair-split)
-    hipError_t e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, false, main_stream(h));
-    if (e == hipSuccess) h->phi_stored = true;
-    return e;
-}
+hipError_t restore_phi(ebm_ctx *h) { return exec_pass(h, h->book.phi_readable()); }
 int state_written_outside(ebm_ctx *h) {
     hipError_t e = restore_phi(h);
     if (e != hipSuccess) return hip_fail("phi restore", e);
-    h->phi_consistent = false;
+    h->book.written_outside();
     return EBM_OK;
 }
 
@@ -80,13 +68,12 @@ namespace {
 // current (check_current; ebm_get_field_as_of has its own rule here); the handle's device and the natural layout (make_readable).
 int check_field(const ebm_ctx *h, int field, const void *out, const char *who) {
     if (!h || !out) return fail(EBM_ERR_ARG, std::string(who) + ": null argument");
-    if (!has_field(h, field)) return fail(EBM_ERR_ARG, std::string(who) + ": field not part of this model");
+    if (!h->book.has(field)) return fail(EBM_ERR_ARG, std::string(who) + ": field not part of this model");
     return EBM_OK;
 }
 int make_readable(ebm_ctx *h, int field) {
     HIPCHK(hipSetDevice(h->device));
-    if (is_split_state_field(h, field)) return set_state_layout(h, false);
-    return is_split_field(h, field) ? ensure_natural(h) : EBM_OK;
+    return h->book.is_split_state_field(field) ? set_state_layout(h, false) : h->book.is_split_field(field) ? ensure_natural(h) : EBM_OK;
 }
 int open_field(ebm_ctx *h, int field, const void *out, const char *who) {
     int rc = check_field(h, field, out, who);
@@ -133,7 +120,7 @@ int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, con
     if (nvars < 1 || nvars > ebm::kMaxQuantities)
         return fail(EBM_ERR_ARG, me + ": nvars = " + std::to_string(nvars) + " is outside 1 ... " + std::to_string(ebm::kMaxQuantities));
     for (int v = 0; v < nvars; ++v) {
-        if (!has_field(h, fields[v]) || quantity_of(h->model, fields[v]) < 0)
+        if (!h->book.has(fields[v]) || quantity_of(h->model, fields[v]) < 0)
             return fail(EBM_ERR_ARG, me + ": fields[" + std::to_string(v) + "] is not a solution variable of this model");
         for (int u = 0; u < v; ++u)
             if (fields[u] == fields[v]) return fail(EBM_ERR_ARG, me + ": field " + field_name(fields[v]) + " is listed twice");
@@ -172,7 +159,7 @@ int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, con
     for (int v = 0; v < nvars; ++v) {
         const int f = fields[v];
         a.row[v] = h->field[f];                          // where it lies: no field is converted
-        if ((is_split_state_field(h, f) && h->state_split) || (is_split_field(h, f) && h->diag_split)) a.split_mask |= 1u << v;
+        if (h->book.held_split(f)) a.split_mask |= 1u << v;
     }
     a.w = b.w.get();
     a.center = center ? b.center.get() : nullptr;
@@ -242,13 +229,14 @@ int ebm_set_field(ebm_handle_t h, int field, const double *host) {
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     if ((rc = get_copier(h))) return rc;
-    if (is_split_field(h, field)) {
+    const bool prognostic = h->book.is_split_state_field(field);
+    if (h->book.is_split_field(field)) {
         rc = ensure_natural(h);                   // the other diagnostic fields keep their values, in the natural layout
         if (rc) return rc;
     }
-    if (is_split_state_field(h, field) && (rc = set_state_layout(h, false))) return rc;     // ... and so do the prognostic ones
+    if (prognostic && (rc = set_state_layout(h, false))) return rc;     // ... and so do the prognostic ones
     // a caller's Ei, h or phi is honoured as it is: the next step loads phi (any prognostic field counts: when in doubt)
-    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;
+    if (prognostic && (rc = state_written_outside(h))) return rc;
     HIPCHK(hipStreamSynchronize(main_stream(h)));
     HIPCHK(h->copier->wait_all());
     HIPCHK(h->copier->upload(h->field[field], (size_t)h->pitch, host, (size_t)h->nlat, (size_t)h->ncol));
@@ -258,12 +246,7 @@ int ebm_set_field(ebm_handle_t h, int field, const double *host) {
         if (e != hipSuccess) return hip_fail("mask_from_t0", e);
         HIPCHK(hipStreamSynchronize(main_stream(h)));
     }
-    if (is_diagnostic(h, field)) {                // the caller's statement of what the field holds: current as of now
-        h->written_epoch[field] = h->epoch;
-        h->written_step[field] = h->state_step;
-    } else {
-        h->epoch += 1;                            // the prognostic state changed: every diagnostic field is older than it now
-    }
+    h->book.field_set(field);
     return EBM_OK;
 }
 
@@ -275,7 +258,7 @@ int ebm_get_field(ebm_handle_t h, int field, double *host) {
 int ebm_get_field_as_of(ebm_handle_t h, int field, long long step, double *host) {
     int rc = check_field(h, field, host, "ebm_get_field_as_of");
     if (rc) return rc;
-    const long long have = is_diagnostic(h, field) ? (h->written_epoch[field] >= 0 ? h->written_step[field] : -2) : h->state_step;
+    const long long have = h->book.written_step(field, -2);
     if (have != step)
         return fail(EBM_ERR_STALE, std::string("ebm_get_field_as_of: field ") + field_name(field) + " is not as of step " +
                                        std::to_string(step) + (have == -2 ? " (it has never been written)"
@@ -286,11 +269,10 @@ int ebm_get_field_as_of(ebm_handle_t h, int field, long long step, double *host)
 
 int ebm_field_step(ebm_handle_t h, int field, long long *written_step, long long *state_step, int *current) {
     if (!h) return fail(EBM_ERR_ARG, "ebm_field_step: null handle");
-    if (!has_field(h, field)) return fail(EBM_ERR_ARG, "ebm_field_step: field not part of this model");
-    const bool diag = is_diagnostic(h, field);
-    if (written_step) *written_step = diag ? (h->written_epoch[field] >= 0 ? h->written_step[field] : -1) : h->state_step;
-    if (state_step) *state_step = h->state_step;
-    if (current) *current = (!diag || h->written_epoch[field] == h->epoch) ? 1 : 0;
+    if (!h->book.has(field)) return fail(EBM_ERR_ARG, "ebm_field_step: field not part of this model");
+    if (written_step) *written_step = h->book.written_step(field);
+    if (state_step) *state_step = h->book.state_step();
+    if (current) *current = h->book.is_current(field) ? 1 : 0;
     return EBM_OK;
 }
 
@@ -333,9 +315,9 @@ int ebm_field_device_ptr(ebm_handle_t h, int field, double **dptr, long long *pi
     int rc = open_field(h, field, dptr, "ebm_field_device_ptr");
     if (rc) return rc;
     // (the caller may write through the view of a prognostic field)
-    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;
+    if (h->book.is_split_state_field(field) && (rc = state_written_outside(h))) return rc;
     // the view is of the natural layout as of this call
-    if (is_split_field(h, field) || is_split_state_field(h, field)) HIPCHK(hipStreamSynchronize(main_stream(h)));
+    if (h->book.is_split_field(field) || h->book.is_split_state_field(field)) HIPCHK(hipStreamSynchronize(main_stream(h)));
     *dptr = h->field[field];
     if (pitch) *pitch = h->pitch;
     return EBM_OK;

@@ -1,5 +1,6 @@
 // Shared by the four translation units of the host runtime behind the C ABI of include/ebm_hip.h: the handle, the error
-// idioms, the handle's stream and the field predicates.
+// idioms and the handle's stream.
+//   ebm_fieldbook.h   (HIP-free) the field predicates and THE rule of field validity, layout and phi: ebm_ctx::book
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the two diffusion operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ebm_hip.h"
+#include "ebm_fieldbook.h"
 #include "ebm_hostcopy.h"
 #include "ebm_internal.h"
 
@@ -123,34 +125,9 @@ struct ebm_ctx {
     // ascending) instead of all of them
     const int *active = nullptr;
     int nactive = 0;
-    // Validity of the fields that only some steps write (diagnostics, the fp64 T0): `epoch` counts every change
-    // of the prognostic state (steps taken, prognostic fields overwritten), `state_step` is the global index of
-    // the last step taken (-1: none); a field is current iff written_epoch[f] == epoch.
-    long long epoch = 0, state_step = -1;
-    long long written_epoch[EBM_F_COUNT], written_step[EBM_F_COUNT];
-    // The MIZ step kernels (4 cells per thread) store the five diagnostic fields in the pair-split layout (whole
-    // 128-B lines per store instruction, csrc/ebm_miz_step.h); whoever reads one of them gets the natural layout:
-    // the first reader after such a step runs the in-place un-permutation once.
-    bool diag_split = false;
-    // The same layout holds the five prognostic fields BETWEEN one-step launches at 4 cells per thread (miz_step_kernel
-    // reads and writes them pair-split).  One rule (set_state_layout): the one-step launch path splits them first if they
-    // are natural; every other reader or writer of a prognostic field — field I/O and views, the fused and resident
-    // kernels, series, hemispheric means, snapshots — un-splits them first.  A steady ebm_run / ebm_step loop converts
-    // nothing; n_conversions counts the conversions of a handle (ebm_state_conversions).
-    bool state_split = false;
-    long long n_conversions = 0;
-    // One more bit of the same rule.  A state-only one-step launch of the reference's step at four cells per thread does not
-    // store phi: after any step phi is concentration(Ei, h) of the stored fields, and the kernel forms it from them
-    // (miz_step_kernel, PHI_DERIVED).
-    //   phi_stored       the phi field in HBM is current.  Cleared by such a launch; false only while state_split.
-    //                    Whoever reads phi otherwise restores it first (restore_phi; convert_state folds it into the
-    //                    un-split pass): a restore with the bit set does nothing, a steady run of launches restores nothing.
-    //   phi_consistent   Ei, h and phi were last written by step kernels of this library, so phi IS that function of Ei and
-    //                    h under the column's parameters.  Cleared by every other writer of one of them and by a change of
-    //                    the parameters (state_written_outside); set again by the next step launch over all columns.  Only
-    //                    then may a launch take the deriving kernel; else it steps with the phi the caller left.
-    bool phi_stored = true, phi_consistent = true;
-    bool derive_phi = false;                       // this handle has the deriving kernel (ebm_create: has_phi_derived_kernel)
+    // Which fields are current, which layout device memory holds, whether phi lies in it: every reader and writer of a field
+    // asks the book first and reports to it afterwards (ebm_fieldbook.h; nothing else of the handle holds any of that)
+    ebm_rt::FieldBook book;
     // ebm_zonal_diffusion: the tables of the last nlon used, kept between calls
     struct ZonalTables {
         int nlon = 0, seg = 1;                     // seg: segments a circle is cut into (a function of nlon only)
@@ -198,92 +175,32 @@ inline hipStream_t main_stream(ebm_ctx *h) {
 // st.x on the device (the same in every parameter set)
 inline const double *x_table(const ebm_ctx *h) { return h->geom.get() + (size_t)ebm::G_X * h->gstride; }
 
-// slab slot of a public field id for this model, -1 if the model does not have it
-inline int slot_of(int model, int f) {
-    if (model == EBM_MODEL_MIZ) return (f >= EBM_F_Ei && f <= EBM_F_T) ? f : -1;   // same order
-    switch (f) {
-        case EBM_F_E: return ebm::C_E;
-        case EBM_F_Tg: return ebm::C_Tg;
-        case EBM_F_T: return ebm::C_T;
-        case EBM_F_h: return ebm::C_h;
-        default: return -1;
-    }
-}
-inline bool has_field(const ebm_ctx *h, int f) { return f >= 0 && f < EBM_F_COUNT && slot_of(h->model, f) >= 0; }
-
-// fields that only diagnostic steps write (everything else is prognostic and always current)
-inline bool is_diagnostic(const ebm_ctx *h, int f) {
-    if (h->model == EBM_MODEL_MIZ)
-        return f == EBM_F_T0 || f == EBM_F_Tw || f == EBM_F_Ti || f == EBM_F_n || f == EBM_F_E || f == EBM_F_T;
-    return f == EBM_F_T || f == EBM_F_h;
-}
-// the diagnostic fields that a 4-cells-per-thread MIZ step stores pair-split (ensure_natural)
-inline bool is_split_field(const ebm_ctx *h, int f) {
-    return h->model == EBM_MODEL_MIZ && (f == EBM_F_Tw || f == EBM_F_Ti || f == EBM_F_n || f == EBM_F_E || f == EBM_F_T);
-}
-// the prognostic fields that a 4-cells-per-thread MIZ one-step launch keeps pair-split (set_state_layout)
-inline bool is_split_state_field(const ebm_ctx *h, int f) {
-    return h->model == EBM_MODEL_MIZ && f >= EBM_F_Ei && f <= EBM_F_phi;
-}
-inline const char *field_name(int f) {
-    static const char *names[EBM_F_COUNT] = {"Ei", "Ew", "h", "D", "phi", "T0", "Tw", "Ti", "n", "E", "T", "Tg"};
-    return (f >= 0 && f < EBM_F_COUNT) ? names[f] : "?";
-}
 // EBM_OK if `f` may be read now, else EBM_ERR_STALE with the two steps in the message
 inline int check_current(const ebm_ctx *h, int f, const char *who) {
-    if (!is_diagnostic(h, f) || h->written_epoch[f] == h->epoch) return EBM_OK;
+    const FieldBook &b = h->book;
+    if (b.is_current(f)) return EBM_OK;
     std::string msg = std::string(who) + ": field " + field_name(f) + " is stale — ";
-    if (h->written_epoch[f] < 0) msg += "it has never been written";
-    else if (h->written_step[f] < 0) msg += "it holds what it held before the first step";
-    else msg += "last written by step " + std::to_string(h->written_step[f]);
-    msg += "; the state is at step " + std::to_string(h->state_step) +
-           (h->written_step[f] == h->state_step && h->written_epoch[f] >= 0 ? " with prognostic fields overwritten since" : "") +
+    if (b.never_written(f)) msg += "it has never been written";
+    else if (b.written_step(f) < 0) msg += "it holds what it held before the first step";
+    else msg += "last written by step " + std::to_string(b.written_step(f));
+    msg += "; the state is at step " + std::to_string(b.state_step()) +
+           (!b.never_written(f) && b.written_step(f) == b.state_step() ? " with prognostic fields overwritten since" : "") +
            " (take a step with write_diag / diag_last, or name the step: ebm_get_field_as_of)";
     return fail(EBM_ERR_STALE, msg);
-}
-
-// quantity index (ebm::MizQuantity / ClassicQuantity) of a public field id, -1 if the step kernels
-// do not produce it (the hidden warm start T0 is not a solution variable)
-inline int quantity_of(int model, int f) {
-    if (model == EBM_MODEL_MIZ) {
-        switch (f) {
-            case EBM_F_Ei: return ebm::Q_Ei;
-            case EBM_F_Ew: return ebm::Q_Ew;
-            case EBM_F_h: return ebm::Q_h;
-            case EBM_F_D: return ebm::Q_D;
-            case EBM_F_phi: return ebm::Q_phi;
-            case EBM_F_n: return ebm::Q_n;
-            case EBM_F_E: return ebm::Q_E;
-            case EBM_F_T: return ebm::Q_T;
-            case EBM_F_Ti: return ebm::Q_Ti;
-            case EBM_F_Tw: return ebm::Q_Tw;
-            default: return -1;
-        }
-    }
-    switch (f) {
-        case EBM_F_E: return ebm::QC_E;
-        case EBM_F_Tg: return ebm::QC_Tg;
-        case EBM_F_T: return ebm::QC_T;
-        case EBM_F_h: return ebm::QC_h;
-        default: return -1;
-    }
 }
 
 // what crosses the units
 ebm::StepArgs base_args(const ebm_ctx *h);        // ebm_drive.hip: the launch arguments every step launch starts from
 void invalidate_graph(ebm_ctx *h);                // ebm_drive.hip: drop the captured graph (it holds old argument values)
-int ensure_natural(ebm_ctx *h);                   // ebm_fields.hip: un-permute the diagnostic fields if a step left them split
-// ebm_fields.hip: THE rule of ebm_ctx::state_split — the prognostic fields into the layout their next user expects
-hipError_t convert_state(ebm_ctx *h, bool split);
+// ebm_fields.hip, the executors of the book's passes (FieldBook, ebm_fieldbook.h): each asks the book, launches the pass it
+// names on the handle's stream and reports it done
+int ensure_natural(ebm_ctx *h);                   // the diagnostic fields natural
+hipError_t convert_state(ebm_ctx *h, bool split); // the prognostic fields in the layout their next user expects
 int set_state_layout(ebm_ctx *h, bool split);     // the same, with the error reported (EBM_ERR_HIP)
-// ebm_fields.hip: the prognostic fields natural (set_state_layout(h, false)), after the diagnostic ones if asked (ensure_natural)
-int natural_layout(ebm_ctx *h, bool diagnostics_too);
-// ebm_fields.hip: the phi field current again in whatever layout the state has (ebm_ctx::phi_stored), for readers that take
-// the fields as they lie — a one-step launch that loads phi, resampling, a change of the parameters
+int natural_layout(ebm_ctx *h, bool diagnostics_too);   // the prognostic fields natural, after the diagnostic ones if asked
+// phi current where it lies, for readers that take the fields as they lie: a one-step launch that loads phi, resampling, export
 hipError_t restore_phi(ebm_ctx *h);
-// Ei, h or phi are about to be written by somebody who is not a step kernel, or the parameters they are tied by change:
-// phi is restored under the present ones, then the state no longer counts as consistent (ebm_ctx::phi_consistent)
-int state_written_outside(ebm_ctx *h);
+int state_written_outside(ebm_ctx *h);            // restore_phi, then FieldBook::written_outside
 int get_copier(ebm_ctx *h);                       // ebm_fields.hip: the handle's pinned staging ring, created on first use
 
 }  // namespace ebm_rt

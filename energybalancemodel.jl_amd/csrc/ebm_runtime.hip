@@ -170,12 +170,7 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     auto h = std::make_unique<ebm_ctx>();
     h->model = model; h->grid = grid; h->nlat = nlat; h->ncol = ncol; h->device = device;
     h->dt = dt; h->cfg = cfg; h->imex = imex;
-    h->derive_phi = model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex);
-    for (int f = 0; f < EBM_F_COUNT; ++f) {
-        h->written_epoch[f] = -1;
-        h->written_step[f] = -1;
-    }
-    h->written_epoch[EBM_F_T0] = 0;                       // the warm start begins at zero, like the reference's (src/miz.jl:47)
+    h->book = FieldBook(model, model == EBM_MODEL_MIZ && cfg.cells == 4, model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex));
     h->num_cus = prop.multiProcessorCount;
     choose_heuristics(h.get(), opt);
     h->pitch = (long long)cfg.threads * cfg.cells;     // >= nlat; padding cells stay zero
@@ -227,7 +222,7 @@ int ebm_reset_counters(ebm_handle_t h) {
 
 int ebm_state_conversions(ebm_handle_t h, long long *count) {
     if (!h || !count) return fail(EBM_ERR_ARG, "ebm_state_conversions: null argument");
-    *count = h->n_conversions;
+    *count = h->book.conversions();
     return EBM_OK;
 }
 

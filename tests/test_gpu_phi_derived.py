@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the state-only one-step kernel that derives phi from Ei and h instead of loading and storing it
-(csrc/ebm_miz_step.h, PHI_DERIVED; ebm_ctx::phi_stored / phi_consistent).
+(csrc/ebm_miz_step.h, PHI_DERIVED; FieldBook::phi_stored / phi_consistent, csrc/ebm_fieldbook.h).
 
 After any step phi is concentration(Ei, h) of the stored fields, so nothing a caller can see may change: every comparison
 here is bitwise (uint64 views, NaN patterns included) and sets no tolerance.  The partner is always a path that stores phi:

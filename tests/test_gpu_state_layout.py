@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) of the prognostic fields' second storage layout.
 
 At four cells per thread the one-launch-per-step MIZ kernel keeps Ei, Ew, h, D, phi pair-split in device memory between
-its launches (csrc/ebm_miz_step.h; ebm_ctx::state_split), every other user of those fields sees the natural layout, and
+its launches (csrc/ebm_miz_step.h; FieldBook::state_split), every other user of those fields sees the natural layout, and
 the runtime converts in place between the two.  Every case here runs one sequence of calls twice: as written, so that
 consecutive steps leave the state in the private layout, and with every field read back after every single step, which
 forces the round trip through the natural layout each time (that path is what the parity tests hold against the oracle).
@@ -230,3 +230,104 @@ def test_a_steady_run_converts_once(pkg):
         eng.run(0, 50, None, False)
         eng.get_field("Ei")
         assert eng.state_conversions() == 0                        # two cells per thread: the pair is the chunk
+
+
+# The alphabet of tests/host_fieldbook_main.cpp (the CPU walk of csrc/ebm_fieldbook.h), as calls of the engine
+WALK_EVENTS = ("step_state step_diag step_save graph fused fused_diag fused_active get_prog get_diag get_T0 set_prog set_diag "
+               "view_prog mean resample export import params sums_phi sums_other").split()
+
+
+@pytest.fixture(scope="module")
+def fieldbook_prog(tmp_path_factory):
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path_factory.mktemp("host_fieldbook") / "host_fieldbook")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-o", out, os.path.join(root, "tests", "host_fieldbook_main.cpp")], check=True)
+    return out
+
+
+def play_event(pkg, eng, ev, buf):
+    """One event of the walk on a MIZ engine whose time table has three entries; what the call returned (None: nothing, or
+    the call was refused because the field is stale)."""
+    nlat, ncol = eng.nlat, eng.ncol
+    first = eng.field_step("Ei")["state_step"] + 1
+    tab = lambda i: float(eng.ttab[i % eng.nt])
+    marker = np.arange(ncol * nlat, dtype=np.float64).reshape(ncol, nlat) * 1e-3
+    par = pkg.default_parameters("MIZ")
+    try:
+        if ev in ("step_state", "step_diag"):
+            return eng.step(tab(first), tab(first + 1), 0.0, ev == "step_diag")
+        if ev == "step_save":       # one year of three OUT_SAVE launches, the annual mean only
+            return eng.integrate(3, 1, None, False, 0, 0, ("Ew",), want_raw=False, want_seasonal=False)["avg"]
+        if ev == "graph":           # (use_graph = False: the same 128 steps, launched one by one)
+            return eng.run(first, 128, None, False)
+        if ev in ("fused", "fused_diag"):
+            return eng.run(first, 8, None, ev == "fused_diag", steps_per_launch=4)
+        if ev == "fused_active":    # one round of ebm_run_until that no column ends
+            return eng.run_until(first, 1, 8, "T", np.full(ncol, 1e30), np.ones(ncol, dtype=np.int64), steps_per_launch=4)["value"]
+        if ev in ("get_prog", "get_diag", "get_T0"):
+            return eng.get_field({"get_prog": "phi", "get_diag": "T", "get_T0": "T0"}[ev])
+        if ev == "set_prog":
+            return eng.set_field("h", start_state(pkg, "sin", nlat, ncol)["h"] + 0.5 + marker)
+        if ev == "set_diag":
+            return eng.set_field("T", marker)
+        if ev == "view_prog":
+            eng.field_device_ptr("phi")
+            return None
+        if ev == "mean":
+            return eng.hemispheric_mean("phi")
+        if ev == "resample":
+            return eng.resample_columns(np.array([1, 2, 0]))
+        if ev in ("export", "import"):
+            buf.fill_(float("nan"))
+            mask = eng.export_columns([0, 1, 2], buf.data_ptr())
+            if ev == "import":
+                eng.import_columns([0, 1, 2], buf.data_ptr(), mask, [1, 2, 0])
+            eng.sync()
+            return np.append(buf.cpu().numpy().ravel(), float(mask))
+        if ev == "params":
+            rows = [{"Lf": par["Lf"] * (1.0 + 0.01 * c)} for c in range(ncol)]
+            return eng.set_column_params(pkg.engine.param_matrix(rows, par, pkg.default_parval))
+        if ev in ("sums_phi", "sums_other"):
+            return eng.ensemble_sums(("phi",) if ev == "sums_phi" else ("T",))
+    except pkg.StaleFieldError:
+        return None
+    raise AssertionError(ev)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_random_call_sequences_convert_as_the_cpu_walk_says(pkg, fieldbook_prog, seed):
+    """Twelve calls drawn from the alphabet of the field book's CPU walk (tests/test_host_fieldbook.py), on MIZ, sin grid,
+    nlat = 257 (128 threads: the pitch exceeds nlat), 3 columns, four cells per thread: as written, and with every current
+    field read back after every call.  What the calls return and every field at the end agree bit for bit, and the
+    as-written run converts the state exactly as often as the stand-alone program says for the same sequence: the model the
+    CPU walk checks the book against is the executor that runs here."""
+    import subprocess
+    import torch
+    nlat, ncol = 257, 3
+    seq = [WALK_EVENTS[i] for i in np.random.default_rng(1700 + seed).integers(0, len(WALK_EVENTS), 12)]
+    seen, final, conversions = {}, {}, {}
+    for natural in (False, True):
+        with open_engine(pkg, "MIZ", "sin", nlat, ncol, use_graph=False, integrate_steps_per_launch=1) as eng:
+            eng.set_time_table(space(pkg, "MIZ", "sin", nlat).t[:3])
+            buf = torch.full((ncol, eng.column_record()[0]), float("nan"), dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            before = eng.state_conversions()
+            seen[natural] = []
+            for ev in seq:
+                seen[natural].append(play_event(pkg, eng, ev, buf))
+                if natural:
+                    eng.get_state([k for k in ALL if eng.field_step(k)["current"]])
+            conversions[natural] = eng.state_conversions() - before
+            final[natural] = {k: eng.get_field(k) if eng.field_step(k)["current"] else None for k in ALL}
+    same(final[False], final[True], seq)
+    assert all(final[False][k] is not None for k in PROG)
+    for i, (u, v) in enumerate(zip(seen[False], seen[True])):
+        assert (u is None) == (v is None), (seq, i)
+        assert u is None or np.array_equal(u, v, equal_nan=True), (seq, i)
+    # (open_engine sets the five prognostic fields first: the replay starts from a caller's state too)
+    r = subprocess.run([fieldbook_prog, "replay", "miz4_derive", "set_prog", *seq], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    print(seq, conversions, r.stdout.splitlines()[-1])
+    assert r.stdout.splitlines()[-1] == f"n_conversions {conversions[False]}", (seq, r.stdout)

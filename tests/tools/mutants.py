@@ -78,18 +78,18 @@ MUTANTS = [
     ("warm_start_forgotten", "cmask[tl] = (unsigned short)smask;                // new warm start", "cmask[tl] = (unsigned short)0;                    // new warm start"),
     ("two_cell_geometry_swaps_h_and_D", "EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)",
      "EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_D) EBM_PUT(S_D, Q_h) EBM_PUT(S_phi, Q_phi)"),
-    ("parked_first_pair_takes_D_for_h", "sEw[0] = v0 ? o[0].q[Q_h] : 0.0;  sEw[T] = v1 ? o[1].q[Q_h] : 0.0;", "sEw[0] = v0 ? o[0].q[Q_D] : 0.0;  sEw[T] = v1 ? o[1].q[Q_h] : 0.0;"),
+    # (parked_first_pair_takes_D_for_h left the list with the line it broke: since the prognostic fields lie pair-split between
+    # one-step launches no pair is parked in LDS)
     ("classic_ghost_diagonal_ignores_the_melting_mask", "const double q = bool_mul(bool_mul(ieee_div(p.dc, den), T0 < 0.0), Ek < 0.0);", "const double q = bool_mul(ieee_div(p.dc, den), Ek < 0.0);"),
     ("classic_surface_temperature_sign", "const double T0 = ieee_div(Cc, p.M - ieee_div(p.kLf, Ek));", "const double T0 = ieee_div(Cc, p.M + ieee_div(p.kLf, Ek));"),
     # sixth batch (round 3): the private store layout of the diagnostic fields, validity tracking, launch chains, the pinned
     # ring, model time across integrate calls, the zonal sweep and its tables
-    ("unsplit_writes_the_first_pair_twice", "*reinterpret_cast<double2 *>(f + 4 * t + 2) = p1;", "*reinterpret_cast<double2 *>(f + 4 * t + 2) = p0;"),
-    ("diagnostic_pairs_stored_on_top_of_each_other", "const unsigned ks = (unsigned)(j * 2 * T + 2 * t);", "const unsigned ks = (unsigned)(2 * t);"),
-    ("diagnostic_layout_flag_never_set", "record_launches(h, 1, 1, step, write_diag != 0, h->cfg.cells == 4);",
-     "record_launches(h, 1, 1, step, write_diag != 0, false);", "ebm_drive.hip"),
-    ("fields_never_go_stale", "    h->epoch += nsteps;", "    h->epoch += 0;", "ebm_drive.hip"),
-    ("classic_kernel_ignores_its_column_offset", "const int T = blockDim.x, t = threadIdx.x, col = a.col0 + (int)blockIdx.x;",
-     "const int T = blockDim.x, t = threadIdx.x, col = (int)blockIdx.x;"),
+    ("unsplit_writes_the_first_pair_twice", "    *(SPLIT ? spl1 : nat1) = p1;", "    *(SPLIT ? spl1 : nat1) = SPLIT ? p1 : p0;"),
+    ("diagnostic_pairs_stored_on_top_of_each_other", "{ return j * 2u * T + 2u * t; }", "{ return 2u * t; }"),
+    ("diagnostic_layout_flag_never_set", "        if (two_layouts_) diag_split_ = split;", "        if (two_layouts_) diag_split_ = false;",
+     "ebm_fieldbook.h"),
+    ("fields_never_go_stale", "        epoch_ += nsteps;", "        epoch_ += 0;", "ebm_fieldbook.h"),
+    ("classic_kernel_ignores_its_column_offset", "    const int b = a.col0 + (int)blockIdx.x;", "    const int b = (int)blockIdx.x;"),
     ("launch_chains_never_joined", "        (void)hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0);", "", "ebm_runtime.h"),
     ("second_chain_does_not_wait_for_earlier_work", "if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);", "",
      "ebm_drive.hip"),

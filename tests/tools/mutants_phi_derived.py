@@ -21,11 +21,11 @@ import sys
 import mutants
 
 mutants.MUTANTS = [
-    ("phi_restore_skipped", "    else if (!h->phi_stored) e = ebm::launch_restore_phi(base_args(h), h->ncol, h->cfg, true, main_stream(h));\n",
-     "", "ebm_fields.hip"),
-    ("set_field_h_leaves_the_state_consistent",
-     "    if (is_split_state_field(h, field) && (rc = state_written_outside(h))) return rc;\n    HIPCHK(hipStreamSynchronize(main_stream(h)));\n    HIPCHK(h->copier->wait_all());",
-     "    HIPCHK(hipStreamSynchronize(main_stream(h)));\n    HIPCHK(h->copier->wait_all());", "ebm_fields.hip"),
+    ("phi_restore_skipped", "return split ? Pass::SPLIT_STATE : phi_stored_ ? Pass::UNSPLIT_STATE : Pass::UNSPLIT_STATE_FORM_PHI;",
+     "return split ? Pass::SPLIT_STATE : Pass::UNSPLIT_STATE;", "ebm_fieldbook.h"),
+    # (every outside writer goes through this one event of the book: ebm_set_field is the one the tests reach first)
+    ("set_field_h_leaves_the_state_consistent", "    void written_outside() { phi_consistent_ = false; }", "    void written_outside() {}",
+     "ebm_fieldbook.h"),
     ("derived_kernel_takes_set_0s_Lf", "for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);",
      "for (int i = 0; i < C; ++i) ph[i] = concentration(*reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p)), Ei[i], hk[i]);"),
     ("derived_phi_not_capped_in_phase_A", "for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);",

@@ -16,9 +16,10 @@ mutants.MUTANTS = [
      "r.rows + (long long)e.y * r.row_stride;"),
     ("resample_leaves_the_active_set", "a.row_stride = a.units = h->amask ? h->cfg.threads / 8 : 0;", "a.row_stride = a.units = 0;"),
     ("resample_leaves_the_noise_state", "        a.nstate = h->noise.state.get();\n", "        a.nstate = nullptr;\n"),
-    ("resample_copies_stale_fields", "(is_diagnostic(h, f) && h->written_epoch[f] != h->epoch)", "false"),
+    # (the fields that travel are the book's current_mask)
+    ("resample_copies_stale_fields", "            if (has(f) && is_current(f)) m |= 1u << f;", "            if (has(f)) m |= 1u << f;", "ebm_fieldbook.h"),
     ("resample_marks_the_state_changed", "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n",
-     "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n    h->epoch += 1;\n"),
+     "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n    h->book.field_set(EBM_F_Ew);\n"),
     ("resample_keeps_the_scratch_dirty", "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n", ""),
 ]
 
