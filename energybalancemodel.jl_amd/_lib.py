@@ -31,7 +31,7 @@ EXPORTS = (
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
     "ebm_equilibrate", "ebm_run_until", "ebm_resample_columns", "ebm_column_record", "ebm_export_columns",
     "ebm_import_columns", "ebm_ensemble_sums", "ebm_ensemble_sums_device", "ebm_sync", "ebm_get_counters",
-    "ebm_reset_counters", "ebm_state_conversions", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
+    "ebm_reset_counters", "ebm_state_conversions", "ebm_zero_line_flags", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
     "ebm_selftest_divide", "ebm_selftest_permute",
 )
 
@@ -46,7 +46,7 @@ class Options(C.Structure):
     """struct ebm_options (include/ebm_hip.h)."""
     _fields_ = [("struct_bytes", C.c_int), ("cells_per_thread", C.c_int), ("use_graph", C.c_int),
                 ("prefetch_cols", C.c_int), ("launch_chains", C.c_int), ("integrate_steps_per_launch", C.c_int),
-                ("fused_state_in_lds", C.c_int)]
+                ("fused_state_in_lds", C.c_int), ("elide_zero_lines", C.c_int)]
 
 
 class EBMError(RuntimeError):
@@ -127,6 +127,7 @@ def load():
     lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_reset_counters.argtypes = [C.c_void_p]
     lib.ebm_state_conversions.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.ebm_zero_line_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
     lib.ebm_timer_start.argtypes = [C.c_void_p]
     lib.ebm_timer_stop.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.ebm_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]

@@ -193,6 +193,47 @@ __device__ __forceinline__ void load_state(const double *__restrict__ f, unsigne
         v[2 * j + 1] = d.y;
     }
 }
+// ---- zero-line flags (miz_step_kernel, ZERO_LINES) -------------------------------------------
+// One 32-bit word per (column, wave), behind the mask rows in their allocation (zero_flag_words, ebm_internal.h); bit
+// 4*j + slot of it, slot = S_Ei, S_Ew, S_h, S_D: the KiB that the wave's access to pair j of that field covers in the
+// pair-split layout holds only zero bits in HBM.  The word is wave-uniform: read with a scalar load through the constant
+// address space (the kernel's one write to it is its last instruction), written by the wave's first lane.  A wave reads its
+// OWN word before it writes it, and nobody else writes that word.  The SUCCESSOR's words, read for the prefetch, belong to a
+// workgroup of the same launch that may be running already and storing them: what is read there may be the old or the new
+// word, and it is a hint only — it decides which lines are prefetched, never what is loaded or stored.
+__device__ __forceinline__ constexpr unsigned zero_flag_bit(int j, int slot) { return 1u << (4 * j + slot); }
+template <int T>
+__device__ __forceinline__ unsigned zero_flag_word(const StepArgs &a, int col, unsigned wave) {
+    typedef const __attribute__((address_space(4))) unsigned ConstWord;
+    return reinterpret_cast<ConstWord *>(reinterpret_cast<uintptr_t>(zero_flag_words(a.amask, a.ncol, T)))[(size_t)col * (T / 64) + wave];
+}
+template <int T>
+__device__ __forceinline__ void store_zero_flag_word(const StepArgs &a, int col, int t, unsigned word) {
+    if ((t & 63) == 0) zero_flag_words(a.amask, a.ncol, T)[(size_t)col * (T / 64) + ((unsigned)t >> 6)] = word;
+}
+// all 64 lanes' two values are zero bits (-0.0 is not)
+__device__ __forceinline__ bool wave_holds_zero_bits(const double2 &d) {
+    const bool mine = (__builtin_bit_cast(unsigned long long, d.x) | __builtin_bit_cast(unsigned long long, d.y)) != 0ull;
+    return __builtin_amdgcn_ballot_w64(mine) == 0ull;
+}
+// one pair, or +0.0 without a load where the wave-uniform `flagged` is set
+__device__ __forceinline__ double2 load_pair_unless_zero(const double *__restrict__ f, unsigned flagged) {
+    double2 d;
+    d.x = 0.0;
+    d.y = 0.0;
+    if (!flagged) d = *reinterpret_cast<const double2 *>(f);
+    return d;
+}
+// load_state with the pairs whose flag is set left at +0.0: bit 4*j of `flags` is pair j's (the word shifted by the slot)
+template <int C, int T>
+__device__ __forceinline__ void load_state_unless_zero(const double *__restrict__ f, unsigned k0, double (&v)[C], unsigned flags) {
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        const double2 d = load_pair_unless_zero(f + state_index<C, T>(k0, j), flags & zero_flag_bit(j, 0));
+        v[2 * j] = d.x;
+        v[2 * j + 1] = d.y;
+    }
+}
 template <int C>
 __device__ __forceinline__ void store_chunk(double *__restrict__ f, const double (&v)[C], unsigned k0, int nlat) {
 #pragma unroll

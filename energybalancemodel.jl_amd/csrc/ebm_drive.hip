@@ -41,8 +41,10 @@ constexpr int kGraphSteps = 64;
 constexpr int kFusedTable = 16384;     // per-step scalars resident on the device at a time (512 KiB)
 
 // mode: ebm::OutMode.  The classic kernel decides about T, h at run time (write_diag).
-hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, int first, int count, hipStream_t s) {
-    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, phi_derived, first, count, s)
+// phi_derived, zero_lines: the book's answers for this launch (step_derives_phi, step_elides_zero_lines)
+hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, bool zero_lines, int first, int count,
+                          hipStream_t s) {
+    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, phi_derived, zero_lines, first, count, s)
                                        : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
 }
 // The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate,
@@ -53,9 +55,9 @@ int chain_count(const ebm_ctx *h, int *first_half) {
     return (*first_half > 0) + (n - *first_half > 0);
 }
 // ... as one chain of launches or as two (ebm_ctx::stream2)
-hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived) {
+hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, bool zero_lines) {
     const int n = h->active ? h->nactive : h->ncol;
-    if (!h->split_col) return launch_columns(h, a, mode, phi_derived, 0, n, main_stream(h));
+    if (!h->split_col) return launch_columns(h, a, mode, phi_derived, zero_lines, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
         hipError_t e = hipEventRecord(h->ev_fork.get(), h->stream.get());
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);
@@ -64,18 +66,28 @@ hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_
     }
     int half = 0;
     (void)chain_count(h, &half);
-    hipError_t e = half > 0 ? launch_columns(h, a, mode, phi_derived, 0, half, h->stream.get()) : hipSuccess;
-    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, phi_derived, half, n - half, h->stream2.get());
+    hipError_t e = half > 0 ? launch_columns(h, a, mode, phi_derived, zero_lines, 0, half, h->stream.get()) : hipSuccess;
+    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, phi_derived, zero_lines, half, n - half, h->stream2.get());
     return e;
 }
 // `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
 // global step `last_step`; the other arguments are FieldBook::steps'.
-void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived) {
+void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived,
+                     bool zero_lines) {
     int half = 0;
     h->n_launches += nlaunch * chain_count(h, &half);
     h->n_steps += nsteps;
     h->clock = last_step + 1;
-    h->book.steps(nsteps, last_step, wrote_diag, split, phi_derived, !h->active);
+    h->book.steps(nsteps, last_step, wrote_diag, split, phi_derived, !h->active, zero_lines);
+}
+// What the runtime owes before an eliding launch, or a replay of captured ones, on flags that somebody may have made untrue
+// (FieldBook::zero_flags_need_clear): all flags clear, on the handle's stream — after whatever disturbed them, before the launch.
+hipError_t clear_untrusted_zero_flags(ebm_ctx *h) {
+    if (!h->book.zero_flags_need_clear()) return hipSuccess;
+    hipError_t e = hipMemsetAsync(ebm::zero_flag_words(h->amask.get(), h->ncol, h->cfg.threads), 0,
+                                  sizeof(unsigned) * ebm::zero_flag_count(h->ncol, h->cfg.threads), main_stream(h));
+    if (e == hipSuccess) h->book.zero_flags_cleared();
+    return e;
 }
 // Every step launch of the library goes through here — a.nfused steps, the last of them global step `last_step` — so here the
 // book is asked (ebm_fieldbook.h): a one-step MIZ launch reads and writes the prognostic fields pair-split, the fused-K and
@@ -85,15 +97,18 @@ void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long 
 hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode, long long last_step, bool capturing = false) {
     const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
     const bool phi_derived = h->book.step_derives_phi(mode, capturing);
+    const bool zero_lines = h->book.step_elides_zero_lines(mode, capturing);
     if (!capturing) {
         if (one_step && !phi_derived)
             if (hipError_t e = restore_phi(h); e != hipSuccess) return e;
         if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
+        if (zero_lines)                                  // (after the conversion: it moves the lines)
+            if (hipError_t e = clear_untrusted_zero_flags(h); e != hipSuccess) return e;
     }
-    hipError_t e = launch_chains(h, a, mode, phi_derived);
+    hipError_t e = launch_chains(h, a, mode, phi_derived, zero_lines);
     // the 4-cells-per-thread MIZ one-step kernels leave the diagnostic fields pair-split, the fused kernels natural
     if (e == hipSuccess && !capturing)
-        record_launches(h, 1, a.nfused, last_step, a.write_diag != 0, one_step && h->cfg.cells == 4, phi_derived);
+        record_launches(h, 1, a.nfused, last_step, a.write_diag != 0, one_step && h->cfg.cells == 4, phi_derived, zero_lines);
     return e;
 }
 
@@ -284,9 +299,12 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
             HIPCHK(hipMemcpyAsync(h->graph.sched.get(), sched.data(), sizeof(ebm::StepSched) * kGraphSteps,
                                   hipMemcpyHostToDevice, main_stream(h)));
             if ((rc = set_state_layout(h, true))) return rc;       // the captured launches expect the one-step layout
+            // ... and, where they elide zero lines, flags that are true (the direct step above took another kernel)
+            const bool zero_lines = h->book.step_elides_zero_lines(ebm::OUT_STATE, true);
+            if (zero_lines) HIPCHK(clear_untrusted_zero_flags(h));
             HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
             record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false,
-                            h->book.step_derives_phi(ebm::OUT_STATE, true));
+                            h->book.step_derives_phi(ebm::OUT_STATE, true), zero_lines);
         }
     }
     for (; s < nsteps; ++s) {

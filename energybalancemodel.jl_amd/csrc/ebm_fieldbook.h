@@ -26,6 +26,18 @@
 //                    parameters.  Cleared by every other writer of one of them and by a change of the parameters
 //                    (written_outside, after phi_readable); set again by the next step launch over all columns.  Only then
 //                    does a launch derive; else it steps with the phi the caller left
+//
+// Zero-line flags.  Where the handle elides zero lines (elide_zero_lines: the deriving kernel's variant that neither loads
+// nor stores state lines that hold only zero bits, csrc/ebm_miz_step.h ZERO_LINES) the device keeps one flag per (column,
+// wave, pair, field of Ei, Ew, h, D): SET MEANS that this KiB of the pair-split field holds only zero bits in HBM.  A clear
+// flag claims nothing, so cleared flags are always true, and only the eliding kernel ever sets one.
+//   zero_flags_trusted   every set flag is true.  Cleared by whoever else may write a prognostic field or move it to the
+//                        other layout: every other step kernel (steps), the split and un-split passes (done), every outside
+//                        writer (state_written_outside: ebm_set_field goes through it, and through the un-split pass
+//                        before).  Before the next eliding launch — a graph replay of such launches included — the
+//                        runtime owes a clear of all flags (zero_flags_need_clear; it reports zero_flags_cleared), and
+//                        that launch rebuilds the flags of the columns it steps from what it stores.
+//                        Flags are per column: an eliding launch over some columns leaves the others' as they were, true
 #pragma once
 #include "../../include/ebm_hip.h"
 #include "ebm_types.h"
@@ -67,7 +79,9 @@ class FieldBook {
 public:
     FieldBook() : FieldBook(EBM_MODEL_CLASSIC, false, false) {}
     // two_layouts: MIZ at four cells per thread; derive_phi: the handle has the deriving kernel
-    FieldBook(int model, bool two_layouts, bool derive_phi) : model_(model), two_layouts_(two_layouts), derive_phi_(derive_phi) {
+    // elide_zero_lines: ... and steps with its zero-line variant (only where derive_phi)
+    FieldBook(int model, bool two_layouts, bool derive_phi, bool elide_zero_lines = false)
+        : model_(model), two_layouts_(two_layouts), derive_phi_(derive_phi), elide_zero_lines_(elide_zero_lines && derive_phi) {
         for (int f = 0; f < EBM_F_COUNT; ++f) written_epoch_[f] = written_step_[f] = -1;
         written_epoch_[EBM_F_T0] = 0;                     // the warm start begins at zero, like the reference's (src/miz.jl:47)
     }
@@ -123,9 +137,10 @@ public:
     void done(Pass p) {
         switch (p) {
             case Pass::NONE: return;
-            case Pass::RESTORE_PHI: phi_stored_ = true; return;
+            case Pass::RESTORE_PHI: phi_stored_ = true; return;      // (phi has no flags)
             case Pass::UNSPLIT_DIAG: diag_split_ = false; return;
             default:
+                zero_flags_disturbed();                   // the lines of Ei, Ew, h, D have moved
                 phi_stored_ = true;
                 state_split_ = p == Pass::SPLIT_STATE;
                 n_conversions_ += 1;
@@ -139,12 +154,22 @@ public:
     // the captured launches derive phi where the handle can: a state somebody else wrote takes one step directly first, with
     // the phi that is stored, and is consistent from then on
     bool replay_needs_a_direct_step() const { return derive_phi_ && !phi_consistent_; }
+    // ... and the variant of it that trusts and maintains the zero-line flags: wherever the handle elides, a deriving launch
+    // does.  Before it is enqueued — or a graph of such launches replayed — untrusted flags are cleared
+    bool step_elides_zero_lines(int mode, bool capturing) const { return elide_zero_lines_ && step_derives_phi(mode, capturing); }
+    bool elides_zero_lines() const { return elide_zero_lines_; }
+    bool zero_flags_trusted() const { return elide_zero_lines_ && zero_flags_trusted_; }
+    bool zero_flags_need_clear() const { return elide_zero_lines_ && !zero_flags_trusted_; }
+    void zero_flags_cleared() { zero_flags_trusted_ = true; }
 
     // events
     // Launches have been enqueued that take `nsteps` steps, the last of them global step `last_step`.  wrote_diag: the last
     // one stored the diagnostic fields, pair-split if `split`.  Every step kernel leaves Ei, h and the phi it stores — or,
     // phi_derived, would have stored — consistent; a launch over a list of active columns says nothing of the others.
-    void steps(long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived, bool all_columns) {
+    // zero_lines: the eliding variant, which keeps the flags of its columns true; every other kernel stores what it likes.
+    void steps(long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived, bool all_columns,
+               bool zero_lines = false) {
+        if (!zero_lines) zero_flags_disturbed();
         phi_stored_ = !phi_derived;
         if (all_columns) phi_consistent_ = true;
         epoch_ += nsteps;
@@ -160,6 +185,12 @@ public:
     // Ei, h or phi are about to be written by somebody who is not a step kernel, or the parameters they are tied by change
     // (phi_readable first: phi is restored under the present ones)
     void written_outside() { phi_consistent_ = false; }
+    // What the runtime reports for every outside writer (state_written_outside, csrc/ebm_fields.hip): any of the prognostic
+    // fields may hold a caller's values from now on — phi is no longer the function of Ei and h, and no zero-line flag holds
+    void state_written_outside() {
+        written_outside();
+        zero_flags_disturbed();
+    }
     // the caller has set field f
     void field_set(int f) {
         if (is_diagnostic(f)) {                           // the caller's statement of what the field holds: current as of now
@@ -171,12 +202,16 @@ public:
     }
 
 private:
+    // somebody who knows nothing of the flags — another step kernel, a layout pass, an outside writer — has written, or
+    // moved, lines of Ei, Ew, h or D
+    void zero_flags_disturbed() { zero_flags_trusted_ = false; }
     int model_;
-    bool two_layouts_, derive_phi_;
+    bool two_layouts_, derive_phi_, elide_zero_lines_;
     long long epoch_ = 0, state_step_ = -1;
     long long written_epoch_[EBM_F_COUNT], written_step_[EBM_F_COUNT];
     bool diag_split_ = false, state_split_ = false;
     bool phi_stored_ = true, phi_consistent_ = true;
+    bool zero_flags_trusted_ = true;                      // (the words start cleared)
     long long n_conversions_ = 0;
 };
 

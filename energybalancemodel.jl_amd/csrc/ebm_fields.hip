@@ -47,7 +47,7 @@ hipError_t restore_phi(ebm_ctx *h) { return exec_pass(h, h->book.phi_readable())
 int state_written_outside(ebm_ctx *h) {
     hipError_t e = restore_phi(h);
     if (e != hipSuccess) return hip_fail("phi restore", e);
-    h->book.written_outside();
+    h->book.state_written_outside();
     return EBM_OK;
 }
 

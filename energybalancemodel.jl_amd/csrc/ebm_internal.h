@@ -80,6 +80,15 @@ struct LaunchCfg {
 // cells per thread the pair is the chunk and the layout is the natural one.
 __host__ __device__ constexpr unsigned split_index(unsigned t, unsigned j, unsigned T) { return j * 2u * T + 2u * t; }
 
+// The zero-line flags of a MIZ handle (miz_step_kernel, ZERO_LINES; ebm_device.h): zero_flag_count 32-bit words, one per
+// (column, wave), which lie behind the ncol rows of `threads` mask words in the allocation of StepArgs::amask — so the
+// launch arguments, and with them every kernel that knows nothing of the flags, are what they were.  Nothing that moves mask
+// rows between columns touches them.
+__host__ __device__ inline unsigned *zero_flag_words(unsigned short *amask, int ncol, int threads) {
+    return reinterpret_cast<unsigned *>(amask + (size_t)ncol * (size_t)threads);
+}
+__host__ __device__ constexpr size_t zero_flag_count(int ncol, int threads) { return (size_t)ncol * (size_t)(threads / 64); }
+
 // cells_requested: 2 (honoured for nlat <= kMaxLat2) or anything else = 4.  A function of nlat and the request only.
 LaunchCfg choose_launch(int nlat, int cells_requested);
 hipError_t prepare_kernels(const LaunchCfg &cfg);   // raises the dynamic-LDS limit if needed
@@ -92,6 +101,9 @@ KernelFn miz_step_kernels_imex(int grid_kind, int mode, int threads);
 // the state-only step that derives phi from Ei and h (miz_step_kernel, PHI_DERIVED): four cells per thread, the reference's step
 KernelFn miz_step_phi_derived_identity(int threads);
 KernelFn miz_step_phi_derived_nonuniform(int threads);
+// ... and neither loads nor stores state lines that are all zero (ZERO_LINES)
+KernelFn miz_step_zero_lines_identity(int threads);
+KernelFn miz_step_zero_lines_nonuniform(int threads);
 // fused-K with the state resident in LDS (miz_resident_kernel): four cells per thread; the reference's step beyond
 // kFusedRegThreads threads, the extension at every size
 KernelFn miz_resident_kernels(int grid_kind, int threads, bool imex);
@@ -102,9 +114,10 @@ bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex);  
 // may a one-step OUT_STATE launch of this handle take the kernel that derives phi?  (the caller answers for the state)
 bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex);
 // `count` workgroups, stepping columns first ... first + count - 1.  phi_derived (OUT_STATE where has_phi_derived_kernel):
-// the kernel that reads Ei and h for phi and leaves the phi field as it was
+// the kernel that reads Ei and h for phi and leaves the phi field as it was; zero_lines (phi_derived only): its variant that
+// trusts and maintains the zero-line flags (zero_flag_words) — the caller answers for them
 hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
-                           int first, int count, hipStream_t s);
+                           bool zero_lines, int first, int count, hipStream_t s);
 hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s);
 // rcp_dt / rcp_cdn of the device-resident parameter block (see Params)
 hipError_t launch_derive_params(Params *p_dev, hipStream_t s);

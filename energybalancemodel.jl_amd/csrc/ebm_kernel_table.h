@@ -37,10 +37,11 @@ KernelFn miz_kernel_for(int threads) {
     else return kernel_for(kUpTo512 + kTwoCellsAbove512, threads, pick);
 }
 // the state-only step that derives phi from Ei and h instead of loading and storing it: four cells per thread, every size
-template <int GRID>
+// (ZERO_LINES: ... and neither loads nor stores state lines that are all zero)
+template <int GRID, bool ZERO_LINES = false>
 [[maybe_unused]] KernelFn miz_step_phi_derived_for(int threads) {
     return kernel_for(kUpTo512 + kAbove512, threads, [](auto tt) -> KernelFn {
-        return miz_step_kernel<4, GRID, OUT_STATE, decltype(tt)::value, false, true>;
+        return miz_step_kernel<4, GRID, OUT_STATE, decltype(tt)::value, false, true, ZERO_LINES>;
     });
 }
 template <int C, int GRID, bool IMEX>

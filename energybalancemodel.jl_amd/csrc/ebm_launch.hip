@@ -17,7 +17,7 @@
 //            floe size / thickness / concentration update, 16-byte stores
 //
 // Kernels of the library, and where each is defined and instantiated:
-//   miz_step_kernel<C, GRID, OUT, T, IMEX>   one step per launch; OUT: state only / + diagnostics / savesol! from
+//   miz_step_kernel<C, GRID, OUT, T, IMEX, PHI_DERIVED, ZERO_LINES>   one step per launch; OUT: state only / + diagnostics / savesol! from
 //                                       registers (annual-mean sums, raw snapshots); IMEX: the implicit-diffusion
 //                                       extension (one more tridiagonal solve per step, see include/ebm_hip.h)
 //                                       [ebm_miz_step.h; miz_step_identity.hip, miz_step_nonuniform.hip, miz_step_imex.hip]
@@ -36,7 +36,7 @@
 // tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 487 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 521 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -526,10 +526,12 @@ namespace {
 bool fused_state_in_lds(const LaunchCfg &cfg, bool imex) {
     return imex || (cfg.cells == 4 && (cfg.threads > kFusedRegThreads || cfg.fused_in_lds));
 }
-KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex, bool phi_derived = false) {
+KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex, bool phi_derived = false, bool zero_lines = false) {
     const int cells = cfg.cells, threads = cfg.threads;
+    if (zero_lines && !phi_derived) return nullptr;
     if (phi_derived) {
         if (mode != OUT_STATE || imex || cells != 4) return nullptr;
+        if (zero_lines) return grid_kind == 0 ? miz_step_zero_lines_identity(threads) : miz_step_zero_lines_nonuniform(threads);
         return grid_kind == 0 ? miz_step_phi_derived_identity(threads) : miz_step_phi_derived_nonuniform(threads);
     }
     if (mode == OUT_LOOP_SAVE) {
@@ -579,6 +581,8 @@ hipError_t prepare_kernels(const LaunchCfg &cfg) {
                     if (e != hipSuccess) return e;
                     if (mode == OUT_STATE && has_phi_derived_kernel(cfg, grid, imex != 0))
                         e = raise(miz_kernel(cfg, grid, mode, false, true), cfg.lds_bytes);
+                    if (e == hipSuccess && mode == OUT_STATE && has_phi_derived_kernel(cfg, grid, imex != 0))
+                        e = raise(miz_kernel(cfg, grid, mode, false, true, true), cfg.lds_bytes);
                     if (e != hipSuccess) return e;
                 }
             // the resident fused-K kernels and their savesol! variants (four cells per thread): 160 T bytes
@@ -600,8 +604,8 @@ bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex) {
 }
 
 hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
-                           int first, int count, hipStream_t s) {
-    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex, phi_derived);
+                           bool zero_lines, int first, int count, hipStream_t s) {
+    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex, phi_derived, zero_lines);
     if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
     // fused launches whose kernel reads N_c from memory: everything but miz_fused_kernel up to kFusedRegThreads threads
     const bool fused = mode == OUT_LOOP || mode == OUT_LOOP_SAVE;

@@ -35,10 +35,24 @@ namespace ebm {
 // phase D stores four fields instead of five: a fifth of the store traffic of a launch.  The phi field in HBM goes stale;
 // the runtime launches this variant only on a state that step kernels wrote last and restores the field before anybody
 // else reads it (ebm_ctx::phi_stored).
-template <int C, int GRID, int OUT, int TT, bool IMEX, bool PHI_DERIVED = false>
+//
+// ZERO_LINES (the PHI_DERIVED kernel only): state lines that hold nothing but zero bits are neither loaded nor stored.  A
+// wave's access to pair j of one field covers 1 KiB of the column in the pair-split layout (128 cells); one flag per (column,
+// wave, pair, field of Ei, Ew, h, D) — eight bits of the wave's flag word, zero_flag_bit — says that this KiB holds only
+// zero bits in HBM.  The word is read once with a scalar load; a flagged pair is not loaded (+0.0 is what the load would
+// have returned), and is not stored if its new values are all zero bits again (padding cells store +0.0 and count as
+// zero).  The new word — the ballots of what the wave holds now, stored or not — is written by one lane after the last
+// store.  The branches around loads and stores are wave-uniform (only the prefetch below is predicated per lane: the two
+// halves of a wave fetch for two different lines); HBM stays complete and current, so no reader of the fields changes.  The flags
+// know nothing about the physics: ice-free cells store Ei = h = D = +0.0, water at the freezing point under ice Ew = +0.0.
+// Whoever else writes a prognostic field, or moves it to another layout, leaves the flags untrusted, and the runtime clears
+// them before the next launch of this variant (FieldBook::zero_flags_trusted).  The L2 prefetch for the
+// successor column skips, lane by lane, the sectors of lines that the successor's flags say it will not load.
+template <int C, int GRID, int OUT, int TT, bool IMEX, bool PHI_DERIVED = false, bool ZERO_LINES = false>
 __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     static_assert(C == 2 || C == 4, "cells per thread");
     static_assert(!PHI_DERIVED || (C == 4 && !IMEX && OUT == OUT_STATE), "phi is derived by the state-only kernel of the reference's step");
+    static_assert(!ZERO_LINES || PHI_DERIVED, "zero lines are elided by the kernel that derives phi");
     static_assert(OUT == OUT_STATE || OUT == OUT_DIAG || OUT == OUT_SAVE, "per-step kernel");
     constexpr bool MAYDIAG = OUT != OUT_STATE;            // diagnostic stores compiled in
     extern __shared__ double smem[];
@@ -60,6 +74,17 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // active-set iteration only uses its sign pattern, so between steps the library carries that
     // pattern (one bit per cell) and writes the fp64 T0 field on diagnostic launches only.
     unsigned short *const cmask = a.amask + (size_t)col * T;            // wave-uniform
+    // ZERO_LINES: this wave's flag word, and the two words that hold the flags of the 2 KiB of the successor column that
+    // this wave prefetches (scalar loads, like the parameter block: nothing of them waits in a VGPR)
+    unsigned zold = 0, znew = 0, znext0 = 0, znext1 = 0;
+    if constexpr (ZERO_LINES) {
+        const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane(t >> 6);
+        zold = zero_flag_word<TT>(a, col, wave);
+        if (a.prefetch > 0 && col + a.prefetch < a.ncol) {
+            znext0 = zero_flag_word<TT>(a, col + a.prefetch, (2u * wave) % (TT / 64)) >> (4u * ((2u * wave) / (TT / 64)));
+            znext1 = zero_flag_word<TT>(a, col + a.prefetch, (2u * wave + 1u) % (TT / 64)) >> (4u * ((2u * wave + 1u) / (TT / 64)));
+        }
+    }
     const double ct = a.sched ? a.sched[a.slot].ct : a.ct;              // per-step scalars (scalar loads)
     const double ft = a.sched ? a.sched[a.slot].ft : a.ft;
     ColumnNoise nz;
@@ -86,12 +111,20 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
         if (it == 0) {
             double Ew[C], hk[C], xk[C], r[C];
-            load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
+            // (ZERO_LINES: a flagged pair is not loaded, it holds +0.0 — the same concentration and water_temperature of the
+            // same bits)
+            if constexpr (ZERO_LINES) load_state_unless_zero<C, TT>(st + S_Ew * a.fstride, kl, Ew, zold >> S_Ew);
+            else load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
             if constexpr (PHI_DERIVED) {
                 // (Ei is not kept: phase D loads its pairs again, as it always has)
                 double Ei[C];
-                load_state<C, TT>(st + S_Ei * a.fstride, kl, Ei);
-                load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+                if constexpr (ZERO_LINES) {
+                    load_state_unless_zero<C, TT>(st + S_Ei * a.fstride, kl, Ei, zold >> S_Ei);
+                    load_state_unless_zero<C, TT>(st + S_h * a.fstride, kl, hk, zold >> S_h);
+                } else {
+                    load_state<C, TT>(st + S_Ei * a.fstride, kl, Ei);
+                    load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+                }
 #pragma unroll
                 for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);
             } else {
@@ -220,8 +253,14 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         MizCellOut o[2];
         __builtin_amdgcn_sched_barrier(0);
         const unsigned ks = state_index<C, TT>(k0, j);    // the pair's place in every field this kernel stores
-        const double2 Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + ks);
-        const double2 Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + ks);
+        double2 Ei2, Dk2;
+        if constexpr (ZERO_LINES) {
+            Ei2 = load_pair_unless_zero(st + S_Ei * a.fstride + ks, zold & zero_flag_bit(j, S_Ei));
+            Dk2 = load_pair_unless_zero(st + S_D * a.fstride + ks, zold & zero_flag_bit(j, S_D));
+        } else {
+            Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + ks);
+            Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + ks);
+        }
         if constexpr (GRID == 0 && !IMEX) {
             const double2 lo = *reinterpret_cast<const double2 *>(geom + G_LO * a.gstride + (k0 + 2 * j));
             const double2 di = *reinterpret_cast<const double2 *>(geom + G_DI * a.gstride + (k0 + 2 * j));
@@ -262,9 +301,17 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
                     const double *nxt = a.state + (size_t)(col + a.prefetch) * (size_t)a.pitch +
                                         ((unsigned)(t >> 6) * 256u + (unsigned)(t & 63) * 4u);
                     auto *sink = (__attribute__((address_space(3))) void *)(smem + 6 * T + (C - 2) * T + (t & ~63));
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_Ew * a.fstride), sink, 4, 0, 0);
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + (PHI_DERIVED ? S_Ei : S_phi) * a.fstride), sink, 4, 0, 0);
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_h * a.fstride), sink, 4, 0, 0);
+                    // ZERO_LINES: lanes 0 .. 31 fetch the sectors of one KiB of the successor's field, lanes 32 .. 63 those of
+                    // the next; a lane skips a field whose KiB the successor will not load
+                    // (measured against prefetching them all the same: 1.45 % of the step, profiles/EXPERIMENTS.md)
+                    unsigned skip = 0;
+                    if constexpr (ZERO_LINES) skip = (t & 32) ? znext1 : znext0;
+                    if (!(skip & (1u << S_Ew)))
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_Ew * a.fstride), sink, 4, 0, 0);
+                    if (!(skip & (1u << (PHI_DERIVED ? S_Ei : S_phi))))
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + (PHI_DERIVED ? S_Ei : S_phi) * a.fstride), sink, 4, 0, 0);
+                    if (!(skip & (1u << S_h)))
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(nxt + S_h * a.fstride), sink, 4, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -272,13 +319,22 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         const unsigned kp = k0 + 2 * j;
         const bool v0 = (int)kp < nlat, v1 = (int)kp + 1 < nlat;
-        // (PHI_DERIVED: the phi field is not stored)
+        // (PHI_DERIVED: the phi field is not stored.  ZERO_LINES: neither is a pair of which all 64 lanes hold zero bits —
+        // the integer pattern, not == 0.0: -0.0 is not what a skipped load returns — where the flag says memory holds
+        // them already; the new flag is the ballot's result either way)
 #define EBM_PUT(slot_, qi)                                                                         \
         if constexpr (!PHI_DERIVED || (slot_) != S_phi) {                                          \
             double2 d_;                                                                            \
             d_.x = v0 ? o[0].q[qi] : 0.0;                                                          \
             d_.y = v1 ? o[1].q[qi] : 0.0;                                                          \
-            EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                         \
+            if constexpr (ZERO_LINES && (slot_) <= S_D) {                                          \
+                const bool zero_ = wave_holds_zero_bits(d_);                                       \
+                if (zero_) znew |= zero_flag_bit(j, (slot_));                                      \
+                if (!(zero_ && (zold & zero_flag_bit(j, (slot_)))))                                \
+                    EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                 \
+            } else {                                                                               \
+                EBM_STORE2(st + (slot_) * a.fstride + ks, d_);                                     \
+            }                                                                                      \
         }
         if (j == C / 2 - 1) EBM_STAMPW(5);                // per wave: arithmetic done, before the last stores
         EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)
@@ -297,6 +353,7 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // the LDS-DMA prefetch must have landed before this wave can end (its LDS is released with the workgroup); it was
     // issued a whole cell update ago
     if constexpr (C == 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (ZERO_LINES) store_zero_flag_word<TT>(a, col, t, znew);
     EBM_STAMP(15);
     EBM_STAMPW(6);                                        // per wave: stores issued
 }

@@ -200,7 +200,7 @@ int set_state_layout(ebm_ctx *h, bool split);     // the same, with the error re
 int natural_layout(ebm_ctx *h, bool diagnostics_too);   // the prognostic fields natural, after the diagnostic ones if asked
 // phi current where it lies, for readers that take the fields as they lie: a one-step launch that loads phi, resampling, export
 hipError_t restore_phi(ebm_ctx *h);
-int state_written_outside(ebm_ctx *h);            // restore_phi, then FieldBook::written_outside
+int state_written_outside(ebm_ctx *h);            // restore_phi, then FieldBook::state_written_outside
 int get_copier(ebm_ctx *h);                       // ebm_fields.hip: the handle's pinned staging ring, created on first use
 
 }  // namespace ebm_rt

@@ -40,6 +40,8 @@ int read_options(const ebm_options *user_opt, ebm_options &opt) {
         return fail(EBM_ERR_ARG, "ebm_create_ex: launch_chains must be -1 (default), 1 or 2");
     if (opt.fused_state_in_lds < -1 || opt.fused_state_in_lds > 1)
         return fail(EBM_ERR_ARG, "ebm_create_ex: fused_state_in_lds must be -1 (default), 0 or 1");
+    if (opt.elide_zero_lines < -1 || opt.elide_zero_lines > 1)
+        return fail(EBM_ERR_ARG, "ebm_create_ex: elide_zero_lines must be -1 (default), 0 or 1");
     if (opt.integrate_steps_per_launch < -1)
         return fail(EBM_ERR_ARG, "ebm_create_ex: integrate_steps_per_launch must be -1 (default), 1 or a number of steps");
     return EBM_OK;
@@ -88,7 +90,8 @@ int allocate(ebm_ctx *h, const double *x) {
     e = dev_alloc(h->state, (size_t)h->nslots * (size_t)h->fstride);
     if (e == hipSuccess) e = hipMemset(h->state.get(), 0, nbytes);
     if (e == hipSuccess && model == EBM_MODEL_MIZ) {
-        const size_t mn = (size_t)ncol * h->cfg.threads;
+        // the mask rows, and behind them the zero-line flag words (ebm::zero_flag_words): all clear
+        const size_t mn = (size_t)ncol * h->cfg.threads + 2 * ebm::zero_flag_count(ncol, h->cfg.threads);
         e = dev_alloc(h->amask, mn);
         if (e == hipSuccess) e = hipMemset(h->amask.get(), 0, sizeof(unsigned short) * mn);
     }
@@ -130,6 +133,7 @@ int ebm_options_default(ebm_options *opt) {
     opt->launch_chains = -1;
     opt->integrate_steps_per_launch = -1;
     opt->fused_state_in_lds = -1;
+    opt->elide_zero_lines = -1;
     return EBM_OK;
 }
 
@@ -170,7 +174,9 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     auto h = std::make_unique<ebm_ctx>();
     h->model = model; h->grid = grid; h->nlat = nlat; h->ncol = ncol; h->device = device;
     h->dt = dt; h->cfg = cfg; h->imex = imex;
-    h->book = FieldBook(model, model == EBM_MODEL_MIZ && cfg.cells == 4, model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex));
+    // (elide_zero_lines: on by default wherever the deriving kernel is — the book ignores it elsewhere)
+    h->book = FieldBook(model, model == EBM_MODEL_MIZ && cfg.cells == 4, model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex),
+                        opt.elide_zero_lines != 0);
     h->num_cus = prop.multiProcessorCount;
     choose_heuristics(h.get(), opt);
     h->pitch = (long long)cfg.threads * cfg.cells;     // >= nlat; padding cells stay zero
@@ -223,6 +229,18 @@ int ebm_reset_counters(ebm_handle_t h) {
 int ebm_state_conversions(ebm_handle_t h, long long *count) {
     if (!h || !count) return fail(EBM_ERR_ARG, "ebm_state_conversions: null argument");
     *count = h->book.conversions();
+    return EBM_OK;
+}
+
+int ebm_zero_line_flags(ebm_handle_t h, unsigned *words, int *trusted) {
+    if (!h || !words || !trusted) return fail(EBM_ERR_ARG, "ebm_zero_line_flags: null argument");
+    if (!h->book.elides_zero_lines())
+        return fail(EBM_ERR_UNSUPPORTED, "ebm_zero_line_flags: this handle does not elide zero lines (ebm_options::elide_zero_lines)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(main_stream(h)));
+    HIPCHK(hipMemcpy(words, ebm::zero_flag_words(h->amask.get(), h->ncol, h->cfg.threads),
+                     sizeof(unsigned) * ebm::zero_flag_count(h->ncol, h->cfg.threads), hipMemcpyDeviceToHost));
+    *trusted = h->book.zero_flags_trusted() ? 1 : 0;
     return EBM_OK;
 }
 

@@ -129,7 +129,13 @@ int ebm_create(ebm_handle_t *out, int model, int grid, int nlat, int ncol, const
  *   nothing but the annual-mean sums (no raw snapshot, no seasonal snapshot, not a year's last step): -1 (default) and
  *   values > 1 = that many steps fused into one launch with the state resident on the chip and the sums taken from
  *   every step (default 64); 1 = one launch per step everywhere.  Bit-identical either way.  MIZ and MIZ_IMEX (not two
- *   cells per thread on meridians of more than 1024 cells); other handles always step one launch at a time. */
+ *   cells per thread on meridians of more than 1024 cells); other handles always step one launch at a time.
+ * elide_zero_lines: the state-only one-launch-per-step MIZ kernel that derives phi (four cells per thread, the reference's
+ *   step) neither loads nor stores a KiB of Ei, Ew, h or D that holds only zero bits — what ice-free cells hold in Ei, h
+ *   and D, and water at the freezing point under ice in Ew.  It keeps one flag per KiB on the device (ebm_zero_line_flags) and
+ *   trusts it only while nothing but that kernel has written the prognostic fields; memory stays complete and current at all
+ *   times, so nothing a caller can see changes, bit for bit.  -1 (default) and 1 = on where the handle has that kernel,
+ *   0 = off. */
 typedef struct ebm_options {
     int struct_bytes;
     int cells_per_thread;
@@ -138,6 +144,7 @@ typedef struct ebm_options {
     int launch_chains;
     int integrate_steps_per_launch;
     int fused_state_in_lds;
+    int elide_zero_lines;
 } ebm_options;
 int ebm_options_default(ebm_options *opt);
 /* ebm_create with explicit options (opt == NULL: the defaults, i.e. exactly ebm_create). */
@@ -608,6 +615,14 @@ int ebm_reset_counters(ebm_handle_t h);
  * field, a fused launch, a series sample or a seasonal snapshot between two such steps costs two.  Since ebm_create (not
  * reset by ebm_reset_counters).  Does not synchronise. */
 int ebm_state_conversions(ebm_handle_t h, long long *count);
+/* The zero-line flags of a handle that elides zero lines (ebm_options::elide_zero_lines; EBM_ERR_UNSUPPORTED on any other),
+ * read-only, for tests and cost tools: words[col * (threads / 64) + wave] with threads = info[0] of ebm_launch_info.  Bit
+ * 4*j + f of a word, j = 0, 1 and f = 0 (Ei), 1 (Ew), 2 (h), 3 (D): the KiB of field f that holds cells 4t + 2j and
+ * 4t + 2j + 1 of the wave's threads t = 64 wave .. 64 wave + 63 — in the layout private to the one-step kernel, where it is
+ * contiguous — held only zero bits when the column was last stepped by the eliding kernel.  *trusted = 1: every set bit is
+ * true now; 0: somebody else has written or moved the prognostic fields since, and the library will clear all flags before
+ * it uses them again.  Synchronises the handle's stream. */
+int ebm_zero_line_flags(ebm_handle_t h, unsigned *words, int *trusted);
 /* HIP-event timing on the handle's stream (the stream the kernels are launched on). */
 int ebm_timer_start(ebm_handle_t h);
 int ebm_timer_stop(ebm_handle_t h, float *elapsed_ms);
