@@ -40,13 +40,15 @@ namespace {
 constexpr int kGraphSteps = 64;
 constexpr int kFusedTable = 16384;     // per-step scalars resident on the device at a time (512 KiB)
 
-// mode: ebm::OutMode.  The classic kernel decides about T, h at run time (write_diag).
-// phi_derived, zero_lines: the book's answers for this launch (step_derives_phi, step_elides_zero_lines)
-hipError_t launch_columns(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, bool zero_lines, int first, int count,
-                          hipStream_t s) {
-    return (h->model == EBM_MODEL_MIZ) ? ebm::launch_miz_step(a, h->grid, mode, h->cfg, h->imex, phi_derived, zero_lines, first, count, s)
-                                       : ebm::launch_classic_step(a, mode, h->cfg, first, count, s);
+// What a step launch of OutMode `mode` asks of the plan (ebm_plan.h): the handle's model and grid, and the book's two answers
+// for this launch (step_derives_phi, step_elides_zero_lines).  capturing: into a graph (build_graph) — ebm_run asks with it
+// again for a replay's bookkeeping, so the two cannot differ.  (The classic kernel decides about T, h at run time: write_diag.)
+ebm::StepVariant step_variant(const ebm_ctx *h, int mode, bool capturing = false) {
+    return {h->model == EBM_MODEL_MIZ ? ebm::STEP_MIZ : ebm::STEP_CLASSIC, h->grid, h->imex, mode,
+            h->book.step_derives_phi(mode, capturing), h->book.step_elides_zero_lines(mode, capturing)};
 }
+// ... and whether this build has a kernel for it (the fused modes: "no fused-K kernel for this shape")
+bool has_step_kernel(const ebm_ctx *h, int mode) { return ebm::has_step_kernel(h->cfg, step_variant(h, mode)); }
 // The launches of one step: columns 0 .. ncol-1, or the entries 0 .. nactive-1 of the active list (ebm_equilibrate,
 // ebm_run_until), as one chain or split in two halves; a chain with no columns is skipped.
 int chain_count(const ebm_ctx *h, int *first_half) {
@@ -55,9 +57,9 @@ int chain_count(const ebm_ctx *h, int *first_half) {
     return (*first_half > 0) + (n - *first_half > 0);
 }
 // ... as one chain of launches or as two (ebm_ctx::stream2)
-hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_derived, bool zero_lines) {
+hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, const ebm::StepPlan &plan) {
     const int n = h->active ? h->nactive : h->ncol;
-    if (!h->split_col) return launch_columns(h, a, mode, phi_derived, zero_lines, 0, n, main_stream(h));
+    if (!h->split_col) return ebm::launch_step_columns(a, plan, 0, n, main_stream(h));
     if (!h->forked) {            // the second chain starts after everything the handle's stream has been given so far
         hipError_t e = hipEventRecord(h->ev_fork.get(), h->stream.get());
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);
@@ -66,19 +68,18 @@ hipError_t launch_chains(ebm_ctx *h, const ebm::StepArgs &a, int mode, bool phi_
     }
     int half = 0;
     (void)chain_count(h, &half);
-    hipError_t e = half > 0 ? launch_columns(h, a, mode, phi_derived, zero_lines, 0, half, h->stream.get()) : hipSuccess;
-    if (e == hipSuccess && n > half) e = launch_columns(h, a, mode, phi_derived, zero_lines, half, n - half, h->stream2.get());
+    hipError_t e = half > 0 ? ebm::launch_step_columns(a, plan, 0, half, h->stream.get()) : hipSuccess;
+    if (e == hipSuccess && n > half) e = ebm::launch_step_columns(a, plan, half, n - half, h->stream2.get());
     return e;
 }
-// `nlaunch` launches (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of them
-// global step `last_step`; the other arguments are FieldBook::steps'.
-void record_launches(ebm_ctx *h, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag, bool split, bool phi_derived,
-                     bool zero_lines) {
+// `nlaunch` launches of `plan` (one per launch chain each, chain_count) have been enqueued that take `nsteps` steps, the last of
+// them global step `last_step`; wrote_diag: the last one stored the diagnostic fields.
+void record_launches(ebm_ctx *h, const ebm::StepPlan &plan, long long nlaunch, long long nsteps, long long last_step, bool wrote_diag) {
     int half = 0;
     h->n_launches += nlaunch * chain_count(h, &half);
     h->n_steps += nsteps;
     h->clock = last_step + 1;
-    h->book.steps(nsteps, last_step, wrote_diag, split, phi_derived, !h->active, zero_lines);
+    h->book.steps(nsteps, last_step, wrote_diag, plan.stores_split, plan.phi_derived, !h->active, plan.zero_lines);
 }
 // What the runtime owes before an eliding launch, or a replay of captured ones, on flags that somebody may have made untrue
 // (FieldBook::zero_flags_need_clear): all flags clear, on the handle's stream — after whatever disturbed them, before the launch.
@@ -95,20 +96,17 @@ hipError_t clear_untrusted_zero_flags(ebm_ctx *h) {
 // nothing but the step launches is enqueued and the book hears nothing; ebm_run makes the state fit the captured kernels
 // before a replay.
 hipError_t launch_step(ebm_ctx *h, const ebm::StepArgs &a, int mode, long long last_step, bool capturing = false) {
-    const bool one_step = mode == ebm::OUT_STATE || mode == ebm::OUT_DIAG || mode == ebm::OUT_SAVE;
-    const bool phi_derived = h->book.step_derives_phi(mode, capturing);
-    const bool zero_lines = h->book.step_elides_zero_lines(mode, capturing);
+    const ebm::StepPlan plan = ebm::plan_step(h->cfg, step_variant(h, mode, capturing));
+    const bool one_step = !ebm::is_fused_mode(mode);
     if (!capturing) {
-        if (one_step && !phi_derived)
+        if (one_step && !plan.phi_derived)
             if (hipError_t e = restore_phi(h); e != hipSuccess) return e;
         if (hipError_t e = convert_state(h, one_step); e != hipSuccess) return e;
-        if (zero_lines)                                  // (after the conversion: it moves the lines)
+        if (plan.zero_lines)                             // (after the conversion: it moves the lines)
             if (hipError_t e = clear_untrusted_zero_flags(h); e != hipSuccess) return e;
     }
-    hipError_t e = launch_chains(h, a, mode, phi_derived, zero_lines);
-    // the 4-cells-per-thread MIZ one-step kernels leave the diagnostic fields pair-split, the fused kernels natural
-    if (e == hipSuccess && !capturing)
-        record_launches(h, 1, a.nfused, last_step, a.write_diag != 0, one_step && h->cfg.cells == 4, phi_derived, zero_lines);
+    hipError_t e = launch_chains(h, a, plan);
+    if (e == hipSuccess && !capturing) record_launches(h, plan, 1, a.nfused, last_step, a.write_diag != 0);
     return e;
 }
 
@@ -300,11 +298,10 @@ int ebm_run(ebm_handle_t h, long long first_step, int nsteps, const double *f_st
                                   hipMemcpyHostToDevice, main_stream(h)));
             if ((rc = set_state_layout(h, true))) return rc;       // the captured launches expect the one-step layout
             // ... and, where they elide zero lines, flags that are true (the direct step above took another kernel)
-            const bool zero_lines = h->book.step_elides_zero_lines(ebm::OUT_STATE, true);
-            if (zero_lines) HIPCHK(clear_untrusted_zero_flags(h));
+            const ebm::StepPlan captured = ebm::plan_step(h->cfg, step_variant(h, ebm::OUT_STATE, true));   // as build_graph's launch_step
+            if (captured.zero_lines) HIPCHK(clear_untrusted_zero_flags(h));
             HIPCHK(hipGraphLaunch(h->graph.exec.get(), main_stream(h)));
-            record_launches(h, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false, false,
-                            h->book.step_derives_phi(ebm::OUT_STATE, true), zero_lines);
+            record_launches(h, captured, kGraphSteps, kGraphSteps, first_step + s + kGraphSteps - 1, false);
         }
     }
     for (; s < nsteps; ++s) {
@@ -568,7 +565,7 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
     // (miz_resident_kernel<SAVE>, miz_fused_kernel<2, ..., SAVE>; plain fused stepping when no mean is asked for): MIZ and
     // MIZ_IMEX, every geometry but two cells per thread at 768 threads.
     const bool may_fuse = h->integrate_spl > 1 && h->model == EBM_MODEL_MIZ &&
-                          (!sums || ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP_SAVE, h->imex));
+                          (!sums || has_step_kernel(h, ebm::OUT_LOOP_SAVE));
     for (long long tinx = 1; tinx <= total; ++tinx) {              // 1-based, as the reference
         if (may_fuse && needs(tinx).plain() && needs(tinx + 1).plain()) {
             long long n = 2;
@@ -656,7 +653,7 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
         ea.slot[v] = vars[v].slot;
         ea.tol[v] = tol[v];
     }
-    if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
+    if (!has_step_kernel(h, ebm::OUT_LOOP))
         return fail(EBM_ERR_UNSUPPORTED, "ebm_equilibrate: no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
     if ((rc = natural_layout(h, true))) return rc;
@@ -716,7 +713,7 @@ int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int eve
             return fail(EBM_ERR_ARG, "ebm_run_until: direction[" + std::to_string(c) + "] is 0 (> 0: upward, < 0: downward)");
     }
     if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_until: call ebm_set_time_table first");
-    if (h->model == EBM_MODEL_MIZ && !ebm::has_miz_kernel(h->cfg, h->grid, ebm::OUT_LOOP, h->imex))
+    if (!has_step_kernel(h, ebm::OUT_LOOP))
         return fail(EBM_ERR_UNSUPPORTED, "ebm_run_until: no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
     if ((rc = natural_layout(h, true))) return rc;

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ebm_plan.h"
 #include "ebm_types.h"
 
 namespace ebm {
@@ -62,17 +63,6 @@ struct StepArgs {
     long long step;                  // global index of the step of a one-step launch without sched (with sched: sched[slot].n)
 };
 
-struct LaunchCfg {
-    int threads;        // workgroup size (multiple of 64)
-    int cells;          // cells per thread (C)
-    size_t lds_bytes;   // dynamic LDS per workgroup
-    // fused-K launches of the reference's step where both kernels exist (four cells per thread, <= kFusedRegThreads threads):
-    // state resident in LDS (128 VGPRs: up to four workgroups per CU fill each other's barrier stalls — launches of many
-    // columns) instead of in registers (fewer LDS round trips: a few columns).  Same bits; set by the runtime, not by
-    // choose_launch — the GEOMETRY stays a function of (nlat, cells) only.
-    bool fused_in_lds;
-};
-
 // THE pair-split permutation of a column at four cells per thread (T threads, pitch 4T): pair j of thread t — the natural
 // cells 4t + 2j and 4t + 2j + 1 — lies at split_index(t, j, T), so that the 16-byte accesses of a wave to one pair cover
 // whole 128-byte lines.  The layout of the annual-mean sums, of the zonal operator's index space, of the diagnostic
@@ -89,36 +79,22 @@ __host__ __device__ inline unsigned *zero_flag_words(unsigned short *amask, int 
 }
 __host__ __device__ constexpr size_t zero_flag_count(int ncol, int threads) { return (size_t)ncol * (size_t)(threads / 64); }
 
-// cells_requested: 2 (honoured for nlat <= kMaxLat2) or anything else = 4.  A function of nlat and the request only.
-LaunchCfg choose_launch(int nlat, int cells_requested);
-hipError_t prepare_kernels(const LaunchCfg &cfg);   // raises the dynamic-LDS limit if needed
-// One workgroup per column.  mode: OutMode; OUT_LOOP runs a.nfused steps per launch.
-// The per-step MIZ kernels, one function per translation unit (miz_step_*.hip, miz_resident*.hip); nullptr = not compiled
+// The step kernels (ebm_plan.h decides which).  One workgroup per column; the fused modes run a.nfused steps per launch.
 using KernelFn = void (*)(const StepArgs);
-KernelFn miz_step_kernels_identity(int cells, int mode, int threads);
-KernelFn miz_step_kernels_nonuniform(int cells, int mode, int threads);
-KernelFn miz_step_kernels_imex(int grid_kind, int mode, int threads);
-// the state-only step that derives phi from Ei and h (miz_step_kernel, PHI_DERIVED): four cells per thread, the reference's step
-KernelFn miz_step_phi_derived_identity(int threads);
-KernelFn miz_step_phi_derived_nonuniform(int threads);
-// ... and neither loads nor stores state lines that are all zero (ZERO_LINES)
-KernelFn miz_step_zero_lines_identity(int threads);
-KernelFn miz_step_zero_lines_nonuniform(int threads);
-// fused-K with the state resident in LDS (miz_resident_kernel): four cells per thread; the reference's step beyond
-// kFusedRegThreads threads, the extension at every size
-KernelFn miz_resident_kernels(int grid_kind, int threads, bool imex);
-KernelFn miz_resident_save_kernels(int grid_kind, int threads, bool imex);   // ... with savesol!'s sums, every size
-KernelFn miz_fused2_save_kernels(int grid_kind, int threads);                // two cells per thread: miz_fused_kernel<2, ..., SAVE>
+// The MIZ kernels, one accessor per translation unit (miz_step_*.hip, miz_resident*.hip), each for the plans that kernel_of
+// sends it; nullptr = size not compiled
+KernelFn miz_step_kernels_identity(const StepPlan &p);      // K_MIZ_STEP of the reference's step, deriving and eliding included
+KernelFn miz_step_kernels_nonuniform(const StepPlan &p);
+KernelFn miz_step_kernels_imex(const StepPlan &p);          // K_MIZ_STEP of the extension, both grids
+KernelFn miz_resident_kernels(const StepPlan &p);           // K_MIZ_RESIDENT without savesol!'s sums
+KernelFn miz_save_kernels(const StepPlan &p);               // K_MIZ_RESIDENT and the two-cell K_MIZ_FUSED with the sums
 
-bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex);   // is this (geometry, mode) compiled?
-// may a one-step OUT_STATE launch of this handle take the kernel that derives phi?  (the caller answers for the state)
-bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex);
-// `count` workgroups, stepping columns first ... first + count - 1.  phi_derived (OUT_STATE where has_phi_derived_kernel):
-// the kernel that reads Ei and h for phi and leaves the phi field as it was; zero_lines (phi_derived only): its variant that
-// trusts and maintains the zero-line flags (zero_flag_words) — the caller answers for them
-hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
-                           bool zero_lines, int first, int count, hipStream_t s);
-hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s);
+hipError_t prepare_kernels(const LaunchCfg &cfg);   // raises the dynamic-LDS limit of every plan of the geometry that needs it
+bool has_step_kernel(const LaunchCfg &cfg, const StepVariant &v);   // is there a plan, and is its kernel compiled?
+// `count` workgroups of the plan's kernel, stepping columns first ... first + count - 1; with noise installed, after the
+// launch's noise sequence where the plan says the kernel reads it from memory.  Whoever asked for a deriving or eliding
+// plan answers for the state and the zero-line flags (zero_flag_words).
+hipError_t launch_step_columns(const StepArgs &a, const StepPlan &plan, int first, int count, hipStream_t s);
 // rcp_dt / rcp_cdn of the device-resident parameter block (see Params)
 hipError_t launch_derive_params(Params *p_dev, hipStream_t s);
 // active set from the T0 field (after ebm_set_field(T0))

@@ -53,6 +53,12 @@ template <int C, int GRID, bool IMEX>
         default: return nullptr;
     }
 }
+// the one-step kernels of the reference's step on one grid, by the plan: eliding, deriving, or the mode's at two or four cells
+template <int GRID>
+[[maybe_unused]] KernelFn miz_step_for(const StepPlan &p) {
+    if (p.phi_derived) return p.zero_lines ? miz_step_phi_derived_for<GRID, true>(p.threads) : miz_step_phi_derived_for<GRID>(p.threads);
+    return p.cells == 2 ? miz_step_by_mode<2, GRID, false>(p.mode, p.threads) : miz_step_by_mode<4, GRID, false>(p.mode, p.threads);
+}
 // every size for both models: the extension has no other fused kernel; the reference's step where the register kernel ends
 // (more than kFusedRegThreads threads) and, below that, where the handle prefers occupancy over latency; integrate (SAVE)
 // has no other fused kernel at four cells per thread

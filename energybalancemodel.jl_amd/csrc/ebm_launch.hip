@@ -21,8 +21,8 @@
 //                                       registers (annual-mean sums, raw snapshots); IMEX: the implicit-diffusion
 //                                       extension (one more tridiagonal solve per step, see include/ebm_hip.h)
 //                                       [ebm_miz_step.h; miz_step_identity.hip, miz_step_nonuniform.hip, miz_step_imex.hip]
-//   miz_fused_kernel<C, GRID, T>        K steps per launch, the whole state in registers (<= 512 threads; 768 with C = 2)
-//                                       [ebm_miz_fused.h; this file, with savesol!'s sums miz_resident_save.hip]
+//   miz_fused_kernel<C, GRID, T, SAVE>  K steps per launch, the whole state in registers (<= 512 threads; 768 with C = 2); SAVE (C = 2):
+//                                       with savesol!'s sums                     [ebm_miz_fused.h; this file, SAVE: miz_resident_save.hip]
 //   miz_resident_kernel<GRID, T, IMEX, SAVE>  K steps per launch, the state resident in LDS (more than 512 threads; the extension;
 //                                       launches of many columns at any size; SAVE: with savesol!'s sums, for ebm_integrate)
 //                                       [ebm_miz_resident.h; miz_resident.hip, SAVE: miz_resident_save.hip]
@@ -31,9 +31,11 @@
 //   finish_mean, hemispheric_means, mask_from_t0, derive_params, divide, permute_fields (split / unsplit), restore_phi,
 //   noise_innovations, noise_sequence, equilibrium_check, passage_check, compact_active: small helpers     [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
-// and every host-side launcher of the MIZ, classic and helper kernels [this file].  The layers below the kernels:
-// ebm_device.h (stores, parameter block, IEEE division, chunk loads), ebm_noise.h, ebm_solve.h (halo exchanges, the
-// tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
+// and every host-side launcher of the MIZ, classic and helper kernels [this file].  Which step kernel a launch takes, with
+// how much LDS and which noise source, is decided in ebm_plan.h (plan_step: plain C++, no HIP); this file only executes a
+// plan: kernel_of looks its instantiation up, launch_step_columns launches it, prepare_kernels readies every plan of a geometry.
+// The layers below the kernels: ebm_device.h (stores, parameter block, IEEE division, chunk loads), ebm_noise.h, ebm_solve.h
+// (halo exchanges, the tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
 // the 521 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
@@ -48,6 +50,8 @@
 // system, not by an operation order.
 //
 // No MFMA: there is no dense contraction on this path; it is HBM-/fp64-VALU-bound.
+#include <set>
+
 #include "ebm_kernel_table.h"
 
 namespace ebm {
@@ -497,140 +501,52 @@ hipError_t launch_restore_phi(const StepArgs &a, int ncol, const LaunchCfg &cfg,
 }
 
 // ---- host-side launchers ----------------------------------------------------------------------
-// Cells per thread: 4 unless the caller asks for 2 (ebm_options::cells_per_thread; nlat <= kMaxLat2 = 1536: the
-// fused kernel then still fits three waves per SIMD).  4 is the throughput geometry (32 contiguous bytes per lane and
-// field); a run of a FEW short meridians is latency-bound on a handful of waves, and 2 cells per thread put twice as
-// many SIMDs to work on every meridian.  The geometry — and with it the tridiagonal partition, i.e. the rounding of the
-// solves — is a function of (nlat, cells) ONLY, never of the number of columns: a member gives the same bits alone, in
-// a large ensemble and under any sharding.
-LaunchCfg choose_launch(int nlat, int cells_requested) {
-    LaunchCfg cfg{};
-    if (nlat > kMaxLat) {
-        cfg.threads = 0;
-        return cfg;
-    }
-    const int cells = (cells_requested == 2 && nlat <= kMaxLat2) ? 2 : 4;
-    const int chunks = (nlat + cells - 1) / cells;
-    cfg.threads = ((chunks + 63) / 64) * 64;
-    if (cells == 2 && cfg.threads > 512) cfg.threads = 768;     // the one size compiled beyond 512 (padding cells stay zero)
-    cfg.cells = cells;
-    // 2 x 3T cyclic reduction + the MIZ stash of Ew, h, Tw (3 C T)
-    cfg.lds_bytes = sizeof(double) * (size_t)cfg.threads * (6 + 3 * (size_t)cells);
-    return cfg;
-}
-
-namespace {
-
-// which fused-K kernel steps a handle's columns (one rule for the kernel table and the LDS size): the two compute the same
-// bits, so the choice is free to depend on the column count (LaunchCfg::fused_in_lds, set by the runtime)
-bool fused_state_in_lds(const LaunchCfg &cfg, bool imex) {
-    return imex || (cfg.cells == 4 && (cfg.threads > kFusedRegThreads || cfg.fused_in_lds));
-}
-KernelFn miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex, bool phi_derived = false, bool zero_lines = false) {
-    const int cells = cfg.cells, threads = cfg.threads;
-    if (zero_lines && !phi_derived) return nullptr;
-    if (phi_derived) {
-        if (mode != OUT_STATE || imex || cells != 4) return nullptr;
-        if (zero_lines) return grid_kind == 0 ? miz_step_zero_lines_identity(threads) : miz_step_zero_lines_nonuniform(threads);
-        return grid_kind == 0 ? miz_step_phi_derived_identity(threads) : miz_step_phi_derived_nonuniform(threads);
-    }
-    if (mode == OUT_LOOP_SAVE) {
-        if (cells == 4) return miz_resident_save_kernels(grid_kind, threads, imex);
-        return imex ? nullptr : miz_fused2_save_kernels(grid_kind, threads);
-    }
-    if (mode == OUT_LOOP) {        // fused-K: state in registers where it fits, resident in LDS otherwise
-        if (fused_state_in_lds(cfg, imex)) return cells != 4 ? nullptr : miz_resident_kernels(grid_kind, threads, imex);
-        if (cells == 2) return grid_kind == 0 ? miz_fused_for<2, 0>(threads) : miz_fused_for<2, 1>(threads);
-        return grid_kind == 0 ? miz_fused_for<4, 0>(threads) : miz_fused_for<4, 1>(threads);
-    }
-    if (imex) return cells != 4 ? nullptr : miz_step_kernels_imex(grid_kind, mode, threads);
-    return grid_kind == 0 ? miz_step_kernels_identity(cells, mode, threads) : miz_step_kernels_nonuniform(cells, mode, threads);
-}
-template <int C>
-KernelFn classic_kernel_c(int mode) {
-    switch (mode) {
-        case OUT_STATE:
-        case OUT_DIAG: return classic_step_kernel<C, OUT_STATE>;
-        case OUT_SAVE: return classic_step_kernel<C, OUT_SAVE>;
-        case OUT_LOOP: return classic_step_kernel<C, OUT_LOOP>;
+// The kernel of a plan: a table lookup that holds no rule (ebm_plan.h has them all).  nullptr: no plan, or a size that this
+// build lacks (EBM_QUICK).
+static KernelFn kernel_of(const StepPlan &p) {
+    switch (p.family) {
+        case K_CLASSIC:
+            if (p.mode == OUT_SAVE) return p.cells == 2 ? classic_step_kernel<2, OUT_SAVE> : classic_step_kernel<4, OUT_SAVE>;
+            if (p.mode == OUT_LOOP) return p.cells == 2 ? classic_step_kernel<2, OUT_LOOP> : classic_step_kernel<4, OUT_LOOP>;
+            return p.cells == 2 ? classic_step_kernel<2, OUT_STATE> : classic_step_kernel<4, OUT_STATE>;
+        case K_MIZ_STEP:
+            return p.imex ? miz_step_kernels_imex(p) : p.grid == 0 ? miz_step_kernels_identity(p) : miz_step_kernels_nonuniform(p);
+        case K_MIZ_FUSED:
+            if (p.save()) return miz_save_kernels(p);
+            if (p.cells == 2) return p.grid == 0 ? miz_fused_for<2, 0>(p.threads) : miz_fused_for<2, 1>(p.threads);
+            return p.grid == 0 ? miz_fused_for<4, 0>(p.threads) : miz_fused_for<4, 1>(p.threads);
+        case K_MIZ_RESIDENT: return p.save() ? miz_save_kernels(p) : miz_resident_kernels(p);
         default: return nullptr;
     }
 }
-KernelFn classic_kernel(int cells, int mode) { return cells == 2 ? classic_kernel_c<2>(mode) : classic_kernel_c<4>(mode); }
-// LDS of a launch: the fused register kernel only needs the solve's buffers; the resident kernel 4T for the solve and
-// 4 fields x 4 cells x T for the state
-size_t miz_lds_bytes(const LaunchCfg &cfg, int mode, bool imex) {
-    if (mode == OUT_LOOP_SAVE) return sizeof(double) * (cfg.cells == 4 ? 20 : 6) * (size_t)cfg.threads;
-    if (mode == OUT_LOOP) return sizeof(double) * (fused_state_in_lds(cfg, imex) ? 20 : 6) * (size_t)cfg.threads;
-    return cfg.lds_bytes;
-}
 
-}  // namespace
+bool has_step_kernel(const LaunchCfg &cfg, const StepVariant &v) { return kernel_of(plan_step(cfg, v)) != nullptr; }
 
-// Dynamic LDS above the 64 KiB default must be requested per kernel.
+// Dynamic LDS above the 64 KiB default must be requested per kernel: every plan of the geometry that needs it, each kernel once.
 hipError_t prepare_kernels(const LaunchCfg &cfg) {
-    auto raise = [](KernelFn fn, size_t bytes) -> hipError_t {
-        if (!fn) return hipErrorInvalidValue;
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    };
-    for (int grid = 0; grid < 2; ++grid)
-        for (int imex = 0; imex < (cfg.cells == 4 ? 2 : 1); ++imex) {
-            if (cfg.lds_bytes > 64 * 1024)
-                for (int mode = OUT_STATE; mode <= OUT_SAVE; ++mode) {   // (the fused register kernel needs 6T doubles <= 24 KiB)
-                    hipError_t e = raise(miz_kernel(cfg, grid, mode, imex != 0), cfg.lds_bytes);
-                    if (e != hipSuccess) return e;
-                    if (mode == OUT_STATE && has_phi_derived_kernel(cfg, grid, imex != 0))
-                        e = raise(miz_kernel(cfg, grid, mode, false, true), cfg.lds_bytes);
-                    if (e == hipSuccess && mode == OUT_STATE && has_phi_derived_kernel(cfg, grid, imex != 0))
-                        e = raise(miz_kernel(cfg, grid, mode, false, true, true), cfg.lds_bytes);
-                    if (e != hipSuccess) return e;
-                }
-            // the resident fused-K kernels and their savesol! variants (four cells per thread): 160 T bytes
-            const size_t bytes = sizeof(double) * 20 * (size_t)cfg.threads;
-            if (cfg.cells != 4 || bytes <= 64 * 1024) continue;
-            hipError_t e = raise(miz_resident_kernels(grid, cfg.threads, imex != 0), bytes);
-            if (e == hipSuccess) e = raise(miz_resident_save_kernels(grid, cfg.threads, imex != 0), bytes);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
+    std::set<KernelFn> raised;
+    hipError_t e = hipSuccess;
+    for_each_variant(cfg, [&](const LaunchCfg &c, const StepVariant &v) {
+        const StepPlan plan = plan_step(c, v);
+        if (e != hipSuccess || !needs_raised_lds(plan)) return;
+        KernelFn fn = kernel_of(plan);
+        if (!fn) e = hipErrorInvalidValue;
+        else if (raised.insert(fn).second)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+    });
+    return e;
 }
 
-bool has_miz_kernel(const LaunchCfg &cfg, int grid_kind, int mode, bool imex) {
-    return miz_kernel(cfg, grid_kind, mode, imex) != nullptr;
-}
-
-bool has_phi_derived_kernel(const LaunchCfg &cfg, int grid_kind, bool imex) {
-    return miz_kernel(cfg, grid_kind, OUT_STATE, imex, true) != nullptr;
-}
-
-hipError_t launch_miz_step(const StepArgs &a, int grid_kind, int mode, const LaunchCfg &cfg, bool imex, bool phi_derived,
-                           bool zero_lines, int first, int count, hipStream_t s) {
-    KernelFn fn = miz_kernel(cfg, grid_kind, mode, imex, phi_derived, zero_lines);
+hipError_t launch_step_columns(const StepArgs &a, const StepPlan &plan, int first, int count, hipStream_t s) {
+    KernelFn fn = kernel_of(plan);
     if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
-    // fused launches whose kernel reads N_c from memory: everything but miz_fused_kernel up to kFusedRegThreads threads
-    const bool fused = mode == OUT_LOOP || mode == OUT_LOOP_SAVE;
-    const bool in_registers = !fused_state_in_lds(cfg, imex) && cfg.threads <= kFusedRegThreads &&
-                              !(mode == OUT_LOOP_SAVE && cfg.cells == 4);
-    if (a.noise && fused && !in_registers) {
+    if (a.noise && plan.noise_from_memory) {
         hipError_t e = launch_noise_sequence(a, first, count, s);
         if (e != hipSuccess) return e;
     }
     StepArgs b = a;
     b.col0 = first;
-    fn<<<dim3(count), dim3(cfg.threads), miz_lds_bytes(cfg, mode, imex), s>>>(b);
-    return hipGetLastError();
-}
-
-hipError_t launch_classic_step(const StepArgs &a, int mode, const LaunchCfg &cfg, int first, int count, hipStream_t s) {
-    KernelFn fn = classic_kernel(cfg.cells, mode);
-    if (!fn || first < 0 || count < 1 || first + count > a.ncol) return hipErrorInvalidValue;
-    if (a.noise && mode == OUT_LOOP) {                  // the fused classic kernel reads N_c from memory
-        hipError_t e = launch_noise_sequence(a, first, count, s);
-        if (e != hipSuccess) return e;
-    }
-    StepArgs b = a;
-    b.col0 = first;
-    fn<<<dim3(count), dim3(cfg.threads), sizeof(double) * 6 * (size_t)cfg.threads, s>>>(b);
+    fn<<<dim3(count), dim3(plan.threads), plan.lds_bytes, s>>>(b);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // Shared by the four translation units of the host runtime behind the C ABI of include/ebm_hip.h: the handle, the error
 // idioms and the handle's stream.
 //   ebm_fieldbook.h   (HIP-free) the field predicates and THE rule of field validity, layout and phi: ebm_ctx::book
+//   ebm_plan.h        (HIP-free) the launch geometry and THE rule of a step launch's kernel, LDS and noise source: plan_step
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the two diffusion operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling

@@ -48,6 +48,11 @@ int read_options(const ebm_options *user_opt, ebm_options &opt) {
 }
 
 // What the options leave to the library, from the shape (h->nlat, ncol, cfg) and the device (num_cus).  No choice changes a bit.
+// dynamic LDS of a one-step launch of the geometry (the MIZ step's, whatever the model: what ebm_launch_info has always reported)
+size_t one_step_lds_bytes(const ebm::LaunchCfg &cfg) {
+    return ebm::plan_step(cfg, {ebm::STEP_MIZ, 0, false, ebm::OUT_STATE, false, false}).lds_bytes;
+}
+
 void choose_heuristics(ebm_ctx *h, const ebm_options &opt) {
     const int nlat = h->nlat, ncol = h->ncol;
     const ebm::LaunchCfg &cfg = h->cfg;
@@ -63,7 +68,7 @@ void choose_heuristics(ebm_ctx *h, const ebm_options &opt) {
         // overlaps the input loads of a workgroup, so each workgroup prefetches into L2 the inputs
         // of the one that follows it on its XCD (workgroups go round-robin over the XCDs and in
         // order within one).
-        int per_cu = (int)((160u * 1024u) / cfg.lds_bytes);                  // workgroups a CU holds: LDS ...
+        int per_cu = (int)((160u * 1024u) / one_step_lds_bytes(cfg));         // workgroups a CU holds: LDS ...
         if (per_cu > 2048 / cfg.threads) per_cu = 2048 / cfg.threads;         // ... and wave slots
         const int ahead = h->num_cus * per_cu;                                // the successor on the same XCD
         // measured: -3.5 % time at one workgroup per CU, -2.5 % at two, nothing beyond
@@ -175,7 +180,7 @@ int ebm_create_ex(ebm_handle_t *out, int model, int grid, int nlat, int ncol, co
     h->model = model; h->grid = grid; h->nlat = nlat; h->ncol = ncol; h->device = device;
     h->dt = dt; h->cfg = cfg; h->imex = imex;
     // (elide_zero_lines: on by default wherever the deriving kernel is — the book ignores it elsewhere)
-    h->book = FieldBook(model, model == EBM_MODEL_MIZ && cfg.cells == 4, model == EBM_MODEL_MIZ && ebm::has_phi_derived_kernel(cfg, grid, imex),
+    h->book = FieldBook(model, model == EBM_MODEL_MIZ && cfg.cells == 4, model == EBM_MODEL_MIZ && ebm::has_step_kernel(cfg, {ebm::STEP_MIZ, grid, imex, ebm::OUT_STATE, true, false}),
                         opt.elide_zero_lines != 0);
     h->num_cus = prop.multiProcessorCount;
     choose_heuristics(h.get(), opt);
@@ -324,7 +329,7 @@ int ebm_launch_info(ebm_handle_t h, int *info) {
     if (!h || !info) return fail(EBM_ERR_ARG, "ebm_launch_info: null argument");
     info[0] = h->cfg.threads;
     info[1] = h->cfg.cells;
-    info[2] = (int)h->cfg.lds_bytes;
+    info[2] = (int)one_step_lds_bytes(h->cfg);
     info[3] = h->ncol;
     return EBM_OK;
 }

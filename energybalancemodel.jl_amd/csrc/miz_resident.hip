@@ -3,9 +3,9 @@
 
 namespace ebm {
 
-KernelFn miz_resident_kernels(int grid_kind, int threads, bool imex) {
-    if (imex) return grid_kind == 0 ? miz_resident_for<0, true, false>(threads) : miz_resident_for<1, true, false>(threads);
-    return grid_kind == 0 ? miz_resident_for<0, false, false>(threads) : miz_resident_for<1, false, false>(threads);
+KernelFn miz_resident_kernels(const StepPlan &p) {
+    if (p.imex) return p.grid == 0 ? miz_resident_for<0, true, false>(p.threads) : miz_resident_for<1, true, false>(p.threads);
+    return p.grid == 0 ? miz_resident_for<0, false, false>(p.threads) : miz_resident_for<1, false, false>(p.threads);
 }
 
 }  // namespace ebm

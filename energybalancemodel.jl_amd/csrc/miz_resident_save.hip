@@ -3,12 +3,11 @@
 
 namespace ebm {
 
-KernelFn miz_resident_save_kernels(int grid_kind, int threads, bool imex) {
-    if (imex) return grid_kind == 0 ? miz_resident_for<0, true, true>(threads) : miz_resident_for<1, true, true>(threads);
-    return grid_kind == 0 ? miz_resident_for<0, false, true>(threads) : miz_resident_for<1, false, true>(threads);
-}
-KernelFn miz_fused2_save_kernels(int grid_kind, int threads) {     // two cells per thread: the register kernel with the sums
-    return grid_kind == 0 ? miz_fused_for<2, 0, true>(threads) : miz_fused_for<2, 1, true>(threads);
+KernelFn miz_save_kernels(const StepPlan &p) {
+    if (p.family == K_MIZ_FUSED)                          // two cells per thread: the register kernel with the sums
+        return p.grid == 0 ? miz_fused_for<2, 0, true>(p.threads) : miz_fused_for<2, 1, true>(p.threads);
+    if (p.imex) return p.grid == 0 ? miz_resident_for<0, true, true>(p.threads) : miz_resident_for<1, true, true>(p.threads);
+    return p.grid == 0 ? miz_resident_for<0, false, true>(p.threads) : miz_resident_for<1, false, true>(p.threads);
 }
 
 }  // namespace ebm

@@ -4,10 +4,6 @@
 
 namespace ebm {
 
-KernelFn miz_step_kernels_identity(int cells, int mode, int threads) {
-    return cells == 2 ? miz_step_by_mode<2, 0, false>(mode, threads) : miz_step_by_mode<4, 0, false>(mode, threads);
-}
-KernelFn miz_step_phi_derived_identity(int threads) { return miz_step_phi_derived_for<0>(threads); }
-KernelFn miz_step_zero_lines_identity(int threads) { return miz_step_phi_derived_for<0, true>(threads); }
+KernelFn miz_step_kernels_identity(const StepPlan &p) { return miz_step_for<0>(p); }
 
 }  // namespace ebm

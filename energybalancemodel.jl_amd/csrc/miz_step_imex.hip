@@ -3,8 +3,8 @@
 
 namespace ebm {
 
-KernelFn miz_step_kernels_imex(int grid_kind, int mode, int threads) {        // the extension: 4 cells per thread
-    return grid_kind == 0 ? miz_step_by_mode<4, 0, true>(mode, threads) : miz_step_by_mode<4, 1, true>(mode, threads);
+KernelFn miz_step_kernels_imex(const StepPlan &p) {        // the extension: 4 cells per thread
+    return p.grid == 0 ? miz_step_by_mode<4, 0, true>(p.mode, p.threads) : miz_step_by_mode<4, 1, true>(p.mode, p.threads);
 }
 
 }  // namespace ebm

@@ -415,8 +415,8 @@ def test_bench_gpus_n_refuses_without_devices():
 
 
 def test_bench_names_the_kernel_the_library_picks():
-    """bench.py's roofline block names the kernel of a workload by the library's own rule (csrc/ebm_launch.hip:
-    fused_state_in_lds; csrc/ebm_runtime.hip: ebm_create_ex): per-step kernel at K = 1; fused with the state in registers for
+    """bench.py's roofline block names the kernel of a workload by the library's own rule (csrc/ebm_plan.h:
+    plan_step; csrc/ebm_runtime.hip: ebm_create_ex): per-step kernel at K = 1; fused with the state in registers for
     a few columns of up to 512 threads and for two cells per thread; resident in LDS for longer meridians, for the
     extension, for more columns than the register kernel runs in one round, or when told so."""
     import importlib.util

@@ -12,8 +12,8 @@ wrong numbers and cannot fault.
 What each does (profiles/r18_noise_mutants.txt has the verdicts):
   noise_768_kernel_takes_the_register_sequence   miz_fused_kernel<2, ..., 768> evaluates the sequence itself although the
                                         launcher has run noise_sequence_kernel for it: N_c advances twice per launch
-  integrate_sequence_kernel_only_for_one_wave    launch_miz_step's in_registers keeps its OUT_LOOP_SAVE && cells == 4 term
-                                        at 64 threads only: beyond one wave ebm_integrate's resident SAVE kernel reads a
+  integrate_sequence_kernel_only_for_one_wave    plan_step's resident plan says noise_from_memory for the SAVE kernel at 64
+                                        threads only: beyond one wave ebm_integrate's resident SAVE kernel reads a
                                         row of nseq that nobody wrote.  (The term dropped altogether, as first proposed, is
                                         caught by tests/test_gpu_noise.py::test_integrate_with_noise at 64 threads.)
   sequence_lane_is_the_thread_from_the_third_wave   sequence() takes threadIdx.x, not threadIdx.x & 63, for its lane from
@@ -30,8 +30,8 @@ import mutants
 mutants.MUTANTS = [
     ("noise_768_kernel_takes_the_register_sequence", "constexpr bool kNoiseMem = TT > kFusedRegThreads;",
      "constexpr bool kNoiseMem = TT > 768;", "ebm_miz_fused.h"),
-    ("integrate_sequence_kernel_only_for_one_wave", "!(mode == OUT_LOOP_SAVE && cfg.cells == 4);",
-     "!(mode == OUT_LOOP_SAVE && cfg.cells == 4 && cfg.threads == 64);", "ebm_launch.hip"),
+    ("integrate_sequence_kernel_only_for_one_wave", "plan(K_MIZ_RESIDENT, 20, true)",
+     "plan(K_MIZ_RESIDENT, 20, !save || T == 64)", "ebm_plan.h"),
     ("sequence_lane_is_the_thread_from_the_third_wave", "const int l = (int)(threadIdx.x & 63u);",
      "const int l = (int)(threadIdx.x < 128u ? threadIdx.x & 63u : threadIdx.x);", "ebm_noise.h"),
     ("step_counter_loses_its_high_word", "unsigned w[4] = {(unsigned)un, (unsigned)(un >> 32),", "unsigned w[4] = {(unsigned)un, 0u,",
