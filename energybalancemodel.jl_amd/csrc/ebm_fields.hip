@@ -110,68 +110,146 @@ hipError_t hemispheric_mean(ebm_ctx *h, int field, double *dev_out) {
     return ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
 }
 
-// ebm_ensemble_sums / _device (include/ebm_hip.h): the checks, then the two launches of ebm_ensemble.hip into dev_out (the
-// caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
-int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, const double *center, double *host_out,
-                  double *dev_out, const char *who) {
-    const std::string me(who);
+// What ebm_ensemble_sums, ebm_ensemble_range and ebm_ensemble_histogram have in common (include/ebm_hip.h), in the order every
+// one of them keeps: the arguments (ensemble_check: no device work, nothing of the handle changes), the call's own checks,
+// then ensemble_open — staleness, phi made current, the launch chains joined, the weights uploaded, the rows where they lie.
+int ensemble_check(const ebm_ctx *h, int nvars, const int *fields, bool each_once, const double *w, bool have_out, const std::string &me) {
     if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
-    if (!fields || (!host_out && !dev_out)) return fail(EBM_ERR_ARG, me + ": null argument");
+    if (!fields || !have_out) return fail(EBM_ERR_ARG, me + ": null argument");
     if (nvars < 1 || nvars > ebm::kMaxQuantities)
         return fail(EBM_ERR_ARG, me + ": nvars = " + std::to_string(nvars) + " is outside 1 ... " + std::to_string(ebm::kMaxQuantities));
     for (int v = 0; v < nvars; ++v) {
         if (!h->book.has(fields[v]) || quantity_of(h->model, fields[v]) < 0)
             return fail(EBM_ERR_ARG, me + ": fields[" + std::to_string(v) + "] is not a solution variable of this model");
-        for (int u = 0; u < v; ++u)
+        for (int u = 0; each_once && u < v; ++u)
             if (fields[u] == fields[v]) return fail(EBM_ERR_ARG, me + ": field " + field_name(fields[v]) + " is listed twice");
     }
     for (int c = 0; w && c < h->ncol; ++c)
         if (!std::isfinite(w[c])) return fail(EBM_ERR_ARG, me + ": w[" + std::to_string(c) + "] is not finite (column " + std::to_string(c) + ")");
-    for (long long i = 0; center && i < (long long)nvars * h->nlat; ++i)
-        if (!std::isfinite(center[i]))
-            return fail(EBM_ERR_ARG, me + ": center[" + std::to_string(i / h->nlat) + "][" + std::to_string(i % h->nlat) + "] is not finite");
+    return EBM_OK;
+}
+struct EnsembleRows {
+    const double *row[ebm::kMaxQuantities];              // where each lies: no field is converted
+    unsigned split_mask = 0;
+    const double *w = nullptr;                           // on the device, the upload enqueued on s
+    hipStream_t s = nullptr;
+    std::vector<double> ones;                            // the unit weights of w = NULL: alive until the call has synchronised
+};
+int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, const char *who, EnsembleRows &r) {
     for (int v = 0; v < nvars; ++v)
         if (int rc = check_current(h, fields[v], who)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    ebm_ctx::EnsembleSums &b = h->sums;
-    const int nblocks = (h->ncol + ebm::kSumsBlock - 1) / ebm::kSumsBlock;
-    const size_t npitch = (size_t)h->pitch;
-    HIPCHK(b.partial.reserve((size_t)nblocks * 3 * (size_t)nvars * npitch));
-    HIPCHK(b.w.reserve((size_t)h->ncol));
-    if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * 3 * (size_t)h->nlat));
+    HIPCHK(h->sums.w.reserve((size_t)h->ncol));
     // phi is read as a field: current first, in the layout the state has.  Nothing else of the handle changes
     for (int v = 0; v < nvars; ++v)
         if (fields[v] == EBM_F_phi && h->model == EBM_MODEL_MIZ) {
             hipError_t e = restore_phi(h);
             if (e != hipSuccess) return hip_fail("phi restore", e);
         }
-    hipStream_t s = main_stream(h);                      // joins the two launch chains: every column's last step has ended
+    r.s = main_stream(h);                                // joins the two launch chains: every column's last step has ended
+    r.ones.assign(w ? 0 : (size_t)h->ncol, 1.0);
+    HIPCHK(hipMemcpyAsync(h->sums.w.get(), w ? w : r.ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, r.s));
+    r.w = h->sums.w.get();
+    for (int v = 0; v < nvars; ++v) {
+        const int f = fields[v];
+        r.row[v] = h->field[f];
+        if (h->book.held_split(f)) r.split_mask |= 1u << v;
+    }
+    return EBM_OK;
+}
+// the result down (host variant) and the end of the call: synchronous
+int ensemble_close(hipError_t e, double *host_out, const double *dev, size_t n, hipStream_t s, const char *who) {
+    if (e == hipSuccess && host_out) e = hipMemcpyAsync(host_out, dev, sizeof(double) * n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(who, e);
+    return EBM_OK;
+}
+
+// ebm_ensemble_sums / _device (include/ebm_hip.h): the checks, then the two launches of ebm_ensemble.hip into dev_out (the
+// caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
+int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, const double *center, double *host_out,
+                  double *dev_out, const char *who) {
+    const std::string me(who);
+    if (int rc = ensemble_check(h, nvars, fields, true, w, host_out || dev_out, me)) return rc;
+    for (long long i = 0; center && i < (long long)nvars * h->nlat; ++i)
+        if (!std::isfinite(center[i]))
+            return fail(EBM_ERR_ARG, me + ": center[" + std::to_string(i / h->nlat) + "][" + std::to_string(i % h->nlat) + "] is not finite");
+    EnsembleRows r;
+    if (int rc = ensemble_open(h, nvars, fields, w, who, r)) return rc;
+    ebm_ctx::EnsembleSums &b = h->sums;
+    const int nblocks = (h->ncol + ebm::kSumsBlock - 1) / ebm::kSumsBlock;
+    const size_t npitch = (size_t)h->pitch;
+    HIPCHK(b.partial.reserve((size_t)nblocks * 3 * (size_t)nvars * npitch));
+    if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * 3 * (size_t)h->nlat));
+    hipStream_t s = r.s;
     if (center && !b.center.get()) {                     // all twelve rows once; the padding cells stay zero
         HIPCHK(b.center.reserve((size_t)ebm::kMaxQuantities * npitch));
         HIPCHK(hipMemsetAsync(b.center.get(), 0, sizeof(double) * ebm::kMaxQuantities * npitch, s));
     }
-    const std::vector<double> ones(w ? 0 : (size_t)h->ncol, 1.0);
-    hipError_t e = hipMemcpyAsync(b.w.get(), w ? w : ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && center)
+    hipError_t e = hipSuccess;
+    if (center)
         e = hipMemcpy2DAsync(b.center.get(), sizeof(double) * npitch, center, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
                              (size_t)nvars, hipMemcpyHostToDevice, s);
     ebm::EnsembleSumsArgs a{};
-    for (int v = 0; v < nvars; ++v) {
-        const int f = fields[v];
-        a.row[v] = h->field[f];                          // where it lies: no field is converted
-        if (h->book.held_split(f)) a.split_mask |= 1u << v;
-    }
-    a.w = b.w.get();
+    for (int v = 0; v < nvars; ++v) a.row[v] = r.row[v];
+    a.split_mask = r.split_mask;
+    a.w = r.w;
     a.center = center ? b.center.get() : nullptr;
     a.partial = b.partial.get();
     a.out = dev_out ? dev_out : b.out.get();
     a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.nblocks = nblocks; a.threads = h->cfg.threads;
     if (e == hipSuccess) e = ebm::launch_ensemble_sums(a, s);
-    if (e == hipSuccess && !dev_out)
-        e = hipMemcpyAsync(host_out, b.out.get(), sizeof(double) * 3 * (size_t)nvars * (size_t)h->nlat, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(who, e);
-    return EBM_OK;
+    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), 3 * (size_t)nvars * (size_t)h->nlat, s, who);
+}
+
+// ebm_ensemble_range / _device and ebm_ensemble_histogram / _device (include/ebm_hip.h): as ensemble_sums, with the two
+// launches of ebm_histogram.hip.  nbins = 0: the range.
+int ensemble_order(ebm_ctx *h, int nvars, const int *fields, const double *w, int nbins, const double *lo, const double *hi,
+                   double *host_out, double *dev_out, bool histogram, const char *who) {
+    const std::string me(who);
+    if (int rc = ensemble_check(h, nvars, fields, !histogram, w, host_out || dev_out, me)) return rc;
+    std::vector<double> edges;                           // [nvars][lo, hi, s][pitch], padding zero
+    const size_t npitch = (size_t)h->pitch;
+    if (histogram) {
+        if (!lo || !hi) return fail(EBM_ERR_ARG, me + ": null argument");
+        if (nbins < 1 || nbins > ebm::kHistMaxBins)
+            return fail(EBM_ERR_ARG, me + ": nbins = " + std::to_string(nbins) + " is outside 1 ... " + std::to_string(ebm::kHistMaxBins));
+        edges.assign(3 * (size_t)nvars * npitch, 0.0);
+        for (int v = 0; v < nvars; ++v)
+            for (int k = 0; k < h->nlat; ++k) {
+                const double l = lo[(size_t)v * h->nlat + k], u = hi[(size_t)v * h->nlat + k];
+                const double width = u - l, scale = (double)nbins / width;       // one IEEE division: part of the definition
+                if (!std::isfinite(l) || !std::isfinite(u) || !(l < u) || !std::isfinite(width) || !std::isfinite(scale))
+                    return fail(EBM_ERR_ARG, me + ": lo[" + std::to_string(v) + "][" + std::to_string(k) + "], hi[" + std::to_string(v) +
+                                                 "][" + std::to_string(k) + "] are not finite edges with lo < hi and finite hi - lo and nbins / (hi - lo)");
+                double *const e = edges.data() + 3 * (size_t)v * npitch + k;
+                e[0] = l; e[npitch] = u; e[2 * npitch] = scale;
+            }
+    }
+    EnsembleRows r;
+    if (int rc = ensemble_open(h, nvars, fields, w, who, r)) return rc;
+    ebm_ctx::EnsembleOrder &b = h->order;
+    const int block = histogram ? ebm::kHistBlock : ebm::kRangeBlock, nslots = histogram ? nbins + 2 : 3;
+    const int nblocks = (h->ncol + block - 1) / block;
+    const size_t nout = (size_t)nslots * (size_t)nvars * (size_t)h->nlat;
+    HIPCHK(b.partial.reserve((size_t)nblocks * (size_t)nslots * (size_t)nvars * npitch));
+    if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * (ebm::kHistMaxBins + 2) * (size_t)h->nlat));
+    hipError_t e = hipSuccess;
+    if (histogram) {
+        HIPCHK(b.edges.reserve(3 * (size_t)ebm::kMaxQuantities * npitch));
+        e = hipMemcpyAsync(b.edges.get(), edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice, r.s);
+    }
+    ebm::EnsembleOrderArgs a{};
+    for (int v = 0; v < nvars; ++v) a.row[v] = r.row[v];
+    a.split_mask = r.split_mask;
+    a.w = r.w;
+    a.edges = b.edges.get();
+    a.partial = b.partial.get();
+    a.out = dev_out ? dev_out : b.out.get();
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.nblocks = nblocks; a.threads = h->cfg.threads;
+    a.nbins = nbins;
+    if (e == hipSuccess) e = histogram ? ebm::launch_ensemble_histogram(a, r.s) : ebm::launch_ensemble_range(a, r.s);
+    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), nout, r.s, who);
 }
 
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
@@ -301,6 +379,24 @@ int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double
 
 int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *dev_out) {
     return ensemble_sums(h, nvars, fields, w, center, nullptr, dev_out, "ebm_ensemble_sums_device");
+}
+
+int ebm_ensemble_range(ebm_handle_t h, int nvars, const int *fields, const double *w, double *out) {
+    return ensemble_order(h, nvars, fields, w, 0, nullptr, nullptr, out, nullptr, false, "ebm_ensemble_range");
+}
+
+int ebm_ensemble_range_device(ebm_handle_t h, int nvars, const int *fields, const double *w, double *dev_out) {
+    return ensemble_order(h, nvars, fields, w, 0, nullptr, nullptr, nullptr, dev_out, false, "ebm_ensemble_range_device");
+}
+
+int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
+                           const double *hi, double *out) {
+    return ensemble_order(h, nvars, fields, w, nbins, lo, hi, out, nullptr, true, "ebm_ensemble_histogram");
+}
+
+int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
+                                  const double *hi, double *dev_out) {
+    return ensemble_order(h, nvars, fields, w, nbins, lo, hi, nullptr, dev_out, true, "ebm_ensemble_histogram_device");
 }
 
 int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {

@@ -235,5 +235,27 @@ struct EnsembleSumsArgs {
     int pitch, nlat, ncol, nvars, nblocks, threads;
 };
 hipError_t launch_ensemble_sums(const EnsembleSumsArgs &a, hipStream_t s);
+// ebm_ensemble_range and ebm_ensemble_histogram (ebm_histogram.hip): order statistics across the columns, per entry v of the
+// call and latitude k < nlat, in the order of the definition (include/ebm_hip.h).  row, split_mask and w as in
+// EnsembleSumsArgs; an entry of a histogram may name the row of an earlier one.  Two launches each.
+//   range      out[v][0..2][k] = n, min, max.  partial[block][v][3][pitch], blocks of kRangeBlock columns (the result does
+//              not depend on the blocking).
+//   histogram  out[v][slot][k], slot < nbins + 2.  edges[v][0..2][pitch] = lo, hi and s = nbins / (hi - lo) in natural
+//              latitude order, padding zero.  partial[block][v][slot][pitch], blocks of kHistBlock columns.
+constexpr int kRangeBlock = 32;      // columns per block of the range: performance only
+constexpr int kHistBlock = 256;      // columns per block of the histogram: part of the definition (include/ebm_hip.h)
+constexpr int kHistMaxBins = 64;
+struct EnsembleOrderArgs {
+    const double *row[kMaxQuantities];
+    unsigned split_mask;
+    const double *w;                 // [ncol], finite; never written by a kernel
+    const double *edges;             // histogram only
+    double *partial;
+    double *out;
+    int pitch, nlat, ncol, nvars, nblocks, threads;
+    int nbins;                       // histogram only
+};
+hipError_t launch_ensemble_range(const EnsembleOrderArgs &a, hipStream_t s);
+hipError_t launch_ensemble_histogram(const EnsembleOrderArgs &a, hipStream_t s);
 
 }  // namespace ebm

@@ -155,6 +155,11 @@ struct ebm_ctx {
     struct EnsembleSums {
         DevVec<double> partial, w, center, out;
     } sums;
+    // ebm_ensemble_range and ebm_ensemble_histogram, kept between calls: the block partials, the uploaded edges
+    // ([12][lo, hi, s][pitch], natural order) and the result of the host variants; the weights are sums.w
+    struct EnsembleOrder {
+        DevVec<double> partial, edges, out;
+    } order;
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
     DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
     ~ebm_ctx();

@@ -236,6 +236,76 @@ class Engine:
         check(self.lib.ebm_ensemble_sums_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr),
                                                 C.c_void_p(int(dev_ptr))), "ebm_ensemble_sums_device")
 
+    def _check_order_args(self, names, weights, repeats, nbins=None, lo=None, hi=None):
+        """The host-side checks of ``ensemble_range`` and ``ensemble_histogram`` (no device call): returns (names, field ids,
+        weights [ncol] or None, lo, hi [len(names), nlat] or None).  A histogram may list a field several times."""
+        if isinstance(names, str):
+            names = (names,)
+        names = tuple(names)
+        if not 1 <= len(names) <= 12:
+            raise ValueError(f"names: expected between 1 and 12 entries of fields of the {self.model} model")
+        _, ids, w, _ = self._check_sums_args(tuple(dict.fromkeys(names)), weights)
+        if not repeats and len(set(names)) != len(names):
+            raise ValueError(f"names: a field is listed twice in {names}")
+        if nbins is None:
+            return names, [FIELD[n] for n in names], w, None, None
+        if isinstance(nbins, (bool, np.bool_)) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
+            raise ValueError(f"nbins: expected an int between 1 and 64, got {nbins!r}")
+        lo, hi = as_f64(lo, (len(names), self.nlat)), as_f64(hi, (len(names), self.nlat))
+        with np.errstate(all="ignore"):
+            width = hi - lo
+            ok = np.isfinite(lo) & np.isfinite(hi) & (lo < hi) & np.isfinite(width) & np.isfinite(float(nbins) / width)
+        if not ok.all():
+            v, k = (int(i[0]) for i in np.nonzero(~ok))
+            raise ValueError(f"lo[{v}][{k}] = {lo[v, k]}, hi[{v}][{k}] = {hi[v, k]}: expected finite edges with lo < hi "
+                             "(and finite hi - lo and nbins / (hi - lo))")
+        return names, [FIELD[n] for n in names], w, lo, hi
+
+    @staticmethod
+    def _check_dev_ptr(dev_ptr):
+        if not isinstance(dev_ptr, (int, np.integer)) or isinstance(dev_ptr, (bool, np.bool_)) or int(dev_ptr) == 0:
+            raise ValueError(f"dev_ptr: expected a device address (int), got {dev_ptr!r}")
+        return C.c_void_p(int(dev_ptr))
+
+    def ensemble_range(self, names, weights=None) -> np.ndarray:
+        """ebm_ensemble_range (the definition is in include/ebm_hip.h): ndarray [len(names), 3, nlat] of the number n of
+        contributing columns, their minimum and their maximum, per latitude, reduced on the device.  A column contributes iff
+        its weight is not 0 and its cell is not NaN (``weights`` [ncol], None: all 1.0; a weight acts only through being zero
+        or not).  +-Inf is data; no contributor gives n = 0, min = +Inf, max = -Inf; of several equal extremes (+0.0, -0.0)
+        the first in ascending column order gives the bits.  Rows are read where they lie: no field is converted, the step
+        clock, the counters and ``field_step`` are unchanged.  StaleFieldError for a stale diagnostic field."""
+        names, ids, w, _, _ = self._check_order_args(names, weights, False)
+        out = np.full((len(names), 3, self.nlat), np.nan)
+        check(self.lib.ebm_ensemble_range(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(out)), "ebm_ensemble_range")
+        return out
+
+    def ensemble_range_device(self, names, dev_ptr: int, weights=None):
+        """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr``."""
+        names, ids, w, _, _ = self._check_order_args(names, weights, False)
+        ptr = self._check_dev_ptr(dev_ptr)
+        check(self.lib.ebm_ensemble_range_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), ptr), "ebm_ensemble_range_device")
+
+    def ensemble_histogram(self, names, lo, hi, nbins: int, weights=None) -> np.ndarray:
+        """ebm_ensemble_histogram (the definition is in include/ebm_hip.h): ndarray [len(names), nbins + 2, nlat], per entry
+        and latitude the summed weights of the contributing columns whose value x falls below ``lo`` (slot 0), into bin
+        min(int((x - lo) * s), nbins - 1) with s = nbins / (hi - lo) (slots 1 ... nbins), or at and above ``hi`` (slot
+        nbins + 1).  ``lo``, ``hi`` [len(names), nlat]: finite, lo < hi; 1 <= nbins <= 64.  A field may be listed several
+        times, each entry with its own edges.  The weights of a slot are added in a fixed order — blocks of 256 columns in
+        ascending column order, then the block partials in ascending order; with ``weights`` None every slot is an exact
+        count, so the histograms of shards add to the unsharded one bit for bit."""
+        names, ids, w, lo, hi = self._check_order_args(names, weights, True, nbins, lo, hi)
+        out = np.full((len(names), int(nbins) + 2, self.nlat), np.nan)
+        check(self.lib.ebm_ensemble_histogram(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo), dptr(hi),
+                                              dptr(out)), "ebm_ensemble_histogram")
+        return out
+
+    def ensemble_histogram_device(self, names, lo, hi, nbins: int, dev_ptr: int, weights=None):
+        """Same reduction, the packed [len(names), nbins + 2, nlat] result left on the device at ``dev_ptr``."""
+        names, ids, w, lo, hi = self._check_order_args(names, weights, True, nbins, lo, hi)
+        ptr = self._check_dev_ptr(dev_ptr)
+        check(self.lib.ebm_ensemble_histogram_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo),
+                                                     dptr(hi), ptr), "ebm_ensemble_histogram_device")
+
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""
         check(self.lib.ebm_get_field_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),

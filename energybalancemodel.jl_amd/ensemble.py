@@ -322,6 +322,71 @@ def moments_center(mean) -> np.ndarray:
     return np.ascontiguousarray(np.where(np.isfinite(m), m, 0.0))
 
 
+# ---- quantiles across the members ----------------------------------------------------------------------------------------------
+# ebm_ensemble_range and ebm_ensemble_histogram reduce across the columns on the device; the bracketing from histograms to
+# quantiles is host NumPy on O(nbins * nlat) numbers.
+
+QUANTILE_NBINS, QUANTILE_PASSES = 32, 4          # the defaults of ``quantiles`` (DESIGN.md section 5)
+QUANTILE_PAD_ULPS = 16.0
+
+
+def widened_bracket(lo, hi, nbins):
+    """[lo, hi) widened on both sides by QUANTILE_PAD_ULPS ulps of max(|lo|, |hi|) — more than the roundings of the bin edges
+    on the host (lo + i * ((hi - lo) / nbins): three) and of t = (x - lo) * s on the device (the difference, s, the product)
+    can move a value across an edge, each at most one ulp of max(|lo|, |hi|) or 2^-53 of hi - lo <= 2 max — and to at least
+    nbins * 2^-1020, so that nbins / (hi - lo) is finite."""
+    pad = QUANTILE_PAD_ULPS * np.spacing(np.maximum(np.abs(lo), np.abs(hi)))
+    lo, hi = lo - pad, hi + pad
+    tiny = nbins * 2.0 ** -1020
+    narrow = hi - lo < tiny
+    return np.where(narrow, lo - tiny, lo), np.where(narrow, hi + tiny, hi)
+
+
+def bracket_quantiles(histogram, rng, q, nbins, passes):
+    """The bracketing of ``EnsembleMoments.quantiles`` for m entries: ``histogram(lo, hi) -> [m, nbins + 2, nlat]`` with lo,
+    hi [m, nlat] (entry i of the call is the field of pair i), ``rng`` [m, 3, nlat] the range of each entry's field, ``q``
+    [m] its level.  Returns (value, halfwidth), each [m, nlat].  Pure NumPy but for the calls of ``histogram``."""
+    rng, q = np.asarray(rng, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    n, mn, mx = rng[:, 0], rng[:, 1], rng[:, 2]
+    value, half = np.full(n.shape, np.nan), np.full(n.shape, np.nan)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(mn) & np.isfinite(mx) & np.isfinite(mx - mn)
+    some = n > 0
+    const = some & finite & (mx == mn)
+    value[const], half[const] = mn[const], 0.0
+    half[some & ~finite] = np.inf
+    live = some & finite & (mx > mn)
+    if not live.any():
+        return value, half
+    lo, hi = widened_bracket(np.where(live, mn, 0.0), np.where(live, mx, 1.0), nbins)      # (a dummy [0, 1) elsewhere)
+    stuck = "quantiles: the bracket could not be restored (did the fields or the weights change between the passes?)"
+    for _ in range(passes):
+        for attempt in range(64):
+            # [m, nlat, slots]: the slots contiguous, so that the cumulative sums run along memory
+            h = np.ascontiguousarray(np.moveaxis(np.asarray(histogram(np.ascontiguousarray(lo), np.ascontiguousarray(hi))), 1, 2))
+            cum = np.cumsum(h, axis=2)
+            target = q[:, None] * cum[:, :, -1]
+            reached = (h > 0.0) & (cum >= target[:, :, None])         # the first slot that holds weight and reaches the target
+            slot = np.argmax(reached, axis=2)
+            out = live & (~reached.any(axis=2) | (slot == 0) | (slot == nbins + 1))
+            if not out.any():
+                break
+            with np.errstate(over="ignore", invalid="ignore"):
+                grow = 4.0 ** attempt * (hi - lo)                     # the sought value left the bracket: widen, repeat the pass
+                lo, hi = np.where(out, lo - grow, lo), np.where(out, hi + grow, hi)
+                usable = np.isfinite(lo) & np.isfinite(hi) & np.isfinite(hi - lo)
+            if not usable.all():
+                raise RuntimeError(stuck)
+        else:
+            raise RuntimeError(stuck)
+        step = (hi - lo) / nbins
+        a, b = widened_bracket(lo + (slot - 1) * step, lo + slot * step, nbins)
+        lo, hi = np.where(live, a, lo), np.where(live, b, hi)
+    width = hi - lo
+    value[live], half[live] = (lo + width / 2.0)[live], (width / 2.0)[live]
+    return value, half
+
+
 class EnsembleMoments:
     """Moments across the members in terms of two methods of the class it is mixed into: ``ensemble_sums(names, weights,
     center) -> ndarray [nvars, 3, nlat]`` and ``ensemble_sums_tensor(names, weights, center)``, the same as a device tensor.
@@ -366,6 +431,89 @@ class EnsembleMoments:
         s2 = np.asarray(self.reduced_sums(names, weights, center, dist))
         m = moments_from_sums(s1, s2)
         return {n: {k: m[k][i] for k in ("weight", "mean", "var")} for i, n in enumerate(names)}
+
+    # ---- order statistics across the members: ebm_ensemble_range and ebm_ensemble_histogram ----------------------------------
+    # The class it is mixed into also has ``ensemble_range(names, weights)``, ``ensemble_histogram(names, lo, hi, nbins,
+    # weights)`` and their ``_tensor`` forms (device tensors, for RCCL).
+
+    def range(self, names, weights=None, dist=None) -> np.ndarray:
+        """[len(names), 3, nlat]: the number n of contributing members, their minimum and their maximum per latitude
+        (ebm_ensemble_range) — of the whole ensemble with ``dist``: n is all-reduced with SUM, min with MIN, max with MAX,
+        which is exact, so every rank holds the bits of the unsharded call (up to which of +0.0 and -0.0 an extreme is)."""
+        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+            return self.ensemble_range(names, weights)
+        import torch
+        if _backend(dist) == "nccl":
+            t = self.ensemble_range_tensor(names, weights)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(self.ensemble_range(names, weights)))
+        parts = []
+        for q, op in enumerate((dist.ReduceOp.SUM, dist.ReduceOp.MIN, dist.ReduceOp.MAX)):
+            part = t[:, q].contiguous()
+            dist.all_reduce(part, op=op)
+            parts.append(part.cpu().numpy())
+        return np.stack(parts, axis=1)
+
+    def histogram(self, names, lo, hi, nbins, weights=None, dist=None) -> np.ndarray:
+        """[len(names), nbins + 2, nlat]: the weighted histogram across the members per latitude (ebm_ensemble_histogram:
+        below ``lo`` | nbins bins | at and above ``hi``) — of the whole ensemble with ``dist`` (all-reduced with SUM; with unit
+        weights every slot is an exact count and the result is the unsharded one bit for bit).  A name may be repeated,
+        each entry with its own rows of ``lo`` and ``hi``."""
+        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+            return self.ensemble_histogram(names, lo, hi, nbins, weights)
+        import torch
+        if _backend(dist) == "nccl":
+            t = self.ensemble_histogram_tensor(names, lo, hi, nbins, weights)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            return t.cpu().numpy()
+        t = torch.from_numpy(np.ascontiguousarray(self.ensemble_histogram(names, lo, hi, nbins, weights)))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.numpy()
+
+    def quantiles(self, names=("T", "phi"), q=(0.05, 0.5, 0.95), weights=None, dist=None, nbins=QUANTILE_NBINS,
+                  passes=QUANTILE_PASSES) -> dict:
+        """Weighted inverted-CDF quantiles ACROSS the members, per latitude: ``{name: {"value": [nq, nlat], "halfwidth": [nq,
+        nlat]}}``.  The quantile q is the smallest contributing value whose cumulative weight reaches q * (sum of the
+        weights); a member contributes iff its weight is not 0 and its cell is not NaN.  ``weights`` must be >= 0.  Nothing
+        but O(nbins * nlat) numbers per pass leaves the device: one ``range`` gives [min, max] per latitude; each of
+        ``passes`` ``histogram`` calls finds the slot in which the cumulative weight — the weight below ``lo`` included —
+        first reaches the target, and the next pass spreads its bins over that bin, widened by 16 ulps of max(|lo|, |hi|) so
+        that the rounding of (x - lo) * s cannot push the sought value out of it; if it lands below or above all the same,
+        the bracket is widened and that pass repeated.  All (name, q) pairs refine in ONE histogram call per pass (a field
+        may be listed several times there), more than 12 pairs in groups of 12.  ``value`` is the midpoint of the final
+        bracket and ``halfwidth`` half its width: the quantile lies within ``value`` +- ``halfwidth``, and halfwidth <=
+        (max - min) * nbins ** -passes up to the widening.  A latitude where max == min returns that value with halfwidth 0
+        and needs no histogram (ice-free latitudes, phi = 0 in every member); one without a contributor returns NaN; one
+        whose min or max is not finite (or whose max - min overflows) returns NaN with halfwidth +Inf.  With weights that
+        are not small integers the cumulative weights are the rounded sums of ebm_ensemble_histogram, compared as they are.
+        Defaults: nbins = 32, passes = 4 — a final halfwidth of 2^-21 of the range.  Measured on one MI355X (DESIGN.md
+        section 5), 32 bins x 4 passes is both finer and faster than 64 bins x 3 passes (2^-19): a histogram call costs up to
+        1.3 times as much at 64 bins (66 KiB of LDS per workgroup instead of 34), and the host arithmetic on the O(nbins *
+        nlat) slots per pair, which is most of the call's time, doubles.  With ``dist`` every rank returns the quantiles of
+        the whole ensemble."""
+        if isinstance(names, str):
+            names = (names,)
+        names = tuple(names)
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        if qs.ndim != 1 or qs.size < 1 or not ((qs >= 0.0) & (qs <= 1.0)).all():
+            raise ValueError(f"q: expected quantile levels in [0, 1], got {q!r}")
+        if not 1 <= int(nbins) <= 64 or int(passes) < 1:
+            raise ValueError(f"expected 1 <= nbins <= 64 and passes >= 1, got nbins = {nbins!r}, passes = {passes!r}")
+        if weights is not None and not (np.asarray(weights, dtype=np.float64) >= 0.0).all():
+            raise ValueError("weights: quantiles need weights >= 0")
+        nbins, passes = int(nbins), int(passes)
+        r = np.asarray(self.range(names, weights, dist))
+        pairs = [(i, j) for i in range(len(names)) for j in range(qs.size)]
+        value = np.full((len(names), qs.size, r.shape[-1]), np.nan)
+        half = np.full_like(value, np.nan)
+        for g in range(0, len(pairs), 12):
+            group = pairs[g:g + 12]
+            idx = [i for i, _ in group]
+            v, hw = bracket_quantiles(lambda lo, hi: np.asarray(self.histogram([names[i] for i in idx], lo, hi, nbins, weights, dist)),
+                                      r[idx], qs[[j for _, j in group]], nbins, passes)
+            for m, (i, j) in enumerate(group):
+                value[i, j], half[i, j] = v[m], hw[m]
+        return {n: {"value": value[i], "halfwidth": half[i]} for i, n in enumerate(names)}
 
 
 class EnsembleRun(ColumnExchange, EnsembleMoments):
@@ -622,6 +770,32 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         nv = 1 if isinstance(names, str) else len(tuple(names))
         out = torch.empty((nv, 3, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
         self.engine.ensemble_sums_device(names, out.data_ptr(), weights, center)
+        return out
+
+    def ensemble_range(self, names, weights=None):
+        """This shard's count, minimum and maximum across its members, per latitude (ebm_ensemble_range): ndarray
+        [len(names), 3, nlat].  See ``Engine.ensemble_range``; ``range`` combines the shards."""
+        return self.engine.ensemble_range(names, weights)
+
+    def ensemble_range_tensor(self, names, weights=None):
+        """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_range_device), ready for RCCL."""
+        import torch
+        nv = 1 if isinstance(names, str) else len(tuple(names))
+        out = torch.empty((nv, 3, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        self.engine.ensemble_range_device(names, out.data_ptr(), weights)
+        return out
+
+    def ensemble_histogram(self, names, lo, hi, nbins, weights=None):
+        """This shard's weighted histogram across its members, per latitude (ebm_ensemble_histogram): ndarray [len(names),
+        nbins + 2, nlat].  See ``Engine.ensemble_histogram``; ``histogram`` adds the shards, ``quantiles`` brackets with it."""
+        return self.engine.ensemble_histogram(names, lo, hi, nbins, weights)
+
+    def ensemble_histogram_tensor(self, names, lo, hi, nbins, weights=None):
+        """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_histogram_device), ready for RCCL."""
+        import torch
+        nv = 1 if isinstance(names, str) else len(tuple(names))
+        out = torch.empty((nv, int(nbins) + 2, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        self.engine.ensemble_histogram_device(names, lo, hi, nbins, out.data_ptr(), weights)
         return out
 
     def field_tensor(self, name):

@@ -9,10 +9,13 @@ EnsembleRun.series instead (ebm_run_series: <T> of every member sampled on the d
 per F, the quartiles of the FIRST time a member's <T> falls below that midpoint, in years at N * dt resolution.  With
 `--until` as well, the same table comes from EnsembleRun.first_passage (ebm_run_until): the level is tested on the device
 every N steps and a member that has fallen takes no further step — its state stays that of its crossing — so the table is
-the same and the script also prints the share of column-steps that were not taken.
+the same and the script also prints the share of column-steps that were not taken.  With `--quantiles` the yearly table
+is followed, per F, by the profile of T(x) and phi(x) across the members at the end of the run: the ensemble mean beside the
+median and the 5-95 % band (EnsembleRun.moments and EnsembleRun.quantiles, both reduced on the device) — where members sit
+on both branches the mean describes none of them.
 
     python examples/noise_induced_transitions.py [--nlat 180] [--nt 2000] [--forcings -2,0,2] [--members 64]
-        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0] [--until]
+        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0] [--until] [--quantiles]
 """
 import argparse
 import os
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--until", action="store_true",
                     help="with --every: stop each member at its first passage (EnsembleRun.first_passage) instead of "
                          "thresholding the whole series")
+    ap.add_argument("--quantiles", action="store_true",
+                    help="after the yearly table: mean, median and 5-95 %% band of T(x) and phi(x) across the members, per F")
     args = ap.parse_args()
     if args.until and not args.every:
         ap.error("--until needs --every N: the level is tested every N steps")
@@ -100,6 +105,12 @@ def main():
             print(f"column-steps taken: {taken} of {total} ({100.0 * (1.0 - taken / total):.1f} % not taken)")
         return
     out = run.seasonal_means(args.years, names=("T",))
+    profiles = []
+    if args.quantiles:
+        # per forcing: the members of the other forcings get weight zero (a conditional mean, a conditional quantile)
+        for i in range(nf):
+            w = (np.arange(nf * n) // n == i).astype(np.float64)
+            profiles.append((run.moments(("T", "phi"), w), run.quantiles(("T", "phi"), (0.05, 0.5, 0.95), w)))
     run.close()
     avgT = out["avg"][0]                                   # [years, members]
     fell = avgT < threshold
@@ -109,6 +120,13 @@ def main():
     for i in range(nf):
         frac = fell[:, i * n:(i + 1) * n].mean(axis=1)
         print(f"{F[i]:5.2f}  " + " ".join(f"{v:5.2f}" for v in frac))
+    lats = np.linspace(0, st.nx - 1, min(st.nx, 10)).astype(int)
+    for i, (m, q) in enumerate(profiles):
+        print(f"\nF = {F[i]:.2f}, end of year {args.years}, across the {n} members:   x     mean     5 %   median    95 %")
+        for name in ("T", "phi"):
+            for k in lats:
+                v = q[name]["value"][:, k]
+                print(f"  {name:>3s}  {st.x[k]:5.3f}  {m[name]['mean'][k]:7.3f}  {v[0]:7.3f}  {v[1]:7.3f}  {v[2]:7.3f}")
 
 
 if __name__ == "__main__":

@@ -164,7 +164,7 @@ const char *ebm_version(void);
  * T, h) and the fp64 warm start EBM_F_T0 are written only by steps that were asked to (ebm_step with
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
- * ebm_ensemble_sums*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
+ * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
  * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
@@ -600,6 +600,59 @@ int ebm_import_columns(ebm_handle_t h, int n, const int *cols, const int *record
 int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *out);
 int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center,
                              double *dev_out);
+
+/* Order statistics ACROSS the columns of a handle, per latitude: the number, minimum and maximum of the members' values
+ * (ebm_ensemble_range) and a weighted histogram of them between per-latitude edges (ebm_ensemble_histogram), reduced on the
+ * device.  Where the members of an ensemble sit on two branches (noise-induced transitions, hysteresis, cloning) the mean
+ * describes no member; median, bands and the distribution itself come from these two calls (EnsembleRun.quantiles brackets
+ * with them), and O((nbins + 2) * nlat) doubles cross the bus, or enter an all-reduce between shards, instead of O(state).
+ * THIS TEXT IS THE DEFINITION.
+ *   Arguments.  fields[nvars], w[ncol], the contribution rule, validity, layout, bookkeeping and ordering are those of
+ *     ebm_ensemble_sums (one piece of code checks them for all three): solution variables only, EBM_F_T0 is not one,
+ *     1 <= nvars <= 12; w NULL = every w_c = 1.0, finite, negative weights legal; column c CONTRIBUTES at (v, k) iff
+ *     w_c != 0.0 and the cell is not NaN; a stale diagnostic field is EBM_ERR_STALE with the message of ebm_hemispheric_mean;
+ *     phi is made current first; no field is converted and ebm_state_conversions does not grow; rows are read in whatever
+ *     layout the handle holds and only the indexing of lo, hi and the output is un-permuted; padding cells never reach a
+ *     result; the step clock, counters[0..3] and ebm_field_step are unchanged; the calls are synchronous on the handle's
+ *     stream, the two launch chains joined first.  In ebm_ensemble_range each field may appear at most once.  In
+ *     ebm_ensemble_histogram a field MAY be listed several times: every entry v has its own rows lo[v], hi[v], so several
+ *     quantiles of one field refine in one call.
+ *   Range.  out[nvars][3][nlat]: out[v][0][k] = the number of contributing columns (a double), out[v][1][k] their minimum,
+ *     out[v][2][k] their maximum.  A weight acts only through being zero or not.  +-Inf is data.  No contributor: n = 0,
+ *     min = +Inf, max = -Inf.  The minimum starts at +Inf and the columns are walked in ascending order, a contributing x
+ *     replacing it iff x < min (strictly), within a block of columns and then over the blocks in ascending order; the
+ *     maximum likewise from -Inf with x > max.  Where several contributors compare equal to the extreme (+0.0 and -0.0) the
+ *     result therefore carries the bits of the first of them in ascending column order, and does not depend on how the
+ *     columns are blocked.
+ *   Histogram.  1 <= nbins <= 64.  lo[nvars][nlat], hi[nvars][nlat]: host arrays in natural latitude order, every entry finite
+ *     with lo < hi, and hi - lo and s = (double)nbins / (hi - lo) finite; s is that one IEEE division, taken on the host.
+ *     out[nvars][nbins + 2][nlat].  A contributing value x at (v, k) goes to ONE slot: slot 0 ("below") if x < lo; slot
+ *     nbins + 1 ("above") if x >= hi; otherwise slot 1 + min((int)t, nbins - 1) with t = (x - lo) * s, a rounded difference
+ *     times a rounded product, nothing contracted.  The clamp is needed: with lo = -1, hi = 2 and x = nextafter(2, -Inf),
+ *     t == nbins exactly for nbins = 1, 2, 3, 5, 7, 32, 63, 64.  -Inf goes below and +Inf above; -0.0 with lo = 0.0 goes to
+ *     bin 0 (slot 1).  A slot's value is the sum of w_c over its contributors in a fixed order: block b holds the columns
+ *     256 b ... min(256 b + 255, ncol - 1); a block partial starts at 0.0 and adds in ascending column order; the result
+ *     starts at 0.0 and adds the block partials in ascending b.  (256, not the sums' 32: the partials are nbins + 2 times
+ *     larger than the sums'.)  With w = NULL every slot is an exact integer whatever the order, so unit-weight histograms of
+ *     shards add to the unsharded one bit for bit, and the ranges of shards combine exactly with SUM, MIN and MAX.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle, fields, out, lo or hi, nvars outside 1 ... 12, a field
+ * that is not a solution variable of the model (or, in the range, is listed twice), a non-finite w[c] (the message names the
+ * column), nbins outside 1 ... 64, an edge pair that breaks the rule above (the message names the first offending entry and
+ * latitude); EBM_ERR_STALE as above.
+ * How it runs (csrc/ebm_histogram.hip): the walk of ebm_ensemble_sums — grid (latitude tiles) x (column blocks) x (entries), a
+ * lane owning one 16-byte pair of cells, whole 128-byte lines, the loads of 16 columns issued ahead of the dependent work,
+ * w_c through the scalar cache — with n, min, max in registers for the range, and for the histogram the slots in LDS as
+ * [slot][cell of the pair][lane], (nbins + 2) KiB per one-wave workgroup, each lane touching only its own two columns of it:
+ * no atomics, no bank conflicts, no scratch.  A second kernel combines the block partials per latitude in ascending order
+ * and writes the natural index.  Device memory, kept by the handle and reused: ceil(ncol / 256) * (nbins + 2) * nvars * pitch
+ * doubles of block partials (range: ceil(ncol / 32) * 3 * nvars * pitch), 36 * pitch doubles of edges, and 12 * 66 * nlat
+ * doubles for the host variants' result. */
+int ebm_ensemble_range(ebm_handle_t h, int nvars, const int *fields, const double *w, double *out);
+int ebm_ensemble_range_device(ebm_handle_t h, int nvars, const int *fields, const double *w, double *dev_out);
+int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
+                           const double *hi, double *out);
+int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
+                                  const double *hi, double *dev_out);
 
 int ebm_sync(ebm_handle_t h);
 

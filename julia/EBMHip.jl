@@ -359,4 +359,58 @@ function ensemble_sums_device!(h::Handle, names::Vector{Symbol}, devout::Ptr{Cdo
                          "ebm_ensemble_sums_device")
 end
 
+"""
+    ensemble_range(h, names; ncol, nlat, weights=nothing) -> Array{Float64,3}
+    ensemble_range_device!(h, names, devout; weights=nothing)
+    ensemble_histogram(h, names, lo, hi, nbins; ncol, nlat, weights=nothing) -> Array{Float64,3}
+    ensemble_histogram_device!(h, names, lo, hi, nbins, devout; weights=nothing)
+
+Order statistics across the columns, per latitude, reduced on the device (`ebm_ensemble_range`, `ebm_ensemble_histogram`;
+the definitions are in the header).  Range: `out[k, q, v]`, q = 1, 2, 3, is the number of contributing columns of
+`names[v]` at latitude `k`, their minimum and their maximum.  Histogram: `out[k, s, v]`, s = 1 ... nbins + 2, the summed
+weights below `lo[k, v]`, in the `nbins` bins of `[lo, hi)`, and at or above `hi[k, v]`; `lo`, `hi`: `nlat x length(names)`,
+finite, `lo < hi`; `1 <= nbins <= 64`; a name may be repeated, each entry with its own column of edges.  A column
+contributes iff its weight is not 0 and its cell is not NaN.  The order of the sums is fixed (blocks of 256 columns); with
+`weights === nothing` every slot is an exact count.  The `_device!` forms write the packed array to the device pointer.
+"""
+function ensemble_range(h::Handle, names::Vector{Symbol}; ncol::Integer, nlat::Integer, weights=nothing)
+    out = Array{Float64,3}(undef, nlat, 3, length(names))
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    weights === nothing || length(weights) == ncol || error("weights: expected $ncol values")
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_range(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, w::Ptr{Cdouble},
+                                                          out::Ptr{Cdouble})::Cint), "ebm_ensemble_range")
+    return out
+end
+
+function ensemble_range_device!(h::Handle, names::Vector{Symbol}, devout::Ptr{Cdouble}; weights=nothing)
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_range_device(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, w::Ptr{Cdouble},
+                                                                 devout::Ptr{Cdouble})::Cint), "ebm_ensemble_range_device")
+end
+
+function ensemble_histogram(h::Handle, names::Vector{Symbol}, lo::Matrix{Float64}, hi::Matrix{Float64}, nbins::Integer;
+                            ncol::Integer, nlat::Integer, weights=nothing)
+    size(lo) == size(hi) == (nlat, length(names)) || error("lo, hi: expected $nlat x $(length(names)) values")
+    out = Array{Float64,3}(undef, nlat, nbins + 2, length(names))
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    weights === nothing || length(weights) == ncol || error("weights: expected $ncol values")
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_histogram(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, w::Ptr{Cdouble},
+                                                              nbins::Cint, lo::Ptr{Cdouble}, hi::Ptr{Cdouble},
+                                                              out::Ptr{Cdouble})::Cint), "ebm_ensemble_histogram")
+    return out
+end
+
+function ensemble_histogram_device!(h::Handle, names::Vector{Symbol}, lo::Matrix{Float64}, hi::Matrix{Float64}, nbins::Integer,
+                                    devout::Ptr{Cdouble}; weights=nothing)
+    f = Cint[FIELD[k] for k in names]
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_histogram_device(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint},
+                                                                     w::Ptr{Cdouble}, nbins::Cint, lo::Ptr{Cdouble},
+                                                                     hi::Ptr{Cdouble}, devout::Ptr{Cdouble})::Cint),
+                         "ebm_ensemble_histogram_device")
+end
+
 end # module EBMHip

@@ -1,0 +1,43 @@
+"""Broken builds of ebm_ensemble_range and ebm_ensemble_histogram (csrc/ebm_histogram.hip), for the mutation check of
+tests/tools/mutants.py, whose anchor rule and build this file uses unchanged: the same commands, restricted to the mutants
+below.  Each changes arithmetic, a comparison or the order of in-bounds reads only — no bound, no launch shape — so a mutant
+computes wrong numbers and cannot fault.
+
+    python tests/tools/mutants_hist.py check        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants_hist.py build        (CPU: one full build per mutant under build/)
+    GPU box, per mutant, EBM_LIB=build/libebm_mut_<name>.so EBM_TEST_NO_CHILDREN=1:
+        python -m pytest tests/test_gpu_ensemble_hist.py -q -m gpu        (must fail)
+
+What each does (profiles/r21_hist_mutants.txt has the verdicts):
+  hist_value_equal_to_hi_stays_inside     `x >= hi` becomes `x > hi`: a value equal to hi has t == nbins and is clamped into
+                                          the last bin instead of going above
+  hist_clamp_dropped                      min((int)t, nbins - 1) becomes min((int)t, nbins): nextafter(hi, -Inf) with t == nbins
+                                          goes to slot nbins + 1 ("above", an allocated slot) instead of the last bin
+  range_counts_zero_weights               the range's `w != 0.0` is dropped: members of weight zero count and give extremes.
+                                          (The same change in the histogram is an equivalent mutant — adding a weight of 0.0 to
+                                          a slot, which is never -0.0, changes no bit — and is not in the list.)
+  hist_blocks_added_in_descending_order   the finish kernel's tail loop adds the block partials from the last to the first:
+                                          rounding differs with weights over two blocks and more
+  range_later_equal_extreme_wins          strict `x < mn` becomes `x <= mn`: of +0.0 and -0.0 the last, not the first, gives
+                                          the bits of the minimum"""
+import sys
+
+import mutants
+
+mutants.MUTANTS = [
+    ("hist_value_equal_to_hi_stays_inside", "const bool below = x < lo, above = x >= hi;", "const bool below = x < lo, above = x > hi;",
+     "ebm_histogram.hip"),
+    ("hist_clamp_dropped", "1 + min(i, nbins - 1);", "1 + min(i, nbins);", "ebm_histogram.hip"),
+    ("range_counts_zero_weights", "const bool in = w != 0.0 && x == x;", "const bool in = x == x;", "ebm_histogram.hip"),
+    ("hist_blocks_added_in_descending_order", "for (; b < a.nblocks; ++b) sum = sum + part[b * stride];",
+     "for (; b < a.nblocks; ++b) sum = sum + part[(a.nblocks - 1 - b) * stride];", "ebm_histogram.hip"),
+    ("range_later_equal_extreme_wins", "mn = (in && x < mn) ? x : mn;", "mn = (in && x <= mn) ? x : mn;", "ebm_histogram.hip"),
+]
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["build"]:
+        mutants.build(sys.argv[2:])
+    elif sys.argv[1:2] == ["check"]:
+        sys.exit(mutants.check())
+    else:
+        print("\n".join(m[0] for m in mutants.MUTANTS))
