@@ -139,7 +139,7 @@ int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, con
     for (int v = 0; v < nvars; ++v)
         if (int rc = check_current(h, fields[v], who)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(h->sums.w.reserve((size_t)h->ncol));
+    HIPCHK(h->ensemble.w.reserve((size_t)h->ncol));
     // phi is read as a field: current first, in the layout the state has.  Nothing else of the handle changes
     for (int v = 0; v < nvars; ++v)
         if (fields[v] == EBM_F_phi && h->model == EBM_MODEL_MIZ) {
@@ -148,8 +148,8 @@ int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, con
         }
     r.s = main_stream(h);                                // joins the two launch chains: every column's last step has ended
     r.ones.assign(w ? 0 : (size_t)h->ncol, 1.0);
-    HIPCHK(hipMemcpyAsync(h->sums.w.get(), w ? w : r.ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, r.s));
-    r.w = h->sums.w.get();
+    HIPCHK(hipMemcpyAsync(h->ensemble.w.get(), w ? w : r.ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, r.s));
+    r.w = h->ensemble.w.get();
     for (int v = 0; v < nvars; ++v) {
         const int f = fields[v];
         r.row[v] = h->field[f];
@@ -165,60 +165,37 @@ int ensemble_close(hipError_t e, double *host_out, const double *dev, size_t n, 
     return EBM_OK;
 }
 
-// ebm_ensemble_sums / _device (include/ebm_hip.h): the checks, then the two launches of ebm_ensemble.hip into dev_out (the
-// caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
-int ensemble_sums(ebm_ctx *h, int nvars, const int *fields, const double *w, const double *center, double *host_out,
-                  double *dev_out, const char *who) {
+// What tells the three apart: the kernels' column block, and the per-latitude input — the center of the sums (null: none) or
+// the edges lo, hi of a histogram of nbins bins
+struct EnsembleCall {
+    enum Kind { SUMS, RANGE, HISTOGRAM } kind;
+    int block;
+    const double *center, *lo, *hi;
+    int nbins;
+    int nslots() const { return kind == HISTOGRAM ? nbins + 2 : 3; }
+};
+// ebm_ensemble_sums, ebm_ensemble_range, ebm_ensemble_histogram and their _device forms (include/ebm_hip.h): the checks, then
+// the two launches of ebm_ensemble.hip into dev_out (the caller's device buffer) or, for host_out, into the handle's own and
+// down.  Synchronous.
+int ensemble_reduce(ebm_ctx *h, int nvars, const int *fields, const double *w, const EnsembleCall &c, double *host_out,
+                    double *dev_out, const char *who) {
     const std::string me(who);
-    if (int rc = ensemble_check(h, nvars, fields, true, w, host_out || dev_out, me)) return rc;
-    for (long long i = 0; center && i < (long long)nvars * h->nlat; ++i)
-        if (!std::isfinite(center[i]))
-            return fail(EBM_ERR_ARG, me + ": center[" + std::to_string(i / h->nlat) + "][" + std::to_string(i % h->nlat) + "] is not finite");
-    EnsembleRows r;
-    if (int rc = ensemble_open(h, nvars, fields, w, who, r)) return rc;
-    ebm_ctx::EnsembleSums &b = h->sums;
-    const int nblocks = (h->ncol + ebm::kSumsBlock - 1) / ebm::kSumsBlock;
-    const size_t npitch = (size_t)h->pitch;
-    HIPCHK(b.partial.reserve((size_t)nblocks * 3 * (size_t)nvars * npitch));
-    if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * 3 * (size_t)h->nlat));
-    hipStream_t s = r.s;
-    if (center && !b.center.get()) {                     // all twelve rows once; the padding cells stay zero
-        HIPCHK(b.center.reserve((size_t)ebm::kMaxQuantities * npitch));
-        HIPCHK(hipMemsetAsync(b.center.get(), 0, sizeof(double) * ebm::kMaxQuantities * npitch, s));
-    }
-    hipError_t e = hipSuccess;
-    if (center)
-        e = hipMemcpy2DAsync(b.center.get(), sizeof(double) * npitch, center, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
-                             (size_t)nvars, hipMemcpyHostToDevice, s);
-    ebm::EnsembleSumsArgs a{};
-    for (int v = 0; v < nvars; ++v) a.row[v] = r.row[v];
-    a.split_mask = r.split_mask;
-    a.w = r.w;
-    a.center = center ? b.center.get() : nullptr;
-    a.partial = b.partial.get();
-    a.out = dev_out ? dev_out : b.out.get();
-    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.nblocks = nblocks; a.threads = h->cfg.threads;
-    if (e == hipSuccess) e = ebm::launch_ensemble_sums(a, s);
-    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), 3 * (size_t)nvars * (size_t)h->nlat, s, who);
-}
-
-// ebm_ensemble_range / _device and ebm_ensemble_histogram / _device (include/ebm_hip.h): as ensemble_sums, with the two
-// launches of ebm_histogram.hip.  nbins = 0: the range.
-int ensemble_order(ebm_ctx *h, int nvars, const int *fields, const double *w, int nbins, const double *lo, const double *hi,
-                   double *host_out, double *dev_out, bool histogram, const char *who) {
-    const std::string me(who);
+    const bool histogram = c.kind == EnsembleCall::HISTOGRAM;
     if (int rc = ensemble_check(h, nvars, fields, !histogram, w, host_out || dev_out, me)) return rc;
-    std::vector<double> edges;                           // [nvars][lo, hi, s][pitch], padding zero
     const size_t npitch = (size_t)h->pitch;
+    for (long long i = 0; c.center && i < (long long)nvars * h->nlat; ++i)
+        if (!std::isfinite(c.center[i]))
+            return fail(EBM_ERR_ARG, me + ": center[" + std::to_string(i / h->nlat) + "][" + std::to_string(i % h->nlat) + "] is not finite");
+    std::vector<double> edges;                           // [nvars][lo, hi, s][pitch], padding zero
     if (histogram) {
-        if (!lo || !hi) return fail(EBM_ERR_ARG, me + ": null argument");
-        if (nbins < 1 || nbins > ebm::kHistMaxBins)
-            return fail(EBM_ERR_ARG, me + ": nbins = " + std::to_string(nbins) + " is outside 1 ... " + std::to_string(ebm::kHistMaxBins));
+        if (!c.lo || !c.hi) return fail(EBM_ERR_ARG, me + ": null argument");
+        if (c.nbins < 1 || c.nbins > ebm::kHistMaxBins)
+            return fail(EBM_ERR_ARG, me + ": nbins = " + std::to_string(c.nbins) + " is outside 1 ... " + std::to_string(ebm::kHistMaxBins));
         edges.assign(3 * (size_t)nvars * npitch, 0.0);
         for (int v = 0; v < nvars; ++v)
             for (int k = 0; k < h->nlat; ++k) {
-                const double l = lo[(size_t)v * h->nlat + k], u = hi[(size_t)v * h->nlat + k];
-                const double width = u - l, scale = (double)nbins / width;       // one IEEE division: part of the definition
+                const double l = c.lo[(size_t)v * h->nlat + k], u = c.hi[(size_t)v * h->nlat + k];
+                const double width = u - l, scale = (double)c.nbins / width;     // one IEEE division: part of the definition
                 if (!std::isfinite(l) || !std::isfinite(u) || !(l < u) || !std::isfinite(width) || !std::isfinite(scale))
                     return fail(EBM_ERR_ARG, me + ": lo[" + std::to_string(v) + "][" + std::to_string(k) + "], hi[" + std::to_string(v) +
                                                  "][" + std::to_string(k) + "] are not finite edges with lo < hi and finite hi - lo and nbins / (hi - lo)");
@@ -228,28 +205,33 @@ int ensemble_order(ebm_ctx *h, int nvars, const int *fields, const double *w, in
     }
     EnsembleRows r;
     if (int rc = ensemble_open(h, nvars, fields, w, who, r)) return rc;
-    ebm_ctx::EnsembleOrder &b = h->order;
-    const int block = histogram ? ebm::kHistBlock : ebm::kRangeBlock, nslots = histogram ? nbins + 2 : 3;
-    const int nblocks = (h->ncol + block - 1) / block;
-    const size_t nout = (size_t)nslots * (size_t)nvars * (size_t)h->nlat;
+    ebm_ctx::Ensemble &b = h->ensemble;
+    const int nslots = c.nslots(), nblocks = (h->ncol + c.block - 1) / c.block;
     HIPCHK(b.partial.reserve((size_t)nblocks * (size_t)nslots * (size_t)nvars * npitch));
     if (!dev_out) HIPCHK(b.out.reserve((size_t)ebm::kMaxQuantities * (ebm::kHistMaxBins + 2) * (size_t)h->nlat));
-    hipError_t e = hipSuccess;
-    if (histogram) {
-        HIPCHK(b.edges.reserve(3 * (size_t)ebm::kMaxQuantities * npitch));
-        e = hipMemcpyAsync(b.edges.get(), edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice, r.s);
+    if (c.center && !b.center.get()) {                   // all twelve rows once; the padding cells stay zero
+        HIPCHK(b.center.reserve((size_t)ebm::kMaxQuantities * npitch));
+        HIPCHK(hipMemsetAsync(b.center.get(), 0, sizeof(double) * ebm::kMaxQuantities * npitch, r.s));
     }
-    ebm::EnsembleOrderArgs a{};
+    if (histogram) HIPCHK(b.edges.reserve(3 * (size_t)ebm::kMaxQuantities * npitch));
+    hipError_t e = hipSuccess;
+    if (c.center)
+        e = hipMemcpy2DAsync(b.center.get(), sizeof(double) * npitch, c.center, sizeof(double) * h->nlat, sizeof(double) * h->nlat,
+                             (size_t)nvars, hipMemcpyHostToDevice, r.s);
+    if (histogram) e = hipMemcpyAsync(b.edges.get(), edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice, r.s);
+    ebm::EnsembleArgs a{};
     for (int v = 0; v < nvars; ++v) a.row[v] = r.row[v];
     a.split_mask = r.split_mask;
     a.w = r.w;
-    a.edges = b.edges.get();
+    a.aux = c.center ? b.center.get() : histogram ? b.edges.get() : nullptr;
     a.partial = b.partial.get();
     a.out = dev_out ? dev_out : b.out.get();
     a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.nblocks = nblocks; a.threads = h->cfg.threads;
-    a.nbins = nbins;
-    if (e == hipSuccess) e = histogram ? ebm::launch_ensemble_histogram(a, r.s) : ebm::launch_ensemble_range(a, r.s);
-    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), nout, r.s, who);
+    a.nslots = nslots;
+    if (e == hipSuccess)
+        e = histogram ? ebm::launch_ensemble_histogram(a, r.s)
+                      : c.kind == EnsembleCall::RANGE ? ebm::launch_ensemble_range(a, r.s) : ebm::launch_ensemble_sums(a, r.s);
+    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), (size_t)nslots * (size_t)nvars * (size_t)h->nlat, r.s, who);
 }
 
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
@@ -374,29 +356,29 @@ int ebm_hemispheric_mean_device(ebm_handle_t h, int field, double *dev_out) {
 }
 
 int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *out) {
-    return ensemble_sums(h, nvars, fields, w, center, out, nullptr, "ebm_ensemble_sums");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::SUMS, ebm::kSumsBlock, center, nullptr, nullptr, 0}, out, nullptr, "ebm_ensemble_sums");
 }
 
 int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *dev_out) {
-    return ensemble_sums(h, nvars, fields, w, center, nullptr, dev_out, "ebm_ensemble_sums_device");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::SUMS, ebm::kSumsBlock, center, nullptr, nullptr, 0}, nullptr, dev_out, "ebm_ensemble_sums_device");
 }
 
 int ebm_ensemble_range(ebm_handle_t h, int nvars, const int *fields, const double *w, double *out) {
-    return ensemble_order(h, nvars, fields, w, 0, nullptr, nullptr, out, nullptr, false, "ebm_ensemble_range");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::RANGE, ebm::kRangeBlock, nullptr, nullptr, nullptr, 0}, out, nullptr, "ebm_ensemble_range");
 }
 
 int ebm_ensemble_range_device(ebm_handle_t h, int nvars, const int *fields, const double *w, double *dev_out) {
-    return ensemble_order(h, nvars, fields, w, 0, nullptr, nullptr, nullptr, dev_out, false, "ebm_ensemble_range_device");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::RANGE, ebm::kRangeBlock, nullptr, nullptr, nullptr, 0}, nullptr, dev_out, "ebm_ensemble_range_device");
 }
 
 int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
                            const double *hi, double *out) {
-    return ensemble_order(h, nvars, fields, w, nbins, lo, hi, out, nullptr, true, "ebm_ensemble_histogram");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::HISTOGRAM, ebm::kHistBlock, nullptr, lo, hi, nbins}, out, nullptr, "ebm_ensemble_histogram");
 }
 
 int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
                                   const double *hi, double *dev_out) {
-    return ensemble_order(h, nvars, fields, w, nbins, lo, hi, nullptr, dev_out, true, "ebm_ensemble_histogram_device");
+    return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::HISTOGRAM, ebm::kHistBlock, nullptr, lo, hi, nbins}, nullptr, dev_out, "ebm_ensemble_histogram_device");
 }
 
 int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {

@@ -220,42 +220,32 @@ struct ExchangeArgs {
 };
 hipError_t launch_export_columns(const ExchangeArgs &a, int n, hipStream_t s);
 hipError_t launch_import_columns(const ExchangeArgs &a, int n, hipStream_t s);
-// ebm_ensemble_sums (ebm_ensemble.hip): out[v][q][k] = S_q of variable v at latitude k < nlat, summed over the columns in
-// the order of the definition — blocks of kSumsBlock columns in ascending column order into partial[block][v][q][pitch], then
-// the blocks in ascending order.  Two launches.  row[v]: the field of variable v, [ncol][pitch], read where it lies; bit v of
-// split_mask: the handle holds it pair-split (then partial is in that layout too; center and out never are).
-constexpr int kSumsBlock = 32;       // columns per block: part of the definition (include/ebm_hip.h)
-struct EnsembleSumsArgs {
-    const double *row[kMaxQuantities];
-    unsigned split_mask;
-    const double *w;                 // [ncol], finite; never written by a kernel
-    const double *center;            // [nvars][pitch], natural layout, or null: nothing is subtracted
-    double *partial;                 // [nblocks][nvars][3][pitch]
-    double *out;                     // [nvars][3][nlat], natural
-    int pitch, nlat, ncol, nvars, nblocks, threads;
-};
-hipError_t launch_ensemble_sums(const EnsembleSumsArgs &a, hipStream_t s);
-// ebm_ensemble_range and ebm_ensemble_histogram (ebm_histogram.hip): order statistics across the columns, per entry v of the
-// call and latitude k < nlat, in the order of the definition (include/ebm_hip.h).  row, split_mask and w as in
-// EnsembleSumsArgs; an entry of a histogram may name the row of an earlier one.  Two launches each.
-//   range      out[v][0..2][k] = n, min, max.  partial[block][v][3][pitch], blocks of kRangeBlock columns (the result does
-//              not depend on the blocking).
-//   histogram  out[v][slot][k], slot < nbins + 2.  edges[v][0..2][pitch] = lo, hi and s = nbins / (hi - lo) in natural
-//              latitude order, padding zero.  partial[block][v][slot][pitch], blocks of kHistBlock columns.
+// ebm_ensemble_sums, ebm_ensemble_range and ebm_ensemble_histogram (ebm_ensemble.hip): out[v][slot][k], slot < nslots, of
+// entry v of the call at latitude k < nlat, reduced over the columns in the order of the definition (include/ebm_hip.h) —
+// blocks of columns in ascending column order into partial[block][v][slot][pitch], then the blocks in ascending order.  Two
+// launches each.  row[v]: the field of entry v, [ncol][pitch], read where it lies (an entry of a histogram may name the row of
+// an earlier one); bit v of split_mask: the handle holds it pair-split (then partial is in that layout too; aux and out never
+// are).
+//   sums       slots S0, S1, S2; blocks of kSumsBlock columns.  aux: center[v][pitch], or null: nothing is subtracted.
+//   range      slots n, min, max; blocks of kRangeBlock columns (the result does not depend on the blocking).  aux: unused.
+//   histogram  nslots = nbins + 2; blocks of kHistBlock columns.  aux: edges[v][0..2][pitch] = lo, hi and s = nbins / (hi - lo),
+//              padding zero.
+constexpr int kSumsBlock = 32;       // columns per block of the sums: part of the definition (include/ebm_hip.h)
 constexpr int kRangeBlock = 32;      // columns per block of the range: performance only
 constexpr int kHistBlock = 256;      // columns per block of the histogram: part of the definition (include/ebm_hip.h)
 constexpr int kHistMaxBins = 64;
-struct EnsembleOrderArgs {
+struct EnsembleArgs {
     const double *row[kMaxQuantities];
     unsigned split_mask;
+    int nslots;
     const double *w;                 // [ncol], finite; never written by a kernel
-    const double *edges;             // histogram only
-    double *partial;
-    double *out;
+    const double *aux;               // the per-latitude input in natural latitude order, or null
+    double *partial;                 // [nblocks][nvars][nslots][pitch]
+    double *out;                     // [nvars][nslots][nlat], natural
     int pitch, nlat, ncol, nvars, nblocks, threads;
-    int nbins;                       // histogram only
 };
-hipError_t launch_ensemble_range(const EnsembleOrderArgs &a, hipStream_t s);
-hipError_t launch_ensemble_histogram(const EnsembleOrderArgs &a, hipStream_t s);
+hipError_t launch_ensemble_sums(const EnsembleArgs &a, hipStream_t s);
+hipError_t launch_ensemble_range(const EnsembleArgs &a, hipStream_t s);
+hipError_t launch_ensemble_histogram(const EnsembleArgs &a, hipStream_t s);
 
 }  // namespace ebm

@@ -3,7 +3,8 @@
 //   ebm_fieldbook.h   (HIP-free) the field predicates and THE rule of field validity, layout and phi: ebm_ctx::book
 //   ebm_plan.h        (HIP-free) the launch geometry and THE rule of a step launch's kernel, LDS and noise source: plan_step
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
-//   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the two diffusion operators
+//   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the one host path of the three
+//                     ensemble reductions (ebm_ensemble.hip), the two diffusion operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling
 //   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate, run-until
 // Not part of the public interface.
@@ -150,16 +151,12 @@ struct ebm_ctx {
         Event uploaded;
         bool in_flight = false;
     } resample;
-    // ebm_ensemble_sums, kept between calls: the block partials, the uploaded weights and centers ([nvars][pitch], padding
-    // zero) and the result of the host variant
-    struct EnsembleSums {
-        DevVec<double> partial, w, center, out;
-    } sums;
-    // ebm_ensemble_range and ebm_ensemble_histogram, kept between calls: the block partials, the uploaded edges
-    // ([12][lo, hi, s][pitch], natural order) and the result of the host variants; the weights are sums.w
-    struct EnsembleOrder {
-        DevVec<double> partial, edges, out;
-    } order;
+    // ebm_ensemble_sums, ebm_ensemble_range and ebm_ensemble_histogram, kept between calls (a call is synchronous, so the
+    // three share them): the block partials, the uploaded weights, centers ([12][pitch], padding zero) and edges
+    // ([12][lo, hi, s][pitch], natural order), and the result of the host variants, sized for the largest
+    struct Ensemble {
+        DevVec<double> partial, w, center, edges, out;
+    } ensemble;
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
     DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
     ~ebm_ctx();

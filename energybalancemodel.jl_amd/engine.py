@@ -188,67 +188,39 @@ class Engine:
         check(self.lib.ebm_hemispheric_mean_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),
               "ebm_hemispheric_mean_device")
 
-    def _check_sums_args(self, names, weights=None, center=None):
-        """The host-side checks of ``ensemble_sums`` (no device call): returns (names, field ids, weights [ncol] or None,
-        center [nvars, nlat] or None) as contiguous float64 arrays."""
+    def _check_ensemble_args(self, names, weights=None, center=None, order=False, repeats=False, nbins=None, lo=None, hi=None):
+        """The host-side checks of ``ensemble_sums`` and, with ``order``, of ``ensemble_range`` and ``ensemble_histogram`` (no
+        device call): returns (names, field ids, weights [ncol] or None, extra) with contiguous float64 arrays — extra is
+        center [nvars, nlat] or None for the sums, None for the range and (lo, hi), each [len(names), nlat], for a histogram
+        (``nbins`` given), which may list a field several times (``repeats``).  The sums refuse a field listed twice before
+        they look at the weights, the range after."""
         if isinstance(names, str):
             names = (names,)
         names = tuple(names)
         allowed = self.prognostic + self.diagnostic
         if not 1 <= len(names) <= 12:
-            raise ValueError(f"names: expected between 1 and 12 fields of the {self.model} model")
+            raise ValueError(f"names: expected between 1 and 12 {'entries of fields' if order else 'fields'} of the {self.model} model")
         for n in names:
             if n not in allowed:
                 raise ValueError(f"names: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
                                  "the warm start T0 is not a solution variable)")
-        if len(set(names)) != len(names):
+        twice = not repeats and len(set(names)) != len(names)
+        if twice and not order:
             raise ValueError(f"names: a field is listed twice in {names}")
         w = None if weights is None else as_f64(weights, (self.ncol,))
         if w is not None and not np.isfinite(w).all():
             c = int(np.flatnonzero(~np.isfinite(w))[0])
             raise ValueError(f"weights[{c}] = {w[c]} is not finite (negative and zero weights are legal)")
-        ctr = None if center is None else as_f64(center, (len(names), self.nlat))
-        if ctr is not None and not np.isfinite(ctr).all():
-            raise ValueError("center: expected finite values")
-        return names, [FIELD[n] for n in names], w, ctr
-
-    def ensemble_sums(self, names, weights=None, center=None) -> np.ndarray:
-        """ebm_ensemble_sums (the definition is in include/ebm_hip.h): the weighted sums ACROSS the columns, per latitude,
-        reduced on the device — ndarray [len(names), 3, nlat] of S0 = sum w_c, S1 = sum w_c d and S2 = sum (w_c d) d with
-        d = x - center[v, k] (d = x without ``center``), over the columns with w_c != 0 whose cell is not NaN (the sentinels
-        of Ti and Tw; a zero weight removes the member; +-Inf propagates).  ``weights`` [ncol] (None: all 1.0; negative ones
-        are legal), ``center`` [len(names), nlat].  Every product and sum is rounded once, in a fixed order — blocks of 32
-        columns in ascending column order, then the block partials in ascending order — so the bits do not depend on the run,
-        the launch geometry or the layout the handle holds the rows in; no field is converted.  StaleFieldError for a stale
-        diagnostic field, as ``hemispheric_mean``.  The step clock, the counters and ``field_step`` are unchanged."""
-        names, ids, w, ctr = self._check_sums_args(names, weights, center)
-        out = np.full((len(names), 3, self.nlat), np.nan)
-        check(self.lib.ebm_ensemble_sums(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), dptr(out)),
-              "ebm_ensemble_sums")
-        return out
-
-    def ensemble_sums_device(self, names, dev_ptr: int, weights=None, center=None):
-        """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()``
-        of a torch tensor on this engine's device: the payload of an all-reduce between shards)."""
-        names, ids, w, ctr = self._check_sums_args(names, weights, center)
-        if not isinstance(dev_ptr, (int, np.integer)) or isinstance(dev_ptr, (bool, np.bool_)) or int(dev_ptr) == 0:
-            raise ValueError(f"dev_ptr: expected a device address (int), got {dev_ptr!r}")
-        check(self.lib.ebm_ensemble_sums_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr),
-                                                C.c_void_p(int(dev_ptr))), "ebm_ensemble_sums_device")
-
-    def _check_order_args(self, names, weights, repeats, nbins=None, lo=None, hi=None):
-        """The host-side checks of ``ensemble_range`` and ``ensemble_histogram`` (no device call): returns (names, field ids,
-        weights [ncol] or None, lo, hi [len(names), nlat] or None).  A histogram may list a field several times."""
-        if isinstance(names, str):
-            names = (names,)
-        names = tuple(names)
-        if not 1 <= len(names) <= 12:
-            raise ValueError(f"names: expected between 1 and 12 entries of fields of the {self.model} model")
-        _, ids, w, _ = self._check_sums_args(tuple(dict.fromkeys(names)), weights)
-        if not repeats and len(set(names)) != len(names):
+        if twice:
             raise ValueError(f"names: a field is listed twice in {names}")
+        ids = [FIELD[n] for n in names]
+        if not order:
+            ctr = None if center is None else as_f64(center, (len(names), self.nlat))
+            if ctr is not None and not np.isfinite(ctr).all():
+                raise ValueError("center: expected finite values")
+            return names, ids, w, ctr
         if nbins is None:
-            return names, [FIELD[n] for n in names], w, None, None
+            return names, ids, w, None
         if isinstance(nbins, (bool, np.bool_)) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
             raise ValueError(f"nbins: expected an int between 1 and 64, got {nbins!r}")
         lo, hi = as_f64(lo, (len(names), self.nlat)), as_f64(hi, (len(names), self.nlat))
@@ -259,13 +231,36 @@ class Engine:
             v, k = (int(i[0]) for i in np.nonzero(~ok))
             raise ValueError(f"lo[{v}][{k}] = {lo[v, k]}, hi[{v}][{k}] = {hi[v, k]}: expected finite edges with lo < hi "
                              "(and finite hi - lo and nbins / (hi - lo))")
-        return names, [FIELD[n] for n in names], w, lo, hi
+        return names, ids, w, (lo, hi)
 
     @staticmethod
     def _check_dev_ptr(dev_ptr):
         if not isinstance(dev_ptr, (int, np.integer)) or isinstance(dev_ptr, (bool, np.bool_)) or int(dev_ptr) == 0:
             raise ValueError(f"dev_ptr: expected a device address (int), got {dev_ptr!r}")
         return C.c_void_p(int(dev_ptr))
+
+    def ensemble_sums(self, names, weights=None, center=None) -> np.ndarray:
+        """ebm_ensemble_sums (the definition is in include/ebm_hip.h): the weighted sums ACROSS the columns, per latitude,
+        reduced on the device — ndarray [len(names), 3, nlat] of S0 = sum w_c, S1 = sum w_c d and S2 = sum (w_c d) d with
+        d = x - center[v, k] (d = x without ``center``), over the columns with w_c != 0 whose cell is not NaN (the sentinels
+        of Ti and Tw; a zero weight removes the member; +-Inf propagates).  ``weights`` [ncol] (None: all 1.0; negative ones
+        are legal), ``center`` [len(names), nlat].  Every product and sum is rounded once, in a fixed order — blocks of 32
+        columns in ascending column order, then the block partials in ascending order — so the bits do not depend on the run,
+        the launch geometry or the layout the handle holds the rows in; no field is converted.  StaleFieldError for a stale
+        diagnostic field, as ``hemispheric_mean``.  The step clock, the counters and ``field_step`` are unchanged."""
+        names, ids, w, ctr = self._check_ensemble_args(names, weights, center)
+        out = np.full((len(names), 3, self.nlat), np.nan)
+        check(self.lib.ebm_ensemble_sums(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), dptr(out)),
+              "ebm_ensemble_sums")
+        return out
+
+    def ensemble_sums_device(self, names, dev_ptr: int, weights=None, center=None):
+        """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()``
+        of a torch tensor on this engine's device: the payload of an all-reduce between shards)."""
+        names, ids, w, ctr = self._check_ensemble_args(names, weights, center)
+        ptr = self._check_dev_ptr(dev_ptr)
+        check(self.lib.ebm_ensemble_sums_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), ptr),
+              "ebm_ensemble_sums_device")
 
     def ensemble_range(self, names, weights=None) -> np.ndarray:
         """ebm_ensemble_range (the definition is in include/ebm_hip.h): ndarray [len(names), 3, nlat] of the number n of
@@ -274,14 +269,14 @@ class Engine:
         or not).  +-Inf is data; no contributor gives n = 0, min = +Inf, max = -Inf; of several equal extremes (+0.0, -0.0)
         the first in ascending column order gives the bits.  Rows are read where they lie: no field is converted, the step
         clock, the counters and ``field_step`` are unchanged.  StaleFieldError for a stale diagnostic field."""
-        names, ids, w, _, _ = self._check_order_args(names, weights, False)
+        names, ids, w, _ = self._check_ensemble_args(names, weights, order=True)
         out = np.full((len(names), 3, self.nlat), np.nan)
         check(self.lib.ebm_ensemble_range(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(out)), "ebm_ensemble_range")
         return out
 
     def ensemble_range_device(self, names, dev_ptr: int, weights=None):
         """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr``."""
-        names, ids, w, _, _ = self._check_order_args(names, weights, False)
+        names, ids, w, _ = self._check_ensemble_args(names, weights, order=True)
         ptr = self._check_dev_ptr(dev_ptr)
         check(self.lib.ebm_ensemble_range_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), ptr), "ebm_ensemble_range_device")
 
@@ -293,7 +288,7 @@ class Engine:
         times, each entry with its own edges.  The weights of a slot are added in a fixed order — blocks of 256 columns in
         ascending column order, then the block partials in ascending order; with ``weights`` None every slot is an exact
         count, so the histograms of shards add to the unsharded one bit for bit."""
-        names, ids, w, lo, hi = self._check_order_args(names, weights, True, nbins, lo, hi)
+        names, ids, w, (lo, hi) = self._check_ensemble_args(names, weights, order=True, repeats=True, nbins=nbins, lo=lo, hi=hi)
         out = np.full((len(names), int(nbins) + 2, self.nlat), np.nan)
         check(self.lib.ebm_ensemble_histogram(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo), dptr(hi),
                                               dptr(out)), "ebm_ensemble_histogram")
@@ -301,7 +296,7 @@ class Engine:
 
     def ensemble_histogram_device(self, names, lo, hi, nbins: int, dev_ptr: int, weights=None):
         """Same reduction, the packed [len(names), nbins + 2, nlat] result left on the device at ``dev_ptr``."""
-        names, ids, w, lo, hi = self._check_order_args(names, weights, True, nbins, lo, hi)
+        names, ids, w, (lo, hi) = self._check_ensemble_args(names, weights, order=True, repeats=True, nbins=nbins, lo=lo, hi=hi)
         ptr = self._check_dev_ptr(dev_ptr)
         check(self.lib.ebm_ensemble_histogram_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo),
                                                      dptr(hi), ptr), "ebm_ensemble_histogram_device")

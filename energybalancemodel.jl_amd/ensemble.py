@@ -758,6 +758,14 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         self.engine.hemispheric_mean_device(name, out.data_ptr())
         return out
 
+    def _reduced_tensor(self, names, nslots, device_call):
+        """A float64 tensor [len(names), nslots, nlat] on this run's device, filled by ``device_call(its address)``."""
+        import torch
+        nv = 1 if isinstance(names, str) else len(tuple(names))
+        out = torch.empty((nv, nslots, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        device_call(out.data_ptr())
+        return out
+
     def ensemble_sums(self, names, weights=None, center=None):
         """This shard's weighted sums across its members, per latitude (ebm_ensemble_sums): ndarray [len(names), 3, nlat] of
         S0, S1, S2, reduced on the device.  See ``Engine.ensemble_sums``; ``moments`` turns them into mean and variance."""
@@ -766,11 +774,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
     def ensemble_sums_tensor(self, names, weights=None, center=None):
         """The same sums as a float64 torch tensor [len(names), 3, nlat] ON THE DEVICE — written there by
         ebm_ensemble_sums_device, never staged through the host — ready to be all-reduced over RCCL (``reduced_sums``)."""
-        import torch
-        nv = 1 if isinstance(names, str) else len(tuple(names))
-        out = torch.empty((nv, 3, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
-        self.engine.ensemble_sums_device(names, out.data_ptr(), weights, center)
-        return out
+        return self._reduced_tensor(names, 3, lambda ptr: self.engine.ensemble_sums_device(names, ptr, weights, center))
 
     def ensemble_range(self, names, weights=None):
         """This shard's count, minimum and maximum across its members, per latitude (ebm_ensemble_range): ndarray
@@ -779,11 +783,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
 
     def ensemble_range_tensor(self, names, weights=None):
         """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_range_device), ready for RCCL."""
-        import torch
-        nv = 1 if isinstance(names, str) else len(tuple(names))
-        out = torch.empty((nv, 3, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
-        self.engine.ensemble_range_device(names, out.data_ptr(), weights)
-        return out
+        return self._reduced_tensor(names, 3, lambda ptr: self.engine.ensemble_range_device(names, ptr, weights))
 
     def ensemble_histogram(self, names, lo, hi, nbins, weights=None):
         """This shard's weighted histogram across its members, per latitude (ebm_ensemble_histogram): ndarray [len(names),
@@ -792,11 +792,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
 
     def ensemble_histogram_tensor(self, names, lo, hi, nbins, weights=None):
         """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_histogram_device), ready for RCCL."""
-        import torch
-        nv = 1 if isinstance(names, str) else len(tuple(names))
-        out = torch.empty((nv, int(nbins) + 2, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
-        self.engine.ensemble_histogram_device(names, lo, hi, nbins, out.data_ptr(), weights)
-        return out
+        return self._reduced_tensor(names, int(nbins) + 2, lambda ptr: self.engine.ensemble_histogram_device(names, lo, hi, nbins, ptr, weights))
 
     def field_tensor(self, name):
         """A packed [ncol, nlat] device tensor copy of a field (device-to-device)."""

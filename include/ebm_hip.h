@@ -639,7 +639,7 @@ int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const
  * that is not a solution variable of the model (or, in the range, is listed twice), a non-finite w[c] (the message names the
  * column), nbins outside 1 ... 64, an edge pair that breaks the rule above (the message names the first offending entry and
  * latitude); EBM_ERR_STALE as above.
- * How it runs (csrc/ebm_histogram.hip): the walk of ebm_ensemble_sums — grid (latitude tiles) x (column blocks) x (entries), a
+ * How it runs (csrc/ebm_ensemble.hip): the walk of ebm_ensemble_sums — grid (latitude tiles) x (column blocks) x (entries), a
  * lane owning one 16-byte pair of cells, whole 128-byte lines, the loads of 16 columns issued ahead of the dependent work,
  * w_c through the scalar cache — with n, min, max in registers for the range, and for the histogram the slots in LDS as
  * [slot][cell of the pair][lane], (nbins + 2) KiB per one-wave workgroup, each lane touching only its own two columns of it:

@@ -157,6 +157,19 @@ def test_zero_weights_select_a_sub_ensemble(pkg):
         assert same_bits(eng.ensemble_sums(names, scattered), ensemble_sums_ref(x, scattered))
 
 
+def test_more_blocks_than_a_batch_of_the_finish_kernel(pkg):
+    """1057 columns are 34 blocks of 32: the finish kernel, which the histogram and the range share, adds 32 block partials per
+    batch of loads, so this is one batch and a tail of two.  With weights: the order shows."""
+    ncol, nlat = 1057, 5
+    x = crafted(1, ncol, nlat, 99)
+    w = weights_for(ncol, 1)
+    center = np.random.default_rng(nlat).normal(0.0, 3.0, (1, nlat))
+    with blank_engine(pkg, "MIZ", nlat, ncol) as eng:
+        eng.set_field("T", x[0])
+        assert same_bits(eng.ensemble_sums("T", w), ensemble_sums_ref(x, w))
+        assert same_bits(eng.ensemble_sums("T", w, center), ensemble_sums_ref(x, w, center))
+
+
 def test_all_variables_of_each_model(pkg):
     ncol, nlat = 33, 181
     x = crafted(10, ncol, nlat, 21)
