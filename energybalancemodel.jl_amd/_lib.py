@@ -31,7 +31,8 @@ EXPORTS = (
     "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
     "ebm_equilibrate", "ebm_run_until", "ebm_resample_columns", "ebm_column_record", "ebm_export_columns",
     "ebm_import_columns", "ebm_ensemble_sums", "ebm_ensemble_sums_device", "ebm_ensemble_range",
-    "ebm_ensemble_range_device", "ebm_ensemble_histogram", "ebm_ensemble_histogram_device", "ebm_sync", "ebm_get_counters",
+    "ebm_ensemble_range_device", "ebm_ensemble_histogram", "ebm_ensemble_histogram_device", "ebm_column_misfits",
+    "ebm_column_misfits_device", "ebm_sync", "ebm_get_counters",
     "ebm_reset_counters", "ebm_state_conversions", "ebm_zero_line_flags", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
     "ebm_selftest_divide", "ebm_selftest_permute",
 )
@@ -128,6 +129,8 @@ def load():
     lib.ebm_ensemble_range_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_void_p]
     lib.ebm_ensemble_histogram.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_int, _dp, _dp, _dp]
     lib.ebm_ensemble_histogram_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_int, _dp, _dp, C.c_void_p]
+    lib.ebm_column_misfits.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, _dp]
+    lib.ebm_column_misfits_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, C.c_void_p]
     lib.ebm_sync.argtypes = [C.c_void_p]
     lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.ebm_reset_counters.argtypes = [C.c_void_p]

@@ -113,6 +113,7 @@ hipError_t hemispheric_mean(ebm_ctx *h, int field, double *dev_out) {
 // What ebm_ensemble_sums, ebm_ensemble_range and ebm_ensemble_histogram have in common (include/ebm_hip.h), in the order every
 // one of them keeps: the arguments (ensemble_check: no device work, nothing of the handle changes), the call's own checks,
 // then ensemble_open — staleness, phi made current, the launch chains joined, the weights uploaded, the rows where they lie.
+// ebm_column_misfits reads the same rows under the same rules and has no member weights (member_weights = false: none uploaded).
 int ensemble_check(const ebm_ctx *h, int nvars, const int *fields, bool each_once, const double *w, bool have_out, const std::string &me) {
     if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
     if (!fields || !have_out) return fail(EBM_ERR_ARG, me + ": null argument");
@@ -135,11 +136,11 @@ struct EnsembleRows {
     hipStream_t s = nullptr;
     std::vector<double> ones;                            // the unit weights of w = NULL: alive until the call has synchronised
 };
-int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, const char *who, EnsembleRows &r) {
+int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, const char *who, EnsembleRows &r, bool member_weights = true) {
     for (int v = 0; v < nvars; ++v)
         if (int rc = check_current(h, fields[v], who)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(h->ensemble.w.reserve((size_t)h->ncol));
+    if (member_weights) HIPCHK(h->ensemble.w.reserve((size_t)h->ncol));
     // phi is read as a field: current first, in the layout the state has.  Nothing else of the handle changes
     for (int v = 0; v < nvars; ++v)
         if (fields[v] == EBM_F_phi && h->model == EBM_MODEL_MIZ) {
@@ -147,9 +148,11 @@ int ensemble_open(ebm_ctx *h, int nvars, const int *fields, const double *w, con
             if (e != hipSuccess) return hip_fail("phi restore", e);
         }
     r.s = main_stream(h);                                // joins the two launch chains: every column's last step has ended
-    r.ones.assign(w ? 0 : (size_t)h->ncol, 1.0);
-    HIPCHK(hipMemcpyAsync(h->ensemble.w.get(), w ? w : r.ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, r.s));
-    r.w = h->ensemble.w.get();
+    if (member_weights) {
+        r.ones.assign(w ? 0 : (size_t)h->ncol, 1.0);
+        HIPCHK(hipMemcpyAsync(h->ensemble.w.get(), w ? w : r.ones.data(), sizeof(double) * (size_t)h->ncol, hipMemcpyHostToDevice, r.s));
+        r.w = h->ensemble.w.get();
+    }
     for (int v = 0; v < nvars; ++v) {
         const int f = fields[v];
         r.row[v] = h->field[f];
@@ -232,6 +235,53 @@ int ensemble_reduce(ebm_ctx *h, int nvars, const int *fields, const double *w, c
         e = histogram ? ebm::launch_ensemble_histogram(a, r.s)
                       : c.kind == EnsembleCall::RANGE ? ebm::launch_ensemble_range(a, r.s) : ebm::launch_ensemble_sums(a, r.s);
     return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), (size_t)nslots * (size_t)nvars * (size_t)h->nlat, r.s, who);
+}
+
+// ebm_column_misfits and its _device form (include/ebm_hip.h): the checks of the ensemble reductions on handle and fields, the
+// call's own on targets and rw, then the rows where they lie and the one launch of ebm_misfit.hip into dev_out (the caller's
+// device buffer) or, for host_out, into the handle's own and down.  Synchronous.
+int column_misfits(ebm_ctx *h, int nvars, const int *fields, int ntargets, const double *target, const double *rw, double *host_out,
+                   double *dev_out, const char *who) {
+    const std::string me(who);
+    if (int rc = ensemble_check(h, nvars, fields, true, nullptr, target && (host_out || dev_out), me)) return rc;
+    if (ntargets < 1 || ntargets > ebm::kMisfitMaxTargets)
+        return fail(EBM_ERR_ARG, me + ": ntargets = " + std::to_string(ntargets) + " is outside 1 ... " + std::to_string(ebm::kMisfitMaxTargets));
+    const long long nlat = h->nlat, per_target = (long long)nvars * nlat;
+    for (long long i = 0; i < ntargets * per_target; ++i)
+        if (std::isinf(target[i]))
+            return fail(EBM_ERR_ARG, me + ": target[" + std::to_string(i / per_target) + "][" + std::to_string(i % per_target / nlat) + "][" +
+                                         std::to_string(i % nlat) + "] is infinite (finite, or NaN for no observation)");
+    for (long long i = 0; rw && i < per_target; ++i)
+        if (!std::isfinite(rw[i]) || rw[i] < 0.0)
+            return fail(EBM_ERR_ARG, me + ": rw[" + std::to_string(i / nlat) + "][" + std::to_string(i % nlat) + "] is not finite and >= 0");
+    EnsembleRows r;
+    if (int rc = ensemble_open(h, nvars, fields, nullptr, who, r, false)) return rc;
+    ebm_ctx::Misfit &b = h->misfit;
+    const size_t npitch = (size_t)h->pitch, nout = 2 * (size_t)ntargets * (size_t)h->ncol;
+    if (!b.target.get()) {                               // all rows once; the padding cells stay zero
+        HIPCHK(b.target.reserve((size_t)ebm::kMisfitMaxTargets * ebm::kMaxQuantities * npitch));
+        HIPCHK(hipMemsetAsync(b.target.get(), 0, sizeof(double) * ebm::kMisfitMaxTargets * ebm::kMaxQuantities * npitch, r.s));
+    }
+    if (rw && !b.rw.get()) {
+        HIPCHK(b.rw.reserve((size_t)ebm::kMaxQuantities * npitch));
+        HIPCHK(hipMemsetAsync(b.rw.get(), 0, sizeof(double) * ebm::kMaxQuantities * npitch, r.s));
+    }
+    if (!dev_out) HIPCHK(b.out.reserve(2 * (size_t)ebm::kMisfitMaxTargets * (size_t)h->ncol));
+    hipError_t e = hipMemcpy2DAsync(b.target.get(), sizeof(double) * npitch, target, sizeof(double) * nlat, sizeof(double) * nlat,
+                                    (size_t)ntargets * nvars, hipMemcpyHostToDevice, r.s);
+    if (e == hipSuccess && rw)
+        e = hipMemcpy2DAsync(b.rw.get(), sizeof(double) * npitch, rw, sizeof(double) * nlat, sizeof(double) * nlat, (size_t)nvars,
+                             hipMemcpyHostToDevice, r.s);
+    ebm::MisfitArgs a{};
+    for (int v = 0; v < nvars; ++v) a.row[v] = r.row[v];
+    a.split_mask = r.split_mask;
+    a.ntargets = ntargets;
+    a.target = b.target.get();
+    a.rw = rw ? b.rw.get() : nullptr;
+    a.out = dev_out ? dev_out : b.out.get();
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.threads = h->cfg.threads;
+    if (e == hipSuccess) e = ebm::launch_column_misfits(a, r.s);
+    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), nout, r.s, who);
 }
 
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
@@ -379,6 +429,15 @@ int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const d
 int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
                                   const double *hi, double *dev_out) {
     return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::HISTOGRAM, ebm::kHistBlock, nullptr, lo, hi, nbins}, nullptr, dev_out, "ebm_ensemble_histogram_device");
+}
+
+int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target, const double *rw, double *out) {
+    return column_misfits(h, nvars, fields, ntargets, target, rw, out, nullptr, "ebm_column_misfits");
+}
+
+int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target, const double *rw,
+                              double *dev_out) {
+    return column_misfits(h, nvars, fields, ntargets, target, rw, nullptr, dev_out, "ebm_column_misfits_device");
 }
 
 int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {

@@ -247,5 +247,20 @@ struct EnsembleArgs {
 hipError_t launch_ensemble_sums(const EnsembleArgs &a, hipStream_t s);
 hipError_t launch_ensemble_range(const EnsembleArgs &a, hipStream_t s);
 hipError_t launch_ensemble_histogram(const EnsembleArgs &a, hipStream_t s);
+// ebm_column_misfits (ebm_misfit.hip): out[t][0][c] = J and out[t][1][c] = N of column c against target t, summed along the
+// column in the order of the definition (include/ebm_hip.h).  One launch, one wave per column.  row[v], split_mask: as above.
+// target[t][v][pitch] and rw[v][pitch] (null: every entry 1.0) in natural latitude order; their padding cells are never read
+// into a result.
+constexpr int kMisfitMaxTargets = 8;
+struct MisfitArgs {
+    const double *row[kMaxQuantities];
+    unsigned split_mask;
+    int ntargets;
+    const double *target;
+    const double *rw;
+    double *out;                     // [ntargets][2][ncol]
+    int pitch, nlat, ncol, nvars, threads;
+};
+hipError_t launch_column_misfits(const MisfitArgs &a, hipStream_t s);
 
 }  // namespace ebm

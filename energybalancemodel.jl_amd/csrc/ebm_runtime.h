@@ -4,7 +4,8 @@
 //   ebm_plan.h        (HIP-free) the launch geometry and THE rule of a step launch's kernel, LDS and noise source: plan_step
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the one host path of the three
-//                     ensemble reductions (ebm_ensemble.hip), the two diffusion operators
+//                     ensemble reductions (ebm_ensemble.hip) and of the column misfits (ebm_misfit.hip), the two diffusion
+//                     operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling
 //   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate, run-until
 // Not part of the public interface.
@@ -157,6 +158,11 @@ struct ebm_ctx {
     struct Ensemble {
         DevVec<double> partial, w, center, edges, out;
     } ensemble;
+    // ebm_column_misfits, kept between calls: the uploaded targets ([8][12][pitch]) and rw ([12][pitch]), natural order,
+    // padding zero, and the result of the host variant ([8][2][ncol])
+    struct Misfit {
+        DevVec<double> target, rw, out;
+    } misfit;
     // ebm_integrate's device buffers, kept between calls while the shape stays the same
     DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
     ~ebm_ctx();

@@ -301,6 +301,51 @@ class Engine:
         check(self.lib.ebm_ensemble_histogram_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo),
                                                      dptr(hi), ptr), "ebm_ensemble_histogram_device")
 
+    def _check_misfit_args(self, names, targets, rweights=None):
+        """The host-side checks of ``column_misfits`` (no device call): returns (names, field ids, targets [ntargets, nvars,
+        nlat], rweights [nvars, nlat] or None) with contiguous float64 arrays.  The field rules are those of
+        ``_check_ensemble_args``; a single target may be given as [nvars, nlat]."""
+        names, ids, _, _ = self._check_ensemble_args(names)
+        y = np.ascontiguousarray(targets, dtype=np.float64)
+        if y.ndim == 2:
+            y = y[None]
+        if y.ndim != 3 or y.shape[1:] != (len(names), self.nlat) or not 1 <= y.shape[0] <= 8:
+            raise ValueError(f"targets: expected [ntargets, {len(names)}, {self.nlat}] with 1 <= ntargets <= 8 "
+                             f"(or one target as [{len(names)}, {self.nlat}]), got {y.shape}")
+        if np.isinf(y).any():
+            t, v, k = (int(i[0]) for i in np.nonzero(np.isinf(y)))
+            raise ValueError(f"targets[{t}][{v}][{k}] = {y[t, v, k]}: expected finite values, or NaN for no observation")
+        r = None if rweights is None else as_f64(rweights, (len(names), self.nlat))
+        if r is not None and not (np.isfinite(r) & (r >= 0.0)).all():
+            v, k = (int(i[0]) for i in np.nonzero(~(np.isfinite(r) & (r >= 0.0))))
+            raise ValueError(f"rweights[{v}][{k}] = {r[v, k]}: expected finite values >= 0")
+        return names, ids, np.ascontiguousarray(y), r
+
+    def column_misfits(self, names, targets, rweights=None) -> np.ndarray:
+        """ebm_column_misfits (the definition is in include/ebm_hip.h): ndarray [ntargets, 2, ncol] — for every target t and
+        column c, ``[t, 0, c]`` = J = sum over the fields in ``names`` and over latitude of (r * d) * d with d = x - target,
+        and ``[t, 1, c]`` = N, the number of cells that entered it, reduced along each column on the device.  ``targets``
+        [ntargets, len(names), nlat] (one target: [len(names), nlat]; 1 <= ntargets <= 8), finite or NaN = "no observation
+        here"; ``rweights`` [len(names), nlat], finite and >= 0 (quadrature weight / sigma^2, or a 0 / 1 band mask), None:
+        all 1.0.  A cell contributes iff its rweight is not 0 and neither the target nor the cell is NaN (the sentinels of
+        Ti and Tw); +-Inf in a contributing cell propagates.  The adds run in a fixed order — 128 chains by cell index mod
+        128, then a fixed tree — so the bits do not depend on the run, the launch geometry or the layout the handle holds the
+        rows in; no field is converted.  StaleFieldError for a stale diagnostic field, as ``hemispheric_mean``.  The step
+        clock, the counters and ``field_step`` are unchanged."""
+        names, ids, y, r = self._check_misfit_args(names, targets, rweights)
+        out = np.full((y.shape[0], 2, self.ncol), np.nan)
+        check(self.lib.ebm_column_misfits(self._h, len(ids), (C.c_int * len(ids))(*ids), int(y.shape[0]), dptr(y), dptr(r), dptr(out)),
+              "ebm_column_misfits")
+        return out
+
+    def column_misfits_device(self, names, targets, dev_ptr: int, rweights=None):
+        """Same reduction, the packed [ntargets, 2, ncol] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()`` of
+        a torch tensor on this engine's device: the payload of an all-gather between shards)."""
+        names, ids, y, r = self._check_misfit_args(names, targets, rweights)
+        ptr = self._check_dev_ptr(dev_ptr)
+        check(self.lib.ebm_column_misfits_device(self._h, len(ids), (C.c_int * len(ids))(*ids), int(y.shape[0]), dptr(y), dptr(r), ptr),
+              "ebm_column_misfits_device")
+
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""
         check(self.lib.ebm_get_field_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),

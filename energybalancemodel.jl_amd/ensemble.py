@@ -106,6 +106,34 @@ def selection_parents(weights, rng) -> np.ndarray:
     return np.searchsorted(cum, u + np.arange(n), side="right").astype(np.int32)
 
 
+def assimilation_weights(J, prior_logw=None) -> dict:
+    """The particle-filter weights of members whose misfits to an observation are ``J`` [n] (``EnsembleRun.misfits``: J =
+    sum (x - y)^2 / sigma^2, so the Gaussian likelihood is exp(-J / 2)): dict(weights [n]: normalised to sum 1; ess: the
+    effective sample size (sum w)^2 / sum w^2, n for equal weights and 1 when one member carries everything; log_evidence:
+    the log of the prior-weighted mean likelihood, log sum_m p_m exp(-J_m / 2) with p the normalised prior — the increment
+    of the log marginal likelihood of this observation).  ``prior_logw`` [n]: log weights carried from earlier
+    observations that were not resampled away (None: equal).  A stable softmax of -J / 2 + prior_logw: the largest
+    exponent is subtracted first, so a member far from the observation gets weight 0.0 by underflow, never NaN; J = +Inf
+    (an Inf cell) gives weight 0.  Host only.  ValueError for a NaN or negative J, a NaN or +Inf prior, and when no member has a
+    positive weight."""
+    J = np.asarray(J, dtype=np.float64)
+    if J.ndim != 1 or J.shape[0] < 1:
+        raise ValueError(f"J: expected a vector of at least one misfit, got shape {J.shape}")
+    if np.isnan(J).any() or (J < 0.0).any():
+        raise ValueError("J: expected misfits >= 0 (not NaN)")
+    prior = np.zeros_like(J) if prior_logw is None else np.asarray(prior_logw, dtype=np.float64)
+    if prior.shape != J.shape or np.isnan(prior).any() or (prior == np.inf).any():
+        raise ValueError(f"prior_logw: expected {J.shape[0]} log weights (finite or -inf)")
+    logw = prior - 0.5 * J
+    top, top_prior = logw.max(), prior.max()
+    if top == -np.inf:
+        raise ValueError("every member has weight zero (no member to continue from)")
+    w = np.exp(logw - top)
+    total = w.sum()
+    log_evidence = (top + np.log(total)) - (top_prior + np.log(np.exp(prior - top_prior).sum()))
+    return dict(weights=w / total, ess=float(total * total / (w * w).sum()), log_evidence=float(log_evidence))
+
+
 # ---- genealogical cloning (Giardina-Kurchan-Lecomte-Tailleur), host side ------------------------------------------------------
 # EXPERIMENTAL: the three gklt_* functions are here so that examples/rare_transitions_gklt.py and the host tests share one
 # statement of the estimator; their signatures may change.  selection_parents and EnsembleRun.resample are the supported part.
@@ -793,6 +821,55 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
     def ensemble_histogram_tensor(self, names, lo, hi, nbins, weights=None):
         """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_histogram_device), ready for RCCL."""
         return self._reduced_tensor(names, int(nbins) + 2, lambda ptr: self.engine.ensemble_histogram_device(names, lo, hi, nbins, ptr, weights))
+
+    def misfits(self, names, targets, rweights=None):
+        """This shard's per-member misfits to the target profiles (ebm_column_misfits): ndarray [ntargets, 2, ncol] of J and
+        the number N of cells behind it, reduced along each member's column on the device.  See ``Engine.column_misfits``."""
+        return self.engine.column_misfits(names, targets, rweights)
+
+    def misfits_tensor(self, names, targets, rweights=None):
+        """The same as a float64 torch tensor [ntargets, 2, ncol] ON THE DEVICE (ebm_column_misfits_device), ready to be
+        all-gathered over RCCL."""
+        import torch
+        y = np.asarray(targets, dtype=np.float64)
+        out = torch.empty((1 if y.ndim == 2 else y.shape[0], 2, self.ncol), dtype=torch.float64, device=torch.device("cuda", self.device))
+        self.engine.column_misfits_device(names, targets, out.data_ptr(), rweights)
+        return out
+
+    def assimilate(self, names, obs, obs_var, rng, quad=None, ess_fraction=0.5, dist=None):
+        """One observation step of a bootstrap particle filter.  ``obs`` [len(names), nlat]: the observed profiles, NaN where
+        nothing was observed; ``obs_var``: the observation error variance, a scalar or [len(names), nlat], > 0; ``quad``: None
+        or quadrature weights [nlat] / [len(names), nlat] >= 0 (0 masks a latitude out).  The misfit J_m = sum quad / obs_var *
+        (x - obs)^2 of every member is reduced on the device (``misfits`` with rweights = quad / obs_var), the weights are
+        ``assimilation_weights(J)`` over ALL members — with ``dist`` the O(members) values of J and N are all-gathered in rank
+        order first — and when the effective sample size falls below ``ess_fraction`` * n the ensemble is resampled:
+        ``selection_parents(weights, rng)``, then ``resample`` (``resample_global`` with ``dist``; every rank must pass a
+        ``rng`` in the same state, so that all draw the same parents).  Returns dict(J [n], N [n], weights [n], ess,
+        log_evidence, parents [n] or None if nothing was resampled), n the members of the whole ensemble."""
+        obs_var = np.asarray(obs_var, dtype=np.float64)
+        if not (np.isfinite(obs_var) & (obs_var > 0.0)).all():
+            raise ValueError("obs_var: expected finite values > 0")
+        if not 0.0 <= float(ess_fraction) <= 1.0:
+            raise ValueError(f"ess_fraction = {ess_fraction}: expected a fraction between 0 and 1")
+        nv = 1 if isinstance(names, str) else len(tuple(names))
+        shape = (nv, self.st.nx)
+        rw = np.ascontiguousarray(np.broadcast_to((1.0 if quad is None else np.asarray(quad, dtype=np.float64)) / obs_var, shape))
+        out = self.misfits(names, np.asarray(obs, dtype=np.float64).reshape(shape), rw)
+        sharded = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
+        if sharded:
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, out[0])
+            out = np.concatenate(parts, axis=1)[None]
+        J, N = out[0, 0], out[0, 1]
+        res = assimilation_weights(J)
+        parents = None
+        if res["ess"] < float(ess_fraction) * J.shape[0]:
+            parents = selection_parents(res["weights"], rng)
+            if sharded:
+                self.resample_global(parents, J.shape[0], dist)
+            else:
+                self.resample(parents)
+        return dict(J=J, N=N, weights=res["weights"], ess=res["ess"], log_evidence=res["log_evidence"], parents=parents)
 
     def field_tensor(self, name):
         """A packed [ncol, nlat] device tensor copy of a field (device-to-device)."""

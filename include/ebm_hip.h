@@ -164,7 +164,7 @@ const char *ebm_version(void);
  * T, h) and the fp64 warm start EBM_F_T0 are written only by steps that were asked to (ebm_step with
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
- * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
+ * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_column_misfits*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
  * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
@@ -653,6 +653,54 @@ int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const d
                            const double *hi, double *out);
 int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
                                   const double *hi, double *dev_out);
+
+/* PER-MEMBER MISFITS TO TARGET PROFILES, reduced ALONG each column on the device: for every column c and every one of
+ * ntargets target profiles, J = the weighted squared distance of the column's profiles to the target and N = the number of
+ * cells that entered it — one number per member, which is what every user of the selection step (ebm_resample_columns)
+ * needs first: the likelihood weight exp(-J / 2) of a particle filter against an observed T(x) or ice profile (rw = quadrature
+ * weight / sigma^2), the reaction coordinate d_A / (d_A + d_B) of a splitting method between the two equilibria that
+ * ebm_equilibrate found, the nearest of several reference profiles where the ensemble mean describes no member.  O(ncol)
+ * doubles cross the bus, or enter an all-gather between shards, instead of O(state).  THIS TEXT IS THE DEFINITION.
+ *   Arguments.  fields[nvars]: solution variables of the model, prognostic or diagnostic, each at most once; EBM_F_T0 is not
+ *     one; 1 <= nvars <= 12 (the rules of ebm_ensemble_sums: one piece of code checks them for both).  1 <= ntargets <= 8.
+ *     target[ntargets][nvars][nlat]: host array in natural latitude order, every entry finite or NaN; NaN means "no
+ *     observation here".  rw[nvars][nlat]: host array, every entry finite and >= 0 (quadrature weight / sigma^2, or a 0 / 1 band
+ *     mask); NULL = every entry 1.0.  out[ntargets][2][ncol]: out[t][0][c] = J, out[t][1][c] = N (a count, stored as a
+ *     double), on the host; the _device variant writes the same packed array into the caller's device buffer dev_out.
+ *   Terms.  Cell k < nlat of variable v of column c, with value x, CONTRIBUTES to target t iff rw[v][k] != 0.0,
+ *     y = target[t][v][k] is not NaN and x is not NaN (the NaN sentinels of Ti and Tw, src/miz.jl:193-194: "no ice / no
+ *     water here").  Its term is d = x - y, then (rw[v][k] * d) * d: a rounded difference and two rounded products, nothing
+ *     contracted into a fused multiply-add.  +-Inf in a contributing x is data and propagates (J = +Inf).
+ *   Order.  The bits depend neither on the launch geometry (cells_per_thread) nor on the layout the handle holds the rows in.
+ *     Unit u is the pair of cells (2u, 2u + 1); units with 2u >= nlat do not exist.  Chain (l, e), l = 0 ... 63 and e = 0, 1,
+ *     starts at 0.0 and adds the contributing terms of the cells k = 2 (l + 64 i) + e: for v ascending in the order of the
+ *     call, and within each v for i = 0, 1, ... ascending — ONE accumulator runs across the variables.  Then
+ *     q_l = chain(l, 0) + chain(l, 1); then, for s = 32, 16, 8, 4, 2, 1 in this order, q_l <- q_l + q_{l + s} for every
+ *     l < s; J = q_0.  A chain without a contributor keeps its 0.0 and is added as such.  N counts the contributors the
+ *     same way and is exact in any order.  No contributor at all: J = 0.0 and N = 0.0.  A term passes through at most
+ *     nvars * ceil(U / 64) + 7 rounded adds, U = ceil(nlat / 2).
+ *   Validity, layout, bookkeeping: those of ebm_ensemble_sums.  A diagnostic field that is older than the state fails with
+ *     EBM_ERR_STALE exactly as ebm_hemispheric_mean does (the same message); phi, left underived by state-only one-step
+ *     launches, is made current first; rows are read in whatever layout the handle holds them and no field is converted
+ *     (ebm_state_conversions does not grow); cells between nlat and the row pitch never reach a result; the step clock,
+ *     counters[0..3] and ebm_field_step are unchanged and the launch is not counted; both calls are synchronous on the
+ *     handle's stream, the two launch chains joined first.  Every model: the classic one has E, Tg, T, h.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle, fields, target or out, nvars outside 1 ... 12,
+ * ntargets outside 1 ... 8, a field that is not a solution variable of the model or is listed twice, an infinite target entry,
+ * a negative or non-finite rw entry (the message names the first offending target, variable and latitude); EBM_ERR_STALE as
+ * above.
+ * How it runs (csrc/ebm_misfit.hip): ONE launch, one wave64 workgroup per column; lane l holds the chains (l, 0) and (l, 1) of
+ * all targets in registers (the kernel is instantiated per ntargets).  16 bytes per lane and load: of a natural row lane l
+ * reads stored unit l + 64 i, a wave 1 KiB in eight whole lines; of a pair-split row (stored unit p is natural unit 2p for
+ * p < threads, 2 (p - threads) + 1 otherwise) an even lane reads l / 2 + 32 i and an odd one threads + (l - 1) / 2 + 32 i, two
+ * contiguous 512-byte runs of whole lines.  Targets and rw are read in the natural layout, shared by all columns.  The loads
+ * of several units are issued ahead of the dependent adds; the finish is the six-step cross-lane tree.  No LDS, no atomics,
+ * no scratch, plain loads and stores.  Device memory, kept by the handle and reused: 8 * 12 * pitch doubles of targets,
+ * 12 * pitch of rw, and 2 * 8 * ncol doubles for the host variant's result. */
+int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target, const double *rw,
+                       double *out);
+int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target,
+                              const double *rw, double *dev_out);
 
 int ebm_sync(ebm_handle_t h);
 

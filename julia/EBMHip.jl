@@ -413,4 +413,37 @@ function ensemble_histogram_device!(h::Handle, names::Vector{Symbol}, lo::Matrix
                          "ebm_ensemble_histogram_device")
 end
 
+"""
+    column_misfits(h, names, target; ncol, nlat, rw=nothing) -> Array{Float64,3}
+    column_misfits_device!(h, names, target, devout; rw=nothing)
+
+Per-member misfits to target profiles, reduced along each column on the device (`ebm_column_misfits`; the definition is in
+the header).  `target`: `nlat x length(names) x ntargets`, finite or NaN ("no observation here"), `1 <= ntargets <= 8`;
+`rw`: `nlat x length(names)`, finite and `>= 0`, `nothing` = all 1.  `out[c, 1, t]` = J, the sum over fields and latitudes of
+`(rw * d) * d` with `d = x - target`; `out[c, 2, t]` = N, the number of cells that entered it.  A cell contributes iff its
+`rw` is not 0 and neither the target nor the cell is NaN.  The order of the adds is fixed.  The `_device!` form writes the
+packed array to the device pointer.
+"""
+function column_misfits(h::Handle, names::Vector{Symbol}, target::Array{Float64,3}; ncol::Integer, nlat::Integer, rw=nothing)
+    size(target)[1:2] == (nlat, length(names)) || error("target: expected $nlat x $(length(names)) x ntargets values")
+    nt = size(target, 3)
+    out = Array{Float64,3}(undef, ncol, 2, nt)
+    f = Cint[FIELD[k] for k in names]
+    r = rw === nothing ? Ptr{Cdouble}(C_NULL) : Matrix{Float64}(rw)
+    rw === nothing || size(rw) == (nlat, length(names)) || error("rw: expected $nlat x $(length(names)) values")
+    GC.@preserve h check(@ccall(libebm.ebm_column_misfits(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, nt::Cint,
+                                                          target::Ptr{Cdouble}, r::Ptr{Cdouble}, out::Ptr{Cdouble})::Cint),
+                         "ebm_column_misfits")
+    return out
+end
+
+function column_misfits_device!(h::Handle, names::Vector{Symbol}, target::Array{Float64,3}, devout::Ptr{Cdouble}; rw=nothing)
+    f = Cint[FIELD[k] for k in names]
+    nt = size(target, 3)
+    r = rw === nothing ? Ptr{Cdouble}(C_NULL) : Matrix{Float64}(rw)
+    GC.@preserve h check(@ccall(libebm.ebm_column_misfits_device(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, nt::Cint,
+                                                                 target::Ptr{Cdouble}, r::Ptr{Cdouble},
+                                                                 devout::Ptr{Cdouble})::Cint), "ebm_column_misfits_device")
+end
+
 end # module EBMHip
