@@ -4,6 +4,8 @@ operations in the same order as the definition states them — every product and
 (NumPy fuses nothing across calls).  The GPU tests compare with it bit for bit."""
 import numpy as np
 
+from support import bits
+
 BLOCK = 32
 
 
@@ -59,10 +61,6 @@ def abs_term_sums(x, w=None, center=None):
     t1 = w[None, :, None] * d
     terms = np.stack([np.broadcast_to(w[None, :, None], x.shape), t1, t1 * d], axis=1)      # [nvars, 3, ncol, nlat]
     return np.where(ok[:, None], np.abs(terms), 0.0).sum(axis=2)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def same_bits(a, b):

@@ -17,8 +17,8 @@ import pytest
 import torch
 
 from column_misfits_ref import column_misfits_ref, same_bits
-from test_gpu_ensemble_sums import CRAFTED, DP, MIZ_ALL, MIZ_PROG, blank_engine, crafted, load
-from test_gpu_until import assert_same_snapshot, forcing_of, make_engine, snapshot
+from support import MIZ_PROG, assert_same_snapshot, forcing_of, make_engine, snapshot
+from test_gpu_ensemble_sums import CRAFTED, DP, MIZ_ALL, blank_engine, crafted, load
 
 pytestmark = pytest.mark.gpu
 

@@ -9,21 +9,15 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, scaled_err, record_error
+from support import CLASSIC_VARS as CLASSIC_ALL, MIZ_PROG as PROG, all_fields, is_miz
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
-DIAG = ("Tw", "Ti", "n", "E", "T")
-MIZ_ALL = PROG + ("T0",) + DIAG
-CLASSIC_ALL = ("E", "Tg", "T", "h")
+MIZ_ALL = all_fields("MIZ")
 MIZ_USED = ("D", "A", "B", "cw", "S0", "S1", "S2", "a0", "a2", "ai", "Fb", "k", "Lf", "Tm", "m1", "m2", "alpha", "rl",
             "Dmin", "Dmax", "hmin", "kappa")
 CLASSIC_USED = ("D", "A", "B", "cw", "S0", "S1", "S2", "a0", "a2", "ai", "Fb", "k", "Lf", "F", "cg", "tau")
 TOL_SHORT = 1e-10    # test_gpu_parity.py: trajectories of <= 50 steps
-
-
-def is_miz(model):
-    return model.startswith("MIZ")
 
 
 def base_params(pkg, model):
@@ -47,13 +41,15 @@ def param_rows(pkg, model, n, seed, spread=0.2):
 
 
 def nt_for(model, nlat):
+    # its own table, not support.steps_per_year: meridians of 1024 cells, and 4096 stepped by the explicit model
     if not is_miz(model):
         return 2000
     return {180: 2000, 1024: 262144, 4096: 1048576}[nlat]
 
 
 def initial_state(pkg, model, st, ncol):
-    """The golden fixtures' mid-year state (ice edge, open water, a live T0 solve) interpolated onto st.x."""
+    """The golden fixtures' mid-year state (ice edge, open water, a live T0 solve) interpolated onto st.x.
+    A new test should take support.midyear_state instead: field-by-field interpolation makes cells no model state has."""
     if is_miz(model):
         g = load_golden(f"miz_{'identity' if st.grid_kind == 'identity' else 'sin'}_180_2000.npz")
         return {k: np.tile(np.interp(st.x, g["x"], g[f"s1000_{k}"]), (ncol, 1)) for k in PROG + ("T0",)}

@@ -20,8 +20,8 @@ import pytest
 import torch
 
 from ensemble_hist_ref import ensemble_histogram_ref, ensemble_range_ref, same_bits, slots_ref
+from support import assert_same_snapshot, forcing_of, make_engine, snapshot
 from test_gpu_ensemble_sums import MIZ_ALL, blank_engine, coverage, crafted, grid, load, weights_for
-from test_gpu_until import assert_same_snapshot, forcing_of, make_engine, snapshot
 
 pytestmark = pytest.mark.gpu
 

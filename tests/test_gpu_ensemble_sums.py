@@ -20,12 +20,11 @@ import pytest
 import torch
 
 from ensemble_sums_ref import ensemble_sums_ref, same_bits
-from test_gpu_until import assert_same_snapshot, forcing_of, make_engine, snapshot
+from support import MIZ_PROG, assert_same_snapshot, forcing_of, make_engine, snapshot
 
 pytestmark = pytest.mark.gpu
 
 MIZ_ALL = ("Ei", "Ew", "h", "D", "phi", "Tw", "Ti", "n", "E", "T")
-MIZ_PROG = ("Ei", "Ew", "h", "D", "phi")
 CRAFTED = ("Ei", "phi", "Ti", "T")                   # two prognostic and two diagnostic fields
 DP = ctypes.POINTER(ctypes.c_double)
 

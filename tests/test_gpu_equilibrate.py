@@ -15,25 +15,16 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from support import MIZ_DIAG as DIAG, MIZ_PROG as PROG, all_fields, is_miz
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
-DIAG = ("Tw", "Ti", "n", "E", "T")
-MIZ_ALL = PROG + ("T0",) + DIAG
-CLASSIC_ALL = ("E", "Tg", "T", "h")
-
-
-def is_miz(model):
-    return model.startswith("MIZ")
-
-
-def all_fields(model):
-    return MIZ_ALL if is_miz(model) else CLASSIC_ALL
+MIZ_ALL = all_fields("MIZ")
 
 
 def golden_state(pkg, model, st, ncol):
-    """The golden fixtures' mid-year state interpolated onto st.x, every column the same."""
+    """The golden fixtures' mid-year state interpolated onto st.x, every column the same.  Not support.midyear_state: that one
+    takes whole nearest cells, which are other numbers than these field-by-field interpolations."""
     if is_miz(model):
         g = load_golden(f"miz_{'identity' if st.grid_kind == 'identity' else 'sin'}_180_2000.npz")
         return {k: np.tile(np.interp(st.x, g["x"], g[f"s1000_{k}"]), (ncol, 1)) for k in PROG + ("T0",)}

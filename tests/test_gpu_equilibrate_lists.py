@@ -58,7 +58,8 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_equilibrate import (PROG, Setup, all_fields, check_against_reference, distances, expected, is_miz, reference)
+from support import MIZ_PROG as PROG, all_fields, is_miz, midyear_state
+from test_gpu_equilibrate import Setup, check_against_reference, distances, expected, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -180,10 +181,9 @@ def type_table(model):
 
 
 def unspun_state(pkg, model, st, table):
-    """One column per type: whole cells of the nearest golden cell (tests/test_gpu_series.py: initial_state explains why not
-    np.interp field by field), open water, or NaN."""
-    from test_gpu_series import initial_state
-    gold = initial_state(model, st, 1)
+    """One column per type: whole cells of the nearest golden cell (support.midyear_state explains why not np.interp field
+    by field), open water, or NaN."""
+    gold = midyear_state(model, st, 1)
     cw = pkg.default_parameters("MIZ" if is_miz(model) else "Classic")["cw"]
     state = {k: np.zeros((len(table), st.nx)) for k in gold}
     for t, (start, temp, *_rest) in enumerate(table):

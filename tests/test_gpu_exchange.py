@@ -3,7 +3,7 @@ of records and back — and of the selection across shards built on them (resamp
 resample_import).
 
 No oracle: every claim is an identity with entry points the library already has, compared on the bit patterns (bits /
-same_bits of tests/test_gpu_until.py):
+same_bits of tests/support.py):
   1. export + import on ONE handle through one buffer, the parents of the moved columns into the moved columns, is
      ebm_resample_columns with the same map (a twin handle);
   2. across two handles that hold different layouts, the destination column reads back as the source column did;
@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_until import (all_fields, bits, forcing_of, initial_state, installer, is_miz, prognostic, same_bits, snapshot)
-from test_gpu_resample import assert_snapshot, make_engine, make_maps, map_claims
+from support import (all_fields, assert_snapshot_by_column as assert_snapshot, bits, forcing_of, is_miz, make_engine, make_maps, map_claims,
+                     member_installer, midyear_state, prognostic, same_bits, snapshot, step_by)
 
 pytestmark = pytest.mark.gpu
 
@@ -231,17 +231,6 @@ def test_a_slot_whose_field_is_stale_in_the_destination_is_ignored(pkg, model, g
 
 # ---- 3: continuation ------------------------------------------------------------------------------------------------------------
 
-def step_by(eng, path, first, n, f):
-    if path == "run_1":
-        eng.run(first, n, f, True, 1)
-    elif path == "fused_7":
-        eng.run(first, n, f, True, 7)
-    else:                                                 # one round of ebm_run_until that nobody leaves early
-        out = eng.run_until(first, 1, n, "T", np.full(eng.ncol, np.inf), np.ones(eng.ncol, dtype=np.int64), f, 4)
-        assert not out["crossed"].any()
-        eng.run(first + n, 1, None, True, 1)              # ... and a diagnostic step, so that every field can be compared
-
-
 CONT = [("MIZ", "sin", 180, 4, ("noise", "params")), ("MIZ", "identity", 180, 2, ("noise", "params")), ("MIZ", "sin", 2, 4, ("noise",)),
         ("MIZ", "sin", 1025, 4, ("noise", "params")), ("MIZ_IMEX", "sin", 180, 4, ("noise",)), ("Classic", "identity", 180, 4, ("noise",))]
 
@@ -278,7 +267,7 @@ def test_continues_like_a_loaded_member(pkg, model, grid, nlat, cells, what, pat
     with ref:
         ref.set_column_forcing(np.linspace(-1.5, 1.5, nD)[2:3])
         if what:
-            installer(pkg, nD, what)(ref, slice(2, 3))
+            member_installer(pkg, nD, what)(ref, slice(2, 3))
         ref.set_state({k: src["fields"][k][1:2] for k in prognostic(model)})
         if is_miz(model):
             ref.set_field("T0", src["fields"]["T0"][1:2])
@@ -318,7 +307,7 @@ def test_sharded_selection_equals_unsharded(pkg, N, W, spl, mapname):
     parents = selection_maps(pkg, N, W)[mapname]
     st = pkg.SpaceTime("sin", 180, 2000, 1)
     par = pkg.default_parameters("MIZ")
-    init = {k: v for k, v in initial_state("MIZ", st, N).items() if k != "T0"}
+    init = {k: v for k, v in midyear_state("MIZ", st, N).items() if k != "T0"}
     fcol = np.linspace(-2.0, 2.0, N)
     rows = [{"D": float(d)} for d in pkg.default_parval["D"] * np.linspace(0.9, 1.1, N)]
     noise = dict(sigma=1.5, tau=0.01, seed=5)

@@ -11,30 +11,18 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from support import (MIZ_PROG as PROG, all_fields as names, assert_same_values as assert_same, host_N, is_miz, noise_args,
+                     noise_module as _noise)
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
-MIZ_ALL = PROG + ("T0", "Tw", "Ti", "n", "E", "T")
-CLASSIC_ALL = ("E", "Tg", "T", "h")
+MIZ_ALL = names("MIZ")
 NLAT, NT = 180, 2000
 FIRST = 1000                     # global index of the first step: mid-year, a live T0 solve
 
 
-def _noise(pkg):
-    import sys
-    return sys.modules[pkg.__name__ + ".noise"]
-
-
-def is_miz(model):
-    return model.startswith("MIZ")
-
-
-def names(model):
-    return MIZ_ALL if is_miz(model) else CLASSIC_ALL
-
-
 def initial_state(st, model, ncol):
+    """Interpolated field by field: not support.midyear_state, whose nearest-cell values are other numbers."""
     if is_miz(model):
         g = load_golden("miz_sin_180_2000.npz")
         return {k: np.tile(np.interp(st.x, g["x"], g[f"s1000_{k}"]), (ncol, 1)) for k in PROG + ("T0",)}
@@ -59,15 +47,6 @@ def make(pkg, model, ncol, state=None, params=None, **opt):
 
 def forcing(nsteps):
     return 0.5 * np.sin(np.arange(nsteps) * 0.37)
-
-
-def noise_args(ncol):
-    return dict(sigma=np.linspace(0.5, 3.0, ncol), rho=np.linspace(0.0, 0.95, ncol), seed=0x5EED_0001_2345_6789)
-
-
-def host_N(pkg, eng, args, first, nsteps, N0=None):
-    """N_c after each of the steps first .. first + nsteps - 1, from the device's innovations (exact recurrence)."""
-    return _noise(pkg).ar1(eng.noise_innovations(first, nsteps), args["sigma"], args["rho"], N0)
 
 
 def reference(pkg, model, ncol, nsteps, f, N, **opt):

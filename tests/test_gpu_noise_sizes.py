@@ -30,11 +30,14 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from test_gpu_noise import MIZ_ALL, PROG, _noise, assert_same, host_N, is_miz, names, noise_args
+from support import (MIZ_PROG as PROG, all_fields as names, assert_same_values as assert_same, host_N, is_miz, noise_args,
+                     noise_module as _noise, prognostic)
 
 pytestmark = pytest.mark.gpu
 
-# steps per year of the MIZ shapes (>= nlat^2 / 4); the classic model: 2000
+MIZ_ALL = names("MIZ")
+
+# steps per year of the MIZ shapes (>= nlat^2 / 4); the classic model: 2000.  Its own table: 2050 cells, and 4096 stepped explicitly
 NT = {180: 2000, 258: 20000, 1025: 270000, 2050: 1100000, 4096: 4200000}
 TABLE = 256
 FIRST = 40 * TABLE               # global index of the first step: entry 0 of the table, a step clock that is not 0
@@ -105,10 +108,6 @@ def open_engine(pkg, shape, table=None, clock=FIRST, **opt):
     eng.set_time_table(t if table is None else table)
     eng.set_step_clock(clock)
     return eng
-
-
-def prognostic(model):
-    return PROG if is_miz(model) else ("E", "Tg")
 
 
 def single_steps(pkg, shape, first, N, f, table=None):

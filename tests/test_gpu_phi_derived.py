@@ -7,7 +7,7 @@ the same calls on a second handle with every `run` taken as ebm_run_fused with K
 and write all five prognostic fields.
 
 Start state: the golden mid-year state (ice, open water, an ice edge, cells with phi == 1) spread onto the grid by nearest
-cell, as tests/test_gpu_series.py does; the first step after it loads the caller's phi, every later one derives it.  The C
+cell (support.midyear_state); the first step after it loads the caller's phi, every later one derives it.  The C
 oracle steps the same state once per shape (shared) to show that the trajectories compared are finite, not NaN against NaN.
 
 Shapes, at four cells per thread: 258 x 3 (128 threads, padding in the last thread), 1025 x 2 (320 threads, a lone cell in
@@ -18,32 +18,16 @@ import functools
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from support import MIZ_PROG as PROG, assert_same_bits as same, forcing_of as forcing, midyear_state
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
 SHAPES = [(258, 3), (1025, 2), (4096, 2), (180, 5)]
 THREADS = {258: 128, 1025: 320, 4096: 1024, 180: 64}
-# steps per year: the reference's explicit step is stable for nt >= nlat^2 / 4 (tests/test_gpu_series.py)
+# steps per year, nt >= nlat^2 / 4: its own table, not support.steps_per_year, because 4096 cells are stepped by the explicit model here
 NT = {180: 2000, 258: 20000, 1025: 270000, 4096: 4200000}
 TABLE = 256            # time-table entries from mid-year on: every test takes fewer steps than that
 MAX_STEPS = 134        # the most steps any test here takes from the start state
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b, what=""):
-    """dicts of arrays, or arrays: equal bit for bit"""
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), what
-        for k in a:
-            same(a[k], b[k], (what, k))
-        return
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape and np.array_equal(bits(a), bits(b)), what
 
 
 class Space:
@@ -66,16 +50,11 @@ def offsets(ncol):
     return np.linspace(-1.5, 1.5, ncol)
 
 
-def forcing(first, n):
-    return 0.5 * np.sin(0.37 * (first + np.arange(n)))
-
-
 @functools.lru_cache(maxsize=None)
 def start_state(pkg, grid, nlat):
+    """One column of support.midyear_state on this file's grid."""
     st, _ = space(pkg, grid, nlat)
-    g = load_golden(f"miz_{'identity' if grid == 'identity' else 'sin'}_180_2000.npz")
-    nearest = np.abs(st.x[:, None] - g["x"][None, :]).argmin(axis=1)
-    state = {k: np.ascontiguousarray(g[f"s1000_{k}"][nearest]) for k in PROG + ("T0",)}
+    state = {k: np.ascontiguousarray(v[0]) for k, v in midyear_state("MIZ", st, 1).items()}
     # (open water, h == 0, on the sin grid only: the identity fixture has ice in every cell)
     assert (state["phi"] == 1.0).any() and ((state["phi"] > 0) & (state["phi"] < 1)).any()
     assert grid == "identity" or (state["h"] == 0.0).any()

@@ -2,11 +2,11 @@
 state of parent[c]; the member's settings stay with the slot.
 
 No oracle: the definition is an identity with entry points the library already has.  Everything is compared on the bit
-patterns (bits / same_bits of tests/test_gpu_until.py): a download before the call, gathered in NumPy, against a download
+patterns (bits / same_bits of tests/support.py): a download before the call, gathered in NumPy, against a download
 after it; and the stepping after a resample against a handle that was loaded through set_state / set_field("T0") /
 set_noise_state with the gathered download and keeps every column's own settings.
 
-Start: the golden mid-year state of tests/test_gpu_until.py, the columns made different by their forcing offsets (and by
+Start: the golden mid-year state of tests/support.py, the columns made different by their forcing offsets (and by
 noise and parameter rows where installed) over a few steps.
 
 Shapes, the smallest at which the copy can go wrong: nlat 2 (pitch 128: the row is nearly all padding), 180 at 2 and at 4
@@ -22,106 +22,15 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_gpu_until import (PROG, all_fields, bits, forcing_of, initial_state, installer, is_miz, prognostic, same_bits, snapshot)
+from support import (MIZ_PROG as PROG, all_fields, assert_snapshot_by_column as assert_snapshot, bits, forcing_of, is_miz, make_engine, make_maps,
+                     map_claims, midyear_state, prognostic, same_bits, snapshot, step_by)
 
 pytestmark = pytest.mark.gpu
-
-NT = {2: 2000, 180: 2000, 1025: 270000}        # the explicit model is stable for nt >= nlat^2 / 4
-
-
-def make_engine(pkg, model, grid, nlat, ncol, cells=4, what=(), **opt):
-    """make_engine of tests/test_gpu_until.py with this file's meridians."""
-    st = pkg.SpaceTime(grid, nlat, NT[nlat], 1)
-    tab = np.array([pkg.cos2pit(float(t)) for t in st.t], dtype=np.float64)
-    vec = pkg.engine.param_vector(pkg.default_parameters("MIZ" if is_miz(model) else "Classic"), pkg.default_parval)
-    eng = pkg.Engine(model, st.grid_kind, st.x, vec, st.dt, ncol, device=0, cells_per_thread=cells, **opt)
-    eng.set_state(initial_state(model, st, ncol))
-    eng.set_column_forcing(np.linspace(-1.5, 1.5, ncol))
-    eng.nt, eng.ttab = len(tab), tab
-    pkg.engine.check(eng.lib.ebm_set_time_table(eng._h, len(tab), pkg.engine.dptr(tab)), "ebm_set_time_table")
-    if what:
-        installer(pkg, ncol, what)(eng, slice(0, ncol))
-    return eng, st
-
-
-# ---- the maps ----------------------------------------------------------------------------------------------------------------
-
-def make_maps(n):
-    c = np.arange(n)
-    if n == 1:
-        return {"identity": c.copy()}
-    swap = c.copy()
-    swap[0], swap[1] = 1, 0
-    rnd = np.random.default_rng(77 + n).integers(0, n, n)
-    if n >= 5:
-        rnd[0] = 0                                     # a fixed point
-        rnd[1], rnd[2] = 2, 1                          # a 2-cycle
-        rnd[3], rnd[4] = 1, 3                          # a chain 1 -> 3 -> 4 hanging off the cycle
-        if n >= 65:
-            rnd[10:30:3] = np.arange(10, 30, 3)        # more fixed points
-            rnd[40], rnd[41], rnd[42] = 41, 42, 40     # a 3-cycle
-    else:
-        rnd = np.array([0, 2, 1])                      # three columns: a fixed point and a cycle
-    return {"identity": c.copy(), "swap": swap, "shift": (c - 1) % n, "chain": np.maximum(c - 1, 0),
-            "fanout": np.full(n, n - 1), "random": rnd}
-
-
-def orbit_returns(p, c):
-    """Is column c on a cycle of p (does following the parents from c come back to c)?"""
-    x = p[c]
-    for _ in range(len(p)):
-        if x == c:
-            return True
-        x = p[x]
-    return False
-
-
-def map_claims(name, p):
-    n = len(p)
-    c = np.arange(n)
-    assert p.shape == (n,) and ((p >= 0) & (p < n)).all()
-    if name == "identity":
-        assert (p == c).all()
-    elif name == "swap":
-        assert p[0] == 1 and p[1] == 0 and (p[2:] == c[2:]).all()
-    elif name == "shift":
-        assert sorted(p.tolist()) == c.tolist() and (p != c).all(), "a permutation without a fixed point"
-        x, steps = 0, 0
-        while True:
-            x, steps = p[x], steps + 1
-            if x == 0:
-                break
-        assert steps == n, "one cycle through every column"
-        assert (p[1:] < c[1:]).all() and p[0] > 0, "ascending order overwrites parents 0 .. n-2 before they are read, " \
-                                                   "descending order overwrites n-1 before column 0 reads it"
-    elif name == "chain":
-        assert p[0] == 0 and (p[1:] == c[1:] - 1).all() and not any(orbit_returns(p, k) for k in range(1, n))
-    elif name == "fanout":
-        assert (p == n - 1).all()
-    elif name == "random":
-        moved = p != c
-        assert (~moved).any(), "a fixed point"
-        assert any(moved[k] and orbit_returns(p, k) for k in range(n)), "a cycle of moved columns"
-        if n >= 5:
-            assert any(moved[k] and moved[p[k]] and not orbit_returns(p, k) for k in range(n)), \
-                "a chain: a moved column off every cycle whose parent is itself overwritten"
-
 
 def gathered(snap, p):
     """The snapshot the definition promises: every row that may be read taken from the parent's; the rest unchanged."""
     return dict(field_step=snap["field_step"], counters=snap["counters"], noise=snap["noise"][p],
                 fields={k: v[p] for k, v in snap["fields"].items()})
-
-
-def assert_snapshot(got, want, what):
-    assert got["field_step"] == want["field_step"], (what, got["field_step"], want["field_step"])
-    assert got["counters"] == want["counters"], (what, got["counters"], want["counters"])
-    bad = np.flatnonzero(bits(got["noise"]) != bits(want["noise"]))
-    assert bad.size == 0, f"{what}: the noise state differs in columns {bad[:10]}"
-    assert got["fields"].keys() == want["fields"].keys(), (what, sorted(got["fields"]), sorted(want["fields"]))
-    for k in want["fields"]:
-        bad = np.flatnonzero((bits(got["fields"][k]) != bits(want["fields"][k])).any(axis=1))
-        assert bad.size == 0, f"{what}: field {k} differs in columns {bad[:10]}"
 
 
 def columns_differ(snap, model, ncol):
@@ -216,15 +125,6 @@ def test_gather_in_the_layout_the_steps_leave(pkg, model, grid, nlat, cells, nco
 
 
 # ---- 2: continuation ----------------------------------------------------------------------------------------------------------
-
-def step_by(eng, path, first, n, f):
-    if path == "run_1":
-        eng.run(first, n, f, True, 1)
-    elif path == "fused_7":
-        eng.run(first, n, f, True, 7)
-    else:
-        eng.run_series(first, n, n, ("T",), f, 4)        # diag = 1: T is a diagnostic field of both models
-
 
 @pytest.mark.parametrize("path", ["run_1", "fused_7", "series"])
 @pytest.mark.parametrize("model, grid, cells, what", [("MIZ", "sin", 4, ("noise", "params")), ("MIZ", "identity", 2, ("noise", "params")),
@@ -417,7 +317,7 @@ def test_refusals_leave_the_handle_alone(pkg):
 def test_ensemble_resample_end_to_end(pkg):
     st = pkg.SpaceTime("sin", 180, 2000, 1)
     members = 16
-    init = {k: v for k, v in initial_state("MIZ", st, members).items() if k != "T0"}
+    init = {k: v for k, v in midyear_state("MIZ", st, members).items() if k != "T0"}
     run = pkg.EnsembleRun("MIZ", st, pkg.default_parameters("MIZ"), init, fcol=np.linspace(-2.0, 2.0, members),
                           noise=dict(sigma=1.5, tau=0.01, seed=5))
     names = PROG + ("T0", "T")

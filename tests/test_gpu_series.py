@@ -17,34 +17,18 @@ import functools
 import numpy as np
 import pytest
 
-from conftest import load_golden
+import support
+from support import (CLASSIC_VARS, MIZ_DIAG as DIAG, MIZ_PROG as PROG, assert_same_snapshot, forcing_of, is_diagnostic, is_miz,
+                     midyear_state, same_bits, snapshot)
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
-DIAG = ("Tw", "Ti", "n", "E", "T")
 MIZ_VARS = PROG + DIAG
-CLASSIC_VARS = ("E", "Tg", "T", "h")
-NT = {2: 2000, 3: 2000, 65: 2000, 180: 2000, 258: 20000, 513: 70000, 1025: 270000, 4096: 2000}
 
 
-def is_miz(model):
-    return model.startswith("MIZ")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-@functools.lru_cache(maxsize=None)
-def space_time(pkg, grid, nlat):
-    st = pkg.SpaceTime(grid, nlat, NT[nlat], 1)
-    tab = np.array([pkg.cos2pit(float(t)) for t in st.t], dtype=np.float64)
-    return st, tab
+def make_engine(pkg, model, grid, nlat, ncol, cells=4, setup=None, **opt):
+    """support.make_engine with a single column's forcing offset at 0.25, as these tests have always had it."""
+    return support.make_engine(pkg, model, grid, nlat, ncol, cells, setup=setup, single_offset=0.25, **opt)
 
 
 def names_of(model, kind):
@@ -55,73 +39,14 @@ def names_of(model, kind):
     return ("phi",) if is_miz(model) else ("E",)          # prognostic only: no diagnostic step is taken
 
 
-def all_fields(model):
-    return PROG + ("T0",) + DIAG if is_miz(model) else CLASSIC_VARS
-
-
-def initial_state(model, st, ncol):
-    """The golden fixtures' mid-year state (ice, open water, a live T0 solve) resampled onto st.x: every cell takes the
-    WHOLE state of the nearest golden cell.  Interpolating each field linearly on its own, as tests/test_gpu_column_params.py
-    does, mixes neighbouring cells' ice thickness, floe size and concentration into cells no model state has (ice
-    concentration without thickness), and on every grid but the golden one the T0 solve of the second step returns NaN
-    everywhere (seen with the CPU oracle as well): bits would still compare equal, but of nothing.  The columns differ
-    through their forcing offsets."""
-    if is_miz(model):
-        g = load_golden(f"miz_{'identity' if st.grid_kind == 'identity' else 'sin'}_180_2000.npz")
-        names, step = PROG + ("T0",), "s1000"
-    else:
-        g = load_golden("classic_identity_180_2000.npz")
-        names, step = ("E", "Tg"), "s522"
-    nearest = np.abs(st.x[:, None] - g["x"][None, :]).argmin(axis=1)
-    return {k: np.tile(g[f"{step}_{k}"][nearest], (ncol, 1)) for k in names}
-
-
-def make_engine(pkg, model, grid, nlat, ncol, cells=4, setup=None, **opt):
-    """A handle at the mid-year state with per-column forcing offsets and the time table; setup(eng, cols) installs more."""
-    st, tab = space_time(pkg, grid, nlat)
-    vec = pkg.engine.param_vector(pkg.default_parameters("MIZ" if is_miz(model) else "Classic"), pkg.default_parval)
-    eng = pkg.Engine(model, st.grid_kind, st.x, vec, st.dt, ncol, device=0, cells_per_thread=cells, **opt)
-    eng.set_state(initial_state(model, st, ncol))
-    eng.set_column_forcing(np.linspace(-1.5, 1.5, ncol) if ncol > 1 else np.array([0.25]))
-    eng.nt, eng.ttab = len(tab), tab
-    pkg.engine.check(eng.lib.ebm_set_time_table(eng._h, len(tab), pkg.engine.dptr(tab)), "ebm_set_time_table")
-    if setup is not None:
-        setup(eng, slice(0, ncol))
-    return eng, st
-
-
 def first_step(st):
     return st.nt // 2
-
-
-def forcing_of(first, nsteps):
-    return 0.5 * np.sin(0.37 * (first + np.arange(nsteps)))
-
-
-def snapshot(eng, model):
-    """Everything the definition says the call leaves behind: the fields that may be read, the validity bookkeeping of
-    every field, the noise state and the counters."""
-    out = {"field_step": {k: eng.field_step(k) for k in all_fields(model)}, "noise": eng.noise_state(),
-           "counters": eng.counters(), "fields": {}}
-    for k in all_fields(model):
-        if out["field_step"][k]["current"]:
-            out["fields"][k] = eng.get_field(k)
-    return out
-
-
-def assert_same_snapshot(a, b, what):
-    assert a["field_step"] == b["field_step"], what
-    assert a["counters"] == b["counters"], (what, a["counters"], b["counters"])
-    assert same_bits(a["noise"], b["noise"]), what
-    assert a["fields"].keys() == b["fields"].keys(), what
-    for k in a["fields"]:
-        assert same_bits(a["fields"][k], b["fields"][k]), (what, k)
 
 
 def by_hand(pkg, eng, st, model, first, nsteps, every, K, names, f):
     """The host loop the definition names: ebm_run_fused for `every` steps, then ebm_hemispheric_mean per variable; and the
     NumPy restatement of the mean applied to the downloaded fields."""
-    diag = any(n in (DIAG if is_miz(model) else ("T", "h")) for n in names)
+    diag = any(is_diagnostic(model, n) for n in names)
     ns = nsteps // every
     dev = np.empty((len(names), ns, eng.ncol))
     host = np.empty_like(dev)
@@ -306,7 +231,7 @@ def test_options_and_columns_alone(pkg, nlat, ncol, variant):
         assert same_bits(s16, series)
         assert c16["launches"] == (nsteps // every) * -(-every // 16)
     # every member alone: its row, forcing, schedule and stream id in a one-column handle
-    state = initial_state(model, st, ncol)
+    state = midyear_state(model, st, ncol)
     for c in range(ncol):
         one, _ = make_engine(pkg, model, grid, nlat, 1, 4, None, **opt)
         with one:
@@ -362,7 +287,7 @@ def test_ensemble_series_is_independent_of_sharding(pkg):
     st = pkg.SpaceTime("sin", 180, 2000, 1)
     par = pkg.default_parameters("MIZ")
     members, nsteps, every = 6, 60, 20
-    init = {k: v for k, v in initial_state("MIZ", st, members).items() if k != "T0"}
+    init = {k: v for k, v in midyear_state("MIZ", st, members).items() if k != "T0"}
     fcol = np.linspace(-2.0, 2.0, members)
     noise = dict(sigma=1.5, tau=0.01, seed=5)
     forcing = pkg.Forcing(0.75)

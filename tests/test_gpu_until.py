@@ -30,119 +30,13 @@ import functools
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from support import (MIZ_PROG as PROG, all_fields, assert_same_snapshot, bits, forcing_of, is_diagnostic, make_engine, midyear_state,
+                     prognostic, same_bits, snapshot)
 from test_host_until import first_crossing
 
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
-DIAG = ("Tw", "Ti", "n", "E", "T")
-NT = {65: 2000, 180: 2000, 1025: 270000}       # the explicit model is stable for nt >= nlat^2 / 4
 FIRST, NEVER = 0, -1                           # targets: stop at the first sample / never; t >= 1: the measured sample t
-
-
-def is_miz(model):
-    return model.startswith("MIZ")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def prognostic(model):
-    return PROG if is_miz(model) else ("E", "Tg")
-
-
-def all_fields(model):
-    return PROG + ("T0",) + DIAG if is_miz(model) else ("E", "Tg", "T", "h")
-
-
-def is_diagnostic(model, name):
-    return name in (DIAG if is_miz(model) else ("T", "h"))
-
-
-@functools.lru_cache(maxsize=None)
-def space_time(pkg, grid, nlat):
-    st = pkg.SpaceTime(grid, nlat, NT[nlat], 1)
-    tab = np.array([pkg.cos2pit(float(t)) for t in st.t], dtype=np.float64)
-    return st, tab
-
-
-def initial_state(model, st, ncol):
-    """The start of tests/test_gpu_series.py: the golden fixtures' mid-year state (ice, open water, a live T0 solve), every
-    cell taking the WHOLE state of the nearest golden cell (interpolating field by field makes cells no model state has).
-    The columns differ through their forcing offsets."""
-    if is_miz(model):
-        g = load_golden(f"miz_{'identity' if st.grid_kind == 'identity' else 'sin'}_180_2000.npz")
-        names, step = PROG + ("T0",), "s1000"
-    else:
-        g = load_golden("classic_identity_180_2000.npz")
-        names, step = ("E", "Tg"), "s522"
-    nearest = np.abs(st.x[:, None] - g["x"][None, :]).argmin(axis=1)
-    return {k: np.tile(g[f"{step}_{k}"][nearest], (ncol, 1)) for k in names}
-
-
-def installer(pkg, ncol_total, what):
-    """setup(eng, cols): the per-member settings named in `what` ("params", "sched", "noise") of the members `cols` of an
-    ensemble of ncol_total — distinct parameter rows, ramps, noise streams and sigmas."""
-    base = pkg.engine.param_vector(pkg.default_parameters("MIZ"), pkg.default_parval)
-    rng = np.random.default_rng(11)
-    rows = np.tile(base, (ncol_total, 1))
-    rows[:, pkg.engine.PARAM_ORDER.index("D")] *= rng.uniform(0.9, 1.1, ncol_total)
-    rows[:, pkg.engine.PARAM_ORDER.index("A")] *= rng.uniform(0.98, 1.02, ncol_total)
-    ramps = [pkg.Forcing(0.0, float(c % 5 + 1), 0.0, (0, 0), (float(c % 5 + 1), -float(c % 5 + 1))) for c in range(ncol_total)]
-
-    def setup(eng, cols):
-        if "params" in what:
-            eng.set_column_params(rows[cols])
-        if "sched" in what:
-            eng.set_column_schedules(ramps[cols])
-        if "noise" in what:
-            eng.set_column_noise(np.linspace(0.5, 2.0, ncol_total)[cols], rho=np.full(ncol_total, 0.9)[cols], seed=2024,
-                                 streams=(100 + np.arange(ncol_total, dtype=np.uint64))[cols])
-    return setup
-
-
-def make_engine(pkg, model, grid, nlat, ncol, cells=4, what=(), **opt):
-    """A handle at the mid-year state with per-column forcing offsets and the time table, plus the settings of `what`."""
-    st, tab = space_time(pkg, grid, nlat)
-    vec = pkg.engine.param_vector(pkg.default_parameters("MIZ" if is_miz(model) else "Classic"), pkg.default_parval)
-    eng = pkg.Engine(model, st.grid_kind, st.x, vec, st.dt, ncol, device=0, cells_per_thread=cells, **opt)
-    eng.set_state(initial_state(model, st, ncol))
-    eng.set_column_forcing(np.linspace(-1.5, 1.5, ncol))
-    eng.nt, eng.ttab = len(tab), tab
-    pkg.engine.check(eng.lib.ebm_set_time_table(eng._h, len(tab), pkg.engine.dptr(tab)), "ebm_set_time_table")
-    if what:
-        installer(pkg, ncol, what)(eng, slice(0, ncol))
-    return eng, st
-
-
-def forcing_of(first, nsteps):
-    return 0.5 * np.sin(0.37 * (first + np.arange(nsteps)))
-
-
-def snapshot(eng, model):
-    """What the definition says the call leaves behind: the fields that may be read, the validity bookkeeping of every
-    field (it holds the last step taken: the step clock minus one), the noise state and the counters."""
-    out = {"field_step": {k: eng.field_step(k) for k in all_fields(model)}, "noise": eng.noise_state(),
-           "counters": eng.counters(), "fields": {}}
-    for k in all_fields(model):
-        if out["field_step"][k]["current"]:
-            out["fields"][k] = eng.get_field(k)
-    return out
-
-
-def assert_same_snapshot(a, b, what):
-    assert a["field_step"] == b["field_step"], what
-    assert a["counters"] == b["counters"], (what, a["counters"], b["counters"])
-    assert same_bits(a["noise"], b["noise"]), what
-    assert a["fields"].keys() == b["fields"].keys(), what
-    for k in a["fields"]:
-        assert same_bits(a["fields"][k], b["fields"][k]), (what, k)
 
 
 # ---- targets and levels ----------------------------------------------------------------------------------------------------
@@ -515,7 +409,7 @@ def test_ensemble_first_passage_is_independent_of_sharding(pkg):
     st = pkg.SpaceTime("sin", 180, 2000, 1)
     par = pkg.default_parameters("MIZ")
     members, every, ns = 8, 20, 5
-    init = {k: v for k, v in initial_state("MIZ", st, members).items() if k != "T0"}
+    init = {k: v for k, v in midyear_state("MIZ", st, members).items() if k != "T0"}
     fcol = np.linspace(-2.0, 2.0, members)
     noise = dict(sigma=1.5, tau=0.01, seed=5)
     forcing = pkg.Forcing(0.75)

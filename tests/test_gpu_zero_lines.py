@@ -2,7 +2,7 @@
 FieldBook::zero_flags_trusted, csrc/ebm_fieldbook.h; DESIGN.md section 3): a KiB of Ei, Ew, h or D that holds only zero bits is
 neither loaded nor stored, on the word of one flag per (column, wave, pair, field).
 
-Nothing a caller can see may change, so every comparison is bitwise (int64 views) and sets no tolerance: a handle with
+Nothing a caller can see may change, so every comparison is bitwise (uint64 views) and sets no tolerance: a handle with
 ebm_options.elide_zero_lines on against one with it off, the same calls on both — all five prognostic fields after phi is
 restored, and the ten solution variables after one diagnostic step.  The flags read back (ebm_zero_line_flags) must EQUAL the
 per-line "all zero bits" computed in numpy from the fields: set over a line that is not zero is a wrong result, clear over a
@@ -28,14 +28,15 @@ import functools
 import numpy as np
 import pytest
 
+from support import MIZ_PROG as PROG, assert_same_bits as same, bits
+
 pytestmark = pytest.mark.gpu
 
-PROG = ("Ei", "Ew", "h", "D", "phi")
 FLAGGED = ("Ei", "Ew", "h", "D")                 # bit 4 j + f of a wave's word: pair j of FLAGGED[f]
 TEN = ("Ei", "Ew", "h", "D", "phi", "E", "T", "Ti", "Tw", "n")
 SHAPES = [(258, 3), (1025, 2), (4096, 2)]
 THREADS = {258: 128, 1025: 320, 4096: 1024}
-NT = {258: 20000, 1025: 270000, 4096: 4200000}   # steps per year: the explicit step is stable for nt >= nlat^2 / 4
+NT = {258: 20000, 1025: 270000, 4096: 4200000}   # steps per year, nt >= nlat^2 / 4; its own: 4096 cells step explicitly here
 GRIDS = ["sin", "identity"]
 SCENARIO = 16                                    # steps
 CHECKPOINTS = (1, 2, 3, 5, 8, 12, 16)            # where the step-by-step test reads flags and fields
@@ -74,16 +75,6 @@ def space(pkg, grid, nlat):
     return Space(pkg, grid, nlat)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def same(a, b, what=""):
-    assert a.keys() == b.keys(), what
-    for k in a:
-        assert a[k].shape == b[k].shape and np.array_equal(bits(a[k]), bits(b[k])), (what, k)
-
-
 def line_flags(fields, nlat):
     """The flag words [ncol][threads / 64] that the fields call for: bit 4 j + f set iff cells 4 t + 2 j and 4 t + 2 j + 1 of
     the wave's threads t hold only zero bits in FLAGGED[f] (cells beyond nlat are padding: zero)."""
@@ -91,7 +82,7 @@ def line_flags(fields, nlat):
     ncol = fields["Ei"].shape[0]
     words = np.zeros((ncol, T // 64), dtype=np.uint32)
     for f, name in enumerate(FLAGGED):
-        padded = np.zeros((ncol, 4 * T), dtype=np.int64)
+        padded = np.zeros((ncol, 4 * T), dtype=np.uint64)
         padded[:, :nlat] = bits(fields[name])
         per_pair = padded.reshape(ncol, T // 64, 64, 2, 2)            # [col][wave][thread][pair][cell]
         zero = (per_pair == 0).all(axis=(2, 4))                        # [col][wave][pair]

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bare_engine
 
 
 def test_symbol_is_declared_exported_and_bound(pkg):
@@ -38,20 +39,6 @@ def test_null_handle_is_refused_without_a_gpu(pkg):
     assert b"bad argument" in lib.ebm_last_error()
 
 
-class _NoDevice:
-    """Stands in for the library: any call is a device call the checks should have prevented."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"{name} reached before the argument checks refused the call")
-
-
-def _bare_engine(pkg, model="MIZ", ncol=3):
-    engine = import_module(pkg.__name__ + ".engine")
-    eng = engine.Engine.__new__(engine.Engine)
-    eng.model, eng.ncol, eng.nlat, eng.lib, eng._h = model, ncol, 18, _NoDevice(), None
-    return eng
-
-
 @pytest.mark.parametrize("kw, exc, msg", [
     (dict(tol={"T0": 1e-3}), ValueError, "unknown field 'T0'"),
     (dict(tol={"Tg": 1e-3}), ValueError, "unknown field 'Tg'"),
@@ -63,7 +50,7 @@ def _bare_engine(pkg, model="MIZ", ncol=3):
     (dict(f_year=np.zeros(7)), ValueError, "shape"),
 ])
 def test_engine_checks_before_the_device(pkg, kw, exc, msg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     args = dict(nt=10, max_years=5, tol={"T": 1e-3})
     args.update(kw)
     with pytest.raises(exc, match=msg):
@@ -71,10 +58,10 @@ def test_engine_checks_before_the_device(pkg, kw, exc, msg):
 
 
 def test_engine_check_accepts_every_solution_variable(pkg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     names, ids, tols, f = eng.check_equilibrate_args(10, 3, {"Ei": 0.0, "T": 1e-3, "n": 2.0}, 2, np.zeros(10))
     assert names == ("Ei", "T", "n") and ids == [0, 10, 8] and list(tols) == [0.0, 1e-3, 2.0] and f.shape == (10,)
-    classic = _bare_engine(pkg, "Classic")
+    classic = bare_engine(pkg, "Classic")
     assert classic.check_equilibrate_args(10, 3, {"E": 1.0, "Tg": 1.0, "T": 1.0, "h": 1.0})[1] == [9, 11, 10, 2]
     with pytest.raises(ValueError, match="unknown field 'phi'"):
         classic.check_equilibrate_args(10, 3, {"phi": 1.0})
@@ -84,7 +71,7 @@ def _bare_run(pkg, schedules=False, step_index=0):
     ensemble = import_module(pkg.__name__ + ".ensemble")
     run = ensemble.EnsembleRun.__new__(ensemble.EnsembleRun)
     run.st = pkg.SpaceTime("sin", 18, 100, 1)
-    run.engine = _bare_engine(pkg)
+    run.engine = bare_engine(pkg)
     run.has_schedules = schedules
     run.step_index = step_index
     run.ncol = 3

@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+from support import compile_host_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEPTH = 5
 SHAPES = ("miz4_derive", "miz4_imex", "miz2", "classic")
@@ -24,9 +26,7 @@ NEVER = {"classic": {"get_T0", "sums_phi"}}
 
 
 def compile_program(out, extra_flags=()):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", *extra_flags, "-o", out,
-                    os.path.join(ROOT, "tests", "host_fieldbook_main.cpp")], check=True)
-    return out
+    return compile_host_program("host_fieldbook_main.cpp", out, ("-Wall",) + tuple(extra_flags))
 
 
 @pytest.fixture(scope="module")

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bare_engine
 
 
 def _noise(pkg):
@@ -115,20 +116,6 @@ def test_null_handle_is_refused_without_a_gpu(pkg):
     assert b"bad argument" in lib.ebm_last_error()
 
 
-class _NoDevice:
-    """Stands in for the library: any call is a device call the checks should have prevented."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"{name} reached before the argument checks refused the call")
-
-
-def _bare_engine(pkg, model="MIZ", ncol=3):
-    engine = import_module(pkg.__name__ + ".engine")
-    eng = engine.Engine.__new__(engine.Engine)
-    eng.model, eng.ncol, eng.nlat, eng.dt, eng.lib, eng._h = model, ncol, 18, 1.0 / 2000, _NoDevice(), None
-    return eng
-
-
 @pytest.mark.parametrize("kw, msg", [
     (dict(sigma=float("nan")), "sigma"),
     (dict(sigma=[1.0, float("inf"), 1.0]), "sigma"),
@@ -150,11 +137,11 @@ def _bare_engine(pkg, model="MIZ", ncol=3):
 ])
 def test_engine_noise_checks_come_before_any_device_call(pkg, kw, msg):
     with pytest.raises(ValueError, match=msg):
-        _bare_engine(pkg).set_column_noise(**kw)
+        bare_engine(pkg, dt=1.0 / 2000).set_column_noise(**kw)
 
 
 def test_engine_noise_state_and_innovation_checks(pkg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg, dt=1.0 / 2000)
     for bad in ([0.0, 0.0], [0.0, float("nan"), 0.0]):
         with pytest.raises(ValueError):
             eng.set_noise_state(bad)
@@ -165,7 +152,7 @@ def test_engine_noise_state_and_innovation_checks(pkg):
 
 
 def test_tau_maps_to_rho_on_the_host(pkg):
-    sig, rho, streams, seed = _bare_engine(pkg).check_noise_args(0.7, tau=0.25, seed=5, streams=np.array([7, 8, 9]))
+    sig, rho, streams, seed = bare_engine(pkg, dt=1.0 / 2000).check_noise_args(0.7, tau=0.25, seed=5, streams=np.array([7, 8, 9]))
     assert np.array_equal(sig, [0.7] * 3) and np.array_equal(rho, [np.exp(-(1.0 / 2000) / 0.25)] * 3)
     assert streams.dtype == np.uint64 and list(streams) == [7, 8, 9] and seed == 5
 
@@ -199,6 +186,6 @@ def test_ensemble_equilibrate_refuses_noise(pkg):
     ens = import_module(pkg.__name__ + ".ensemble")
     run = ens.EnsembleRun.__new__(ens.EnsembleRun)
     run.st, run.has_schedules, run.has_noise, run.step_index = _st(pkg), False, True, 0
-    run.engine = _bare_engine(pkg)
+    run.engine = bare_engine(pkg, dt=1.0 / 2000)
     with pytest.raises(ValueError, match="noise="):
         run.equilibrate(5)

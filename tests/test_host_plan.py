@@ -11,6 +11,8 @@ from collections import Counter
 
 import pytest
 
+from support import compile_host_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATE, DIAG, SAVE, LOOP, LOOP_SAVE = range(5)
 REG_THREADS = 512            # kFusedRegThreads (csrc/ebm_types.h)
@@ -18,9 +20,7 @@ KIB64 = 64 * 1024
 
 
 def compile_program(out, extra_flags=()):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", *extra_flags, "-o", out,
-                    os.path.join(ROOT, "tests", "host_plan_main.cpp")], check=True)
-    return out
+    return compile_host_program("host_plan_main.cpp", out, ("-Wall", "-Werror") + tuple(extra_flags))
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_host_until import _bare_engine
+from support import bare_engine
 
 
 # ---- the symbol ----------------------------------------------------------------------------------------------------------
@@ -108,13 +108,13 @@ def test_selection_refusals(pkg, weights, msg):
     ([0, 1, 3], r"parents\[2\] = 3 is outside \[0, 3\)"),
 ])
 def test_engine_checks_before_the_device(pkg, parents, msg):
-    eng = _bare_engine(pkg)                               # its library refuses every call: a device call fails the test
+    eng = bare_engine(pkg)                               # its library refuses every call: a device call fails the test
     with pytest.raises(ValueError, match=msg):
         eng.resample_columns(parents)
 
 
 def test_engine_check_returns_what_the_abi_takes(pkg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     for given in ([2, 0, 0], np.array([2, 0, 0], dtype=np.int64), np.array([2, 0, 0], dtype=np.uint8), np.array([9, 2, 9, 0, 9, 0])[1::2]):
         p = eng.check_resample_args(given)
         assert p.dtype == np.int32 and p.flags.c_contiguous and p.tolist() == [2, 0, 0]
@@ -123,7 +123,7 @@ def test_engine_check_returns_what_the_abi_takes(pkg):
 def test_ensemble_resample_is_the_engine_call_and_keeps_the_step_index(pkg):
     ensemble = import_module(pkg.__name__ + ".ensemble")
     run = ensemble.EnsembleRun.__new__(ensemble.EnsembleRun)
-    run.engine, run.step_index, run.ncol = _bare_engine(pkg), 40, 3
+    run.engine, run.step_index, run.ncol = bare_engine(pkg), 40, 3
     with pytest.raises(ValueError, match="outside"):
         run.resample([0, 1, 7])
     seen = []

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bare_engine
 
 
 def test_symbol_is_declared_exported_and_bound(pkg):
@@ -38,20 +39,6 @@ def test_null_handle_is_refused_without_a_gpu(pkg):
     assert b"null argument" in lib.ebm_last_error()
 
 
-class _NoDevice:
-    """Stands in for the library: any call is a device call the checks should have prevented."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"{name} reached before the argument checks refused the call")
-
-
-def _bare_engine(pkg, model="MIZ", ncol=3):
-    engine = import_module(pkg.__name__ + ".engine")
-    eng = engine.Engine.__new__(engine.Engine)
-    eng.model, eng.ncol, eng.nlat, eng.lib, eng._h = model, ncol, 18, _NoDevice(), None
-    return eng
-
-
 BAD = [
     (dict(every=0), "every = 0"),
     (dict(every=-3), "every = -3"),
@@ -67,7 +54,7 @@ BAD = [
 
 @pytest.mark.parametrize("kw, msg", BAD)
 def test_engine_checks_before_the_device(pkg, kw, msg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     args = dict(first_step=0, nsteps=12, every=4, names=("T", "phi"))
     args.update(kw)
     with pytest.raises(ValueError, match=msg):
@@ -75,12 +62,12 @@ def test_engine_checks_before_the_device(pkg, kw, msg):
 
 
 def test_engine_check_accepts_every_solution_variable(pkg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     miz = ("Ei", "Ew", "h", "D", "phi", "Tw", "Ti", "n", "E", "T")
     names, ids, f = eng.check_series_args(5, 12, 4, miz, np.zeros(12))
     assert names == miz and ids == [0, 1, 2, 3, 4, 6, 7, 8, 9, 10] and f.shape == (12,)
     assert eng.check_series_args(0, 12, 4, "T")[0] == ("T",)
-    classic = _bare_engine(pkg, "Classic")
+    classic = bare_engine(pkg, "Classic")
     assert classic.check_series_args(0, 12, 12, ("E", "Tg", "T", "h"))[1] == [9, 11, 10, 2]
     with pytest.raises(ValueError, match="unknown field 'phi'"):
         classic.check_series_args(0, 12, 4, ("phi",))
@@ -92,7 +79,7 @@ def _bare_run(pkg, step_index=0):
     ensemble = import_module(pkg.__name__ + ".ensemble")
     run = ensemble.EnsembleRun.__new__(ensemble.EnsembleRun)
     run.st = pkg.SpaceTime("sin", 18, 100, 1)
-    run.engine = _bare_engine(pkg)
+    run.engine = bare_engine(pkg)
     run.has_schedules = False
     run.step_index = step_index
     run.ncol = 3

@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import assert_same_bits as same_bits, compile_host_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NLATS = (2, 3, 5, 64, 65, 180, 257)
 GRIDS = ("identity", "sin")
@@ -18,9 +20,7 @@ GRID = {"identity": 0, "sin": 1}
 
 def compile_program(out, extra_flags=()):
     """The flags are the library's own arithmetic: no contraction of a*b+c (csrc/Makefile)."""
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", *extra_flags, "-o", out,
-                    os.path.join(ROOT, "tests", "host_tables_main.cpp")], check=True)
-    return out
+    return compile_host_program("host_tables_main.cpp", out, ("-ffp-contract=off",) + tuple(extra_flags))
 
 
 @pytest.fixture(scope="module")
@@ -53,12 +53,6 @@ def tables(prog, oracle, tmp, model, kind, nlat, par=None):
     slab = out[5:].reshape(len(G), gstride)
     assert not slab[:, nlat:].any(), "padding written"
     return st, par, out[:5], {n: slab[i, :nlat] for n, i in G.items()}
-
-
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
-    assert got.shape == want.shape, what
-    assert np.array_equal(got.view(np.int64), want.view(np.int64)), what      # signs of zero included
 
 
 @pytest.mark.parametrize("nlat", NLATS)

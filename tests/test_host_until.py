@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bare_engine
 
 
 def first_crossing(series, level, direction):
@@ -101,20 +102,6 @@ def test_null_arguments_are_refused_without_a_gpu(pkg):
 
 # ---- Engine.check_until_args ---------------------------------------------------------------------------------------------
 
-class _NoDevice:
-    """Stands in for the library: any call is a device call the checks should have prevented."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"{name} reached before the argument checks refused the call")
-
-
-def _bare_engine(pkg, model="MIZ", ncol=3):
-    engine = import_module(pkg.__name__ + ".engine")
-    eng = engine.Engine.__new__(engine.Engine)
-    eng.model, eng.ncol, eng.nlat, eng.lib, eng._h = model, ncol, 18, _NoDevice(), None
-    return eng
-
-
 GOOD = dict(first_step=0, max_samples=4, every=5, name="T", level=[1.0, 2.0, 3.0], direction=[1, -1, 1])
 BAD = [
     (dict(every=0), "every = 0"),
@@ -137,7 +124,7 @@ BAD = [
 
 @pytest.mark.parametrize("kw, msg", BAD)
 def test_engine_checks_before_the_device(pkg, kw, msg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     args = dict(GOOD)
     args.update(kw)
     with pytest.raises(ValueError, match=msg):
@@ -145,14 +132,14 @@ def test_engine_checks_before_the_device(pkg, kw, msg):
 
 
 def test_engine_check_returns_what_the_abi_takes(pkg):
-    eng = _bare_engine(pkg)
+    eng = bare_engine(pkg)
     fid, lev, d, f = eng.check_until_args(7, 4, 5, "phi", [np.inf, -np.inf, 0.25], [5, -2, 1], np.zeros(20), 1)
     assert fid == 4 and f.shape == (20,)
     assert lev.dtype == np.float64 and lev.tolist() == [np.inf, -np.inf, 0.25]
     assert d.dtype == np.int32 and d.flags.c_contiguous and d.tolist() == [1, -1, 1]
     for name, want in (("Ei", 0), ("Ti", 7), ("T", 10), ("E", 9)):
         assert eng.check_until_args(0, 1, 1, name, np.zeros(3), np.ones(3, dtype=np.int64))[0] == want
-    classic = _bare_engine(pkg, "Classic")
+    classic = bare_engine(pkg, "Classic")
     assert classic.check_until_args(0, 1, 1, "Tg", np.zeros(3), np.ones(3, dtype=np.int64))[0] == 11
     with pytest.raises(ValueError, match="unknown field 'phi'"):
         classic.check_until_args(0, 1, 1, "phi", np.zeros(3), np.ones(3, dtype=np.int64))
@@ -181,7 +168,7 @@ def _bare_run(pkg, step_index=0):
     ensemble = import_module(pkg.__name__ + ".ensemble")
     run = ensemble.EnsembleRun.__new__(ensemble.EnsembleRun)
     run.st = pkg.SpaceTime("sin", 18, 100, 1)
-    run.engine = _bare_engine(pkg)
+    run.engine = bare_engine(pkg)
     run.has_schedules = False
     run.step_index = step_index
     run.ncol = 3

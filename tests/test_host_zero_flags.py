@@ -11,15 +11,15 @@ import subprocess
 
 import pytest
 
+from support import compile_host_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEPTH = 6
 N_EVENTS = 13
 
 
 def compile_program(out, extra_flags=()):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", *extra_flags, "-o", out,
-                    os.path.join(ROOT, "tests", "host_zero_flags_main.cpp")], check=True)
-    return out
+    return compile_host_program("host_zero_flags_main.cpp", out, ("-Wall", "-Werror") + tuple(extra_flags))
 
 
 @pytest.fixture(scope="module")
