@@ -51,9 +51,12 @@ typedef double ebm_dvec2 __attribute__((ext_vector_type(2)));
         if ((threadIdx.x & 63) == 0 && a.stamps)                                       \
             a.stamps[(size_t)a.ncol * 16 + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (n)] = t_; \
     } while (0)
+// the two pairs are waited for here, so that the stamp that follows is taken once they have arrived
+#define EBM_ARRIVED2(u, v) asm volatile("" ::"v"((u).x), "v"((u).y), "v"((v).x), "v"((v).y))
 #else
 #define EBM_STAMP(n) do {} while (0)
 #define EBM_STAMPW(n) do {} while (0)
+#define EBM_ARRIVED2(u, v) do {} while (0)
 #endif
 
 // The parameter block is never written by a kernel: read it through the constant address space so

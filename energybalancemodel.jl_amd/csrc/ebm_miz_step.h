@@ -48,6 +48,11 @@ namespace ebm {
 // Whoever else writes a prognostic field, or moves it to another layout, leaves the flags untrusted, and the runtime clears
 // them before the next launch of this variant (FieldBook::zero_flags_trusted).  The L2 prefetch for the
 // successor column skips, lane by lane, the sectors of lines that the successor's flags say it will not load.
+//
+// Order of loads and stores in phase D (four cells per thread): after the Tbar halo a lane requests Ei and D of BOTH its
+// pairs (flagged pairs excepted), then updates pair 0, stores it, updates pair 1 (the L2 prefetch for the successor leaves
+// within it), stores it.  No load of the state follows a store.  IMEX, OUT_SAVE and the two-cell kernels
+// request a pair's Ei and D at the top of that pair (see EARLY below).
 template <int C, int GRID, int OUT, int TT, bool IMEX, bool PHI_DERIVED = false, bool ZERO_LINES = false>
 __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     static_assert(C == 2 || C == 4, "cells per thread");
@@ -248,18 +253,41 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // after the step's last barrier (every wave has used the old N_c), and before the cell updates: their register budget
     // has no room for a value that only waits for the kernel's last line
     if (a.noise) nz.store(a, col);
-#pragma unroll
-    for (int j = 0; j < C / 2; ++j) {
-        MizCellOut o[2];
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned ks = state_index<C, TT>(k0, j);    // the pair's place in every field this kernel stores
-        double2 Ei2, Dk2;
+    // Ei and D of pair j, where pair j of the lane whose first cell is kq lies (ZERO_LINES: a flagged pair is not loaded)
+    auto load_pair_inputs = [&](int j, unsigned kq, double2 &Ei2, double2 &Dk2) {
+        const unsigned ks = state_index<C, TT>(kq, j);
         if constexpr (ZERO_LINES) {
             Ei2 = load_pair_unless_zero(st + S_Ei * a.fstride + ks, zold & zero_flag_bit(j, S_Ei));
             Dk2 = load_pair_unless_zero(st + S_D * a.fstride + ks, zold & zero_flag_bit(j, S_D));
         } else {
             Ei2 = *reinterpret_cast<const double2 *>(st + S_Ei * a.fstride + ks);
             Dk2 = *reinterpret_cast<const double2 *>(st + S_D * a.fstride + ks);
+        }
+    };
+    // EARLY: both pairs' Ei and D are requested here, before the first pair's arithmetic and so before any store of this wave.
+    // gfx950 counts loads and stores in one vmcnt, retired in issue order: requested after the first pair's stores, as the
+    // other kernels do, the second pair's inputs come back only once those stores are acknowledged.  Four more VGPRs per
+    // field wait through the first pair's cell updates; the state-only and diagnostic four-cell kernels of the reference's
+    // step have room for them (no scratch, <= 128 VGPRs).  OUT_SAVE keeps the pair-by-pair order (its sums need the
+    // registers: with both pairs requested here it spills at 960 threads), like IMEX (whose second solve stands
+    // between) and the two-cell kernels (one pair).  The identity grid's tables stay pair by pair.
+    constexpr bool EARLY = C == 4 && !IMEX && OUT != OUT_SAVE;
+    double2 Ei2a[C / 2], Dk2a[C / 2];
+    if constexpr (EARLY) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < C / 2; ++j) load_pair_inputs(j, k0, Ei2a[j], Dk2a[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < C / 2; ++j) {
+        MizCellOut o[2];
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned ks = state_index<C, TT>(k0, j);    // the pair's place in every field this kernel stores
+        if constexpr (!EARLY) load_pair_inputs(j, k0, Ei2a[j], Dk2a[j]);
+        const double2 Ei2 = Ei2a[j], Dk2 = Dk2a[j];
+        if (C == 4 && j == 1) {
+            EBM_ARRIVED2(Ei2, Dk2);
+            EBM_STAMPW(7);                                // per wave: the second pair's Ei and D have arrived
         }
         if constexpr (GRID == 0 && !IMEX) {
             const double2 lo = *reinterpret_cast<const double2 *>(geom + G_LO * a.gstride + (k0 + 2 * j));
