@@ -22,22 +22,6 @@ FIELD = {"Ei": 0, "Ew": 1, "h": 2, "D": 3, "phi": 4, "T0": 5, "Tw": 6, "Ti": 7, 
          "E": 9, "T": 10, "Tg": 11}
 PARAM_ORDER = ("D", "A", "B", "cw", "S0", "S1", "S2", "a0", "a2", "ai", "Fb", "k", "Lf", "F",
                "cg", "tau", "Tm", "m1", "m2", "alpha", "rl", "Dmin", "Dmax", "hmin", "kappa")
-EXPORTS = (
-    "ebm_create", "ebm_create_ex", "ebm_options_default", "ebm_field_step", "ebm_get_field_as_of", "ebm_destroy", "ebm_last_error", "ebm_version", "ebm_set_field",
-    "ebm_get_field", "ebm_hemispheric_mean", "ebm_hemispheric_mean_device", "ebm_get_field_device",
-    "ebm_field_device_ptr", "ebm_diffusion", "ebm_zonal_diffusion", "ebm_set_column_forcing", "ebm_set_column_schedule",
-    "ebm_set_column_params", "ebm_set_column_noise", "ebm_get_noise_state", "ebm_set_noise_state", "ebm_noise_innovations",
-    "ebm_set_step_clock", "ebm_set_time_table",
-    "ebm_step", "ebm_run", "ebm_run_fused", "ebm_run_series", "ebm_integrate", "ebm_integrate_hemispheric",
-    "ebm_equilibrate", "ebm_run_until", "ebm_resample_columns", "ebm_column_record", "ebm_export_columns",
-    "ebm_import_columns", "ebm_ensemble_sums", "ebm_ensemble_sums_device", "ebm_ensemble_range",
-    "ebm_ensemble_range_device", "ebm_ensemble_histogram", "ebm_ensemble_histogram_device", "ebm_column_misfits",
-    "ebm_column_misfits_device", "ebm_sync", "ebm_get_counters",
-    "ebm_reset_counters", "ebm_state_conversions", "ebm_zero_line_flags", "ebm_timer_start", "ebm_timer_stop", "ebm_launch_info",
-    "ebm_selftest_divide", "ebm_selftest_permute",
-)
-
-_dp = C.POINTER(C.c_double)
 _lib = None
 
 STATUS = {0: "EBM_OK", -1: "EBM_ERR_ARG", -2: "EBM_ERR_HIP", -3: "EBM_ERR_UNSUPPORTED", -4: "EBM_ERR_NO_DEVICE",
@@ -49,6 +33,73 @@ class Options(C.Structure):
     _fields_ = [("struct_bytes", C.c_int), ("cells_per_thread", C.c_int), ("use_graph", C.c_int),
                 ("prefetch_cols", C.c_int), ("launch_chains", C.c_int), ("integrate_steps_per_launch", C.c_int),
                 ("fused_state_in_lds", C.c_int), ("elide_zero_lines", C.c_int)]
+
+
+# The C ABI, one row per prototype of include/ebm_hip.h, in its parameter order (tests/test_host.py holds every row against
+# the header).  _h: an ebm_handle_t; _dev: a device address (the header's double *dev_...); every function returns int
+# (an ebm_status) but those of RESTYPES.
+_i, _ll, _u, _ull, _d, _h, _dev = C.c_int, C.c_longlong, C.c_uint, C.c_ulonglong, C.c_double, C.c_void_p, C.c_void_p
+_ip, _llp, _up, _dp = C.POINTER(_i), C.POINTER(_ll), C.POINTER(_u), C.POINTER(_d)
+_create = [C.POINTER(_h), _i, _i, _i, _i, _dp, _dp, _d, _i]
+SIGNATURES = {
+    "ebm_create": _create,
+    "ebm_create_ex": _create + [C.POINTER(Options)],
+    "ebm_options_default": [C.POINTER(Options)],
+    "ebm_field_step": [_h, _i, _llp, _llp, _ip],
+    "ebm_get_field_as_of": [_h, _i, _ll, _dp],
+    "ebm_destroy": [_h],
+    "ebm_last_error": [],
+    "ebm_version": [],
+    "ebm_set_field": [_h, _i, _dp],
+    "ebm_get_field": [_h, _i, _dp],
+    "ebm_hemispheric_mean": [_h, _i, _dp],
+    "ebm_hemispheric_mean_device": [_h, _i, _dev],
+    "ebm_get_field_device": [_h, _i, _dev],
+    "ebm_field_device_ptr": [_h, _i, C.POINTER(_dev), _llp],
+    "ebm_diffusion": [_h, _dp, _dp, _dp],
+    "ebm_zonal_diffusion": [_h, _i, _dp, _dp, _dp],
+    "ebm_set_column_forcing": [_h, _dp],
+    "ebm_set_column_schedule": [_h, _dp],
+    "ebm_set_column_params": [_h, _dp],
+    "ebm_set_column_noise": [_h, _dp, _dp, C.POINTER(_ull), _ull],
+    "ebm_get_noise_state": [_h, _dp],
+    "ebm_set_noise_state": [_h, _dp],
+    "ebm_noise_innovations": [_h, _ll, _i, _dp],
+    "ebm_set_step_clock": [_h, _ll],
+    "ebm_set_time_table": [_h, _i, _dp],
+    "ebm_step": [_h, _d, _d, _d, _i],
+    "ebm_run": [_h, _ll, _i, _dp, _i],
+    "ebm_run_fused": [_h, _ll, _i, _dp, _i, _i],
+    "ebm_run_series": [_h, _ll, _i, _dp, _i, _i, _i, _ip, _dp],
+    "ebm_integrate": [_h, _i, _i, _dp, _i, _i, _i, _i, _ip, _dp, _dp, _dp, _dp],
+    "ebm_integrate_hemispheric": [_h, _i, _i, _dp, _i, _i, _i, _ip, _dp, _dp, _dp],
+    "ebm_equilibrate": [_h, _i, _i, _i, _dp, _i, _ip, _dp, _ip, _ip, _dp],
+    "ebm_run_until": [_h, _ll, _i, _i, _dp, _i, _i, _dp, _ip, _ip, _ip, _dp],
+    "ebm_resample_columns": [_h, _ip],
+    "ebm_column_record": [_h, _llp, _up],
+    "ebm_export_columns": [_h, _i, _ip, _dev, _up],
+    "ebm_import_columns": [_h, _i, _ip, _ip, _dev, _u],
+    "ebm_ensemble_sums": [_h, _i, _ip, _dp, _dp, _dp],
+    "ebm_ensemble_sums_device": [_h, _i, _ip, _dp, _dp, _dev],
+    "ebm_ensemble_range": [_h, _i, _ip, _dp, _dp],
+    "ebm_ensemble_range_device": [_h, _i, _ip, _dp, _dev],
+    "ebm_ensemble_histogram": [_h, _i, _ip, _dp, _i, _dp, _dp, _dp],
+    "ebm_ensemble_histogram_device": [_h, _i, _ip, _dp, _i, _dp, _dp, _dev],
+    "ebm_column_misfits": [_h, _i, _ip, _i, _dp, _dp, _dp],
+    "ebm_column_misfits_device": [_h, _i, _ip, _i, _dp, _dp, _dev],
+    "ebm_sync": [_h],
+    "ebm_get_counters": [_h, _llp],
+    "ebm_reset_counters": [_h],
+    "ebm_state_conversions": [_h, _llp],
+    "ebm_zero_line_flags": [_h, _up, _ip],
+    "ebm_timer_start": [_h],
+    "ebm_timer_stop": [_h, C.POINTER(C.c_float)],
+    "ebm_launch_info": [_h, _ip],
+    "ebm_selftest_divide": [_i, _i, _dp, _dp, _dp],
+    "ebm_selftest_permute": [_i, _i, _i, _dp, _dp, _dp],
+}
+RESTYPES = {"ebm_last_error": C.c_char_p, "ebm_version": C.c_char_p}
+EXPORTS = tuple(SIGNATURES)
 
 
 class EBMError(RuntimeError):
@@ -79,68 +130,9 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    lib.ebm_last_error.restype = C.c_char_p
-    lib.ebm_version.restype = C.c_char_p
-    lib.ebm_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
-                               C.c_double, C.c_int]
-    lib.ebm_create_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
-                                  C.c_double, C.c_int, C.POINTER(Options)]
-    lib.ebm_options_default.argtypes = [C.POINTER(Options)]
-    lib.ebm_field_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
-    lib.ebm_get_field_as_of.argtypes = [C.c_void_p, C.c_int, C.c_longlong, _dp]
-    lib.ebm_destroy.argtypes = [C.c_void_p]
-    lib.ebm_set_field.argtypes = [C.c_void_p, C.c_int, _dp]
-    lib.ebm_get_field.argtypes = [C.c_void_p, C.c_int, _dp]
-    lib.ebm_hemispheric_mean.argtypes = [C.c_void_p, C.c_int, _dp]
-    lib.ebm_hemispheric_mean_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.ebm_get_field_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.ebm_diffusion.argtypes = [C.c_void_p, _dp, _dp, _dp]
-    lib.ebm_zonal_diffusion.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
-    lib.ebm_field_device_ptr.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
-                                         C.POINTER(C.c_longlong)]
-    lib.ebm_set_column_forcing.argtypes = [C.c_void_p, _dp]
-    lib.ebm_set_column_schedule.argtypes = [C.c_void_p, _dp]
-    lib.ebm_set_column_params.argtypes = [C.c_void_p, _dp]
-    lib.ebm_set_column_noise.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_ulonglong), C.c_ulonglong]
-    lib.ebm_get_noise_state.argtypes = [C.c_void_p, _dp]
-    lib.ebm_set_noise_state.argtypes = [C.c_void_p, _dp]
-    lib.ebm_noise_innovations.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp]
-    lib.ebm_set_step_clock.argtypes = [C.c_void_p, C.c_longlong]
-    lib.ebm_set_time_table.argtypes = [C.c_void_p, C.c_int, _dp]
-    lib.ebm_step.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
-    lib.ebm_run.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int]
-    lib.ebm_run_fused.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int, C.c_int]
-    lib.ebm_run_series.argtypes = [C.c_void_p, C.c_longlong, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp]
-    lib.ebm_integrate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
-                                  C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp]
-    lib.ebm_integrate_hemispheric.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_int), _dp, _dp, _dp]
-    lib.ebm_equilibrate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_int), _dp,
-                                    C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
-    lib.ebm_run_until.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int),
-                                  C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]
-    lib.ebm_resample_columns.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    lib.ebm_column_record.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_uint)]
-    lib.ebm_export_columns.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_uint)]
-    lib.ebm_import_columns.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_uint]
-    lib.ebm_ensemble_sums.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp]
-    lib.ebm_ensemble_sums_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, _dp, C.c_void_p]
-    lib.ebm_ensemble_range.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, _dp]
-    lib.ebm_ensemble_range_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_void_p]
-    lib.ebm_ensemble_histogram.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_int, _dp, _dp, _dp]
-    lib.ebm_ensemble_histogram_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_int, _dp, _dp, C.c_void_p]
-    lib.ebm_column_misfits.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, _dp]
-    lib.ebm_column_misfits_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, C.c_void_p]
-    lib.ebm_sync.argtypes = [C.c_void_p]
-    lib.ebm_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
-    lib.ebm_reset_counters.argtypes = [C.c_void_p]
-    lib.ebm_state_conversions.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
-    lib.ebm_zero_line_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
-    lib.ebm_timer_start.argtypes = [C.c_void_p]
-    lib.ebm_timer_stop.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    lib.ebm_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    lib.ebm_selftest_divide.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
-    lib.ebm_selftest_permute.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
+    for name, argtypes in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)
     _lib = lib
     return lib
 
@@ -155,6 +147,16 @@ def check(rc: int, what: str):
 
 def dptr(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def iptr(a):
+    """``dptr`` for an int32 array."""
+    return None if a is None else a.ctypes.data_as(_ip)
+
+
+def field_ids(ids):
+    """The ``const int *fields`` argument: the field ids as a C int array."""
+    return (C.c_int * len(ids))(*ids)
 
 
 def as_f64(a, shape=None):

@@ -13,12 +13,23 @@ import os
 import numpy as np
 
 from . import _lib, noise
-from ._lib import FIELD, GRID, MODEL, PARAM_ORDER, as_f64, check, dptr
+from ._lib import FIELD, GRID, MODEL, PARAM_ORDER, as_f64, check, dptr, field_ids, iptr
 
 MIZ_PROGNOSTIC = ("Ei", "Ew", "h", "D", "phi")
 MIZ_DIAGNOSTIC = ("Tw", "Ti", "n", "E", "T")
 CLASSIC_PROGNOSTIC = ("E", "Tg")
 CLASSIC_DIAGNOSTIC = ("T", "h")
+_HOST = object()        # the destination of a reduction whose result comes back as a new host array (Engine._reduced)
+
+
+def as_names(names) -> tuple:
+    """A caller's field list as a tuple; one field may be given as its name."""
+    return (names,) if isinstance(names, str) else tuple(names)
+
+
+def _refuse_repeats(names):
+    if len(set(names)) != len(names):
+        raise ValueError(f"names: a field is listed twice in {names}")
 
 
 def schedule_words(forcing):
@@ -67,6 +78,10 @@ def _env_int(name):
     return None if v in (None, "") else int(v)
 
 
+def _flag(v) -> int:
+    return int(bool(v))
+
+
 class Engine:
     """``cells_per_thread`` (2 or 4; default 4), ``use_graph`` (True / False; default: by size), ``prefetch_cols`` and
     ``launch_chains`` (1 or 2; default 1), ``integrate_steps_per_launch`` (default 64; 1 = ``integrate`` launches every step),
@@ -96,20 +111,12 @@ class Engine:
             use_graph = bool(_env_int("EBM_GRAPH"))
         if prefetch_cols is None:
             prefetch_cols = _env_int("EBM_PREFETCH_COLS")
-        if cells_per_thread is not None:
-            opt.cells_per_thread = int(cells_per_thread)
-        if use_graph is not None:
-            opt.use_graph = int(bool(use_graph))
-        if prefetch_cols is not None:
-            opt.prefetch_cols = max(0, int(prefetch_cols))
-        if launch_chains is not None:
-            opt.launch_chains = int(launch_chains)
-        if integrate_steps_per_launch is not None:
-            opt.integrate_steps_per_launch = int(integrate_steps_per_launch)
-        if fused_state_in_lds is not None:
-            opt.fused_state_in_lds = int(bool(fused_state_in_lds))
-        if elide_zero_lines is not None:
-            opt.elide_zero_lines = int(bool(elide_zero_lines))
+        for name, value, conv in (("cells_per_thread", cells_per_thread, int), ("use_graph", use_graph, _flag),
+                                  ("prefetch_cols", prefetch_cols, lambda v: max(0, int(v))), ("launch_chains", launch_chains, int),
+                                  ("integrate_steps_per_launch", integrate_steps_per_launch, int),
+                                  ("fused_state_in_lds", fused_state_in_lds, _flag), ("elide_zero_lines", elide_zero_lines, _flag)):
+            if value is not None:                    # None: the library's default stays
+                setattr(opt, name, conv(value))
         h = C.c_void_p()
         gk = GRID["identity"] if grid_kind == "identity" else GRID["nonuniform"]
         check(self.lib.ebm_create_ex(C.byref(h), MODEL[model], gk, self.nlat, self.ncol,
@@ -178,9 +185,7 @@ class Engine:
 
     def hemispheric_mean(self, name: str) -> np.ndarray:
         """Per-column hemispheric mean of a field, reduced on the device (ebm_hemispheric_mean)."""
-        out = np.empty(self.ncol)
-        check(self.lib.ebm_hemispheric_mean(self._h, FIELD[name], dptr(out)), "ebm_hemispheric_mean")
-        return out
+        return self._reduced("ebm_hemispheric_mean", (self.ncol,), _HOST, FIELD[name])
 
     def hemispheric_mean_device(self, name: str, dev_ptr: int):
         """Same reduction, result left on the device at ``dev_ptr`` (``ncol`` doubles, e.g. the
@@ -188,39 +193,54 @@ class Engine:
         check(self.lib.ebm_hemispheric_mean_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),
               "ebm_hemispheric_mean_device")
 
-    def _check_ensemble_args(self, names, weights=None, center=None, order=False, repeats=False, nbins=None, lo=None, hi=None):
-        """The host-side checks of ``ensemble_sums`` and, with ``order``, of ``ensemble_range`` and ``ensemble_histogram`` (no
-        device call): returns (names, field ids, weights [ncol] or None, extra) with contiguous float64 arrays — extra is
-        center [nvars, nlat] or None for the sums, None for the range and (lo, hi), each [len(names), nlat], for a histogram
-        (``nbins`` given), which may list a field several times (``repeats``).  The sums refuse a field listed twice before
-        they look at the weights, the range after."""
-        if isinstance(names, str):
-            names = (names,)
-        names = tuple(names)
+    def _fields(self, names, arg="names", most=None, what="fields", t0_note=True, repeats=True):
+        """(names, field ids) of a caller's field list, or ValueError: more than ``most`` entries or none (None: no bound), a
+        name that is not a solution variable of this model, a field listed twice (unless ``repeats``)."""
+        names = as_names(names)
         allowed = self.prognostic + self.diagnostic
-        if not 1 <= len(names) <= 12:
-            raise ValueError(f"names: expected between 1 and 12 {'entries of fields' if order else 'fields'} of the {self.model} model")
+        if most is not None and not 1 <= len(names) <= most:
+            raise ValueError(f"{arg}: expected between 1 and {most} {what} of the {self.model} model")
         for n in names:
-            if n not in allowed:
-                raise ValueError(f"names: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
-                                 "the warm start T0 is not a solution variable)")
-        twice = not repeats and len(set(names)) != len(names)
-        if twice and not order:
-            raise ValueError(f"names: a field is listed twice in {names}")
+            if not isinstance(n, str) or n not in allowed:
+                raise ValueError(f"{arg}: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}"
+                                 + ("; the warm start T0 is not a solution variable)" if t0_note else ")"))
+        if not repeats:
+            _refuse_repeats(names)
+        return names, [FIELD[n] for n in names]
+
+    def _check_weights(self, weights):
+        """The member weights of the ensemble reductions as a contiguous float64 array [ncol], or None."""
         w = None if weights is None else as_f64(weights, (self.ncol,))
         if w is not None and not np.isfinite(w).all():
             c = int(np.flatnonzero(~np.isfinite(w))[0])
             raise ValueError(f"weights[{c}] = {w[c]} is not finite (negative and zero weights are legal)")
-        if twice:
-            raise ValueError(f"names: a field is listed twice in {names}")
-        ids = [FIELD[n] for n in names]
-        if not order:
-            ctr = None if center is None else as_f64(center, (len(names), self.nlat))
-            if ctr is not None and not np.isfinite(ctr).all():
-                raise ValueError("center: expected finite values")
-            return names, ids, w, ctr
-        if nbins is None:
-            return names, ids, w, None
+        return w
+
+    def _check_sums_args(self, names, weights=None, center=None):
+        """The host-side checks of ``ensemble_sums`` (no device call): returns (names, field ids, weights [ncol] or None,
+        center [nvars, nlat] or None) with contiguous float64 arrays.  A field listed twice is refused before the weights
+        are looked at."""
+        names, ids = self._fields(names, most=12, repeats=False)
+        w = self._check_weights(weights)
+        ctr = None if center is None else as_f64(center, (len(names), self.nlat))
+        if ctr is not None and not np.isfinite(ctr).all():
+            raise ValueError("center: expected finite values")
+        return names, ids, w, ctr
+
+    def _check_range_args(self, names, weights=None):
+        """The host-side checks of ``ensemble_range`` (no device call): returns (names, field ids, weights [ncol] or None).  A
+        field listed twice is refused after the weights have been looked at."""
+        names, ids = self._fields(names, most=12, what="entries of fields")
+        w = self._check_weights(weights)
+        _refuse_repeats(names)
+        return names, ids, w
+
+    def _check_histogram_args(self, names, lo, hi, nbins, weights=None):
+        """The host-side checks of ``ensemble_histogram`` (no device call): returns (names, field ids, weights [ncol] or
+        None, (lo, hi)), the edges each [len(names), nlat], with contiguous float64 arrays.  A field may be listed several
+        times."""
+        names, ids = self._fields(names, most=12, what="entries of fields")
+        w = self._check_weights(weights)
         if isinstance(nbins, (bool, np.bool_)) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
             raise ValueError(f"nbins: expected an int between 1 and 64, got {nbins!r}")
         lo, hi = as_f64(lo, (len(names), self.nlat)), as_f64(hi, (len(names), self.nlat))
@@ -239,6 +259,17 @@ class Engine:
             raise ValueError(f"dev_ptr: expected a device address (int), got {dev_ptr!r}")
         return C.c_void_p(int(dev_ptr))
 
+    def _reduced(self, fn, shape, dev_ptr, *args):
+        """The call of a host / ``_device`` pair, after the pair's checks.  Each ``x_device`` method is the body of its pair and
+        ``x`` calls it with _HOST for an address: then ``fn(handle, *args, out)`` writes a new host array of ``shape``, which
+        is returned; else ``fn_device(handle, *args, dev_ptr)`` leaves the same packed result at that device address."""
+        if dev_ptr is _HOST:
+            out = np.full(shape, np.nan)
+            check(getattr(self.lib, fn)(self._h, *args, dptr(out)), fn)
+            return out
+        ptr = self._check_dev_ptr(dev_ptr)
+        check(getattr(self.lib, fn + "_device")(self._h, *args, ptr), fn + "_device")
+
     def ensemble_sums(self, names, weights=None, center=None) -> np.ndarray:
         """ebm_ensemble_sums (the definition is in include/ebm_hip.h): the weighted sums ACROSS the columns, per latitude,
         reduced on the device — ndarray [len(names), 3, nlat] of S0 = sum w_c, S1 = sum w_c d and S2 = sum (w_c d) d with
@@ -248,19 +279,13 @@ class Engine:
         columns in ascending column order, then the block partials in ascending order — so the bits do not depend on the run,
         the launch geometry or the layout the handle holds the rows in; no field is converted.  StaleFieldError for a stale
         diagnostic field, as ``hemispheric_mean``.  The step clock, the counters and ``field_step`` are unchanged."""
-        names, ids, w, ctr = self._check_ensemble_args(names, weights, center)
-        out = np.full((len(names), 3, self.nlat), np.nan)
-        check(self.lib.ebm_ensemble_sums(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), dptr(out)),
-              "ebm_ensemble_sums")
-        return out
+        return self.ensemble_sums_device(names, _HOST, weights, center)
 
     def ensemble_sums_device(self, names, dev_ptr: int, weights=None, center=None):
         """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()``
         of a torch tensor on this engine's device: the payload of an all-reduce between shards)."""
-        names, ids, w, ctr = self._check_ensemble_args(names, weights, center)
-        ptr = self._check_dev_ptr(dev_ptr)
-        check(self.lib.ebm_ensemble_sums_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(ctr), ptr),
-              "ebm_ensemble_sums_device")
+        names, ids, w, ctr = self._check_sums_args(names, weights, center)
+        return self._reduced("ebm_ensemble_sums", (len(names), 3, self.nlat), dev_ptr, len(ids), field_ids(ids), dptr(w), dptr(ctr))
 
     def ensemble_range(self, names, weights=None) -> np.ndarray:
         """ebm_ensemble_range (the definition is in include/ebm_hip.h): ndarray [len(names), 3, nlat] of the number n of
@@ -269,16 +294,12 @@ class Engine:
         or not).  +-Inf is data; no contributor gives n = 0, min = +Inf, max = -Inf; of several equal extremes (+0.0, -0.0)
         the first in ascending column order gives the bits.  Rows are read where they lie: no field is converted, the step
         clock, the counters and ``field_step`` are unchanged.  StaleFieldError for a stale diagnostic field."""
-        names, ids, w, _ = self._check_ensemble_args(names, weights, order=True)
-        out = np.full((len(names), 3, self.nlat), np.nan)
-        check(self.lib.ebm_ensemble_range(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), dptr(out)), "ebm_ensemble_range")
-        return out
+        return self.ensemble_range_device(names, _HOST, weights)
 
     def ensemble_range_device(self, names, dev_ptr: int, weights=None):
         """Same reduction, the packed [len(names), 3, nlat] result left on the device at ``dev_ptr``."""
-        names, ids, w, _ = self._check_ensemble_args(names, weights, order=True)
-        ptr = self._check_dev_ptr(dev_ptr)
-        check(self.lib.ebm_ensemble_range_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), ptr), "ebm_ensemble_range_device")
+        names, ids, w = self._check_range_args(names, weights)
+        return self._reduced("ebm_ensemble_range", (len(names), 3, self.nlat), dev_ptr, len(ids), field_ids(ids), dptr(w))
 
     def ensemble_histogram(self, names, lo, hi, nbins: int, weights=None) -> np.ndarray:
         """ebm_ensemble_histogram (the definition is in include/ebm_hip.h): ndarray [len(names), nbins + 2, nlat], per entry
@@ -288,24 +309,19 @@ class Engine:
         times, each entry with its own edges.  The weights of a slot are added in a fixed order — blocks of 256 columns in
         ascending column order, then the block partials in ascending order; with ``weights`` None every slot is an exact
         count, so the histograms of shards add to the unsharded one bit for bit."""
-        names, ids, w, (lo, hi) = self._check_ensemble_args(names, weights, order=True, repeats=True, nbins=nbins, lo=lo, hi=hi)
-        out = np.full((len(names), int(nbins) + 2, self.nlat), np.nan)
-        check(self.lib.ebm_ensemble_histogram(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo), dptr(hi),
-                                              dptr(out)), "ebm_ensemble_histogram")
-        return out
+        return self.ensemble_histogram_device(names, lo, hi, nbins, _HOST, weights)
 
     def ensemble_histogram_device(self, names, lo, hi, nbins: int, dev_ptr: int, weights=None):
         """Same reduction, the packed [len(names), nbins + 2, nlat] result left on the device at ``dev_ptr``."""
-        names, ids, w, (lo, hi) = self._check_ensemble_args(names, weights, order=True, repeats=True, nbins=nbins, lo=lo, hi=hi)
-        ptr = self._check_dev_ptr(dev_ptr)
-        check(self.lib.ebm_ensemble_histogram_device(self._h, len(ids), (C.c_int * len(ids))(*ids), dptr(w), int(nbins), dptr(lo),
-                                                     dptr(hi), ptr), "ebm_ensemble_histogram_device")
+        names, ids, w, (lo, hi) = self._check_histogram_args(names, lo, hi, nbins, weights)
+        return self._reduced("ebm_ensemble_histogram", (len(names), int(nbins) + 2, self.nlat), dev_ptr, len(ids), field_ids(ids),
+                             dptr(w), int(nbins), dptr(lo), dptr(hi))
 
     def _check_misfit_args(self, names, targets, rweights=None):
         """The host-side checks of ``column_misfits`` (no device call): returns (names, field ids, targets [ntargets, nvars,
         nlat], rweights [nvars, nlat] or None) with contiguous float64 arrays.  The field rules are those of
-        ``_check_ensemble_args``; a single target may be given as [nvars, nlat]."""
-        names, ids, _, _ = self._check_ensemble_args(names)
+        ``_check_sums_args``; a single target may be given as [nvars, nlat]."""
+        names, ids = self._fields(names, most=12, repeats=False)
         y = np.ascontiguousarray(targets, dtype=np.float64)
         if y.ndim == 2:
             y = y[None]
@@ -332,19 +348,14 @@ class Engine:
         128, then a fixed tree — so the bits do not depend on the run, the launch geometry or the layout the handle holds the
         rows in; no field is converted.  StaleFieldError for a stale diagnostic field, as ``hemispheric_mean``.  The step
         clock, the counters and ``field_step`` are unchanged."""
-        names, ids, y, r = self._check_misfit_args(names, targets, rweights)
-        out = np.full((y.shape[0], 2, self.ncol), np.nan)
-        check(self.lib.ebm_column_misfits(self._h, len(ids), (C.c_int * len(ids))(*ids), int(y.shape[0]), dptr(y), dptr(r), dptr(out)),
-              "ebm_column_misfits")
-        return out
+        return self.column_misfits_device(names, targets, _HOST, rweights)
 
     def column_misfits_device(self, names, targets, dev_ptr: int, rweights=None):
         """Same reduction, the packed [ntargets, 2, ncol] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()`` of
         a torch tensor on this engine's device: the payload of an all-gather between shards)."""
         names, ids, y, r = self._check_misfit_args(names, targets, rweights)
-        ptr = self._check_dev_ptr(dev_ptr)
-        check(self.lib.ebm_column_misfits_device(self._h, len(ids), (C.c_int * len(ids))(*ids), int(y.shape[0]), dptr(y), dptr(r), ptr),
-              "ebm_column_misfits_device")
+        return self._reduced("ebm_column_misfits", (y.shape[0], 2, self.ncol), dev_ptr, len(ids), field_ids(ids), int(y.shape[0]),
+                             dptr(y), dptr(r))
 
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""
@@ -383,23 +394,19 @@ class Engine:
     def set_column_schedules(self, forcings):
         """Per-column Forcing schedules evaluated on the device (ebm_set_column_schedule):
         ``forcings`` is a sequence of ``ncol`` Forcing objects, or None to clear."""
-        if forcings is None:
-            check(self.lib.ebm_set_column_schedule(self._h, None), "ebm_set_column_schedule")
-            return
-        if len(forcings) != self.ncol:
-            raise ValueError(f"expected {self.ncol} Forcing objects, got {len(forcings)}")
-        a = np.array([schedule_words(f) for f in forcings], dtype=np.float64)
+        a = None
+        if forcings is not None:
+            if len(forcings) != self.ncol:
+                raise ValueError(f"expected {self.ncol} Forcing objects, got {len(forcings)}")
+            a = np.array([schedule_words(f) for f in forcings], dtype=np.float64)
         check(self.lib.ebm_set_column_schedule(self._h, dptr(a)), "ebm_set_column_schedule")
 
     def set_column_params(self, matrix):
         """Per-column parameter rows (ebm_set_column_params): ``matrix`` [ncol, 25] in PARAM_ORDER (see
         ``param_matrix``), or None to return every column to the vector the engine was created with.  Column c then
         gives the bits of an engine created with row c; distinct rows share nothing but the launch."""
-        if matrix is None:
-            check(self.lib.ebm_set_column_params(self._h, None), "ebm_set_column_params")
-            return
-        a = as_f64(matrix)
-        if a.shape != (self.ncol, len(PARAM_ORDER)):
+        a = None if matrix is None else as_f64(matrix)
+        if a is not None and a.shape != (self.ncol, len(PARAM_ORDER)):
             raise ValueError(f"expected parameter rows of shape {(self.ncol, len(PARAM_ORDER))}, got {a.shape}")
         check(self.lib.ebm_set_column_params(self._h, dptr(a)), "ebm_set_column_params")
 
@@ -413,10 +420,7 @@ class Engine:
         autocorrelation in [0, 1) (default 0: white) or ``tau`` its e-folding time in years (rho = exp(-dt/tau)), ``seed``
         the handle's seed and ``streams`` the [ncol] stream ids (default 0 .. ncol-1; a shard passes its members' global
         indices).  Resets the noise state to 0.  ``sigma=None`` clears the noise."""
-        if sigma is None:
-            check(self.lib.ebm_set_column_noise(self._h, None, None, None, 0), "ebm_set_column_noise")
-            return
-        sig, r, st, seed = self.check_noise_args(sigma, rho, seed, streams, tau)
+        sig, r, st, seed = (None, None, None, 0) if sigma is None else self.check_noise_args(sigma, rho, seed, streams, tau)
         sp = None if st is None else st.ctypes.data_as(C.POINTER(C.c_ulonglong))
         check(self.lib.ebm_set_column_noise(self._h, dptr(sig), dptr(r), sp, C.c_ulonglong(seed)), "ebm_set_column_noise")
 
@@ -471,18 +475,7 @@ class Engine:
 
     def check_series_args(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
         """The host-side checks of ``run_series`` (no device call): returns (names, field ids, f_steps)."""
-        if isinstance(names, str):
-            names = (names,)
-        names = tuple(names)
-        allowed = self.prognostic + self.diagnostic
-        if not 1 <= len(names) <= len(allowed):
-            raise ValueError(f"names: expected between 1 and {len(allowed)} fields of the {self.model} model")
-        for n in names:
-            if n not in allowed:
-                raise ValueError(f"names: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
-                                 "the warm start T0 is not a solution variable)")
-        if len(set(names)) != len(names):
-            raise ValueError(f"names: a field is listed twice in {names}")
+        names, ids = self._fields(names, most=len(self.prognostic + self.diagnostic), repeats=False)
         if int(first_step) < 0 or int(nsteps) < 0:
             raise ValueError("run_series: first_step and nsteps must be >= 0")
         if int(every) < 1:
@@ -492,7 +485,7 @@ class Engine:
         if int(steps_per_launch) < 1:
             raise ValueError(f"steps_per_launch = {steps_per_launch}: need at least one step per launch")
         f = None if f_steps is None else as_f64(f_steps, (int(nsteps),))
-        return names, [FIELD[n] for n in names], f
+        return names, ids, f
 
     def run_series(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
         """ebm_run_series: ``nsteps`` steps from global step ``first_step`` exactly as ``run`` takes them (``diag_last`` iff
@@ -502,10 +495,9 @@ class Engine:
         ``hemispheric_mean`` returns there.  One download at the end; nothing is synchronised between samples."""
         names, ids, f = self.check_series_args(first_step, nsteps, every, names, f_steps, steps_per_launch)
         nv, ns = len(names), int(nsteps) // int(every)
-        fields = (C.c_int * nv)(*ids)
         out = np.full((nv, ns, self.ncol), np.nan)
         check(self.lib.ebm_run_series(self._h, int(first_step), int(nsteps), dptr(f), int(every), int(steps_per_launch), nv,
-                                      fields, dptr(out)), "ebm_run_series")
+                                      field_ids(ids), dptr(out)), "ebm_run_series")
         return out
 
     def integrate(self, nt, dur, f_steps, lastonly, winter_inx, summer_inx, names,
@@ -516,7 +508,7 @@ class Engine:
         same shape, whose arrays are filled again instead of allocating new ones (a caller that integrates year
         after year into the same buffers)."""
         nv = len(names)
-        fields = (C.c_int * nv)(*[FIELD[n] for n in names])
+        fields = field_ids([FIELD[n] for n in names])
         nraw = nt if lastonly else nt * dur
         f = None if f_steps is None else as_f64(f_steps, (nt * dur,))
         shape = (nv, dur, self.ncol, self.nlat)
@@ -546,7 +538,7 @@ class Engine:
         on the device — dict(winter, summer, avg), each [nvars, dur, ncol].  The data of the reference's
         hysteresis plot (src/plot.jl:173-225) for every column, without the fields crossing the bus."""
         nv = len(names)
-        fields = (C.c_int * nv)(*[FIELD[n] for n in names])
+        fields = field_ids([FIELD[n] for n in names])
         f = None if f_steps is None else as_f64(f_steps, (nt * dur,))
         out = {k: np.full((nv, dur, self.ncol), np.nan) for k in ("winter", "summer", "avg")}
         check(self.lib.ebm_integrate_hemispheric(self._h, nt, dur, dptr(f), int(winter_inx), int(summer_inx), nv, fields,
@@ -558,11 +550,7 @@ class Engine:
         """The host-side checks of ``equilibrate`` (no device call): returns (names, field ids, tolerances, f_year)."""
         if not hasattr(tol, "items") or len(tol) < 1:
             raise ValueError("tol: expected a dict of field name -> absolute tolerance, e.g. {'T': 1e-3}")
-        names = tuple(tol)
-        allowed = self.prognostic + self.diagnostic
-        for n in names:
-            if n not in allowed:
-                raise ValueError(f"tol: unknown field {n!r} for the {self.model} model (expected one of {', '.join(allowed)})")
+        names, ids = self._fields(tuple(tol), "tol", t0_note=False)
         tols = np.array([float(tol[n]) for n in names], dtype=np.float64)
         for n, t in zip(names, tols):
             if not t >= 0.0:
@@ -572,7 +560,7 @@ class Engine:
         if int(nt) < 1:
             raise ValueError(f"nt = {nt}: need at least one step per year")
         f = None if f_year is None else as_f64(f_year, (int(nt),))
-        return names, [FIELD[n] for n in names], tols, f
+        return names, ids, tols, f
 
     def equilibrate(self, nt, max_years, f_year=None, tol=None, min_years=2):
         """ebm_equilibrate: whole years of ``nt`` steps (forcing ``f_year[i] + fcol[c]``, the same every year) until each
@@ -584,22 +572,17 @@ class Engine:
         tol = {"T": 1e-3} if tol is None else tol
         names, ids, tols, f = self.check_equilibrate_args(nt, max_years, tol, min_years, f_year)
         nv = len(names)
-        fields = (C.c_int * nv)(*ids)
         years = np.zeros(self.ncol, dtype=np.int32)
         conv = np.zeros(self.ncol, dtype=np.int32)
         resid = np.full((nv, self.ncol), np.nan)
-        ip = C.POINTER(C.c_int)
-        check(self.lib.ebm_equilibrate(self._h, int(nt), int(max_years), int(min_years), dptr(f), nv, fields, dptr(tols),
-                                       years.ctypes.data_as(ip), conv.ctypes.data_as(ip), dptr(resid)), "ebm_equilibrate")
+        check(self.lib.ebm_equilibrate(self._h, int(nt), int(max_years), int(min_years), dptr(f), nv, field_ids(ids), dptr(tols),
+                                       iptr(years), iptr(conv), dptr(resid)), "ebm_equilibrate")
         return dict(years=years.astype(np.int64), converged=conv.astype(bool), resid={n: resid[i] for i, n in enumerate(names)})
 
     def check_until_args(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
         """The host-side checks of ``run_until`` (no device call): returns (field id, level [ncol] float64, direction [ncol]
         int32, f_steps)."""
-        allowed = self.prognostic + self.diagnostic
-        if not isinstance(name, str) or name not in allowed:
-            raise ValueError(f"name: unknown field {name!r} for the {self.model} model (expected one of {', '.join(allowed)}; "
-                             "the warm start T0 is not a solution variable)")
+        _, (fid,) = self._fields((name,), "name")
         if int(first_step) < 0:
             raise ValueError("run_until: first_step must be >= 0")
         if int(max_samples) < 1:
@@ -618,7 +601,7 @@ class Engine:
             raise ValueError("direction: 0 is neither upward (> 0) nor downward (< 0)")
         d = np.ascontiguousarray(np.sign(d), dtype=np.int32)
         f = None if f_steps is None else as_f64(f_steps, (int(max_samples) * int(every),))
-        return FIELD[name], lev, d, f
+        return fid, lev, d, f
 
     def run_until(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
         """ebm_run_until: rounds of ``every`` steps from global step ``first_step``, at most ``max_samples`` of them; after
@@ -631,10 +614,8 @@ class Engine:
         samples = np.zeros(self.ncol, dtype=np.int32)
         crossed = np.zeros(self.ncol, dtype=np.int32)
         value = np.full(self.ncol, np.nan)
-        ip = C.POINTER(C.c_int)
         check(self.lib.ebm_run_until(self._h, int(first_step), int(max_samples), int(every), dptr(f), int(steps_per_launch), fid,
-                                     dptr(lev), d.ctypes.data_as(ip), samples.ctypes.data_as(ip), crossed.ctypes.data_as(ip),
-                                     dptr(value)), "ebm_run_until")
+                                     dptr(lev), iptr(d), iptr(samples), iptr(crossed), dptr(value)), "ebm_run_until")
         samples = samples.astype(np.int64)
         return dict(samples=samples, crossed=crossed.astype(bool), value=value, steps=int(samples.max()) * int(every))
 
@@ -659,7 +640,7 @@ class Engine:
         so a clone parts from its parent at the next step.  The step clock, the counters and the validity of the fields
         are unchanged; ``parents[c] == c`` moves nothing.  Asynchronous."""
         p = self.check_resample_args(parents)
-        check(self.lib.ebm_resample_columns(self._h, p.ctypes.data_as(C.POINTER(C.c_int))), "ebm_resample_columns")
+        check(self.lib.ebm_resample_columns(self._h, iptr(p)), "ebm_resample_columns")
 
     def column_record(self):
         """ebm_column_record: ``(record_doubles, mask)`` — the doubles of one exported column (a function of the model, nlat
@@ -708,8 +689,7 @@ class Engine:
         N_c.  Returns the mask (bit f: the slot of field f was written).  Changes nothing in the handle.  Asynchronous."""
         c, _ = self.check_exchange_args(cols, ptr)
         m = C.c_uint()
-        check(self.lib.ebm_export_columns(self._h, len(c), c.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(int(ptr)), C.byref(m)),
-              "ebm_export_columns")
+        check(self.lib.ebm_export_columns(self._h, len(c), iptr(c), C.c_void_p(int(ptr)), C.byref(m)), "ebm_export_columns")
         return int(m.value)
 
     def import_columns(self, cols, ptr, mask, records=None):
@@ -720,9 +700,7 @@ class Engine:
         if mask is None:
             raise ValueError("mask: expected the integer the export returned")
         c, r = self.check_exchange_args(cols, ptr, records, mask, distinct=True)
-        ip = C.POINTER(C.c_int)
-        check(self.lib.ebm_import_columns(self._h, len(c), c.ctypes.data_as(ip), None if r is None else r.ctypes.data_as(ip),
-                                          C.c_void_p(int(ptr)), int(mask)), "ebm_import_columns")
+        check(self.lib.ebm_import_columns(self._h, len(c), iptr(c), iptr(r), C.c_void_p(int(ptr)), int(mask)), "ebm_import_columns")
 
     def sync(self):
         check(self.lib.ebm_sync(self._h), "ebm_sync")

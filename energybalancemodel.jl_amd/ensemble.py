@@ -11,9 +11,26 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import Engine, param_matrix, param_vector
+from .engine import Engine, as_names, param_matrix, param_vector
 from .infrastructure import default_parval
 from .noise import check_args as check_noise_args
+
+
+def _sharded(dist) -> bool:
+    """More than one rank: ``dist`` (torch.distributed) is given, initialised and its world is larger than one."""
+    return dist is not None and dist.is_initialized() and dist.get_world_size() > 1
+
+
+def _backend(dist) -> str:
+    try:
+        return str(dist.get_backend())
+    except Exception:
+        return ""
+
+
+def _steps_per_launch(k):
+    """The steps fused into one launch by ``run``, ``series`` and ``first_passage``: the caller's, 64 if None."""
+    return 64 if k is None else k
 
 
 def shard_columns(ncol: int, world_size: int, rank: int) -> slice:
@@ -282,7 +299,7 @@ class ColumnExchange:
         exchange is one ``all_to_all_single`` with the plan's split sizes and the payload stays on the device; with any
         other backend (gloo has no all-to-all) the records go through the host by ``isend`` / ``irecv``.  With ``dist``
         absent or a world of one it is ``resample``."""
-        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+        if not _sharded(dist):
             return self.resample(parents_global)
         import torch
         ws, rank = dist.get_world_size(), dist.get_rank()
@@ -420,20 +437,34 @@ class EnsembleMoments:
     center) -> ndarray [nvars, 3, nlat]`` and ``ensemble_sums_tensor(names, weights, center)``, the same as a device tensor.
     EnsembleRun is one."""
 
+    def _across_ranks(self, dist, kind, *args, slot_ops=None) -> np.ndarray:
+        """This shard's packed result [entries, slots, nlat] of ``ensemble_<kind>(*args)``, all-reduced over the ranks of
+        ``dist``: with the "nccl" backend (RCCL) the payload is the device tensor ``ensemble_<kind>_tensor(*args)`` wrote and
+        comes to the host once, afterwards; with any other backend (gloo) it is staged on the CPU, as ``gather_columns``
+        does.  One SUM over everything, or slot q on its own with ``ReduceOp`` ``slot_ops[q]``.  With ``dist`` absent or a
+        world of one: the shard's own result."""
+        if not _sharded(dist):
+            return getattr(self, "ensemble_" + kind)(*args)
+        import torch
+        if _backend(dist) == "nccl":
+            t = getattr(self, "ensemble_" + kind + "_tensor")(*args)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(getattr(self, "ensemble_" + kind)(*args)))
+        if slot_ops is None:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            return t.cpu().numpy()
+        parts = []
+        for q, op in enumerate(slot_ops):
+            part = t[:, q].contiguous()
+            dist.all_reduce(part, op=getattr(dist.ReduceOp, op))
+            parts.append(part.cpu().numpy())
+        return np.stack(parts, axis=1)
+
     def reduced_sums(self, names, weights=None, center=None, dist=None) -> np.ndarray:
         """This shard's packed sums, all-reduced (SUM) over the ranks of ``dist``: with the "nccl" backend (RCCL) the payload
         is the device tensor the reduction wrote and comes to the host once, afterwards; with any other backend (gloo) it is
         staged on the CPU, as ``gather_columns`` does.  With ``dist`` absent or a world of one: the shard's own sums."""
-        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-            return self.ensemble_sums(names, weights, center)
-        import torch
-        if _backend(dist) == "nccl":
-            t = self.ensemble_sums_tensor(names, weights, center)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            return t.cpu().numpy()
-        t = torch.from_numpy(np.ascontiguousarray(self.ensemble_sums(names, weights, center)))
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        return t.numpy()
+        return self._across_ranks(dist, "sums", names, weights, center)
 
     def moments(self, names=("T", "phi"), weights=None, dist=None) -> dict:
         """Weighted mean and variance ACROSS the members, per latitude, of every field in ``names``: ``{name: {"weight": S0,
@@ -451,9 +482,7 @@ class EnsembleMoments:
         at most D(m) = min(m, 32) + ceil(m / 32) - 2 rounded adds and the combination of n shards adds n - 1 more, so the
         combined sums agree with the unsharded ones to within (D(ncol) + max_r D(ncol_r) + n - 1) * 2^-53 * sum|terms| per
         latitude, ncol_r the members of shard r."""
-        if isinstance(names, str):
-            names = (names,)
-        names = tuple(names)
+        names = as_names(names)
         s1 = np.asarray(self.reduced_sums(names, weights, None, dist))
         center = moments_center(moments_from_sums(s1)["mean"])
         s2 = np.asarray(self.reduced_sums(names, weights, center, dist))
@@ -468,35 +497,14 @@ class EnsembleMoments:
         """[len(names), 3, nlat]: the number n of contributing members, their minimum and their maximum per latitude
         (ebm_ensemble_range) — of the whole ensemble with ``dist``: n is all-reduced with SUM, min with MIN, max with MAX,
         which is exact, so every rank holds the bits of the unsharded call (up to which of +0.0 and -0.0 an extreme is)."""
-        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-            return self.ensemble_range(names, weights)
-        import torch
-        if _backend(dist) == "nccl":
-            t = self.ensemble_range_tensor(names, weights)
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(self.ensemble_range(names, weights)))
-        parts = []
-        for q, op in enumerate((dist.ReduceOp.SUM, dist.ReduceOp.MIN, dist.ReduceOp.MAX)):
-            part = t[:, q].contiguous()
-            dist.all_reduce(part, op=op)
-            parts.append(part.cpu().numpy())
-        return np.stack(parts, axis=1)
+        return self._across_ranks(dist, "range", names, weights, slot_ops=("SUM", "MIN", "MAX"))
 
     def histogram(self, names, lo, hi, nbins, weights=None, dist=None) -> np.ndarray:
         """[len(names), nbins + 2, nlat]: the weighted histogram across the members per latitude (ebm_ensemble_histogram:
         below ``lo`` | nbins bins | at and above ``hi``) — of the whole ensemble with ``dist`` (all-reduced with SUM; with unit
         weights every slot is an exact count and the result is the unsharded one bit for bit).  A name may be repeated,
         each entry with its own rows of ``lo`` and ``hi``."""
-        if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-            return self.ensemble_histogram(names, lo, hi, nbins, weights)
-        import torch
-        if _backend(dist) == "nccl":
-            t = self.ensemble_histogram_tensor(names, lo, hi, nbins, weights)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            return t.cpu().numpy()
-        t = torch.from_numpy(np.ascontiguousarray(self.ensemble_histogram(names, lo, hi, nbins, weights)))
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        return t.numpy()
+        return self._across_ranks(dist, "histogram", names, lo, hi, nbins, weights)
 
     def quantiles(self, names=("T", "phi"), q=(0.05, 0.5, 0.95), weights=None, dist=None, nbins=QUANTILE_NBINS,
                   passes=QUANTILE_PASSES) -> dict:
@@ -519,9 +527,7 @@ class EnsembleMoments:
         1.3 times as much at 64 bins (66 KiB of LDS per workgroup instead of 34), and the host arithmetic on the O(nbins *
         nlat) slots per pair, which is most of the call's time, doubles.  With ``dist`` every rank returns the quantiles of
         the whole ensemble."""
-        if isinstance(names, str):
-            names = (names,)
-        names = tuple(names)
+        names = as_names(names)
         qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
         if qs.ndim != 1 or qs.size < 1 or not ((qs >= 0.0) & (qs <= 1.0)).all():
             raise ValueError(f"q: expected quantile levels in [0, 1], got {q!r}")
@@ -611,18 +617,26 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         self.has_noise = noise_args is not None
         self.step_index = 0
 
+    def _forcing_table(self, forcing, first_step, nsteps):
+        """The scalar forcing of global steps first_step .. first_step + nsteps - 1, evaluated at the middle of each step
+        ([nsteps] float64; the bits of these times are part of the model time), or None without ``forcing``."""
+        if forcing is None:
+            return None
+        T = (np.arange(first_step, first_step + nsteps) + 0.5) * self.st.dt
+        return np.array([forcing(float(t)) for t in T])
+
+    def _device_tensor(self, *shape):
+        """An uninitialised float64 tensor of ``shape`` on this run's device."""
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", self.device))
+
     def run(self, nsteps, forcing=None, diag_last=True, steps_per_launch=None):
         """Advance ``nsteps`` steps; ``forcing`` is a Forcing or None.  Nothing leaves the device between the
         steps of this call, so they are fused ``steps_per_launch`` to a launch (ebm_run_fused: the state stays in
         registers or LDS, bit-identical to one launch per step for every model and size); default 64, 1 = one
         launch per step (ebm_run)."""
-        if steps_per_launch is None:
-            steps_per_launch = 64
-        f = None
-        if forcing is not None:
-            T = (np.arange(self.step_index, self.step_index + nsteps) + 0.5) * self.st.dt
-            f = np.array([forcing(float(t)) for t in T])
-        self.engine.run(self.step_index, nsteps, f, diag_last, steps_per_launch)
+        f = self._forcing_table(forcing, self.step_index, nsteps)
+        self.engine.run(self.step_index, nsteps, f, diag_last, _steps_per_launch(steps_per_launch))
         self.step_index += nsteps
 
     def series(self, nsteps, every, names=("T", "phi"), forcing=None, steps_per_launch=None):
@@ -632,13 +646,9 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         (ebm_run_series): [len(names), nsteps // every, ncol].  Sample j is the state after ``every * (j + 1)`` steps of
         this call — a member's <T>(t) or ice area <phi>(t) at ``every * dt`` resolution, for crossing and residence times.
         Members are independent, so a sharded ensemble gives the bits of an unsharded one."""
-        if steps_per_launch is None:
-            steps_per_launch = 64
+        steps_per_launch = _steps_per_launch(steps_per_launch)
         self.engine.check_series_args(self.step_index, nsteps, every, names, None, steps_per_launch)    # before any device call
-        f = None
-        if forcing is not None:
-            T = (np.arange(self.step_index, self.step_index + nsteps) + 0.5) * self.st.dt
-            f = np.array([forcing(float(t)) for t in T])
+        f = self._forcing_table(forcing, self.step_index, nsteps)
         out = self.engine.run_series(self.step_index, nsteps, every, names, f, steps_per_launch)
         self.step_index += nsteps
         return out
@@ -654,8 +664,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         taken; value [ncol]: the member's last mean).  Members are independent, so a sharded ensemble gives the results of
         an unsharded one; shards may stop at different rounds (no collective sits inside the call).  ``step_index``
         advances by the steps of this shard's slowest member; stepping on continues every member from its own state."""
-        if steps_per_launch is None:
-            steps_per_launch = 64
+        steps_per_launch = _steps_per_launch(steps_per_launch)
         if int(every) < 1:
             raise ValueError(f"every = {every}: the mean is tested every `every` >= 1 steps")
         if int(max_steps) < int(every) or int(max_steps) % int(every):
@@ -663,10 +672,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         lev, d = passage_levels(self.ncol, level, direction)
         rounds = int(max_steps) // int(every)
         self.engine.check_until_args(self.step_index, rounds, every, name, lev, d, None, steps_per_launch)    # before any device call
-        f = None
-        if forcing is not None:
-            T = (np.arange(self.step_index, self.step_index + int(max_steps)) + 0.5) * self.st.dt
-            f = np.array([forcing(float(t)) for t in T])
+        f = self._forcing_table(forcing, self.step_index, int(max_steps))
         first = self.step_index
         out = self.engine.run_until(first, rounds, every, name, lev, d, f, steps_per_launch)
         self.step_index += out["steps"]
@@ -691,10 +697,9 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         tensor [len(cols), R], record i the packed state of member cols[i] (ebm_export_columns: every field in the natural
         layout, the warm start, N_c), and the mask of the fields that travel.  Nothing in the run changes.  The handle is
         synchronised before the tensor is returned: it is complete and any stream may read it."""
-        import torch
         c, _ = self.engine.check_exchange_args(cols, 16)
         R, _ = self.engine.column_record()
-        out = torch.empty((len(c), R), dtype=torch.float64, device=torch.device("cuda", self.device))
+        out = self._device_tensor(len(c), R)
         mask = self.engine.export_columns(c, out.data_ptr() if len(c) else 0)
         self.engine.sync()
         return out, mask
@@ -736,10 +741,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         st = self.st
         if self.step_index % st.nt:
             raise ValueError(f"seasonal_means starts a year: {self.step_index} steps taken so far is not a multiple of nt = {st.nt}")
-        f = None
-        if forcing is not None:
-            T = (np.arange(self.step_index, self.step_index + st.nt * years) + 0.5) * st.dt
-            f = np.array([forcing(float(t)) for t in T])
+        f = self._forcing_table(forcing, self.step_index, st.nt * years)
         self.engine.set_step_clock(self.step_index)
         out = self.engine.integrate_hemispheric(st.nt, years, f, st.winter.inx, st.summer.inx, tuple(names))
         self.step_index += st.nt * years
@@ -764,10 +766,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         if self.step_index % st.nt:
             raise ValueError(f"equilibrate starts a year: {self.step_index} steps taken so far is not a multiple of nt = {st.nt}")
         tol = {"T": 1e-3} if tol is None else tol
-        f = None
-        if forcing is not None:
-            T = (np.arange(self.step_index, self.step_index + st.nt) + 0.5) * st.dt
-            f = np.array([forcing(float(t)) for t in T])
+        f = self._forcing_table(forcing, self.step_index, st.nt)
         self.engine.check_equilibrate_args(st.nt, max_years, tol, min_years, f)
         self.engine.set_step_clock(self.step_index)
         out = self.engine.equilibrate(st.nt, max_years, f, tol, min_years)
@@ -781,16 +780,13 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         """Per-column hemispheric mean (reference src/utilities.jl:397-403) as a torch tensor ON THE
         DEVICE — reduced there by ebm_hemispheric_mean_device, never staged through the host — ready
         to be gathered over RCCL (gather_columns)."""
-        import torch
-        out = torch.empty(self.ncol, dtype=torch.float64, device=torch.device("cuda", self.device))
+        out = self._device_tensor(self.ncol)
         self.engine.hemispheric_mean_device(name, out.data_ptr())
         return out
 
     def _reduced_tensor(self, names, nslots, device_call):
         """A float64 tensor [len(names), nslots, nlat] on this run's device, filled by ``device_call(its address)``."""
-        import torch
-        nv = 1 if isinstance(names, str) else len(tuple(names))
-        out = torch.empty((nv, nslots, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        out = self._device_tensor(len(as_names(names)), nslots, self.st.nx)
         device_call(out.data_ptr())
         return out
 
@@ -830,9 +826,8 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
     def misfits_tensor(self, names, targets, rweights=None):
         """The same as a float64 torch tensor [ntargets, 2, ncol] ON THE DEVICE (ebm_column_misfits_device), ready to be
         all-gathered over RCCL."""
-        import torch
         y = np.asarray(targets, dtype=np.float64)
-        out = torch.empty((1 if y.ndim == 2 else y.shape[0], 2, self.ncol), dtype=torch.float64, device=torch.device("cuda", self.device))
+        out = self._device_tensor(1 if y.ndim == 2 else y.shape[0], 2, self.ncol)
         self.engine.column_misfits_device(names, targets, out.data_ptr(), rweights)
         return out
 
@@ -851,11 +846,10 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
             raise ValueError("obs_var: expected finite values > 0")
         if not 0.0 <= float(ess_fraction) <= 1.0:
             raise ValueError(f"ess_fraction = {ess_fraction}: expected a fraction between 0 and 1")
-        nv = 1 if isinstance(names, str) else len(tuple(names))
-        shape = (nv, self.st.nx)
+        shape = (len(as_names(names)), self.st.nx)
         rw = np.ascontiguousarray(np.broadcast_to((1.0 if quad is None else np.asarray(quad, dtype=np.float64)) / obs_var, shape))
         out = self.misfits(names, np.asarray(obs, dtype=np.float64).reshape(shape), rw)
-        sharded = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
+        sharded = _sharded(dist)
         if sharded:
             parts = [None] * dist.get_world_size()
             dist.all_gather_object(parts, out[0])
@@ -873,8 +867,7 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
 
     def field_tensor(self, name):
         """A packed [ncol, nlat] device tensor copy of a field (device-to-device)."""
-        import torch
-        out = torch.empty((self.ncol, self.st.nx), dtype=torch.float64, device=torch.device("cuda", self.device))
+        out = self._device_tensor(self.ncol, self.st.nx)
         self.engine.get_field_device(name, out.data_ptr())
         return out
 
@@ -887,7 +880,7 @@ def broadcast_inputs(arrays: dict | None, dist=None, device=None, src: int = 0) 
     table, the per-column forcing offsets — from rank ``src`` to every rank (I/O only, a few KB;
     SURVEY §8(e)).  ``arrays`` maps names to fp64 arrays on ``src`` and is ignored elsewhere;
     every rank returns the same dict.  With dist=None (single process) returns ``arrays``."""
-    if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+    if not _sharded(dist):
         return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in (arrays or {}).items()}
     import torch
     rank = dist.get_rank()
@@ -911,13 +904,6 @@ def broadcast_inputs(arrays: dict | None, dist=None, device=None, src: int = 0) 
     return out
 
 
-def _backend(dist) -> str:
-    try:
-        return str(dist.get_backend())
-    except Exception:
-        return ""
-
-
 def gather_columns(local, ncol_total: int, dist=None, device=None, dst: int = 0):
     """Gather per-column data ([ncol_local, ...]) from all ranks to rank ``dst`` (I/O only).
 
@@ -928,8 +914,7 @@ def gather_columns(local, ncol_total: int, dist=None, device=None, dst: int = 0)
     host once, on ``dst``.  With "gloo" (CPU tests) host tensors are gathered.  Returns the
     [ncol_total, ...] NumPy array on ``dst`` and None elsewhere.  With dist=None (single process)
     returns ``local`` as a NumPy array."""
-    import_torch = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
-    if not import_torch:
+    if not _sharded(dist):
         return local.cpu().numpy() if hasattr(local, "cpu") else local
     import torch
     ws, rank = dist.get_world_size(), dist.get_rank()

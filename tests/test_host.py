@@ -210,7 +210,8 @@ _C2J = {  # C parameter type (normalised) -> the Julia ccall argument types that
 }
 
 
-def _header_prototypes():
+def _header_prototypes(with_names=False):
+    """name -> (return type, parameter types); with ``with_names`` each parameter is (type, name)."""
     hdr = open(os.path.join(ROOT, "include", "ebm_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     protos = {}
@@ -221,7 +222,8 @@ def _header_prototypes():
                 continue
             a = re.sub(r"\s+", " ", a)
             m = re.match(r"(.*?)(\**)\s*([A-Za-z_][A-Za-z0-9_]*)$", a)          # type, stars, name
-            params.append((m.group(1).strip() + m.group(2)).replace(" *", "*"))
+            ctype = (m.group(1).strip() + m.group(2)).replace(" *", "*")
+            params.append((ctype, m.group(3)) if with_names else ctype)
         protos[name] = (ret.replace(" ", ""), params)
     return protos
 
@@ -278,6 +280,42 @@ def test_julia_shim_ccalls_match_the_header():
         assert len(args) == len(types), f"{name}: {len(args)} arguments for {len(types)} parameter types"
         for jt, ct in zip(types, cparams):
             assert jt in _C2J[ct], f"{name}: Julia {jt} does not bind C {ct}"
+
+
+def test_ctypes_signature_table_matches_the_header(pkg):
+    """The whole ABI of the Python binding, as the Julia shim's above: _lib.SIGNATURES (data; neither the library nor a GPU is
+    needed) has exactly the header's functions, each with the header's number of parameters and, per parameter, a ctypes
+    type that binds the C type.  A host pointer is typed; a device address — double * named dev_... in the header — is a
+    c_void_p, and only that is."""
+    import sys
+    lib = sys.modules[pkg.__name__ + "._lib"]
+    P = ctypes.POINTER
+    c2py = {  # C parameter type (normalised) -> the ctypes type that binds it
+        "int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint,
+        "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "float*": P(ctypes.c_float),
+        "const int*": P(ctypes.c_int), "int*": P(ctypes.c_int), "long long*": P(ctypes.c_longlong),
+        "unsigned*": P(ctypes.c_uint), "const unsigned long long*": P(ctypes.c_ulonglong),
+        "const double*": P(ctypes.c_double), "double*": P(ctypes.c_double), "double**": P(ctypes.c_void_p),
+        "ebm_handle_t": ctypes.c_void_p, "ebm_handle_t*": P(ctypes.c_void_p),
+        "const ebm_options*": P(lib.Options), "ebm_options*": P(lib.Options),
+    }
+    protos = _header_prototypes(with_names=True)
+    assert len(protos) >= 55 and len(protos["ebm_integrate"][1]) == 13
+    assert set(lib.SIGNATURES) == set(protos), set(lib.SIGNATURES) ^ set(protos)
+    assert set(lib.EXPORTS) == set(lib.SIGNATURES) and len(lib.EXPORTS) == len(lib.SIGNATURES)
+    device_addresses = 0
+    for name, (cret, cparams) in protos.items():
+        assert lib.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_char_p if cret == "constchar*" else ctypes.c_int), name
+        argtypes = lib.SIGNATURES[name]
+        assert len(argtypes) == len(cparams), f"{name}: {len(argtypes)} ctypes types for {len(cparams)} C parameters"
+        for i, (pt, (ct, cname)) in enumerate(zip(argtypes, cparams)):
+            want = c2py[ct]
+            if cname.startswith("dev_"):
+                assert ct in ("double*", "const double*"), (name, cname, ct)
+                want = ctypes.c_void_p
+                device_addresses += 1
+            assert pt is want, f"{name}: parameter {i} ({ct} {cname}) is bound as {pt.__name__}, expected {want.__name__}"
+    assert device_addresses >= 8
 
 
 def test_julia_shim_options_struct_matches_the_header(pkg):

@@ -330,8 +330,8 @@ def test_engine_checks_raise_before_any_device_call(pkg):
         eng.ensemble_range_device(("T", "phi"), 0)
     with pytest.raises(ValueError):
         eng.ensemble_histogram_device(("T", "T"), lo, hi, 7, 0)
-    names, ids, w, (l, u) = eng._check_ensemble_args(("T", "phi", "T"), [0, 1, 2, 0, 1], order=True, repeats=True, nbins=7,
-                                                         lo=np.zeros((3, 4)), hi=np.ones((3, 4)))
+    names, ids, w, (l, u) = eng._check_histogram_args(("T", "phi", "T"), lo=np.zeros((3, 4)), hi=np.ones((3, 4)), nbins=7,
+                                                      weights=[0, 1, 2, 0, 1])
     assert names == ("T", "phi", "T") and ids == [10, 4, 10] and w.dtype == np.float64 and l.shape == u.shape == (3, 4)
 
 

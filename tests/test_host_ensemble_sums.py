@@ -196,7 +196,7 @@ def test_engine_checks_raise_before_any_device_call(pkg):
         eng.ensemble_sums("T", [1, 1, np.nan, 1, 1])
     with pytest.raises(ValueError):
         eng.ensemble_sums_device(("T", "phi"), 0, ok_w, ok_c)
-    names, ids, w, c = eng._check_ensemble_args("T", [0, -1, 2, 0, 1], None)
+    names, ids, w, c = eng._check_sums_args("T", [0, -1, 2, 0, 1], None)
     assert names == ("T",) and ids == [10] and w.dtype == np.float64 and c is None
     eng._h = None
 
