@@ -1,185 +1,223 @@
-"""Mutation check of the GPU test suite: deliberately broken builds of the library must be caught.
+"""Mutation check of the test suite: deliberately broken copies of the product must be caught.
 
-    python tests/tools/mutants.py check          (here, CPU: every anchor occurs exactly once; no copy, no build)
-    python tests/tools/mutants.py build          (here, CPU: one full build per mutant under build/)
-    bash   tests/tools/mutants_run.sh            (GPU box: the -m gpu suite with -x against every mutant)
+    python tests/tools/mutants.py list
+    python tests/tools/mutants.py check [LIST ...]        (CPU, no build; no argument: every list)
+    python tests/tools/mutants.py build LIST [NAME ...]   (CPU; csrc lists only: one full build per mutant under build/)
+    python tests/tools/mutants.py run   LIST [NAME ...]   (GPU box, or CPU for the host and plan lists)
 
-Each mutant is ONE small textual change of a file of csrc/ — a sign, a dropped select, a broken halo — of the kind a
-transcription error would be.  A 3-tuple's anchor is looked for in every .hip and .h file of csrc/: it must occur exactly
-once in all of them together, and the file that holds it is the one edited.  A 4-tuple names its file.  The runner records the first test that fails for each; a mutant that the whole
-suite lets pass is a hole in the suite.  Nothing here is product code: the mutants live under build/ only."""
-import os, shutil, subprocess, sys
+The lists are the data modules tests/tools/mutants_<list>.py, found by file name: KIND, TESTS (the pytest arguments that must
+catch every mutant), LIMIT (seconds per pytest session) and MUTANTS, tuples (name, anchor, replacement[, file[, "survives"]]).
+Each mutant is ONE small textual change — a sign, a dropped select, a broken halo — of the kind a transcription error would
+be.  The anchor must occur exactly once: in the named file, or, of a 3-tuple, in all source files of the list's directory
+together, and the file that holds it is the one edited.  That directory is csrc/ for KIND "csrc", whose mutants `build` compiles
+from a patched copy of csrc/ into build/libebm_mut_<name>.so and `run` loads through EBM_LIB, and the package directory for
+KIND "tree", whose mutants `run` patches into a temporary copy of the tree, running pytest inside the copy.  Nothing here is
+product code, and no product file is ever edited in place.
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-MUTANTS = [
-    ("flux_metric_sign", "return ieee_div((1.0 - xx * xx) * dT, hi_x - lo_x);", "return ieee_div((1.0 + xx * xx) * dT, hi_x - lo_x);"),
-    ("uniform_stencil_skips_equatorward_neighbour", "y = (k > 0) ? y + g0 * tbm : y;", "y = (k > 1) ? y + g0 * tbm : y;"),
-    ("water_temp_keeps_nan", "return __builtin_isnan(tw) ? 0.0 : tw;", "return tw;"),
-    ("t0_rhs_forcing_sign", "return -((p.ai * S - p.A) + dif + f);", "return -((p.ai * S - p.A) + dif - f);"),
-    ("lead_ring_radius_sign", "const double Dr = Dk + p.two_rl;", "const double Dr = Dk - p.two_rl;"),
-    ("ice_enthalpy_not_clamped", "const double cEi = jl_clamp(rEi, -INFINITY, 0.0);", "const double cEi = rEi;"),
-    ("lateral_growth_guard_inverted", "if (hk == 0.0) lat_grow = 0.0;", "if (hk != 0.0) lat_grow = 0.0;"),
-    ("welding_quadratic", "const double weld = p.c_weld * ph * (Dk * Dk * Dk);", "const double weld = p.c_weld * ph * (Dk * Dk);"),
-    ("concentration_not_capped", "if (phi_n > 1.0) phi_n = 1.0;", ""),
-    ("halo_left_is_own_value", "left = t > 0 ? l : 0.0;", "left = t > 0 ? first : 0.0;"),
-    ("back_substitution_drops_left_interface", "x[i] = __builtin_fma(-cp[i], x[i + 1], __builtin_fma(lp[i], L, dp[i]));",
-     "x[i] = __builtin_fma(-cp[i], x[i + 1], dp[i]);"),
-    # (an EQUIVALENT mutant, kept as a control: with E == +-0 both forms give +-0 — the suite cannot and need not see it)
-    ("classic_zero_enthalpy_is_ice", "const double Tk = bool_mul(ieee_div(Ek, p.cw), Ek >= 0.0)", "const double Tk = bool_mul(ieee_div(Ek, p.cw), Ek > 0.0)"),
-    # second batch
-    ("schedule_ramp_ignores_its_start", "else if (tyear < d2) v = base + up * (tyear - d1);", "else if (tyear < d2) v = base + up * tyear;"),
-    ("floe_number_linear_in_D", "double n = ieee_div(ph, alpha * (Dk * Dk));", "double n = ieee_div(ph, alpha * Dk);"),
-    ("olr_slope_sign", "const double L = p.A + p.B * (tb - Tm);", "const double L = p.A - p.B * (tb - Tm);"),
-    ("water_albedo_sign", "const double sol_w = 0.0 + (p.a0 - p.a2 * (xk * xk)) * S;", "const double sol_w = 0.0 + (p.a0 + p.a2 * (xk * xk)) * S;"),
-    ("lateral_flux_without_pi", "double Flat = ieee_div(ph * hk * Lf * wl * M_PI, alpha * Dk);", "double Flat = ieee_div(ph * hk * Lf * wl, alpha * Dk);"),
-    ("surplus_of_ice_not_given_to_water", "const double Ew_n = cEw + psiEidt;", "const double Ew_n = cEw;"),
-    ("lead_share_added_not_subtracted", "const double Qp = psi - Ql;", "const double Qp = psi + Ql;"),
-    ("lateral_melt_sign", "const double lat_melt = p.c_latmelt * wl;", "const double lat_melt = -(p.c_latmelt * wl);"),
-    ("thickness_tendency_sign", "double rh = hk + (p.c_ht * Fvi) * dt;", "double rh = hk - (p.c_ht * Fvi) * dt;"),
-    ("new_ice_thickness_uses_Dmin", "double h_n = div_with_rcp(n * rh + dn * p.hmin, total, rtotal);", "double h_n = div_with_rcp(n * rh + dn * p.Dmin, total, rtotal);"),
-    ("mean_temperature_uses_old_concentration", "o.q[Q_T] = Ti * phi_n + (1.0 - phi_n) * Tw;", "o.q[Q_T] = Ti * ph + (1.0 - ph) * Tw;"),
-    ("insolation_seasonal_sign", "return p.S0 - p.S1 * xk * ct - p.S2 * (xk * xk);", "return p.S0 + p.S1 * xk * ct - p.S2 * (xk * xk);"),
-    ("t0_conduction_ignores_hmin", "return __builtin_fma(p.k, fast_rcp((hk == 0.0) ? p.hmin : hk), p.B);", "return __builtin_fma(p.k, fast_rcp(hk), p.B);"),
-    # (the second EQUIVALENT control: at T0 == Tm exactly both branches of the piecewise-linear system agree)
-    ("active_set_includes_melting_point", "snew |= (xs[i] < 0.0) ? (1u << i) : 0u;", "snew |= (xs[i] <= 0.0) ? (1u << i) : 0u;"),
-    ("active_rows_ignore_concentration", "g[i] = ((smask >> i) & 1u) ? ph[i] : 0.0;", "g[i] = ((smask >> i) & 1u) ? 1.0 : 0.0;"),
-    ("classic_ocean_heat_flux_sign", "Ek = Ek + p.dt * (Cc - p.M * Tk + p.Fb);", "Ek = Ek + p.dt * (Cc - p.M * Tk - p.Fb);"),
-    # (merged with resident_extension_matrix_diagonal_sign: the step and the resident kernel share imex_row)
-    ("extension_matrix_diagonal_sign", "rb = 1.0 + p.theta_imex * (lo + up);", "rb = 1.0 - p.theta_imex * (lo + up);"),
-    # third batch: the host runtime (tables, time bookkeeping, savesol!) and the small kernels; a 4-tuple names the file
-    ("uniform_table_metric_linear", "lam[i - 1] = (1.0 - xb * xb) / (dx * dx);", "lam[i - 1] = (1.0 - xb) / (dx * dx);", "ebm_tables.h"),
-    ("polar_ghost_cell_misplaced", "double xp = k < nx - 1 ? x[k + 1] : 2.0 - x[nx - 1];", "double xp = k < nx - 1 ? x[k + 1] : 1.0 - x[nx - 1];", "ebm_tables.h"),
-    ("solver_table_uses_wrong_spacing", "double l = p.D * g1[k] / (g3[k] * g4[k]);", "double l = p.D * g1[k] / (g2[k] * g4[k]);", "ebm_tables.h"),
-    ("classic_ghost_diagonal_sign", "kdiag[k] = one - (dtD * g1[k]) / p.cg;", "kdiag[k] = one + (dtD * g1[k]) / p.cg;", "ebm_tables.h"),
-    ("model_time_at_step_start", "return nt > 0.0 ? (double)(2 * step + 1) / (2.0 * nt) : 0.0;", "return nt > 0.0 ? (double)(2 * step) / (2.0 * nt) : 0.0;", "ebm_drive.hip"),
-    ("lastonly_keeps_one_step_too_many", "s.raw = stage && (!lastonly || tinx > total - nt);", "s.raw = stage && (!lastonly || tinx >= total - nt);", "ebm_drive.hip"),
-    ("winter_snapshot_one_step_late", "s.season = ti == winter_inx ? 1 :", "s.season = ti == winter_inx + 1 ? 1 :", "ebm_drive.hip"),
-    ("annual_mean_divides_by_nt_minus_1", "m.x = s.x / nt;", "m.x = s.x / (nt - 1.0);"),
-    ("annual_sum_not_restarted", "z.x = 0.0;", "z.x = s.x;"),
-    # (the one term expression of the library: hemispheric_means_of_column, which every mean of every entry point goes through)
-    ("hemispheric_mean_without_the_half", "terms[v * row + i] = ieee_div((f[k0 + i] + f[k0 + i + 1]) * dx, 2.0);", "terms[v * row + i] = (f[k0 + i] + f[k0 + i + 1]) * dx;"),
-    # fourth batch: code that only the fused-K kernels, savesol!-in-the-step, the extension and the classic solve run
-    # (a seventh mutant of this batch removed the barrier that closed the classic kernel's K-step loop and SURVIVED: the
-    # barrier was redundant — see the comment there — and is gone)
-    ("fused_steps_all_use_the_first_scalars", "const StepSched sc = a.sched[a.slot + step];", "const StepSched sc = a.sched[a.slot];"),
-    ("fused_diagnostics_of_the_first_step", "const bool diag = a.write_diag && step == nloop - 1;", "const bool diag = a.write_diag && step == 0;"),
-    ("running_sum_drops_every_second_cell", "s.y = s.y + x1;", "s.y = s.y + x0;"),
-    ("snapshot_ring_ignores_its_offset", "EBM_STORE2(a.stage + (size_t)v * a.stage_var_stride + a.stage_offset + col_off + kp, d);",
-     "EBM_STORE2(a.stage + (size_t)v * a.stage_var_stride + col_off + kp, d);"),
-    ("extension_lower_diagonal_sign", "ra = -(p.theta_imex * lo);", "ra = (p.theta_imex * lo);"),
-    ("classic_ghost_layer_uses_this_steps_sun", "const double S_ip1 = Sb[i] - (p.S1 * ct_next) * xk[i];", "const double S_ip1 = Sb[i] - (p.S1 * ct) * xk[i];"),
-    # fifth batch: the solver's own algebra, the store paths of the two launch geometries, the iteration's control flow
-    ("column_offsets_all_take_the_first", "double f = a.fcol ? ft + a.fcol[col] : ft;", "double f = a.fcol ? ft + a.fcol[0] : ft;"),
-    ("partition_interface_row_sign", "const double RB = __builtin_fma(ce, vn, __builtin_fma(-ae, cp[C - 2], be));", "const double RB = __builtin_fma(ce, vn, __builtin_fma(ae, cp[C - 2], be));"),
-    ("second_level_left_coupling_sign", "lq[i] = -(a2[i] * lq[i - 1]) * w;", "lq[i] = (a2[i] * lq[i - 1]) * w;"),
-    ("cyclic_reduction_lower_sign", "const double nqa = -(qa * am) * r;", "const double nqa = (qa * am) * r;"),
-    ("t0_diagonal_without_olr", "return __builtin_fma(p.k, fast_rcp((hk == 0.0) ? p.hmin : hk), p.B);", "return __builtin_fma(p.k, fast_rcp((hk == 0.0) ? p.hmin : hk), 0.0);"),
-    ("newton_stops_after_one_iteration", "} while (again && it < kMaxNewton);", "} while (false);"),
-    ("warm_start_forgotten", "cmask[tl] = (unsigned short)smask;                // new warm start", "cmask[tl] = (unsigned short)0;                    // new warm start"),
-    ("two_cell_geometry_swaps_h_and_D", "EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_h) EBM_PUT(S_D, Q_D) EBM_PUT(S_phi, Q_phi)",
-     "EBM_PUT(S_Ei, Q_Ei) EBM_PUT(S_Ew, Q_Ew) EBM_PUT(S_h, Q_D) EBM_PUT(S_D, Q_h) EBM_PUT(S_phi, Q_phi)"),
-    # (parked_first_pair_takes_D_for_h left the list with the line it broke: since the prognostic fields lie pair-split between
-    # one-step launches no pair is parked in LDS)
-    ("classic_ghost_diagonal_ignores_the_melting_mask", "const double q = bool_mul(bool_mul(ieee_div(p.dc, den), T0 < 0.0), Ek < 0.0);", "const double q = bool_mul(ieee_div(p.dc, den), Ek < 0.0);"),
-    ("classic_surface_temperature_sign", "const double T0 = ieee_div(Cc, p.M - ieee_div(p.kLf, Ek));", "const double T0 = ieee_div(Cc, p.M + ieee_div(p.kLf, Ek));"),
-    # sixth batch (round 3): the private store layout of the diagnostic fields, validity tracking, launch chains, the pinned
-    # ring, model time across integrate calls, the zonal sweep and its tables
-    ("unsplit_writes_the_first_pair_twice", "    *(SPLIT ? spl1 : nat1) = p1;", "    *(SPLIT ? spl1 : nat1) = SPLIT ? p1 : p0;"),
-    ("diagnostic_pairs_stored_on_top_of_each_other", "{ return j * 2u * T + 2u * t; }", "{ return 2u * t; }"),
-    ("diagnostic_layout_flag_never_set", "        if (two_layouts_) diag_split_ = split;", "        if (two_layouts_) diag_split_ = false;",
-     "ebm_fieldbook.h"),
-    ("fields_never_go_stale", "        epoch_ += nsteps;", "        epoch_ += 0;", "ebm_fieldbook.h"),
-    ("classic_kernel_ignores_its_column_offset", "    const int b = a.col0 + (int)blockIdx.x;", "    const int b = (int)blockIdx.x;"),
-    ("launch_chains_never_joined", "        (void)hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0);", "", "ebm_runtime.h"),
-    ("second_chain_does_not_wait_for_earlier_work", "if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2.get(), h->ev_fork.get(), 0);", "",
-     "ebm_drive.hip"),
-    ("zonal_last_row_coefficient_sign", "            f = -a * ee[i];", "            f = a * ee[i];"),
-    ("zonal_back_substitution_drops_the_wrap_term", "const double U = __builtin_fma(a * mm[i], Un, __builtin_fma(ee[i], W, dd[i]));",
-     "const double U = __builtin_fma(a * mm[i], Un, dd[i]);"),
-    ("zonal_coefficient_linear_in_dlambda", "a = theta * D / (mm * (dl * dl));", "a = theta * D / (mm * dl);", "ebm_tables.h"),
-    ("annual_means_all_from_the_first_variable", "const size_t base = (size_t)blockIdx.y * (size_t)var_stride + (size_t)col * (size_t)threads * cells;",
-     "const size_t base = (size_t)col * (size_t)threads * cells;"),
-    ("ring_pieces_reuse_the_first_two_offsets", "const size_t r0 = i * rows_per;", "const size_t r0 = (i % 2) * rows_per;", "ebm_hostcopy.h"),
-    # (added after the zonal sweep was partitioned along the circle)
-    ("zonal_segment_end_takes_the_wrong_neighbour", "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)((s_ + 1) % S) * P], sg[o + (size_t)s_ * P]); };",
-     "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)s_ * P], sg[o + (size_t)s_ * P]); };"),
-    ("zonal_reduced_diagonal_without_the_spike_sum", "const double a2 = a * ep_last, B2 = B - a * cp_last - a * alpha;", "const double a2 = a * ep_last, B2 = B - a * cp_last;", "ebm_tables.h"),
-    ("integrate_restarts_model_time", "f, diag, clock0 + tinx - 1,", "f, diag, tinx - 1,", "ebm_drive.hip"),
-    ("as_of_query_inverted", "    if (have != step)", "    if (have == step)", "ebm_fields.hip"),
-    # seventh batch: the LDS-resident fused-K kernel, its compact solve, its halo exchange and its vote
-    ("resident_diagnostics_of_the_first_step", "const bool diag = a.write_diag != 0 && step + 1 == nloop;", "const bool diag = a.write_diag != 0 && step == 0;"),
-    ("resident_newton_stops_after_one_iteration", "} while (it < kMaxNewton && again);", "} while (false);"),
-    ("resident_floe_size_not_written_back", "            sD(i) = valid ? o.q[Q_D] : 0.0;\n", ""),
-    ("resident_vote_reads_only_the_first_wave", "for (int w = 0; w < TT / 64; ++w) any |= F[w];", "for (int w = 0; w < 1; ++w) any |= F[w];"),
-    ("wave_halo_takes_its_own_edge", "const double pl = E[w > 0 ? w - 1 : 0],", "const double pl = E[w],"),
-    # (two buffer-aliasing mutants of the compact solve were tried and are NOT in this list — the reduction's second buffer
-    # overlapping the first by a third, the interface solution written into the buffer the reduction is still read from: both
-    # are RACES between waves that resume from the same barrier within a few cycles of each other, both passed every test on
-    # the box, and no test can catch such a race deterministically (no GPU sanitizer on this pool).  The buffer plan is argued
-    # in the comments of partition_solve_r instead.  What a wrong buffer does deterministically is covered by the next one.)
-    ("compact_summaries_overrun_into_the_state", "double *const W1 = COMPACT ? P0 : P1;", "double *const W1 = P1;"),
-    ("resident_state_words_one_slot_low", "win[((4 + 4 * (F) + (i)) * T) >> 13][((4 + 4 * (F) + (i)) * T) & 8191]", "win[((3 + 4 * (F) + (i)) * T) >> 13][((3 + 4 * (F) + (i)) * T) & 8191]"),
-    # eighth batch: ebm_integrate's fused stretches
-    ("resident_sums_of_the_second_pair_land_on_the_first", "(unsigned)((i / 2) * 2 * T) + 2u * (unsigned)td,", "2u * (unsigned)td,"),
-    ("integrate_fused_stretch_restarts_its_forcing", "(int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,", "(int)n, f_steps, 0, h->integrate_spl,", "ebm_drive.hip"),
-    ("integrate_fused_stretch_one_table_entry_late", "rc = fused_range(h, tinx - 1, clock0 + tinx - 1,", "rc = fused_range(h, tinx, clock0 + tinx - 1,", "ebm_drive.hip"),
-    # (the step plan is one function now: the loop body reads the same result, so the winter step, fused through or
-    # not, is not taken for a snapshot step)
-    ("integrate_fuses_through_the_winter_snapshot", "s.snapshot = (ti == winter_inx && (winter || hm_winter)) || (ti == summer_inx && (summer || hm_summer));",
-     "s.snapshot = ti == summer_inx && (summer || hm_summer);", "ebm_drive.hip"),
-]
+`run` first runs TESTS against the unbroken product and gives no verdict unless that passes.  Then one line per mutant:
+KILLED (pytest's exit status is 1 and it names a FAILED test), SURVIVED (exit status 0: a hole in the suite, unless the mutant
+is marked "survives", an equivalent one kept as a control) or BROKEN (anything else — a collection error, no test ran, a
+library that was not built — which says nothing about the suite).  A time limit, an abort, a segmentation fault or a GPU fault
+ends the run there: nothing more is started.  Exit status 0: the baseline passed and every mutant did what its list expects.
+`run LIST --oracle-free` runs the list's ORACLE_FREE arguments in place of TESTS.  The sessions' outputs are
+mut_<name>.txt, the verdicts mutants_<list>.log, both in the suite's output directory (that of tests/conftest.py's
+measured_errors.jsonl, git-ignored): the one place under the repository root that `run` writes to."""
+import collections, glob, importlib.util, os, re, shutil, signal, subprocess, sys, tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+PKG = "energybalancemodel.jl_amd"
+BASE = {"csrc": os.path.join(PKG, "csrc"), "tree": PKG}
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from conftest import _ERRLOG  # noqa: E402             the suite's record of measured errors: the sessions' outputs go beside it
+OUT = os.path.dirname(_ERRLOG)
+NOT_COPIED = shutil.ignore_patterns(".git", "profiles", "build", os.path.basename(OUT), "__pycache__", ".pytest_cache")
+TROUBLE = {124: "its time limit", 137: "a kill", 134: "an abort", 139: "a segmentation fault"}
+GPU_FAULT = "an illegal memory access was encountered"
 
 
-def sources(csrc):
-    return sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+def lists():
+    found = {}
+    for path in sorted(glob.glob(os.path.join(HERE, "mutants_*.py"))):
+        spec = importlib.util.spec_from_file_location(os.path.basename(path)[:-3], path)
+        found[spec.name[len("mutants_"):]] = module = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(module)
+    return found
 
 
-def locate(csrc, old, where):
-    """The file of csrc/ that a mutant edits, or a string saying why there is none."""
-    counts = {f: open(os.path.join(csrc, f)).read().count(old) for f in (where or sources(csrc))}
+def fields(mutant):
+    return (*mutant, None, None)[:5]                # name, anchor, replacement, file, "survives"
+
+
+def locate(base, old, where):
+    """The file of the directory `base` that a mutant edits, or a string saying why there is none."""
+    files = [where] if where else sorted(f for f in os.listdir(base) if f.endswith((".hip", ".h", ".py")))
+    counts = {f: open(os.path.join(base, f)).read().count(old) for f in files}
     hits = {f: n for f, n in counts.items() if n}
     if sum(hits.values()) != 1:
         return None, f"anchor occurs {sum(hits.values())} times" + (f" ({hits})" if hits else "")
     return next(iter(hits)), None
 
 
-def check():
-    csrc = os.path.join(ROOT, "energybalancemodel.jl_amd", "csrc")
-    bad = 0
-    for name, old, new, *where in MUTANTS:
-        f, why = locate(csrc, old, where)
-        if f is None:
-            print(f"{name}: {why}")
-            bad += 1
-    print(f"{len(MUTANTS)} mutants, {bad} whose anchor does not occur exactly once")
+def patch(tree, lst, mutant):
+    """Apply one mutant to the copy `tree` of the repository (or of the part of it that holds the list's directory)."""
+    name, old, new, where, _ = fields(mutant)
+    base = os.path.join(tree, BASE[lst.KIND])
+    target, why = locate(base, old, where)
+    assert target is not None, (name, why)
+    path = os.path.join(base, target)
+    text = open(path).read()
+    open(path, "w").write(text.replace(old, new))
+
+
+def check(names):
+    found, total, bad = lists(), 0, 0
+    for key in names or found:
+        lst = found[key]
+        for m in lst.MUTANTS:
+            target, why = locate(os.path.join(ROOT, BASE[lst.KIND]), m[1], fields(m)[3])
+            if target is None:
+                print(f"{key}: {m[0]}: {why}")
+                bad += 1
+        print(f"{key}: {len(lst.MUTANTS)} mutants")
+        total += len(lst.MUTANTS)
+    print(f"{len(names or found)} lists, {total} mutants, {bad} whose anchor does not occur exactly once")
     return 1 if bad else 0
 
 
-def build(only=None):
-    src = os.path.join(ROOT, "energybalancemodel.jl_amd", "csrc")
+def build(key, only):
+    lst = lists()[key]
+    assert lst.KIND == "csrc", f"{key}: a {lst.KIND} list needs no build"
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    for name, old, new, *where in MUTANTS:
-        if only and name not in only:
+    for m in lst.MUTANTS:
+        if only and m[0] not in only:
             continue
-        target, why = locate(src, old, where)
-        assert target is not None, (name, why)
-        work = f"/tmp/mutant_{name}"
+        work = os.path.join(tempfile.gettempdir(), f"mutant_{m[0]}")
         shutil.rmtree(work, ignore_errors=True)
-        os.makedirs(os.path.join(work, "energybalancemodel.jl_amd"))
-        shutil.copytree(src, os.path.join(work, "energybalancemodel.jl_amd", "csrc"), ignore=shutil.ignore_patterns("build"))
+        shutil.copytree(os.path.join(ROOT, BASE["csrc"]), os.path.join(work, BASE["csrc"]), ignore=NOT_COPIED)
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(work, "include"))
-        path = os.path.join(work, "energybalancemodel.jl_amd", "csrc", target)
-        text = open(path).read()
-        open(path, "w").write(text.replace(old, new))
-        out = os.path.join(ROOT, "build", f"libebm_mut_{name}.so")
-        subprocess.check_call(["make", "-j8", "-C", os.path.dirname(path), f"OUT={out}", f"BUILD={work}/obj"], stdout=subprocess.DEVNULL)
+        patch(work, lst, m)
+        out = os.path.join(ROOT, "build", f"libebm_mut_{m[0]}.so")
+        subprocess.check_call(["make", "-j8", "-C", os.path.join(work, BASE["csrc"]), f"OUT={out}", f"BUILD={work}/obj"],
+                              stdout=subprocess.DEVNULL)
         print("built", out, flush=True)
 
 
+class Trouble(Exception):
+    pass
+
+
+def session(tests, limit, cwd, lib, log):
+    """One pytest session under its own time limit, its output in `log`: (exit status, output)."""
+    env = dict(os.environ, EBM_TEST_NO_CHILDREN="1", PYTHONDONTWRITEBYTECODE="1")
+    if lib:
+        env["EBM_LIB"] = lib
+    cmd = ["timeout", "-k", "10", str(limit), sys.executable, "-m", "pytest", *tests, "-q", "-p", "no:cacheprovider"]
+    with open(log, "w") as fh:
+        proc = subprocess.Popen(cmd, cwd=cwd, env=env, stdout=fh, stderr=subprocess.STDOUT)
+        try:
+            rc = proc.wait()
+        except BaseException:
+            proc.terminate()                        # `timeout` hands the signal on to pytest
+            proc.wait()
+            raise
+    text = open(log, errors="replace").read()
+    rc = 128 - rc if rc < 0 else rc                 # a signal's number, as a shell would report it
+    if rc in TROUBLE or GPU_FAULT in text:
+        raise Trouble(f"ended on {TROUBLE[rc]} (exit status {rc})" if rc in TROUBLE else f"'{GPU_FAULT}', exit status {rc}")
+    return rc, text
+
+
+def in_copy(lst, mutant, tests, log):
+    """A `tree` session: pytest inside a temporary copy of the tree, patched with `mutant` unless that is None."""
+    tmp = tempfile.mkdtemp(prefix="ebm_mutant_")
+    try:
+        tree = shutil.copytree(ROOT, os.path.join(tmp, "tree"), ignore=NOT_COPIED)
+        if mutant:
+            patch(tree, lst, mutant)
+        return session(tests, lst.LIMIT, tree, None, log)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def counts(text):
+    """(failed, passed) of pytest's summary line."""
+    last = next((l for l in reversed(text.splitlines()) if re.search(r"\d+ (failed|passed|skipped|deselected|errors?)\b", l)), "")
+    return tuple(int((re.search(rf"(\d+) {what}", last) or [0, 0])[1]) for what in ("failed", "passed"))
+
+
+def run(key, args):
+    lst = lists()[key]
+    oracle_free = "--oracle-free" in args
+    only = [a for a in args if a != "--oracle-free"]
+    tests, stem = (lst.ORACLE_FREE, "mut_anchors_") if oracle_free else (lst.TESTS, "mut_")
+    unknown = set(only) - {m[0] for m in lst.MUTANTS}
+    assert not unknown, f"{key} has no mutant {sorted(unknown)}"
+    os.makedirs(OUT, exist_ok=True)
+    report = open(os.path.join(OUT, f"mutants_{key}.log"), "w")
+
+    def say(line):
+        print(line, flush=True)
+        report.write(line + "\n")
+        report.flush()
+
+    name, log = "baseline", os.path.join(OUT, f"{stem}baseline_{key}.txt")
+    try:
+        rc, text = in_copy(lst, None, tests, log) if lst.KIND == "tree" else session(tests, lst.LIMIT, ROOT, None, log)
+        if rc != 0 or counts(text)[1] == 0:
+            say(f"{key}: the baseline does not pass ({' '.join(tests)}: exit status {rc}, {counts(text)[1]} passed): no verdicts; see {log}")
+            return 2
+        say(f"{key}: baseline: {counts(text)[1]} passed")
+        unexpected = 0
+        for m in lst.MUTANTS:
+            name, _, _, _, expect = fields(m)
+            if only and name not in only:
+                continue
+            log = os.path.join(OUT, f"{stem}{name}.txt")
+            lib = os.path.join(ROOT, "build", f"libebm_mut_{name}.so")
+            if lst.KIND == "tree":
+                rc, text = in_copy(lst, m, tests, log)
+            elif os.path.exists(lib):
+                rc, text = session(tests, lst.LIMIT, ROOT, lib, log)
+            else:
+                rc, text = None, ""
+            failed = [l for l in text.splitlines() if l.startswith("FAILED ")]
+            if rc == 1 and failed:
+                verdict = "KILLED"
+                say(f"{name}: KILLED, {'%d failed, %d passed' % counts(text)}, first: {failed[0][:140]}")
+                if "-x" not in tests:
+                    per_function = collections.Counter(re.split(r"[\[ ]", l.split("::")[1])[0] for l in failed)
+                    for function in sorted(per_function):
+                        say(f"    {per_function[function]:6d} {function}")
+            elif rc == 0:
+                verdict = "SURVIVED"
+                say(f"{name}: SURVIVED, {counts(text)[1]} passed" + (" (equivalent by construction: expected)" if expect == "survives" else ""))
+            else:
+                verdict = "BROKEN"
+                say(f"{name}: BROKEN, " + (f"{lib} is not built" if rc is None else f"pytest's exit status {rc} is no verdict; see {log}"))
+            unexpected += verdict != ("SURVIVED" if expect == "survives" else "KILLED")
+        say(f"{key}: {unexpected} of {len(only) or len(lst.MUTANTS)} mutants did not do what the list expects")
+        return 1 if unexpected else 0
+    except Trouble as t:
+        say(f"{key}: {name}: {t}; nothing more is started; see {log}")
+        return 3
+    except KeyboardInterrupt:
+        say(f"{key}: interrupted during {name}")
+        return 130
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(check())
+    signal.signal(signal.SIGTERM, signal.default_int_handler)       # a runner that is ended ends its session and removes its copy
+    command, args = sys.argv[1:2], sys.argv[2:]
+    if command == ["list"]:
+        for key, lst in lists().items():
+            print(f"{key}: {lst.KIND}, {len(lst.MUTANTS)} mutants, limit {lst.LIMIT} s, pytest {' '.join(lst.TESTS)}")
+            print("".join(f"    {m[0]}\n" for m in lst.MUTANTS), end="")
+    elif command == ["check"]:
+        sys.exit(check(args))
+    elif command == ["build"] and args:
+        build(args[0], args[1:])
+    elif command == ["run"] and args:
+        sys.exit(run(args[0], args[1:]))
     else:
-        print("\n".join(m[0] for m in MUTANTS))
+        sys.exit(__doc__)

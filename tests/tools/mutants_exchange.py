@@ -2,16 +2,15 @@
 rule and build this file uses unchanged, restricted to the mutants below.  Every mutant stays within the bounds of the
 arrays and of the caller's buffer.
 
-    python tests/tools/mutants_exchange.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_exchange.py build        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py check exchange        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build exchange        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run exchange          (GPU box: tests/test_gpu_exchange.py against each build)
 
-Then tests/test_gpu_exchange.py against every build/libebm_mut_*.so (EBM_LIB names the library).  What it does with each is
-recorded in profiles/r15_exchange_mutants.txt."""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+What tests/test_gpu_exchange.py does with each is recorded in profiles/r15_exchange_mutants.txt."""
+KIND = "csrc"
+TESTS = ("tests/test_gpu_exchange.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     # the two halves of a pair-split row swapped: natural unit u at split unit ((u & 1) ^ 1) * T + (u >> 1)
     ("exchange_wrong_split_unit", "const int p = split ? (u & 1) * T + (u >> 1) : u;", "const int p = split ? ((u & 1) ^ 1) * T + (u >> 1) : u;"),
     # every imported column takes record 0 whatever `records` says
@@ -22,11 +21,3 @@ mutants.MUTANTS = [
     ("import_writes_stale_slots", "ebm::ExchangeArgs a = exchange_args(h, r, r.current, const_cast<double *>(dev_buf));",
      "ebm::ExchangeArgs a = exchange_args(h, r, mask, const_cast<double *>(dev_buf));"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

@@ -3,10 +3,9 @@ tests/tools/mutants.py, whose anchor rule and build this file uses unchanged: th
 below.  Each changes arithmetic, a comparison or the order of in-bounds reads only — no bound, no launch shape — so a mutant
 computes wrong numbers and cannot fault.
 
-    python tests/tools/mutants_hist.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_hist.py build        (CPU: one full build per mutant under build/)
-    GPU box, per mutant, EBM_LIB=build/libebm_mut_<name>.so EBM_TEST_NO_CHILDREN=1:
-        python -m pytest tests/test_gpu_ensemble_hist.py -q -m gpu        (must fail)
+    python tests/tools/mutants.py check hist        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build hist        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run hist          (GPU box: tests/test_gpu_ensemble_hist.py must fail against each build)
 
 What each does (profiles/r22_hist_mutants.txt has the verdicts; the range's `w != 0.0 && x == x` is named `counts`, the sums'
 `in`, so that each anchor occurs once):
@@ -22,11 +21,10 @@ What each does (profiles/r22_hist_mutants.txt has the verdicts; the range's `w !
                                           and more
   range_later_equal_extreme_wins          strict `x < mn` becomes `x <= mn`: of +0.0 and -0.0 the last, not the first, gives
                                           the bits of the minimum"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_ensemble_hist.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("hist_value_equal_to_hi_stays_inside", "const bool below = x < lo, above = x >= hi;", "const bool below = x < lo, above = x > hi;",
      "ebm_ensemble.hip"),
     ("hist_clamp_dropped", "1 + min(i, nbins - 1);", "1 + min(i, nbins);", "ebm_ensemble.hip"),
@@ -35,11 +33,3 @@ mutants.MUTANTS = [
      "for (; b < a.nblocks; ++b) r = Combine::of(r, part[(a.nblocks - 1 - b) * stride], q);", "ebm_ensemble.hip"),
     ("range_later_equal_extreme_wins", "mn = (counts && x < mn) ? x : mn;", "mn = (counts && x <= mn) ? x : mn;", "ebm_ensemble.hip"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

@@ -3,10 +3,9 @@ rule and build this file uses unchanged: the same commands, restricted to the mu
 condition or the order of in-bounds reads only — no bound, no launch shape — so a mutant computes wrong numbers and cannot
 fault.
 
-    python tests/tools/mutants_misfits.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_misfits.py build        (CPU: one full build per mutant under build/)
-    GPU box, per mutant, EBM_LIB=build/libebm_mut_<name>.so EBM_TEST_NO_CHILDREN=1:
-        python -m pytest tests/test_gpu_column_misfits.py -q -m gpu        (must fail)
+    python tests/tools/mutants.py check misfits        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build misfits        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run misfits          (GPU box: tests/test_gpu_column_misfits.py must fail against each build)
 
 What each does (profiles/r23_misfit_mutants.txt has the verdicts):
   misfit_term_contracted_to_fma           J + (r d) d becomes fma(r d, d, J): one rounding less per term
@@ -17,11 +16,10 @@ What each does (profiles/r23_misfit_mutants.txt has the verdicts):
   misfit_nan_target_counts                `y == y` is dropped: a cell without an observation counts and makes J NaN
   misfit_odd_tail_padding_cell_read       the second cell of the last unit of an odd nlat, a padding cell, enters chain (l, 1)
   misfit_split_row_read_as_natural        the split flag is ignored: a pair-split row is walked in stored order"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_column_misfits.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("misfit_term_contracted_to_fma", "J = in ? J + t2 : J;", "J = in ? fma(t1, d, J) : J;", "ebm_misfit.hip"),
     ("misfit_tree_ascending", "for (int s = 32; s >= 1; s >>= 1) {", "for (int s = 1; s <= 32; s <<= 1) {", "ebm_misfit.hip"),
     ("misfit_variables_descending", "for (int v = 0; v < a.nvars; ++v) {", "for (int v = a.nvars - 1; v >= 0; --v) {", "ebm_misfit.hip"),
@@ -30,11 +28,3 @@ mutants.MUTANTS = [
     ("misfit_odd_tail_padding_cell_read", "live1 = k + 1 < a.nlat;", "live1 = k < a.nlat;", "ebm_misfit.hip"),
     ("misfit_split_row_read_as_natural", "const bool split = (a.split_mask >> v) & 1u;", "const bool split = false;", "ebm_misfit.hip"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

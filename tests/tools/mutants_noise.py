@@ -3,11 +3,11 @@ tests/tools/mutants.py, whose anchor rule and build this file uses unchanged: th
 below.  Each changes arithmetic or a predicate only — no address, no index bound, no launch shape — so a mutant computes
 wrong numbers and cannot fault.
 
-    python tests/tools/mutants_noise.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_noise.py build        (CPU: one full build per mutant under build/)
-    GPU box, per mutant, EBM_LIB=build/libebm_mut_<name>.so EBM_TEST_NO_CHILDREN=1:
-        python -m pytest tests/test_gpu_noise.py -q -m gpu        (the noise tests as they were: 180 cells, one or two waves)
-        python -m pytest tests/test_gpu_noise_sizes.py -q -m gpu  (must fail)
+    python tests/tools/mutants.py check noise        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build noise        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run noise          (GPU box: tests/test_gpu_noise_sizes.py must fail against each build)
+The verdicts below also say what tests/test_gpu_noise.py does (the noise tests as they were: 180 cells, one or two waves),
+which `run` does not ask.
 
 What each does (profiles/r18_noise_mutants.txt has the verdicts):
   noise_768_kernel_takes_the_register_sequence   miz_fused_kernel<2, ..., 768> evaluates the sequence itself although the
@@ -23,11 +23,10 @@ What each does (profiles/r18_noise_mutants.txt has the verdicts):
   step_counter_loses_its_high_word      noise_innovation feeds Philox the low 32 bits of the step only: steps 2^32 + k
                                         repeat steps k.  Both noise files must fail (tests/test_gpu_noise.py:
                                         test_innovations_match_the_host_restatement)"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_noise_sizes.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("noise_768_kernel_takes_the_register_sequence", "constexpr bool kNoiseMem = TT > kFusedRegThreads;",
      "constexpr bool kNoiseMem = TT > 768;", "ebm_miz_fused.h"),
     ("integrate_sequence_kernel_only_for_one_wave", "plan(K_MIZ_RESIDENT, 20, true)",
@@ -37,11 +36,3 @@ mutants.MUTANTS = [
     ("step_counter_loses_its_high_word", "unsigned w[4] = {(unsigned)un, (unsigned)(un >> 32),", "unsigned w[4] = {(unsigned)un, 0u,",
      "ebm_noise.h"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

@@ -2,20 +2,19 @@
 tests/tools/mutants.py, whose anchor rule and build this file uses unchanged: the same commands, restricted to the mutants
 below.  Wrong-number mutants only — an index, a flag, a field taken for another; none removes a wait or a barrier.
 
-    python tests/tools/mutants_pair_loads.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_pair_loads.py build        (CPU: one full build per mutant under build/)
-    GPU box, per mutant: EBM_LIB=build/libebm_mut_<name>.so EBM_TEST_NO_CHILDREN=1 python -m pytest tests/test_gpu_pair_loads.py -m gpu -q
+    python tests/tools/mutants.py check pair_loads        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build pair_loads        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run pair_loads          (GPU box: tests/test_gpu_pair_loads.py against each build)
 
 Each must fail tests/test_gpu_pair_loads.py (profiles/r25_pair_loads_mutants.txt):
   second_pair_loaded_at_first_pairs_index    every pair's Ei and D come from pair 0's place in the field
   second_pairs_Ei_gated_by_first_pairs_flag  pair 1's Ei is loaded, or left at +0.0, on the word of pair 0's flag
   second_pairs_D_gated_by_first_pairs_flag   the same for D
   second_pairs_Ei_and_D_swapped              pair 1's cell updates take the requested D for Ei and Ei for D"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_pair_loads.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("second_pair_loaded_at_first_pairs_index", "const unsigned ks = state_index<C, TT>(kq, j);", "const unsigned ks = state_index<C, TT>(kq, 0);"),
     ("second_pairs_Ei_gated_by_first_pairs_flag", "Ei2 = load_pair_unless_zero(st + S_Ei * a.fstride + ks, zold & zero_flag_bit(j, S_Ei));",
      "Ei2 = load_pair_unless_zero(st + S_Ei * a.fstride + ks, zold & zero_flag_bit(0, S_Ei));"),
@@ -24,11 +23,3 @@ mutants.MUTANTS = [
     ("second_pairs_Ei_and_D_swapped", "const double2 Ei2 = Ei2a[j], Dk2 = Dk2a[j];",
      "const double2 Ei2 = j ? Dk2a[j] : Ei2a[j], Dk2 = j ? Ei2a[j] : Dk2a[j];"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

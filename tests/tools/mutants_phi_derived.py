@@ -2,9 +2,9 @@
 tests/tools/mutants.py, whose list, anchor rule and build this file uses unchanged: the same commands, restricted to the
 mutants below.
 
-    python tests/tools/mutants_phi_derived.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_phi_derived.py build        (CPU: one full build per mutant under build/)
-    bash   tests/tools/mutants_run.sh                      (GPU box: the -m gpu suite against every build/libebm_mut_*.so)
+    python tests/tools/mutants.py check phi_derived        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build phi_derived        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run phi_derived          (GPU box: tests/test_gpu_phi_derived.py against each build)
 
 What tests/test_gpu_phi_derived.py does with each of its 102 cases (profiles/r14_phi_derived_mutants.txt):
   phi_restore_skipped                   the un-split pass moves the stale phi field instead of forming it: every case that
@@ -16,11 +16,10 @@ What tests/test_gpu_phi_derived.py does with each of its 102 cases (profiles/r14
   derived_phi_not_capped_in_phase_A     the cap at 1 dropped where the kernel forms phi for itself only (the shared piece,
                                         and with it every kernel that stores phi, keeps it): every case whose state has
                                         cells with -Ei / (Lf h) > 1 and derives at least once (76)"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_phi_derived.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("phi_restore_skipped", "return split ? Pass::SPLIT_STATE : phi_stored_ ? Pass::UNSPLIT_STATE : Pass::UNSPLIT_STATE_FORM_PHI;",
      "return split ? Pass::SPLIT_STATE : Pass::UNSPLIT_STATE;", "ebm_fieldbook.h"),
     # (every outside writer goes through this one event of the book: ebm_set_field is the one the tests reach first)
@@ -31,11 +30,3 @@ mutants.MUTANTS = [
     ("derived_phi_not_capped_in_phase_A", "for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);",
      "for (int i = 0; i < C; ++i) ph[i] = (hk[i] == 0.0) ? 0.0 : ieee_div(-Ei[i], p.Lf * hk[i]);"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

@@ -1,16 +1,15 @@
 """Broken builds of ebm_resample_columns for the mutation check of tests/tools/mutants.py, whose anchor rule and build this
 file uses unchanged, restricted to the mutants below.
 
-    python tests/tools/mutants_resample.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_resample.py build        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py check resample        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build resample        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run resample          (GPU box: tests/test_gpu_resample.py against each build)
 
-Then tests/test_gpu_resample.py against every build/libebm_mut_*.so (EBM_LIB names the library).  What it does with each is
-recorded in profiles/r14_resample_mutants.txt."""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+What tests/test_gpu_resample.py does with each is recorded in profiles/r14_resample_mutants.txt."""
+KIND = "csrc"
+TESTS = ("tests/test_gpu_resample.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     # the scatter pass reads the parent's row of the array itself: an in-place gather, no staging
     ("resample_scatters_in_place", "STAGE ? r.rows + (long long)e.y * r.row_stride : stage;",
      "r.rows + (long long)e.y * r.row_stride;"),
@@ -22,11 +21,3 @@ mutants.MUTANTS = [
      "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n    h->book.field_set(EBM_F_Ew);\n"),
     ("resample_keeps_the_scratch_dirty", "    if (borrowed) HIPCHK(hipMemsetAsync(h->scratch.get(), 0, sizeof(double) * moved * (size_t)h->pitch, s));\n", ""),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))

@@ -1,9 +1,9 @@
 """Broken builds of ebm_run_until for the mutation check of tests/tools/mutants.py, whose list, anchor rule and build this
 file uses unchanged: the same commands, restricted to the mutants below.
 
-    python tests/tools/mutants_until.py check        (CPU: every anchor occurs exactly once)
-    python tests/tools/mutants_until.py build        (CPU: one full build per mutant under build/)
-    bash   tests/tools/mutants_run.sh                (GPU box: the -m gpu suite against every build/libebm_mut_*.so)
+    python tests/tools/mutants.py check until        (CPU: every anchor occurs exactly once)
+    python tests/tools/mutants.py build until        (CPU: one full build per mutant under build/)
+    python tests/tools/mutants.py run until          (GPU box: tests/test_gpu_until.py against each build)
 
 What tests/test_gpu_until.py does with each (profiles/r13_until_mutants.txt):
   passage_level_must_be_passed_not_met    a measured level is met with equality at the bit, so nobody stops there: every
@@ -17,11 +17,10 @@ What tests/test_gpu_until.py does with each (profiles/r13_until_mutants.txt):
                                           stepped and live ones left behind, so the cases of tests/test_gpu_equilibrate.py
                                           and tests/test_gpu_equilibrate_lists.py in which a column freezes before the last
                                           year fail too"""
-import sys
-
-import mutants
-
-mutants.MUTANTS = [
+KIND = "csrc"
+TESTS = ("tests/test_gpu_until.py", "-m", "gpu")
+LIMIT = 300
+MUTANTS = [
     ("passage_level_must_be_passed_not_met", "const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;",
      "const bool crossed = p.direction[col] > 0 ? acc > level : acc < level;"),
     ("passage_nan_mean_counts_as_crossed", "const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;",
@@ -30,11 +29,3 @@ mutants.MUTANTS = [
      "const int lane = threadIdx.x, col = (int)blockIdx.x;"),
     ("passage_round_steps_the_stale_list", "        std::swap(cur, nxt);\n", "", "ebm_drive.hip"),
 ]
-
-if __name__ == "__main__":
-    if sys.argv[1:2] == ["build"]:
-        mutants.build(sys.argv[2:])
-    elif sys.argv[1:2] == ["check"]:
-        sys.exit(mutants.check())
-    else:
-        print("\n".join(m[0] for m in mutants.MUTANTS))
