@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "ebm_runtime.h"
+#include "ebm_savesol.h"
 
 using namespace ebm_rt;
 
@@ -423,14 +424,107 @@ int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const doubl
     return EBM_OK;
 }
 
-// integrate + savesol! (ebm_integrate) with, optionally, the per-column hemispheric means of the seasonal
-// outputs reduced on the device (ebm_integrate_hemispheric): hm_* are [nvars][dur][ncol] host arrays.
-//
-// Host output never stalls the stepping: what has to leave the device is first copied device -> device into a
-// buffer of its own on the compute stream (seasonal snapshots; the annual means come out of ONE finish-mean
-// launch; raw snapshots are written by the step kernel into one half of a two-part staging buffer), then the
-// handle's copier moves it to the caller's arrays — DMA into the pinned ring on its own stream, host threads
-// from there — while the following steps run.  A buffer is reused only after the job that reads it has finished.
+// The outputs of one integrate call on their way to the host: the copier, views into the handle's buffers
+// (ebm_ctx::integrate) and one method per action.  Host output never stalls the stepping: what has to leave the device is
+// first copied device -> device into a buffer of its own on the compute stream (seasonal snapshots; the annual means come out
+// of ONE finish-mean launch; raw snapshots are written by the step kernel into one half of the staging buffer), then the
+// handle's copier moves it to the caller's arrays — DMA into the pinned ring on its own stream, host threads from there —
+// while the following steps run.  A buffer is reused only after the job that reads it has finished.  When the owner goes out
+// of scope, on every path, the copier finishes what it was given: it reads these buffers and writes the caller's arrays.
+struct IntegrateOutputs {
+    IntegrateOutputs(ebm_ctx *handle, const ebm::SaveConfig &c, int nv, const FieldRef *v)
+        : h(handle), cp(handle->copier.get()), cfg(c), nvars(nv), vars(v), ncell((size_t)handle->ncol * handle->nlat),
+          npitch((size_t)handle->ncol * handle->pitch) {}
+    ~IntegrateOutputs() { (void)cp->wait_all(); }
+    // The handle's buffers, grown to this call's needs; the running sums start from zero.
+    int reserve(const ebm::RawStaging &staging, bool want_hm, bool want_snap) {
+        ebm_ctx::Integrate &b = h->integrate;
+        if (cfg.keep_raw) HIPCHK(b.stage.reserve(staging.total_elems()));
+        if (want_hm) HIPCHK(b.hm.reserve((size_t)h->ncol * (size_t)nvars));
+        if (cfg.want_sums) {
+            HIPCHK(b.sums.reserve(npitch * (size_t)nvars));
+            sums = b.sums.get();
+            HIPCHK(restart_sums());
+            HIPCHK(b.mean.reserve(npitch * (size_t)nvars));
+        }
+        if (want_snap) HIPCHK(b.snap.reserve(npitch * (size_t)nvars));
+        mean = b.mean.get(); snap = b.snap.get(); hm = b.hm.get();
+        stage = cfg.keep_raw ? b.stage.get() : nullptr;
+        return EBM_OK;
+    }
+    hipError_t restart_sums() const { return hipMemsetAsync(sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)); }
+    // one asynchronous job per saved variable: [ncol][pitch] on the device -> packed [ncol][nlat], row (v, year) of dst_base
+    hipError_t fields_out(double *dst_base, long long year, const double *dev_base) const {
+        hipError_t e = cp->order_after(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
+            CopyJob j;
+            j.src = dev_base + (size_t)v * npitch; j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat;
+            j.nrows = (size_t)h->ncol; j.dst = dst_base + cfg.row(v, year) * ncell;
+            cp->submit(j);
+        }
+        return e;
+    }
+    // seasonal snapshot: the state fields of this step, device -> device, then out
+    hipError_t snapshot_out(double *dst_base, long long year) const {
+        hipError_t e = cp->wait_all();                                       // the previous snapshot has left `snap`
+        for (int v = 0; v < nvars && e == hipSuccess; ++v)
+            e = hipMemcpyAsync(snap + (size_t)v * npitch, h->field[vars[v].field], sizeof(double) * npitch, hipMemcpyDeviceToDevice, main_stream(h));
+        if (e == hipSuccess) e = fields_out(dst_base, year, snap);
+        return e;
+    }
+    // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set — the state fields
+    // through their slots (from_mean false), or the [nvars][ncol*pitch] buffer of annual means — reduced on the device in one
+    // launch, [nvars][ncol] -> out[v][year][col]
+    hipError_t means_out(double *out, long long year, bool from_mean) const {
+        ebm::MeansArgs m{};
+        m.state = from_mean ? mean : h->state.get(); m.fstride = from_mean ? (long long)npitch : h->fstride;
+        for (int v = 0; v < nvars; ++v) m.slot[v] = from_mean ? v : vars[v].slot;
+        m.x = x_table(h); m.out = hm; m.var_stride = h->ncol;
+        m.pitch = (int)h->pitch; m.nlat = h->nlat; m.nvars = nvars;
+        hipError_t e = ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
+        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v)
+            e = hipMemcpy(out + cfg.row(v, year) * h->ncol, hm + (size_t)v * h->ncol, sizeof(double) * (size_t)h->ncol,
+                          hipMemcpyDeviceToHost);
+        return e;
+    }
+    // a year's end: ONE launch forms all means from the sums (and zeroes them)
+    hipError_t annual_mean_out(double *avg, double *hm_avg, long long year) const {
+        hipError_t e = cp->wait_all();                                       // last year's means have left `mean`
+        if (e == hipSuccess)
+            e = ebm::launch_finish_mean(mean, sums, (double)cfg.nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h));
+        if (e == hipSuccess && avg) e = fields_out(avg, year, mean);
+        if (e == hipSuccess && hm_avg) e = means_out(hm_avg, year, true);
+        return e;
+    }
+    // the half just filled goes out while the steps fill the other one — whose previous contents must have left
+    hipError_t flush_out(double *raw, const ebm::RawStaging &staging, const ebm::RawFlush &f) const {
+        hipError_t e = cp->wait_all();
+        if (e == hipSuccess) e = cp->order_after(main_stream(h));
+        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
+            CopyJob j;      // `count` snapshots of ncol rows each: (count * ncol) rows of nlat doubles, pitch apart
+            j.src = stage + staging.half_base_elems(f.half) + (size_t)v * staging.var_stride_elems();
+            j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat; j.nrows = (size_t)f.count * h->ncol;
+            j.dst = raw + staging.dst_snapshot(f, v) * ncell;
+            cp->submit(j);
+        }
+        return e;
+    }
+
+    ebm_ctx *const h;
+    HostCopier *const cp;
+    const ebm::SaveConfig &cfg;
+    const int nvars;
+    const FieldRef *const vars;
+    const size_t ncell, npitch;      // packed cells per snapshot (host side); device elements per field
+    double *sums = nullptr, *mean = nullptr, *snap = nullptr, *stage = nullptr, *hm = nullptr;
+};
+constexpr size_t kRawStageBytes = 128ull << 20;     // one half of the raw staging buffer, at most (and at least a snapshot)
+
+// integrate + savesol! (ebm_integrate) with, optionally, the per-column hemispheric means of the seasonal outputs reduced on
+// the device (ebm_integrate_hemispheric): hm_* are [nvars][dur][ncol] host arrays.  What every step owes, which stretches are
+// fused and where a raw snapshot is staged is ebm_savesol.h's; here are the argument checks, the buffers, and one loop over
+// the walk's items: the launches of the item, then what the item says, through IntegrateOutputs.
 static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps, int lastonly,
                           int winter_inx, int summer_inx, int nvars, const int *fields, double *raw,
                           double *winter, double *summer, double *avg, double *hm_winter, double *hm_summer,
@@ -447,169 +541,55 @@ static int integrate_impl(ebm_handle_t h, int nt, int dur, const double *f_steps
     for (int v = 0; v < nvars; ++v) save.var_of[vars[v].quantity] = (signed char)v;
     HIPCHK(hipSetDevice(h->device));
     if ((rc = get_copier(h))) return rc;
-    HostCopier *cp = h->copier.get();
-    HIPCHK(cp->wait_all());
-    // on every return: let the copier finish what it was given (it reads this call's device buffers and writes the caller's
-    // arrays)
-    const auto drain = finally([cp] { (void)cp->wait_all(); });
-    const size_t ncell = (size_t)h->ncol * h->nlat;          // packed cells per snapshot (host side)
-    const size_t npitch = (size_t)h->ncol * h->pitch;        // device elements per field
-    const long long total = (long long)nt * dur;
-    const long long nraw = lastonly ? nt : total;
-    const bool want_hm = (hm_winter || hm_summer || hm_avg) && nvars > 0;
-    const bool want_sums = (avg || hm_avg) && nvars > 0;
-    const bool want_snap = (winter || summer) && nvars > 0;
-    // Device buffers (kept in the handle between calls): raw snapshots are staged as two halves of
-    // [var][chunk][ncol][pitch]; the annual-mean sums are [var][ncol*pitch] (pair-split layout), the means and the
-    // seasonal snapshots [var][ncol*pitch] in the natural layout.
-    long long chunk = 0;
-    if (raw && nvars > 0) {
-        chunk = (long long)((128ull << 20) / (sizeof(double) * npitch * (size_t)nvars));
-        if (chunk < 1) chunk = 1;
-        if (chunk > nraw) chunk = nraw;
-        HIPCHK(h->ig_stage.reserve(2 * npitch * (size_t)nvars * (size_t)chunk));
-    }
-    if (want_hm) HIPCHK(h->ig_hm.reserve((size_t)h->ncol * (size_t)nvars));
-    if (want_sums) {
-        HIPCHK(h->ig_sums.reserve(npitch * (size_t)nvars));
-        HIPCHK(hipMemsetAsync(h->ig_sums.get(), 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));
-        HIPCHK(h->ig_mean.reserve(npitch * (size_t)nvars));
-    }
-    if (want_snap) HIPCHK(h->ig_snap.reserve(npitch * (size_t)nvars));
-    double *const sums = want_sums ? h->ig_sums.get() : nullptr, *const mean = h->ig_mean.get(), *const snap = h->ig_snap.get();
-    double *const hm = h->ig_hm.get();
-    double *const stage = (raw && nvars > 0) ? h->ig_stage.get() : nullptr;
-    // hemispheric_mean (src/utilities.jl:397-403) of every saved variable of a padded device field set — the state fields
-    // through their slots, or the [nvars][ncol*pitch] buffer of annual means — reduced on the device in one launch,
-    // [nvars][ncol] -> out[v][year][col]
-    ebm::MeansArgs of_state{}, of_mean{};
-    of_state.state = h->state.get(); of_state.fstride = h->fstride;
-    of_mean.state = h->ig_mean.get(); of_mean.fstride = (long long)npitch;
-    for (int v = 0; v < nvars; ++v) {
-        of_state.slot[v] = vars[v].slot;
-        of_mean.slot[v] = v;
-    }
-    auto means_to_host = [&](double *out, long long year, ebm::MeansArgs m) -> hipError_t {
-        m.x = x_table(h); m.out = hm; m.var_stride = h->ncol;
-        m.pitch = (int)h->pitch; m.nlat = h->nlat; m.nvars = nvars;
-        hipError_t e = ebm::launch_hemispheric_means(m, h->ncol, main_stream(h));
-        if (e == hipSuccess) e = hipStreamSynchronize(main_stream(h));
-        for (int v = 0; v < nvars && e == hipSuccess; ++v)
-            e = hipMemcpy(out + ((size_t)v * dur + (size_t)(year - 1)) * h->ncol, hm + (size_t)v * h->ncol,
-                          sizeof(double) * (size_t)h->ncol, hipMemcpyDeviceToHost);
-        return e;
-    };
-    save.sums = sums;
-    save.sum_stride = (long long)npitch;
-    save.stage_var_stride = chunk * (long long)npitch;
-    // one asynchronous job per saved variable: [ncol][pitch] on the device -> packed [ncol][nlat] at dst
-    auto fields_to_host = [&](double *dst_base, long long year, const double *dev_base) -> hipError_t {
-        hipError_t e = cp->order_after(main_stream(h));
-        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
-            CopyJob j;
-            j.src = dev_base + (size_t)v * npitch; j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat;
-            j.nrows = (size_t)h->ncol; j.dst = dst_base + ((size_t)v * dur + (size_t)(year - 1)) * ncell;
-            cp->submit(j);
-        }
-        return e;
-    };
-    // seasonal snapshot: the state fields of this step, device -> device, then out
-    auto season_to_host = [&](double *dst_base, long long year) -> hipError_t {
-        hipError_t e = cp->wait_all();                                       // the previous snapshot has left `snap`
-        for (int v = 0; v < nvars && e == hipSuccess; ++v)
-            e = hipMemcpyAsync(snap + (size_t)v * npitch, h->field[fields[v]], sizeof(double) * npitch, hipMemcpyDeviceToDevice, main_stream(h));
-        if (e == hipSuccess) e = fields_to_host(dst_base, year, snap);
-        return e;
-    };
-    long long staged = 0, raw_base = 0;   // snapshots in the current half of the staging buffer; raw index of its first
-    int half = 0;
+    HIPCHK(h->copier->wait_all());
+    ebm::SaveConfig cfg{nt, dur, lastonly != 0, winter_inx, summer_inx};
+    cfg.keep_raw = raw && nvars > 0;
+    cfg.want_winter = winter || hm_winter;
+    cfg.want_summer = summer || hm_summer;
+    cfg.want_sums = (avg || hm_avg) && nvars > 0;
+    // Stretches that need nothing but the running sums are fused, integrate_spl steps to a launch, with the state resident on
+    // the chip (miz_resident_kernel<SAVE>, miz_fused_kernel<2, ..., SAVE>; plain fused stepping when no mean is asked for): MIZ
+    // and MIZ_IMEX, every geometry but two cells per thread at 768 threads.
+    cfg.may_fuse = h->integrate_spl > 1 && h->model == EBM_MODEL_MIZ && (!cfg.want_sums || has_step_kernel(h, ebm::OUT_LOOP_SAVE));
+    IntegrateOutputs out(h, cfg, nvars, vars);
+    ebm::RawStaging staging;
+    if (cfg.keep_raw) staging = ebm::RawStaging(kRawStageBytes, out.npitch, nvars, cfg.nraw());
+    if ((rc = out.reserve(staging, (hm_winter || hm_summer || hm_avg) && nvars > 0, (winter || summer) && nvars > 0))) return rc;
+    save.sums = out.sums;
+    save.sum_stride = (long long)out.npitch;
+    save.stage_var_stride = (long long)staging.var_stride_elems();
+    double *const season_fields[] = {nullptr, winter, summer}, *const season_means[] = {nullptr, hm_winter, hm_summer};
     const long long clock0 = h->clock;    // model time continues from the handle's step clock (0 after ebm_create)
-    auto flush = [&]() -> hipError_t {
-        if (!staged) return hipSuccess;
-        // the half just filled goes out while the steps fill the other one — whose previous contents must have left
-        hipError_t e = cp->wait_all();
-        if (e == hipSuccess) e = cp->order_after(main_stream(h));
-        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
-            CopyJob j;      // `staged` snapshots of ncol rows each: (staged * ncol) rows of nlat doubles, pitch apart
-            j.src = stage + (size_t)half * (size_t)nvars * chunk * npitch + (size_t)v * chunk * npitch;
-            j.src_pitch = (size_t)h->pitch; j.row_elems = (size_t)h->nlat; j.nrows = (size_t)staged * h->ncol;
-            j.dst = raw + ((size_t)v * nraw + raw_base) * ncell;
-            cp->submit(j);
-        }
-        raw_base += staged;
-        staged = 0;
-        half ^= 1;
-        return e;
-    };
-    // What step tinx (1-based, as the reference; any tinx >= 1) needs besides the running sums: savesol!,
-    // src/infrastructure.jl:549-591.  The loop below reads it, and a stretch may be fused iff none of its steps needs anything.
-    struct StepNeeds {
-        bool raw;            // its raw snapshot is kept
-        int season;          // the seasonal index it falls on: 1 winter, 2 summer (winter first, as savesol!'s chain), 0 neither
-        bool snapshot;       // a seasonal output is taken from it: the step stores the diagnostic fields
-        bool year_end, last; // the last step of a year / of the run (or beyond it)
-        bool plain() const { return !raw && !snapshot && !year_end && !last; }
-    };
-    auto needs = [&](long long tinx) {
-        const long long ti = (tinx - 1) % nt + 1;
-        StepNeeds s;
-        s.raw = stage && (!lastonly || tinx > total - nt);
-        s.season = ti == winter_inx ? 1 : ti == summer_inx ? 2 : 0;
-        s.snapshot = (ti == winter_inx && (winter || hm_winter)) || (ti == summer_inx && (summer || hm_summer));
-        s.year_end = ti == nt;
-        s.last = tinx >= total;
-        return s;
-    };
-    // Stretches that need nothing but the running sums (no raw snapshot, no seasonal snapshot, not a year's last step, not the
-    // run's last step) are fused, integrate_spl steps to a launch, with the state resident on the chip
-    // (miz_resident_kernel<SAVE>, miz_fused_kernel<2, ..., SAVE>; plain fused stepping when no mean is asked for): MIZ and
-    // MIZ_IMEX, every geometry but two cells per thread at 768 threads.
-    const bool may_fuse = h->integrate_spl > 1 && h->model == EBM_MODEL_MIZ &&
-                          (!sums || has_step_kernel(h, ebm::OUT_LOOP_SAVE));
-    for (long long tinx = 1; tinx <= total; ++tinx) {              // 1-based, as the reference
-        if (may_fuse && needs(tinx).plain() && needs(tinx + 1).plain()) {
-            long long n = 2;
-            while (n < (1 << 30) && needs(tinx + n).plain()) ++n;
-            rc = fused_range(h, tinx - 1, clock0 + tinx - 1, (int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,
-                             sums ? &save : nullptr);
+    ebm::SaveWalk walk(cfg);
+    ebm::RawFlush full;
+    for (ebm::SaveItem it; walk.next(it);) {
+        const double *const f = f_steps ? f_steps + it.first : nullptr;
+        if (it.n > 1) {
+            rc = fused_range(h, it.first, clock0 + it.first, (int)it.n, f, 0, h->integrate_spl, it.sums ? &save : nullptr);
             if (rc) return rc;
-            tinx += n - 1;
             continue;
         }
-        const StepNeeds s = needs(tinx);
-        const long long ti = (tinx - 1) % nt + 1;
-        const long long year = (tinx - 1) / nt + 1;                // ceil(st.T[tinx])
-        const double f = f_steps ? f_steps[tinx - 1] : 0.0;
         // savesol! from the step kernel's registers: the annual-mean sums on every step, the raw snapshot on the steps that
         // are kept; the diagnostic FIELDS are only stored on steps whose snapshot is copied out of them (seasons) and on
         // the last one
-        const int diag = (s.snapshot || s.last) ? 1 : 0;
-        save.stage = s.raw ? stage + (size_t)half * (size_t)nvars * chunk * npitch : nullptr;
-        save.stage_offset = staged * (long long)npitch;
-        rc = do_step(h, h->ttab[ti - 1], h->ttab[ti % nt], f, diag, clock0 + tinx - 1, (sums || s.raw) ? &save : nullptr);
+        const ebm::SaveStep &s = it.step;
+        const bool kept = s.raw_index >= 0;
+        const ebm::RawSlot slot = staging.slot();
+        save.stage = kept ? out.stage + staging.half_base_elems(slot.half) : nullptr;
+        save.stage_offset = (long long)staging.slot_elems(slot);
+        rc = do_step(h, h->ttab[s.tab], h->ttab[s.tab_next], f ? *f : 0.0, s.diag() ? 1 : 0, clock0 + it.first,
+                     (it.sums || kept) ? &save : nullptr);
         if (rc) return rc;
-        if (s.raw && ++staged == chunk) HIPCHK(flush());
+        if (kept && staging.kept(full)) HIPCHK(out.flush_out(raw, staging, full));
         if (s.snapshot && (rc = natural_layout(h, true))) return rc;
-        if (s.season == 1) {
-            if (winter) HIPCHK(season_to_host(winter, year));
-            if (hm_winter) HIPCHK(means_to_host(hm_winter, year, of_state));
-        } else if (s.season == 2) {
-            if (summer) HIPCHK(season_to_host(summer, year));
-            if (hm_summer) HIPCHK(means_to_host(hm_summer, year, of_state));
-        } else if (s.year_end) {
-            if (sums) {
-                HIPCHK(cp->wait_all());                                      // last year's means have left `mean`
-                HIPCHK(ebm::launch_finish_mean(mean, sums, (double)nt, h->ncol, nvars, (long long)npitch, h->cfg, main_stream(h)));
-                if (avg) HIPCHK(fields_to_host(avg, year, mean));
-                if (hm_avg) HIPCHK(means_to_host(hm_avg, year, of_mean));
-            }
-        }
-        if (sums && s.year_end && s.season)                                  // year ended on a seasonal index:
-            HIPCHK(hipMemsetAsync(sums, 0, sizeof(double) * npitch * (size_t)nvars, main_stream(h)));  // no mean is taken, restart sums
+        if (season_fields[s.season]) HIPCHK(out.snapshot_out(season_fields[s.season], s.year));
+        if (season_means[s.season]) HIPCHK(out.means_out(season_means[s.season], s.year, false));
+        if (s.mean) HIPCHK(out.annual_mean_out(avg, hm_avg, s.year));
+        if (s.restart) HIPCHK(out.restart_sums());
     }
-    HIPCHK(flush());
+    if (staging.flush(full)) HIPCHK(out.flush_out(raw, staging, full));
     HIPCHK(hipStreamSynchronize(main_stream(h)));
-    HIPCHK(cp->wait_all());
+    HIPCHK(h->copier->wait_all());
     return EBM_OK;
 }
 

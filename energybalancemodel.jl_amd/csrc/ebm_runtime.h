@@ -2,6 +2,8 @@
 // idioms and the handle's stream.
 //   ebm_fieldbook.h   (HIP-free) the field predicates and THE rule of field validity, layout and phi: ebm_ctx::book
 //   ebm_plan.h        (HIP-free) the launch geometry and THE rule of a step launch's kernel, LDS and noise source: plan_step
+//   ebm_savesol.h     (HIP-free) THE rule of savesol!: what every step of an integrate owes its outputs, which stretches are
+//                     fused, and where a raw snapshot lies in the staging buffer: SaveWalk, RawStaging
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the one host path of the three
 //                     ensemble reductions (ebm_ensemble.hip) and of the column misfits (ebm_misfit.hip), the two diffusion
@@ -163,8 +165,12 @@ struct ebm_ctx {
     struct Misfit {
         DevVec<double> target, rw, out;
     } misfit;
-    // ebm_integrate's device buffers, kept between calls while the shape stays the same
-    DevVec<double> ig_sums, ig_mean, ig_snap, ig_stage, ig_hm;
+    // ebm_integrate's device buffers, kept between calls while the shape stays the same: the annual-mean sums
+    // [var][ncol*pitch] (pair-split layout), the means and the seasonal snapshots [var][ncol*pitch] in the natural layout, the
+    // raw snapshots staged as two halves of [var][chunk][ncol][pitch] (ebm::RawStaging), the hemispheric means [var][ncol]
+    struct Integrate {
+        DevVec<double> sums, mean, snap, stage, hm;
+    } integrate;
     ~ebm_ctx();
 };
 
