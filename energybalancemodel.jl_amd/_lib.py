@@ -20,6 +20,7 @@ MODEL = {"MIZ": 0, "Classic": 1, "MIZ_IMEX": 2}     # MIZ_IMEX: extension, see i
 GRID = {"identity": 0, "nonuniform": 1}
 FIELD = {"Ei": 0, "Ew": 1, "h": 2, "D": 3, "phi": 4, "T0": 5, "Tw": 6, "Ti": 7, "n": 8,
          "E": 9, "T": 10, "Tg": 11}
+SCALAR_KIND = {"integral": 0, "mean": 1, "edge_ge": 2, "edge_le": 3}     # enum ebm_scalar_kind
 PARAM_ORDER = ("D", "A", "B", "cw", "S0", "S1", "S2", "a0", "a2", "ai", "Fb", "k", "Lf", "F",
                "cg", "tau", "Tm", "m1", "m2", "alpha", "rl", "Dmin", "Dmax", "hmin", "kappa")
 _lib = None
@@ -87,6 +88,10 @@ SIGNATURES = {
     "ebm_ensemble_histogram_device": [_h, _i, _ip, _dp, _i, _dp, _dp, _dev],
     "ebm_column_misfits": [_h, _i, _ip, _i, _dp, _dp, _dp],
     "ebm_column_misfits_device": [_h, _i, _ip, _i, _dp, _dp, _dev],
+    "ebm_column_scalars": [_h, _i, _ip, _dp, _dp],
+    "ebm_column_scalars_device": [_h, _i, _ip, _dp, _dev],
+    "ebm_run_series_scalars": [_h, _ll, _i, _dp, _i, _i, _i, _ip, _dp, _dp],
+    "ebm_run_until_scalar": [_h, _ll, _i, _i, _dp, _i, _ip, _d, _dp, _ip, _ip, _ip, _dp],
     "ebm_sync": [_h],
     "ebm_get_counters": [_h, _llp],
     "ebm_reset_counters": [_h],

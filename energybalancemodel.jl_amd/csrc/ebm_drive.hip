@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 
 #include "ebm_runtime.h"
 #include "ebm_savesol.h"
@@ -367,15 +368,58 @@ int ebm_run_fused(ebm_handle_t h, long long first_step, int nsteps, const double
     return fused_range(h, first_step, first_step, nsteps, f_steps, diag_last, steps_per_launch, nullptr);
 }
 
-// ebm_run_series (include/ebm_hip.h).  Every sample is the stepping of ebm_run_fused over `every` steps — so a launch never
-// spans a sample — followed by one launch of hemispheric_means_kernel on the handle's stream, which writes the sample's
-// slot of the device series.  Nothing is synchronised between samples; the series comes down once, at the end.
+// ebm_run_series and ebm_run_series_scalars (include/ebm_hip.h): ONE loop, the reduction passed in.  Every sample is the
+// stepping of ebm_run_fused over `every` steps — so a launch never spans a sample — followed by one launch of the caller's
+// reduction on the handle's stream (reduce(out, stride): row v of the sample at out + v * stride), which writes the sample's
+// slot of the device series [nout][nsamples][ncol].  Nothing is synchronised between samples; the series comes down once, at
+// the end.  series_call: the checks the two share, before anything of theirs.
+static int series_call(const std::string &who, bool null_argument, long long first_step, int nsteps, int every, int steps_per_launch) {
+    if (null_argument) return fail(EBM_ERR_ARG, who + ": null argument");
+    if (nsteps < 0 || first_step < 0 || steps_per_launch < 1) return fail(EBM_ERR_ARG, who + ": bad argument");
+    if (every < 1) return fail(EBM_ERR_ARG, who + ": every must be >= 1");
+    if (nsteps % every) return fail(EBM_ERR_ARG, who + ": nsteps must be a multiple of every");
+    return EBM_OK;
+}
+using SampleReduce = std::function<hipError_t(double *out, long long stride)>;
+static int series_driver(ebm_ctx *h, const std::string &who, long long first_step, int nsteps, const double *f_steps, int every,
+                         int steps_per_launch, int nout, int diag, const SampleReduce &reduce, double *series) {
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, who + ": call ebm_set_time_table first");
+    const int nsamples = nsteps / every;
+    if (nsamples == 0) return EBM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    int rc = get_copier(h);
+    if (rc) return rc;
+    const size_t per_var = (size_t)nsamples * (size_t)h->ncol;
+    DevBuf<double> dev;
+    HIPCHK(dev_alloc(dev, (size_t)nout * per_var));
+    // the launches that write `dev` end before it is freed, on every path
+    const auto done = finally([h] { (void)hipStreamSynchronize(main_stream(h)); });
+    for (int j = 0; j < nsamples; ++j) {
+        const long long first = first_step + (long long)j * every;
+        const double *f = f_steps ? f_steps + (size_t)j * every : nullptr;
+        rc = steps_per_launch == 1 ? ebm_run(h, first, every, f, diag)
+                                   : fused_range(h, first, first, every, f, diag, steps_per_launch, nullptr);
+        if (rc) return rc;
+        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split, and the
+        // prognostic ones too: the reduction reads the natural layout (two conversions per sample then)
+        if ((rc = natural_layout(h, diag != 0))) return rc;
+        hipError_t e = reduce(dev.get() + (size_t)j * (size_t)h->ncol, (long long)per_var);
+        if (e != hipSuccess) return hip_fail(who + ": reduction", e);
+    }
+    HostCopier *c = h->copier.get();
+    HIPCHK(c->wait_all());
+    HIPCHK(c->order_after(main_stream(h)));
+    CopyJob job;     // [nout * nsamples] packed rows of ncol doubles
+    job.src = dev.get(); job.src_pitch = (size_t)h->ncol; job.row_elems = (size_t)h->ncol;
+    job.nrows = (size_t)nout * (size_t)nsamples; job.dst = series;
+    hipError_t e = c->run(job);
+    if (e != hipSuccess) return hip_fail(who, e);
+    return EBM_OK;
+}
+
 int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
                    int nvars, const int *fields, double *series) {
-    if (!h || !fields || !series) return fail(EBM_ERR_ARG, "ebm_run_series: null argument");
-    if (nsteps < 0 || first_step < 0 || steps_per_launch < 1) return fail(EBM_ERR_ARG, "ebm_run_series: bad argument");
-    if (every < 1) return fail(EBM_ERR_ARG, "ebm_run_series: every must be >= 1");
-    if (nsteps % every) return fail(EBM_ERR_ARG, "ebm_run_series: nsteps must be a multiple of every");
+    if (int rc = series_call("ebm_run_series", !h || !fields || !series, first_step, nsteps, every, steps_per_launch)) return rc;
     if (nvars < 1 || nvars > ebm::kMaxQuantities) return fail(EBM_ERR_ARG, "ebm_run_series: bad number of fields");
     FieldRef vars[ebm::kMaxQuantities];
     int rc = resolve_fields(h, "ebm_run_series", nvars, fields, vars);
@@ -386,42 +430,33 @@ int ebm_run_series(ebm_handle_t h, long long first_step, int nsteps, const doubl
         if (vars[v].diagnostic) diag = 1;
         sa.slot[v] = vars[v].slot;
     }
-    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_series: call ebm_set_time_table first");
-    const int nsamples = nsteps / every;
-    if (nsamples == 0) return EBM_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if ((rc = get_copier(h))) return rc;
-    const size_t per_var = (size_t)nsamples * (size_t)h->ncol;
-    DevBuf<double> dev;
-    HIPCHK(dev_alloc(dev, (size_t)nvars * per_var));
-    // the launches that write `dev` end before it is freed, on every path
-    const auto done = finally([h] { (void)hipStreamSynchronize(main_stream(h)); });
     sa.state = h->state.get(); sa.fstride = h->fstride;
     sa.x = x_table(h);
-    sa.var_stride = (long long)per_var;
     sa.pitch = (int)h->pitch; sa.nlat = h->nlat; sa.nvars = nvars;
-    for (int j = 0; j < nsamples; ++j) {
-        const long long first = first_step + (long long)j * every;
-        const double *f = f_steps ? f_steps + (size_t)j * every : nullptr;
-        rc = steps_per_launch == 1 ? ebm_run(h, first, every, f, diag)
-                                   : fused_range(h, first, first, every, f, diag, steps_per_launch, nullptr);
-        if (rc) return rc;
-        // a one-launch-per-step diagnostic step at four cells per thread leaves the MIZ diagnostic fields pair-split, and the
-        // prognostic ones too: the reduction reads the natural layout (two conversions per sample then)
-        if ((rc = natural_layout(h, diag != 0))) return rc;
-        sa.out = dev.get() + (size_t)j * (size_t)h->ncol;
-        hipError_t e = ebm::launch_hemispheric_means(sa, h->ncol, main_stream(h));
-        if (e != hipSuccess) return hip_fail("ebm_run_series: reduction", e);
-    }
-    HostCopier *c = h->copier.get();
-    HIPCHK(c->wait_all());
-    HIPCHK(c->order_after(main_stream(h)));
-    CopyJob job;     // [nvars * nsamples] packed rows of ncol doubles
-    job.src = dev.get(); job.src_pitch = (size_t)h->ncol; job.row_elems = (size_t)h->ncol;
-    job.nrows = (size_t)nvars * (size_t)nsamples; job.dst = series;
-    hipError_t e = c->run(job);
-    if (e != hipSuccess) return hip_fail("ebm_run_series", e);
-    return EBM_OK;
+    return series_driver(h, "ebm_run_series", first_step, nsteps, f_steps, every, steps_per_launch, nvars, diag,
+                         [&](double *out, long long stride) {
+                             sa.out = out; sa.var_stride = stride;
+                             return ebm::launch_hemispheric_means(sa, h->ncol, main_stream(h));
+                         }, series);
+}
+
+// ... with the nscal column scalars of ebm_column_scalars for a sample (one launch of column_scalars_kernel)
+int ebm_run_series_scalars(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
+                           int nscal, const int *spec, const double *level, double *series) {
+    if (int rc = series_call("ebm_run_series_scalars", !h || !spec || !level || !series, first_step, nsteps, every, steps_per_launch))
+        return rc;
+    ScalarRef sc[ebm::kMaxQuantities];
+    int rc = resolve_scalars(h, "ebm_run_series_scalars", nscal, spec, level, sc);
+    if (rc) return rc;
+    int diag = 0;
+    for (int s = 0; s < nscal; ++s)
+        if (sc[s].diagnostic) diag = 1;
+    ebm::ScalarArgs a = scalar_args(h, nscal, sc);
+    return series_driver(h, "ebm_run_series_scalars", first_step, nsteps, f_steps, every, steps_per_launch, nscal, diag,
+                         [&](double *out, long long stride) {
+                             a.out = out; a.out_stride = stride;
+                             return ebm::launch_column_scalars(a, h->ncol, main_stream(h));
+                         }, series);
 }
 
 // The outputs of one integrate call on their way to the host: the copier, views into the handle's buffers
@@ -678,26 +713,30 @@ int ebm_equilibrate(ebm_handle_t h, int nt, int max_years, int min_years, const 
 // the same bits — then passage_check_kernel takes each active column's mean and compares it with the column's level, and
 // the list advances (ActiveRounds): one stream synchronisation per round.  The fused kernels read and write the natural layout, so the fields of columns frozen in different rounds
 // share one layout.
-int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
-                  int field, const double *level, const int *direction, int *samples, int *crossed, double *value) {
-    if (!h || !level || !direction || !samples || !crossed) return fail(EBM_ERR_ARG, "ebm_run_until: null argument");
-    if (every < 1 || max_samples < 1) return fail(EBM_ERR_ARG, "ebm_run_until: every and max_samples must be >= 1");
-    if (steps_per_launch < 1 || first_step < 0) return fail(EBM_ERR_ARG, "ebm_run_until: bad argument");
-    FieldRef var;
-    int rc = resolve_fields(h, "ebm_run_until", 1, &field, &var);
-    if (rc) return rc;
+// (the two entry points below share until_call — the checks before the field's own — and until_driver, the rounds: `var` the
+// field, pa.scalar .. pa.edge_level the sample the check takes of it)
+static int until_call(const std::string &who, bool null_argument, long long first_step, int max_samples, int every, int steps_per_launch) {
+    if (null_argument) return fail(EBM_ERR_ARG, who + ": null argument");
+    if (every < 1 || max_samples < 1) return fail(EBM_ERR_ARG, who + ": every and max_samples must be >= 1");
+    if (steps_per_launch < 1 || first_step < 0) return fail(EBM_ERR_ARG, who + ": bad argument");
+    return EBM_OK;
+}
+static int until_driver(ebm_ctx *h, const std::string &who, long long first_step, int max_samples, int every, const double *f_steps,
+                        int steps_per_launch, int field, bool diagnostic, ebm::PassageArgs pa, const double *level, const int *direction,
+                        int *samples, int *crossed, double *value) {
+    int rc = EBM_OK;
     const int ncol = h->ncol;
     for (int c = 0; c < ncol; ++c) {
-        if (level[c] != level[c]) return fail(EBM_ERR_ARG, "ebm_run_until: level[" + std::to_string(c) + "] is NaN");
+        if (level[c] != level[c]) return fail(EBM_ERR_ARG, who + ": level[" + std::to_string(c) + "] is NaN");
         if (direction[c] == 0)
-            return fail(EBM_ERR_ARG, "ebm_run_until: direction[" + std::to_string(c) + "] is 0 (> 0: upward, < 0: downward)");
+            return fail(EBM_ERR_ARG, who + ": direction[" + std::to_string(c) + "] is 0 (> 0: upward, < 0: downward)");
     }
-    if (h->ttab.empty()) return fail(EBM_ERR_ARG, "ebm_run_until: call ebm_set_time_table first");
+    if (h->ttab.empty()) return fail(EBM_ERR_ARG, who + ": call ebm_set_time_table first");
     if (!has_step_kernel(h, ebm::OUT_LOOP))
-        return fail(EBM_ERR_UNSUPPORTED, "ebm_run_until: no fused-K kernel for this shape in this build");
+        return fail(EBM_ERR_UNSUPPORTED, who + ": no fused-K kernel for this shape in this build");
     HIPCHK(hipSetDevice(h->device));
     if ((rc = natural_layout(h, true))) return rc;
-    const int diag = var.diagnostic ? 1 : 0;
+    const int diag = diagnostic ? 1 : 0;
     // this call's device memory: value | level, and the active list with the round each column was last tested in and, as
     // its extra array, the directions
     DevBuf<double> dbl;
@@ -708,8 +747,7 @@ int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int eve
     // (value needs no initial contents: round 1 tests every column)
     HIPCHK(hipMemcpy(level_dev, level, sizeof(double) * (size_t)ncol, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(rounds.extra, direction, sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice));
-    ebm::PassageArgs pa{};
-    pa.field = h->field[var.field];
+    pa.field = h->field[field];
     pa.x = x_table(h);
     pa.level = level_dev; pa.direction = rounds.extra;
     pa.value = value_dev; pa.samples = rounds.round_of; pa.frozen = rounds.frozen;
@@ -725,14 +763,39 @@ int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int eve
         pa.cols = rounds.cur;
         pa.round = j;
         hipError_t e = ebm::launch_passage_check(pa, rounds.nactive, main_stream(h));
-        if (e != hipSuccess) return hip_fail("ebm_run_until: check", e);
+        if (e != hipSuccess) return hip_fail(who + ": check", e);
         if (j == max_samples) break;                             // (no further round: no list is needed)
-        if ((rc = rounds.advance("ebm_run_until")) < 0) return rc;
+        if ((rc = rounds.advance(who.c_str())) < 0) return rc;
         if (rc == 0) break;                                      // every column has crossed
     }
     if ((rc = rounds.download(samples, crossed))) return rc;
     if (value) HIPCHK(hipMemcpy(value, value_dev, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost));
     return EBM_OK;
+}
+
+int ebm_run_until(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
+                  int field, const double *level, const int *direction, int *samples, int *crossed, double *value) {
+    if (int rc = until_call("ebm_run_until", !h || !level || !direction || !samples || !crossed, first_step, max_samples, every, steps_per_launch))
+        return rc;
+    FieldRef var;
+    if (int rc = resolve_fields(h, "ebm_run_until", 1, &field, &var)) return rc;
+    return until_driver(h, "ebm_run_until", first_step, max_samples, every, f_steps, steps_per_launch, var.field, var.diagnostic,
+                        ebm::PassageArgs{}, level, direction, samples, crossed, value);
+}
+
+// ... with m_c the column scalar spec[4], scalar_level of ebm_column_scalars (passage_scalar_kernel takes it)
+int ebm_run_until_scalar(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
+                         const int *spec, double scalar_level, const double *level, const int *direction, int *samples, int *crossed,
+                         double *value) {
+    if (int rc = until_call("ebm_run_until_scalar", !h || !spec || !level || !direction || !samples || !crossed, first_step, max_samples, every,
+                            steps_per_launch))
+        return rc;
+    ScalarRef sc;
+    if (int rc = resolve_scalars(h, "ebm_run_until_scalar", 1, spec, &scalar_level, &sc)) return rc;
+    ebm::PassageArgs pa{};
+    pa.scalar = 1; pa.kind = sc.kind; pa.k0 = sc.k0; pa.k1 = sc.k1; pa.edge_level = sc.level;
+    return until_driver(h, "ebm_run_until_scalar", first_step, max_samples, every, f_steps, steps_per_launch, sc.field, sc.diagnostic, pa,
+                        level, direction, samples, crossed, value);
 }
 
 }  // extern "C"

@@ -60,6 +60,38 @@ int get_copier(ebm_ctx *h) {
     return EBM_OK;
 }
 
+static_assert((int)EBM_S_INTEGRAL == (int)ebm::S_INTEGRAL && (int)EBM_S_MEAN == (int)ebm::S_MEAN && (int)EBM_S_EDGE_GE == (int)ebm::S_EDGE_GE &&
+              (int)EBM_S_EDGE_LE == (int)ebm::S_EDGE_LE && (int)EBM_S_COUNT == (int)ebm::S_KINDS, "enum ebm_scalar_kind");
+int resolve_scalars(const ebm_ctx *h, const char *who, int nscal, const int *spec, const double *level, ScalarRef *out) {
+    const std::string me(who);
+    if (nscal < 1 || nscal > ebm::kMaxQuantities)
+        return fail(EBM_ERR_ARG, me + ": nscal = " + std::to_string(nscal) + " is outside 1 ... " + std::to_string(ebm::kMaxQuantities));
+    for (int s = 0; s < nscal; ++s) {
+        const int kind = spec[4 * s], f = spec[4 * s + 1], k0 = spec[4 * s + 2], k1 = spec[4 * s + 3];
+        const std::string it = me + ": scalar " + std::to_string(s) + ": ";
+        const bool edge = kind == EBM_S_EDGE_GE || kind == EBM_S_EDGE_LE;
+        if (kind < 0 || kind >= EBM_S_COUNT) return fail(EBM_ERR_ARG, it + "unknown kind " + std::to_string(kind));
+        if (!h->book.has(f) || quantity_of(h->model, f) < 0) return fail(EBM_ERR_ARG, it + "its field is not a solution variable of this model");
+        if (k0 < 0 || k1 > h->nlat - 1 || k0 > k1)
+            return fail(EBM_ERR_ARG, it + "the band k0 = " + std::to_string(k0) + ", k1 = " + std::to_string(k1) + " is not 0 <= k0 <= k1 <= " +
+                                         std::to_string(h->nlat - 1));
+        if (!edge && k0 == k1) return fail(EBM_ERR_ARG, it + "an integral over one cell (k0 == k1 = " + std::to_string(k0) + ")");
+        if (edge && level[s] != level[s]) return fail(EBM_ERR_ARG, it + "the level of an edge is NaN");
+        out[s] = {f, kind, k0, k1, level[s], h->book.is_diagnostic(f)};
+    }
+    return EBM_OK;
+}
+ebm::ScalarArgs scalar_args(const ebm_ctx *h, int nscal, const ScalarRef *sc) {
+    ebm::ScalarArgs a{};
+    for (int s = 0; s < nscal; ++s) {
+        a.row[s] = h->field[sc[s].field];
+        a.kind[s] = sc[s].kind; a.k0[s] = sc[s].k0; a.k1[s] = sc[s].k1; a.level[s] = sc[s].level;
+    }
+    a.x = x_table(h);
+    a.pitch = (int)h->pitch; a.nscal = nscal;
+    return a;
+}
+
 }  // namespace ebm_rt
 
 namespace {
@@ -284,6 +316,25 @@ int column_misfits(ebm_ctx *h, int nvars, const int *fields, int ntargets, const
     return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), nout, r.s, who);
 }
 
+// ebm_column_scalars and its _device form (include/ebm_hip.h): the checks, then every field readable as ebm_hemispheric_mean
+// makes its one (open_field's steps, the arguments of all scalars before the first conversion), and the one launch into dev_out
+// (the caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
+int column_scalars(ebm_ctx *h, int nscal, const int *spec, const double *level, double *host_out, double *dev_out, const char *who) {
+    if (!h || !spec || !level || !(host_out || dev_out)) return fail(EBM_ERR_ARG, std::string(who) + ": null argument");
+    ScalarRef sc[ebm::kMaxQuantities];
+    if (int rc = resolve_scalars(h, who, nscal, spec, level, sc)) return rc;
+    for (int s = 0; s < nscal; ++s)
+        if (int rc = check_current(h, sc[s].field, who)) return rc;
+    for (int s = 0; s < nscal; ++s)
+        if (int rc = make_readable(h, sc[s].field)) return rc;
+    if (!dev_out) HIPCHK(h->scalars_out.reserve((size_t)ebm::kMaxQuantities * (size_t)h->ncol));
+    ebm::ScalarArgs a = scalar_args(h, nscal, sc);
+    a.out = dev_out ? dev_out : h->scalars_out.get();
+    a.out_stride = h->ncol;
+    const hipStream_t st = main_stream(h);
+    return ensemble_close(ebm::launch_column_scalars(a, h->ncol, st), dev_out ? nullptr : host_out, a.out, (size_t)nscal * (size_t)h->ncol, st, who);
+}
+
 // ebm_diffusion / ebm_zonal_diffusion: three fields of [ncol][pitch], zero-padded, kept until the handle is destroyed
 int get_scratch(ebm_ctx *h) {
     if (h->scratch) return EBM_OK;
@@ -438,6 +489,14 @@ int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntarget
 int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target, const double *rw,
                               double *dev_out) {
     return column_misfits(h, nvars, fields, ntargets, target, rw, nullptr, dev_out, "ebm_column_misfits_device");
+}
+
+int ebm_column_scalars(ebm_handle_t h, int nscal, const int *spec, const double *level, double *out) {
+    return column_scalars(h, nscal, spec, level, out, nullptr, "ebm_column_scalars");
+}
+
+int ebm_column_scalars_device(ebm_handle_t h, int nscal, const int *spec, const double *level, double *dev_out) {
+    return column_scalars(h, nscal, spec, level, nullptr, dev_out, "ebm_column_scalars_device");
 }
 
 int ebm_get_field_device(ebm_handle_t h, int field, double *dev_out) {

@@ -167,8 +167,28 @@ struct PassageArgs {
     double *value;                   // [ncol]
     int *samples, *frozen;           // [ncol]
     int pitch, nlat, round;
+    // ebm_run_until_scalar: m = the column scalar (kind, k0, k1, edge_level) of the field in place of its mean
+    int scalar;                      // 0: the hemispheric mean (ebm_run_until)
+    int kind, k0, k1;
+    double edge_level;
 };
 hipError_t launch_passage_check(const PassageArgs &p, int nactive, hipStream_t s);
+// Column scalars (ebm_column_scalars, include/ebm_hip.h: the definition): out[s * out_stride + col] = scalar s of column col <
+// ncol, by column_scalar (ebm_launch.hip) — the integral kinds through hemispheric_means_of_column on the band, the edge kinds
+// by a search for the first hit and one interpolation.  One wave per (column, scalar), one launch.  row[s]: the field of
+// scalar s, [ncol][pitch], natural layout (several scalars may name one row); 0 <= k0[s] <= k1[s] < nlat, checked by the caller.
+// ebm_run_series_scalars: `out` is the sample's first word in the device series [nscal][nsamples][ncol].
+enum ScalarKind { S_INTEGRAL = 0, S_MEAN = 1, S_EDGE_GE = 2, S_EDGE_LE = 3, S_KINDS = 4 };     // enum ebm_scalar_kind
+struct ScalarArgs {
+    const double *row[kMaxQuantities];
+    const double *x;
+    double *out;
+    long long out_stride;
+    double level[kMaxQuantities];
+    int kind[kMaxQuantities], k0[kMaxQuantities], k1[kMaxQuantities];
+    int pitch, nscal;
+};
+hipError_t launch_column_scalars(const ScalarArgs &a, int ncol, hipStream_t s);
 // the next active list: out = the entries of in[0 .. n) whose column is not frozen, in order; *count = their number
 // (one workgroup)
 hipError_t launch_compact_active(const int *in, int n, const int *frozen, int *out, int *count, hipStream_t s);

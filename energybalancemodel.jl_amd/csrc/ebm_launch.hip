@@ -30,6 +30,7 @@
 //   diffusion_kernel<GRID>              the diffusion operator on its own (ebm_diffusion)                  [this file]
 //   finish_mean, hemispheric_means, mask_from_t0, derive_params, divide, permute_fields (split / unsplit), restore_phi,
 //   noise_innovations, noise_sequence, equilibrium_check, passage_check, compact_active: small helpers     [this file]
+//   column_scalars, passage_scalar: band integrals / means and edge positions per column (column_scalar)   [this file]
 //   zonal_sweep, zonal_seg_forward / _backward, zonal_reduced_solve: the zonal diffusion substep           [ebm_zonal.hip]
 // and every host-side launcher of the MIZ, classic and helper kernels [this file].  Which step kernel a launch takes, with
 // how much LDS and which noise source, is decided in ebm_plan.h (plan_step: plain C++, no HIP); this file only executes a
@@ -38,7 +39,7 @@
 // (halo exchanges, the tridiagonal solve), ebm_miz_pieces.h (the pieces of the MIZ step), ebm_kernel_table.h (sizes and lookup).
 // C = cells per thread (4; 2 for a few short meridians), GRID = 0 identity / 1 any other grid, T =
 // workgroup size as a compile-time constant (the lists of sizes and the lookup are in ebm_kernel_table.h).  Every one of
-// the 521 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
+// the 523 kernels uses 0 bytes of scratch (tests/tools/resource_usage.py).
 // The three MIZ step kernels are bit-identical by contract: every piece of the step that they do not do differently
 // (pointwise physics, Tbar stencil, implicit-diffusion increments and rows, neighbour selection) has one definition, in
 // ebm_miz_pieces.h; what stays in each kernel is how it holds its state and loads its tables.
@@ -315,22 +316,97 @@ hipError_t launch_equilibrium_check(const EquilArgs &e, int nactive, hipStream_t
 // ebm_run_until's test after a round, one wave per active column c = cols[b] (PassageArgs): the hemispheric mean of the one
 // field (hemispheric_means_of_column: lane 0 holds it), then the comparison with the column's level.  A NaN mean fails both
 // comparisons: it never crosses.
+// (one lane: the round's verdict on column col, whose sample is acc — the mean here, a column scalar below)
+__device__ __forceinline__ void passage_verdict(const PassageArgs &p, int col, double acc) {
+    const double level = p.level[col];
+    const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;
+    p.value[col] = acc;
+    p.samples[col] = p.round;
+    p.frozen[col] = crossed ? 1 : 0;
+}
 __global__ void __launch_bounds__(64) passage_check_kernel(const PassageArgs p) {
     __shared__ double terms[kMeanTile];
     const int lane = threadIdx.x, col = p.cols[blockIdx.x];
     const double *const f = p.field + (size_t)col * (size_t)p.pitch;
     const double acc = hemispheric_means_of_column<64>([&](int) { return f; }, p.x, p.nlat, 1, terms, kMeanTile);
-    if (lane == 0) {
-        const double level = p.level[col];
-        const bool crossed = p.direction[col] > 0 ? acc >= level : acc <= level;
-        p.value[col] = acc;
-        p.samples[col] = p.round;
-        p.frozen[col] = crossed ? 1 : 0;
+    if (lane == 0) passage_verdict(p, col, acc);
+}
+
+// A COLUMN SCALAR (include/ebm_hip.h, ebm_column_scalars: the definition) of the row f of one column, by one wave; lane 0
+// returns it.  kind, k0, k1 and level are the same in every lane.
+//   integral kinds  hemispheric_means_of_column over the cells k0 .. k1 (shifted pointers: the one sum of the library, so the
+//                   full range IS ebm_hemispheric_mean); S_MEAN divides once by x[k1] - x[k0]
+//   edge kinds      the smallest K in k0 .. k1 with a hit: tiles of 256 cells, lane l loads the cells l, l + 64, l + 128, l + 192
+//                   of the tile (four coalesced 512-byte requests in flight), keeps the first of its hits, and a cross-lane min
+//                   gives the tile's; the walk ends at the first tile with a hit, so a row is read at most once.  Then lane 0
+//                   loads f[K-1], f[K], x[K-1], x[K] and interpolates: the value depends on K and these four only
+// terms: the mean's LDS tile (kMeanTile doubles); the edge kinds use no LDS.
+constexpr int kNoHit = 0x7fffffff;                       // later than any cell
+__device__ __forceinline__ bool scalar_hit(int kind, double v, double level) { return kind == S_EDGE_GE ? v >= level : v <= level; }
+__device__ __forceinline__ int earlier_hit(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ double column_scalar(int kind, const double *__restrict__ f, const double *__restrict__ x, int k0, int k1,
+                                                double level, double *terms) {
+    const int lane = threadIdx.x;
+    if (kind == S_INTEGRAL || kind == S_MEAN) {
+        const double *const band = f + k0;
+        const double acc = hemispheric_means_of_column<64>([&](int) { return band; }, x + k0, k1 - k0 + 1, 1, terms, kMeanTile);
+        return kind == S_MEAN ? ieee_div(acc, x[k1] - x[k0]) : acc;
     }
+    int K = kNoHit;
+    for (int base = k0; base <= k1 && K == kNoHit; base += 256) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = base + 64 * u + lane;
+            v[u] = k <= k1 ? f[k] : __builtin_nan("");        // (NaN hits nothing)
+        }
+        int first = kNoHit;
+#pragma unroll
+        for (int u = 3; u >= 0; --u)
+            if (scalar_hit(kind, v[u], level)) first = base + 64 * u + lane;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) first = earlier_hit(first, __shfl_xor(first, off, 64));
+        K = first;
+    }
+    if (lane != 0) return 0.0;
+    if (K == kNoHit) return __builtin_inf();             // no edge in the band
+    if (K == k0) return x[k0];
+    const double a = f[K - 1], b = f[K];
+    if (!__builtin_isfinite(a) || !__builtin_isfinite(b)) return x[K];
+    const double t = ieee_div(level - a, b - a);
+    return x[K - 1] + t * (x[K] - x[K - 1]);
+}
+// ebm_column_scalars, ebm_run_series_scalars (ScalarArgs): one wave per (column, scalar), blockIdx = (col, s)
+__global__ void __launch_bounds__(64) column_scalars_kernel(const ScalarArgs a) {
+    __shared__ double terms[kMeanTile];
+    const int col = blockIdx.x, s = blockIdx.y;
+    const double *const f = a.row[s] + (size_t)col * (size_t)a.pitch;
+    const double v = column_scalar(a.kind[s], f, a.x, a.k0[s], a.k1[s], a.level[s], terms);
+    if (threadIdx.x == 0) a.out[(size_t)s * (size_t)a.out_stride + col] = v;
+}
+hipError_t launch_column_scalars(const ScalarArgs &a, int ncol, hipStream_t s) {
+    if (ncol < 1 || a.nscal < 1 || a.nscal > kMaxQuantities) return hipErrorInvalidValue;
+    for (int i = 0; i < a.nscal; ++i)
+        if (a.kind[i] < 0 || a.kind[i] >= S_KINDS || a.k0[i] < 0 || a.k0[i] > a.k1[i] || a.k1[i] >= a.pitch) return hipErrorInvalidValue;
+    column_scalars_kernel<<<dim3((unsigned)ncol, (unsigned)a.nscal), 64, 0, s>>>(a);
+    return hipGetLastError();
+}
+// ebm_run_until_scalar's test after a round: passage_check_kernel with the column scalar for a sample
+__global__ void __launch_bounds__(64) passage_scalar_kernel(const PassageArgs p) {
+    __shared__ double terms[kMeanTile];
+    const int col = p.cols[blockIdx.x];
+    const double *const f = p.field + (size_t)col * (size_t)p.pitch;
+    const double m = column_scalar(p.kind, f, p.x, p.k0, p.k1, p.edge_level, terms);
+    if (threadIdx.x == 0) passage_verdict(p, col, m);
 }
 hipError_t launch_passage_check(const PassageArgs &p, int nactive, hipStream_t s) {
     if (nactive < 1 || p.nlat < 1 || p.nlat > p.pitch) return hipErrorInvalidValue;
-    passage_check_kernel<<<nactive, 64, 0, s>>>(p);
+    if (!p.scalar) {
+        passage_check_kernel<<<nactive, 64, 0, s>>>(p);
+        return hipGetLastError();
+    }
+    if (p.kind < 0 || p.kind >= S_KINDS || p.k0 < 0 || p.k0 > p.k1 || p.k1 >= p.nlat) return hipErrorInvalidValue;
+    passage_scalar_kernel<<<nactive, 64, 0, s>>>(p);
     return hipGetLastError();
 }
 

@@ -165,6 +165,7 @@ struct ebm_ctx {
     struct Misfit {
         DevVec<double> target, rw, out;
     } misfit;
+    DevVec<double> scalars_out;                    // ebm_column_scalars: the result of the host variant ([12][ncol]), kept between calls
     // ebm_integrate's device buffers, kept between calls while the shape stays the same: the annual-mean sums
     // [var][ncol*pitch] (pair-split layout), the means and the seasonal snapshots [var][ncol*pitch] in the natural layout, the
     // raw snapshots staged as two halves of [var][chunk][ncol][pitch] (ebm::RawStaging), the hemispheric means [var][ncol]
@@ -217,5 +218,15 @@ int natural_layout(ebm_ctx *h, bool diagnostics_too);   // the prognostic fields
 hipError_t restore_phi(ebm_ctx *h);
 int state_written_outside(ebm_ctx *h);            // restore_phi, then FieldBook::state_written_outside
 int get_copier(ebm_ctx *h);                       // ebm_fields.hip: the handle's pinned staging ring, created on first use
+// A caller's column scalars (ebm_column_scalars, ebm_run_series_scalars, ebm_run_until_scalar; ebm_fields.hip): spec[nscal][4]
+// and level[nscal] checked by the rules of include/ebm_hip.h — the message names the first offending scalar — into out[s]
+struct ScalarRef {
+    int field, kind, k0, k1;
+    double level;
+    bool diagnostic;
+};
+int resolve_scalars(const ebm_ctx *h, const char *who, int nscal, const int *spec, const double *level, ScalarRef *out);
+// ... and as launch arguments: the rows where they lie (natural layout: the caller's duty), the bands, x
+ebm::ScalarArgs scalar_args(const ebm_ctx *h, int nscal, const ScalarRef *sc);
 
 }  // namespace ebm_rt

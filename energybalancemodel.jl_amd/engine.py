@@ -473,19 +473,23 @@ class Engine:
             check(self.lib.ebm_run(self._h, int(first_step), int(nsteps), dptr(a), int(diag_last)),
                   "ebm_run")
 
-    def check_series_args(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
-        """The host-side checks of ``run_series`` (no device call): returns (names, field ids, f_steps)."""
-        names, ids = self._fields(names, most=len(self.prognostic + self.diagnostic), repeats=False)
+    @staticmethod
+    def _check_sampling(who, first_step, nsteps, every, f_steps, steps_per_launch):
+        """The step arguments of ``run_series`` and ``run_series_scalars`` (no device call): returns f_steps."""
         if int(first_step) < 0 or int(nsteps) < 0:
-            raise ValueError("run_series: first_step and nsteps must be >= 0")
+            raise ValueError(f"{who}: first_step and nsteps must be >= 0")
         if int(every) < 1:
             raise ValueError(f"every = {every}: a sample is taken every `every` >= 1 steps")
         if int(nsteps) % int(every):
             raise ValueError(f"nsteps = {nsteps} is not a multiple of every = {every}")
         if int(steps_per_launch) < 1:
             raise ValueError(f"steps_per_launch = {steps_per_launch}: need at least one step per launch")
-        f = None if f_steps is None else as_f64(f_steps, (int(nsteps),))
-        return names, ids, f
+        return None if f_steps is None else as_f64(f_steps, (int(nsteps),))
+
+    def check_series_args(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
+        """The host-side checks of ``run_series`` (no device call): returns (names, field ids, f_steps)."""
+        names, ids = self._fields(names, most=len(self.prognostic + self.diagnostic), repeats=False)
+        return names, ids, self._check_sampling("run_series", first_step, nsteps, every, f_steps, steps_per_launch)
 
     def run_series(self, first_step, nsteps, every, names, f_steps=None, steps_per_launch=64):
         """ebm_run_series: ``nsteps`` steps from global step ``first_step`` exactly as ``run`` takes them (``diag_last`` iff
@@ -579,16 +583,15 @@ class Engine:
                                        iptr(years), iptr(conv), dptr(resid)), "ebm_equilibrate")
         return dict(years=years.astype(np.int64), converged=conv.astype(bool), resid={n: resid[i] for i, n in enumerate(names)})
 
-    def check_until_args(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
-        """The host-side checks of ``run_until`` (no device call): returns (field id, level [ncol] float64, direction [ncol]
-        int32, f_steps)."""
-        _, (fid,) = self._fields((name,), "name")
+    def _check_passage(self, who, what, first_step, max_samples, every, level, direction, f_steps, steps_per_launch):
+        """The arguments of ``run_until`` and ``run_until_scalar`` but the tested quantity `what` (no device call): returns
+        (level [ncol] float64, direction [ncol] int32, f_steps)."""
         if int(first_step) < 0:
-            raise ValueError("run_until: first_step must be >= 0")
+            raise ValueError(f"{who}: first_step must be >= 0")
         if int(max_samples) < 1:
             raise ValueError(f"max_samples = {max_samples}: need at least one round")
         if int(every) < 1:
-            raise ValueError(f"every = {every}: the mean is tested every `every` >= 1 steps")
+            raise ValueError(f"every = {every}: the {what} is tested every `every` >= 1 steps")
         if int(steps_per_launch) < 1:
             raise ValueError(f"steps_per_launch = {steps_per_launch}: need at least one step per launch")
         lev = as_f64(level, (self.ncol,))
@@ -601,7 +604,13 @@ class Engine:
             raise ValueError("direction: 0 is neither upward (> 0) nor downward (< 0)")
         d = np.ascontiguousarray(np.sign(d), dtype=np.int32)
         f = None if f_steps is None else as_f64(f_steps, (int(max_samples) * int(every),))
-        return fid, lev, d, f
+        return lev, d, f
+
+    def check_until_args(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
+        """The host-side checks of ``run_until`` (no device call): returns (field id, level [ncol] float64, direction [ncol]
+        int32, f_steps)."""
+        _, (fid,) = self._fields((name,), "name")
+        return (fid, *self._check_passage("run_until", "mean", first_step, max_samples, every, level, direction, f_steps, steps_per_launch))
 
     def run_until(self, first_step, max_samples, every, name, level, direction, f_steps=None, steps_per_launch=64):
         """ebm_run_until: rounds of ``every`` steps from global step ``first_step``, at most ``max_samples`` of them; after
@@ -616,6 +625,93 @@ class Engine:
         value = np.full(self.ncol, np.nan)
         check(self.lib.ebm_run_until(self._h, int(first_step), int(max_samples), int(every), dptr(f), int(steps_per_launch), fid,
                                      dptr(lev), iptr(d), iptr(samples), iptr(crossed), dptr(value)), "ebm_run_until")
+        samples = samples.astype(np.int64)
+        return dict(samples=samples, crossed=crossed.astype(bool), value=value, steps=int(samples.max()) * int(every))
+
+    # -- column scalars -----------------------------------------------------------------
+    def check_scalar_args(self, specs):
+        """The host-side checks of the column-scalar calls (no device call; the rules of ebm_column_scalars in
+        include/ebm_hip.h).  ``specs``: between 1 and 12 scalars, each ``(kind, name, k0, k1)`` or ``(kind, name, k0, k1,
+        level)`` — kind one of "integral", "mean", "edge_ge", "edge_le"; name a solution variable of the model; 0 <= k0 <= k1
+        <= nlat - 1 the band's first and last cell, both inclusive, k0 < k1 for the integral kinds; level not NaN for the
+        edge kinds (ignored, and 0.0 if absent, otherwise).  The message names the first offending scalar.  Returns (spec
+        int32 [n, 4] = kind, field id, k0, k1; level float64 [n])."""
+        specs = list(specs) if isinstance(specs, (list, tuple)) else None
+        if specs is not None and len(specs) in (4, 5) and isinstance(specs[0], str):
+            raise ValueError("specs: expected a sequence of scalars, got one (wrap it in a list)")
+        if specs is None or not 1 <= len(specs) <= 12:
+            raise ValueError("specs: expected between 1 and 12 column scalars (kind, name, k0, k1[, level])")
+        allowed = self.prognostic + self.diagnostic
+        spec, level = np.zeros((len(specs), 4), dtype=np.int32), np.zeros(len(specs))
+        for s, one in enumerate(specs):
+            if not isinstance(one, (list, tuple)) or len(one) not in (4, 5):
+                raise ValueError(f"scalar {s}: expected (kind, name, k0, k1[, level]), got {one!r}")
+            kind, name, k0, k1 = one[:4]
+            lev = 0.0 if len(one) == 4 or one[4] is None else float(one[4])
+            if not isinstance(kind, str) or kind not in _lib.SCALAR_KIND:
+                raise ValueError(f"scalar {s}: unknown kind {kind!r} (expected one of {', '.join(_lib.SCALAR_KIND)})")
+            if not isinstance(name, str) or name not in allowed:
+                raise ValueError(f"scalar {s}: unknown field {name!r} for the {self.model} model (expected one of "
+                                 f"{', '.join(allowed)}; the warm start T0 is not a solution variable)")
+            for k in (k0, k1):
+                if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+                    raise ValueError(f"scalar {s}: the band k0 = {k0!r}, k1 = {k1!r} is not a pair of cell indices (int)")
+            if not 0 <= k0 <= k1 <= self.nlat - 1:
+                raise ValueError(f"scalar {s}: the band k0 = {k0}, k1 = {k1} is not 0 <= k0 <= k1 <= {self.nlat - 1}")
+            edge = kind.startswith("edge")
+            if not edge and k0 == k1:
+                raise ValueError(f"scalar {s}: an integral over one cell (k0 == k1 = {k0})")
+            if edge and (len(one) == 4 or one[4] is None or np.isnan(lev)):
+                raise ValueError(f"scalar {s}: an edge needs a level that is not NaN")
+            spec[s] = (_lib.SCALAR_KIND[kind], FIELD[name], int(k0), int(k1))
+            level[s] = lev
+        return spec, level
+
+    def column_scalars(self, specs) -> np.ndarray:
+        """ebm_column_scalars (the definition is in include/ebm_hip.h): ndarray [len(specs), ncol] of per-column scalars
+        reduced ALONG each column on the device — "integral" / "mean" of a field over the cells k0 .. k1 (the trapezoid sum
+        of ``hemispheric_mean``, in its order: the full range gives its bits; the mean divides by x[k1] - x[k0]), and
+        "edge_ge" / "edge_le": the position x, linearly interpolated between the two cells, where walking poleward from k0
+        the field first is >= (<=) the level; +Inf if it never is.  ``specs`` as ``check_scalar_args`` takes them
+        (``ensemble.scalar_spec`` builds one from a band in the grid's coordinate).  Fields are made readable as
+        ``hemispheric_mean`` does; StaleFieldError for a stale diagnostic field.  The step clock, the counters and
+        ``field_step`` are unchanged."""
+        return self.column_scalars_device(specs, _HOST)
+
+    def column_scalars_device(self, specs, dev_ptr: int):
+        """Same reduction, the packed [len(specs), ncol] result left on the device at ``dev_ptr``."""
+        spec, level = self.check_scalar_args(specs)
+        return self._reduced("ebm_column_scalars", (len(spec), self.ncol), dev_ptr, len(spec), iptr(spec), dptr(level))
+
+    def run_series_scalars(self, first_step, nsteps, every, specs, f_steps=None, steps_per_launch=64):
+        """ebm_run_series_scalars: ``run_series`` with the column scalars ``specs`` for a sample — ndarray [len(specs),
+        nsteps // every, ncol]; sample j is bit for bit what ``column_scalars`` returns after step first_step +
+        (j+1)*every - 1.  Stepping, the diagnostics rule and the one download at the end are ``run_series``'s."""
+        spec, level = self.check_scalar_args(specs)
+        f = self._check_sampling("run_series_scalars", first_step, nsteps, every, f_steps, steps_per_launch)
+        out = np.full((len(spec), int(nsteps) // int(every), self.ncol), np.nan)
+        check(self.lib.ebm_run_series_scalars(self._h, int(first_step), int(nsteps), dptr(f), int(every), int(steps_per_launch),
+                                              len(spec), iptr(spec), dptr(level), dptr(out)), "ebm_run_series_scalars")
+        return out
+
+    def check_until_scalar_args(self, first_step, max_samples, every, spec, level, direction, f_steps=None, steps_per_launch=64):
+        """The host-side checks of ``run_until_scalar`` (no device call): returns (spec int32 [4], the scalar's own level,
+        level [ncol] float64, direction [ncol] int32, f_steps)."""
+        sp, sl = self.check_scalar_args([spec])
+        return (sp[0], float(sl[0]), *self._check_passage("run_until_scalar", "scalar", first_step, max_samples, every, level,
+                                                          direction, f_steps, steps_per_launch))
+
+    def run_until_scalar(self, first_step, max_samples, every, spec, level, direction, f_steps=None, steps_per_launch=64):
+        """ebm_run_until_scalar: ``run_until`` with the column scalar ``spec`` (one entry of ``check_scalar_args``) in place
+        of the hemispheric mean — a member stops when its ice edge has passed ``level``, or its band mean has.  A NaN scalar
+        never crosses; the +Inf of a band without an edge crosses an upward test.  Returns ``run_until``'s dict."""
+        sp, sl, lev, d, f = self.check_until_scalar_args(first_step, max_samples, every, spec, level, direction, f_steps, steps_per_launch)
+        samples = np.zeros(self.ncol, dtype=np.int32)
+        crossed = np.zeros(self.ncol, dtype=np.int32)
+        value = np.full(self.ncol, np.nan)
+        check(self.lib.ebm_run_until_scalar(self._h, int(first_step), int(max_samples), int(every), dptr(f), int(steps_per_launch),
+                                            iptr(sp), sl, dptr(lev), iptr(d), iptr(samples), iptr(crossed), dptr(value)),
+              "ebm_run_until_scalar")
         samples = samples.astype(np.int64)
         return dict(samples=samples, crossed=crossed.astype(bool), value=value, steps=int(samples.max()) * int(every))
 

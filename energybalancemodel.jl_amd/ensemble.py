@@ -94,6 +94,30 @@ def passage_levels(ncol: int, level, direction):
     return lev, np.ascontiguousarray(np.broadcast_to(out, (ncol,)))
 
 
+def scalar_spec(st, kind, name, band=None, level=None):
+    """One column scalar for ``EnsembleRun.scalars`` / ``scalar_series`` / ``first_passage_scalar`` (the tuple
+    ``Engine.check_scalar_args`` takes): ``kind`` "integral", "mean", "edge_ge" or "edge_le" of field ``name`` over ``band`` =
+    (x_lo, x_hi) in the grid's coordinate ``st.x`` — the cells whose x lies inside, both ends inclusive; None: the whole
+    meridian.  An empty band is refused, and so is a band of one cell for the integral kinds.  ``level``: the edge kinds'.
+    Host only (no device call)."""
+    x = np.asarray(st.x, dtype=np.float64)
+    if band is None:
+        k0, k1 = 0, len(x) - 1
+    else:
+        lo, hi = (float(b) for b in band)
+        if not lo <= hi:
+            raise ValueError(f"band: expected (x_lo, x_hi) with x_lo <= x_hi, got {band!r}")
+        inside = np.flatnonzero((x >= lo) & (x <= hi))
+        if inside.size == 0:
+            raise ValueError(f"band: no cell of the grid lies in [{lo}, {hi}]")
+        k0, k1 = int(inside[0]), int(inside[-1])
+    if kind in ("integral", "mean") and k0 == k1:
+        raise ValueError(f"band: one cell (x[{k0}] = {x[k0]}) carries no {kind}")
+    if kind in ("edge_ge", "edge_le") and (level is None or np.isnan(float(level))):
+        raise ValueError(f"{kind}: needs a level that is not NaN")
+    return (kind, name, k0, k1) if level is None else (kind, name, k0, k1, float(level))
+
+
 def selection_parents(weights, rng) -> np.ndarray:
     """Systematic resampling: the parents [n] (int32, ascending) of the next generation of ``n = len(weights)`` members,
     member m getting ``floor(n w_m)`` or ``ceil(n w_m)`` offspring (w: the weights normalised to sum 1).  One uniform
@@ -675,6 +699,51 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
         f = self._forcing_table(forcing, self.step_index, int(max_steps))
         first = self.step_index
         out = self.engine.run_until(first, rounds, every, name, lev, d, f, steps_per_launch)
+        self.step_index += out["steps"]
+        last = first + out["samples"] * int(every) - 1
+        step = np.where(out["crossed"], last, -1)
+        time = np.where(out["crossed"], (last + 0.5) * self.st.dt, np.nan)
+        return dict(step=step, time=time, crossed=out["crossed"], samples=out["samples"], value=out["value"])
+
+    def scalars(self, specs):
+        """This shard's per-member column scalars (ebm_column_scalars), [len(specs), ncol]: band integrals and means and edge
+        positions of the present state, reduced along each column on the device.  ``specs``: a sequence of ``scalar_spec``
+        results.  Scalars are per member, so a sharded ensemble gives the bits of an unsharded one (no collective)."""
+        return self.engine.column_scalars(specs)
+
+    def ice_edge(self, level=0.15, name="phi"):
+        """Each member's ice-edge position [ncol] in the grid's coordinate: walking poleward, where ``name`` first reaches
+        ``level`` (linearly interpolated between the two cells); +Inf for a member without ice, x[0] for one that is covered
+        to the equator."""
+        return self.scalars([scalar_spec(self.st, "edge_ge", name, None, level)])[0]
+
+    def scalar_series(self, nsteps, every, specs, forcing=None, steps_per_launch=None):
+        """``series`` with the column scalars ``specs`` for a sample (ebm_run_series_scalars): [len(specs), nsteps // every,
+        ncol], sample j what ``scalars`` would return after ``every * (j + 1)`` steps of this call.  ``step_index`` advances."""
+        steps_per_launch = _steps_per_launch(steps_per_launch)
+        self.engine.check_scalar_args(specs)                                                          # before any device call
+        self.engine._check_sampling("scalar_series", self.step_index, nsteps, every, None, steps_per_launch)
+        f = self._forcing_table(forcing, self.step_index, nsteps)
+        out = self.engine.run_series_scalars(self.step_index, nsteps, every, specs, f, steps_per_launch)
+        self.step_index += nsteps
+        return out
+
+    def first_passage_scalar(self, max_steps, every, spec, level, direction="up", forcing=None, steps_per_launch=None):
+        """``first_passage`` on a column scalar (ebm_run_until_scalar): every member of this shard advances until its scalar
+        ``spec`` (one ``scalar_spec``) crosses the member's ``level`` — its ice edge passes a latitude, its Arctic-band mean
+        thickness reaches zero.  The +Inf of a member that has lost its ice crosses an upward test; a NaN never crosses.
+        Arguments, result and ``step_index`` as ``first_passage``; ``value`` is the member's last scalar."""
+        steps_per_launch = _steps_per_launch(steps_per_launch)
+        if int(every) < 1:
+            raise ValueError(f"every = {every}: the scalar is tested every `every` >= 1 steps")
+        if int(max_steps) < int(every) or int(max_steps) % int(every):
+            raise ValueError(f"max_steps = {max_steps} is not a positive multiple of every = {every}")
+        lev, d = passage_levels(self.ncol, level, direction)
+        rounds = int(max_steps) // int(every)
+        self.engine.check_until_scalar_args(self.step_index, rounds, every, spec, lev, d, None, steps_per_launch)   # before any device call
+        f = self._forcing_table(forcing, self.step_index, int(max_steps))
+        first = self.step_index
+        out = self.engine.run_until_scalar(first, rounds, every, spec, lev, d, f, steps_per_launch)
         self.step_index += out["steps"]
         last = first + out["samples"] * int(every) - 1
         step = np.where(out["crossed"], last, -1)

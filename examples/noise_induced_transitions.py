@@ -45,11 +45,16 @@ def main():
     ap.add_argument("--until", action="store_true",
                     help="with --every: stop each member at its first passage (EnsembleRun.first_passage) instead of "
                          "thresholding the whole series")
+    ap.add_argument("--until-edge", type=float, default=None, metavar="X",
+                    help="with --every: stop each member when its ice edge (phi >= 0.15, walking poleward) has come down to "
+                         "x = X (EnsembleRun.first_passage_scalar), and print those first-passage times")
     ap.add_argument("--quantiles", action="store_true",
                     help="after the yearly table: mean, median and 5-95 %% band of T(x) and phi(x) across the members, per F")
     args = ap.parse_args()
     if args.until and not args.every:
         ap.error("--until needs --every N: the level is tested every N steps")
+    if args.until_edge is not None and (not args.every or args.until):
+        ap.error("--until-edge X needs --every N (the edge is tested every N steps) and excludes --until")
     if args.every < 0 or (args.every and (args.nt * args.years) % args.every):
         ap.error("--every must be positive and divide nt * years")
     pkg = graft.load_package()
@@ -81,6 +86,23 @@ def main():
     run = pkg.EnsembleRun("MIZ", st, par, init, fcol=fcol,
                           noise=dict(sigma=args.sigma, tau=args.tau, seed=args.seed), noise_streams=np.arange(nf * n))
     threshold = np.repeat(0.5 * (cold_T + warm_T), n)
+    if args.every and args.until_edge is not None:
+        # the transition seen where the model is known for it: the ice edge of a warm-branch member comes down to X
+        edge = pkg.scalar_spec(st, "edge_ge", "phi", None, 0.15)
+        print(f"\nice edge at the start, per forcing (x): " + " ".join(f"{v:.3f}" for v in run.ice_edge()[::n]))
+        fp = run.first_passage_scalar(args.nt * args.years, args.every, edge, level=args.until_edge, direction="down")
+        run.close()
+        first = np.where(fp["crossed"], fp["samples"] * args.every * st.dt, np.inf)                      # years
+        print(f"{nf * n} members ({n} per forcing), noise sigma = {args.sigma} W m^-2, tau = {args.tau} y, the ice edge tested "
+              f"every {args.every} steps for {args.years} years; first time it is at or below x = {args.until_edge} (years; inf: never):")
+        print("    F   fell   25 %     50 %     75 %")
+        for i in range(nf):
+            t = first[i * n:(i + 1) * n]
+            q = np.quantile(t, [0.25, 0.5, 0.75], method="lower")
+            print(f"{F[i]:5.2f}  {np.isfinite(t).mean():5.2f}  " + "  ".join(f"{v:7.3f}" for v in q))
+        taken, total = int(fp["samples"].sum()) * args.every, nf * n * args.nt * args.years
+        print(f"column-steps taken: {taken} of {total} ({100.0 * (1.0 - taken / total):.1f} % not taken)")
+        return
     if args.every:
         if args.until:
             # "<T> < threshold", as the series is thresholded below: at or under the next number down

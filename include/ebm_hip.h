@@ -164,7 +164,7 @@ const char *ebm_version(void);
  * T, h) and the fp64 warm start EBM_F_T0 are written only by steps that were asked to (ebm_step with
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
- * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_column_misfits*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
+ * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_column_misfits*, ebm_column_scalars*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
  * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
@@ -701,6 +701,57 @@ int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntarget
                        double *out);
 int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target,
                               const double *rw, double *dev_out);
+
+/* COLUMN SCALARS: numbers that reduce ALONG a column — the integral or mean of a field over a band of latitudes, and the
+ * position of an edge: where, walking poleward, a field first reaches a level (the ice edge: the first cell with phi >= 0.15).
+ * The number this model is known for, per member, without a field leaving the device.  THIS TEXT IS THE DEFINITION.
+ *   A column scalar is described by four ints and one double: spec[s] = {kind, field, k0, k1}, where 0 <= k0 <= k1 <= nlat-1
+ *     are 0-based cell indices, both inclusive, and level[s], which the edge kinds use and the others ignore.  `field` is a
+ *     solution variable of the model under the rules of ebm_run_series: EBM_F_T0 is not one; a diagnostic field that is older
+ *     than the state gives EBM_ERR_STALE with ebm_hemispheric_mean's message; phi, left underived by state-only one-step
+ *     launches, is made current first.  f: the field's row of the column, x: the grid.
+ *   EBM_S_INTEGRAL requires k0 < k1.  Start at 0.0 and add ((f[i]+f[i+1]) * (x[i+1]-x[i])) / 2.0 for i = k0 .. k1-1, strictly
+ *     left to right: the very operations of ebm_hemispheric_mean, whose result the full range k0 = 0, k1 = nlat-1 therefore
+ *     gives bit for bit.  A NaN in the band gives NaN.
+ *   EBM_S_MEAN is that integral divided once, with the library's IEEE division, by x[k1] - x[k0].
+ *   EBM_S_EDGE_GE / EBM_S_EDGE_LE require a level that is not NaN.  hit(k) is f[k] >= level for GE and f[k] <= level for LE; it
+ *     is false for NaN.  K is the smallest k in k0 .. k1 with a hit.  No hit: the value is +Inf ("no edge in the band"), so
+ *     that edge >= x* is true of an ice-free column, which is what a first-passage test on ice loss needs.  K == k0: the value
+ *     is x[k0].  Otherwise let a = f[K-1] and b = f[K]; if either is not finite, the value is x[K]; otherwise
+ *     t = (level - a) / (b - a) and the value is x[K-1] + t * (x[K] - x[K-1]), every operation rounded once, nothing contracted
+ *     into a fused multiply-add.  The value depends only on K and four loads, so the bits do not depend on the order of the
+ *     search.  Walking poleward (ascending k) is the only direction: the model has one hemisphere.
+ *   1 <= nscal <= 12; the same field may appear in several scalars.
+ * ebm_column_scalars: out[nscal][ncol] on the host; the _device variant writes the same packed array into the caller's device
+ * buffer.  Both make every field readable exactly as ebm_hemispheric_mean makes its one (the same layout conversions, counted
+ * by ebm_state_conversions the same way), leave the step clock, the counters and ebm_field_step unchanged, and are synchronous.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL argument, nscal outside 1 ... 12, an unknown kind, a field that
+ * is not a solution variable of the model, k0 or k1 out of range or k0 > k1, k0 == k1 of an integral kind, a NaN level of an
+ * edge kind — the message names the first offending scalar; EBM_ERR_STALE as above.
+ * How it runs (csrc/ebm_launch.hip): ONE launch, one wave64 workgroup per (column, scalar).  The integral kinds are the
+ * library's one mean walk (hemispheric_means_of_column) over the band: they cost what ebm_hemispheric_mean costs on as many
+ * terms.  The edge kinds walk the band in tiles of 256 cells — each lane four coalesced loads, a cross-lane min of the first
+ * hit — and stop at the first tile with a hit, so a row is read at most once; lane 0 then loads the four cells and interpolates.
+ * No LDS beyond the mean's tile, no atomics, no scratch, plain loads and stores; rows are read in the natural layout. */
+enum ebm_scalar_kind { EBM_S_INTEGRAL = 0, EBM_S_MEAN = 1, EBM_S_EDGE_GE = 2, EBM_S_EDGE_LE = 3, EBM_S_COUNT };
+int ebm_column_scalars(ebm_handle_t h, int nscal, const int *spec, const double *level, double *out);
+int ebm_column_scalars_device(ebm_handle_t h, int nscal, const int *spec, const double *level, double *dev_out);
+/* ebm_run_series with the nscal column scalars for a sample, and nothing else different: stepping, the diag rule (diag = 1 iff
+ * one of the scalars' fields is diagnostic), sample steps, launch counts, the state afterwards, the refusals and the one
+ * download at the end are those of ebm_run_series.  series[nscal][nsamples][ncol]: series[s][j][c] is bit for bit what
+ * ebm_column_scalars puts into out[s][c] after ebm_run_fused(h, first_step, (j+1)*every, f_steps, diag, steps_per_launch) from
+ * the same start.  One loop in the library drives both calls. */
+int ebm_run_series_scalars(ebm_handle_t h, long long first_step, int nsteps, const double *f_steps, int every, int steps_per_launch,
+                           int nscal, const int *spec, const double *level, double *series);
+/* ebm_run_until with m_c = the column scalar spec[4] = {kind, field, k0, k1}, scalar_level of column c in place of the mean, and
+ * nothing else different: rounds, crossing rule, freezing, outputs, clock, counters, validity bookkeeping and the one stream
+ * synchronisation per round are those of ebm_run_until (diag = 1 iff the field is diagnostic).  A NaN m_c never crosses; the
+ * +Inf of a band without an edge crosses an upward test: "stop when the ice edge has passed x*, or the ice is gone".
+ * level[ncol], direction[ncol]: the per-column thresholds of ebm_run_until.  Refusals: those of ebm_run_until and, for the
+ * scalar, of ebm_column_scalars.  One loop in the library drives both calls. */
+int ebm_run_until_scalar(ebm_handle_t h, long long first_step, int max_samples, int every, const double *f_steps, int steps_per_launch,
+                         const int *spec, double scalar_level, const double *level, const int *direction, int *samples,
+                         int *crossed, double *value);
 
 int ebm_sync(ebm_handle_t h);
 

@@ -446,4 +446,59 @@ function column_misfits_device!(h::Handle, names::Vector{Symbol}, target::Array{
                                                                  devout::Ptr{Cdouble})::Cint), "ebm_column_misfits_device")
 end
 
+"""
+    column_scalars(h, spec, level; ncol) / column_scalars_device!(h, spec, level, devout)
+
+Column scalars (`ebm_column_scalars`; the definition is in the header): `spec` is `4 x nscal` (`Cint`), column `s` =
+`(kind, field, k0, k1)` with `kind` one of `SCALAR_KIND`, `field = FIELD[name]` and `k0 <= k1` the band's first and last cell,
+0-based and inclusive; `level[s]` is the level of an edge kind.  `out[c, s]`: the band integral or mean (the sum of
+`hemispheric_mean`, in its order), or the interpolated position where the field first reaches the level walking poleward,
+`Inf` if it never does.  `run_series_scalars!` and `run_until_scalar!` are `run_series!` and `run_until!` with these scalars
+in place of the hemispheric means.
+"""
+const SCALAR_KIND = Dict(:integral => 0, :mean => 1, :edge_ge => 2, :edge_le => 3)
+
+function column_scalars(h::Handle, spec::Matrix{Cint}, level::Vector{Float64}; ncol::Integer)
+    nscal = size(spec, 2)
+    (size(spec, 1) == 4 && length(level) == nscal) || error("spec: expected 4 x nscal, level: nscal values")
+    out = Matrix{Float64}(undef, ncol, nscal)
+    GC.@preserve h check(ccall((:ebm_column_scalars, libebm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                               h.ptr, nscal, spec, level, out), "ebm_column_scalars")
+    return out
+end
+
+function column_scalars_device!(h::Handle, spec::Matrix{Cint}, level::Vector{Float64}, devout::Ptr{Cdouble})
+    GC.@preserve h check(ccall((:ebm_column_scalars_device, libebm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                               h.ptr, size(spec, 2), spec, level, devout), "ebm_column_scalars_device")
+end
+
+function run_series_scalars!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, every::Integer, spec::Matrix{Cint},
+                             level::Vector{Float64}; ncol::Integer, steps_per_launch::Integer=64)
+    nsteps, nscal = length(fsteps), size(spec, 2)
+    (every >= 1 && nsteps % every == 0) || throw(ArgumentError("the number of steps must be a multiple of every >= 1"))
+    series = Array{Float64,3}(undef, ncol, div(nsteps, every), nscal)
+    GC.@preserve h check(ccall((:ebm_run_series_scalars, libebm), Cint,
+                               (Ptr{Cvoid}, Clonglong, Cint, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                               h.ptr, first_step, nsteps, fsteps, every, steps_per_launch, nscal, spec, level, series),
+                         "ebm_run_series_scalars")
+    return series
+end
+
+function run_until_scalar!(h::Handle, first_step::Integer, fsteps::Vector{Float64}, every::Integer, spec::Vector{Cint},
+                           scalar_level::Float64, level::Vector{Float64}, direction::Vector{<:Integer};
+                           steps_per_launch::Integer=64)
+    nsteps = length(fsteps)
+    (every >= 1 && nsteps >= every && nsteps % every == 0) ||
+        throw(ArgumentError("the number of steps must be a positive multiple of every >= 1"))
+    ncol = length(level)
+    (length(direction) == ncol && length(spec) == 4) || throw(ArgumentError("level and direction: one entry per column; spec: 4 ints"))
+    samples, crossed, value = zeros(Cint, ncol), zeros(Cint, ncol), fill(NaN, ncol)
+    GC.@preserve h check(ccall((:ebm_run_until_scalar, libebm), Cint,
+                               (Ptr{Cvoid}, Clonglong, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cint}, Cdouble, Ptr{Cdouble}, Ptr{Cint},
+                                Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+                               h.ptr, first_step, div(nsteps, every), every, fsteps, steps_per_launch, spec, scalar_level, level,
+                               Cint.(sign.(direction)), samples, crossed, value), "ebm_run_until_scalar")
+    return Int.(samples), crossed .!= 0, value
+end
+
 end # module EBMHip
