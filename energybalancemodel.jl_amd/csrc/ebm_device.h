@@ -148,8 +148,9 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // Forcing of one column at one step: the step's scalar, plus the column's constant offset, plus the
 // column's own Forcing{false} schedule (src/infrastructure.jl:208-241) evaluated at the model time
 // T of the step exactly as the reference does (:294-307): hold, ramp up, hold, ramp down, hold.
-__device__ __forceinline__ double column_forcing(const StepArgs &a, int col, double ft, double tyear) {
-    double f = a.fcol ? ft + a.fcol[col] : ft;
+// (schedule_forcing: the schedule's part alone, on top of f = the step's scalar plus the column's offset — for the kernel
+// that has requested the offset already, miz_step_kernel's StepHead)
+__device__ __forceinline__ double schedule_forcing(const StepArgs &a, int col, double f, double tyear) {
     if (a.fsched) {
         const double *w = a.fsched + (size_t)kSchedWords * col;     // wave-uniform: scalar loads
         const double base = w[0], peak = w[1], cool = w[2], up = w[3], down = w[4];
@@ -162,6 +163,9 @@ __device__ __forceinline__ double column_forcing(const StepArgs &a, int col, dou
         f = f + v;
     }
     return f;
+}
+__device__ __forceinline__ double column_forcing(const StepArgs &a, int col, double ft, double tyear) {
+    return schedule_forcing(a, col, a.fcol ? ft + a.fcol[col] : ft, tyear);
 }
 
 // ---- chunk loads / stores: 8*C contiguous bytes per lane, 16-byte accesses ------------------
@@ -237,6 +241,78 @@ __device__ __forceinline__ void load_state_unless_zero(const double *__restrict_
         v[2 * j + 1] = d.y;
     }
 }
+// ---- the head of a one-step launch (miz_step_kernel) -------------------------------------------
+// Every word that a wave needs before its first vector load and that depends on nothing but the kernel arguments and the
+// column: its own zero-line flag word, the successor column's two (for the L2 prefetch), the step's scalars (entry `slot` of
+// the schedule table, or the launch arguments), the column's forcing offset and its parameter set.  All are requested in
+// one batch of scalar loads behind ONE wait: asked for one by one, each where it is first used, they form a chain of
+// dependent scalar-cache misses in front of the state loads (profiles/EXPERIMENTS.md, r30).  A table that is absent is not
+// branched around — the branch would end the batch: the load goes to the parameter block instead (a.p, always there and
+// larger than any entry), and what it returns is dropped.
+struct StepHead {
+    unsigned zold, znext0, znext1;   // ZERO_LINES only (else 0)
+    int pset;
+    double ct, ft, tyear, fcol;      // fcol: the column's offset, +0.0 bits without a table (never added then)
+    long long n;
+};
+template <bool ZERO_LINES, int T>
+__device__ __forceinline__ StepHead step_head(const StepArgs &a, int col, unsigned wave) {
+    typedef const __attribute__((address_space(4))) unsigned long long ConstU64;
+    typedef const __attribute__((address_space(4))) int ConstInt;
+    const uintptr_t spare = reinterpret_cast<uintptr_t>(a.p);
+    StepHead h;
+    h.zold = h.znext0 = h.znext1 = 0;
+    if constexpr (ZERO_LINES) {
+        constexpr unsigned W = T / 64;
+        // (no successor: the column's own words, unused.  readfirstlane: free where the load is scalar, as in the shipped
+        // library; the -DEBM_STAMPS build of the 64-thread kernel loads the words per lane, and the pin below wants SGPRs)
+        const int nxt = (a.prefetch > 0 && col + a.prefetch < a.ncol) ? col + a.prefetch : col;
+        h.zold = (unsigned)__builtin_amdgcn_readfirstlane((int)zero_flag_word<T>(a, col, wave));
+        h.znext0 = (unsigned)__builtin_amdgcn_readfirstlane((int)zero_flag_word<T>(a, nxt, (2u * wave) % W));
+        h.znext1 = (unsigned)__builtin_amdgcn_readfirstlane((int)zero_flag_word<T>(a, nxt, (2u * wave + 1u) % W));
+    }
+    ConstU64 *const se = reinterpret_cast<ConstU64 *>(a.sched ? reinterpret_cast<uintptr_t>(a.sched + a.slot) : spare);
+    static_assert(sizeof(Params) >= sizeof(StepSched), "the spare target holds a whole entry");
+    static_assert(offsetof(StepSched, ct) % 8 == 0 && offsetof(StepSched, ft) % 8 == 0 && offsetof(StepSched, tyear) % 8 == 0 &&
+                  offsetof(StepSched, n) % 8 == 0 && sizeof(double) == 8 && sizeof(long long) == 8, "the entry as 64-bit words");
+    unsigned long long ct = se[offsetof(StepSched, ct) / 8], ft = se[offsetof(StepSched, ft) / 8],
+                       ty = se[offsetof(StepSched, tyear) / 8], n = se[offsetof(StepSched, n) / 8];
+    unsigned long long fc = reinterpret_cast<ConstU64 *>(a.fcol ? reinterpret_cast<uintptr_t>(a.fcol + col) : spare)[0];
+    int ps = reinterpret_cast<ConstInt *>(a.pset ? reinterpret_cast<uintptr_t>(a.pset + col) : spare)[0];
+    // the one wait: every word is consumed here, so every request stands above this line and none is sunk to its use
+    // (one asm for all of them, and not `volatile`: hipcc takes a volatile asm for a write to memory and reads every
+    // plain-pointer word after it — the forcing schedule, N_c — with per-lane vector loads instead of scalar ones)
+    if constexpr (ZERO_LINES)
+        asm("" : "+s"(h.zold), "+s"(h.znext0), "+s"(h.znext1), "+s"(ct), "+s"(ft), "+s"(ty), "+s"(n), "+s"(fc), "+s"(ps));
+    else
+        asm("" : "+s"(ct), "+s"(ft), "+s"(ty), "+s"(n), "+s"(fc), "+s"(ps));
+    if constexpr (ZERO_LINES) {
+        constexpr unsigned W = T / 64;
+        h.znext0 >>= 4u * ((2u * wave) / W);
+        h.znext1 >>= 4u * ((2u * wave + 1u) / W);
+    }
+    h.ct = a.sched ? __builtin_bit_cast(double, ct) : a.ct;
+    h.ft = a.sched ? __builtin_bit_cast(double, ft) : a.ft;
+    h.tyear = a.sched ? __builtin_bit_cast(double, ty) : a.tyear;
+    h.n = a.sched ? (long long)n : a.step;
+    h.fcol = __builtin_bit_cast(double, fc);
+    h.pset = a.pset ? ps : 0;
+    return h;
+}
+// The same words asked for in place, each where it is first used and none where its table is absent: the head of the kernels
+// that do not take the batch (miz_step_kernel: IMEX, two cells per thread; none of them elides zero lines).
+__device__ __forceinline__ StepHead step_head_in_place(const StepArgs &a, int col) {
+    StepHead h;
+    h.zold = h.znext0 = h.znext1 = 0;
+    h.pset = param_set(a, col);
+    h.ct = a.sched ? a.sched[a.slot].ct : a.ct;
+    h.ft = a.sched ? a.sched[a.slot].ft : a.ft;
+    h.tyear = a.sched ? a.sched[a.slot].tyear : a.tyear;
+    h.n = a.sched ? a.sched[a.slot].n : a.step;
+    h.fcol = a.fcol ? a.fcol[col] : 0.0;
+    return h;
+}
+
 template <int C>
 __device__ __forceinline__ void store_chunk(double *__restrict__ f, const double (&v)[C], unsigned k0, int nlat) {
 #pragma unroll

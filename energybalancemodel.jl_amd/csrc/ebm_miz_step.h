@@ -49,6 +49,12 @@ namespace ebm {
 // them before the next launch of this variant (FieldBook::zero_flags_trusted).  The L2 prefetch for the
 // successor column skips, lane by lane, the sectors of lines that the successor's flags say it will not load.
 //
+// Order of requests in phase A (BATCH_HEAD: four cells per thread, the reference's step; IMEX and the two-cell kernels keep
+// the head they had): a phase requests its inputs before anything that waits or writes.  The scalar words of the
+// head in one batch behind one wait (StepHead), then the state, the mask word, the tables; the forcing, the noise record and
+// Tm under the loads' latency.  Phase D keeps the order below: x, Ei and D requested ahead of the mask store and the
+// counters' atomic, and ahead of the halo, measured 2.2 % slower on the headline (profiles/EXPERIMENTS.md, r30).
+//
 // Order of loads and stores in phase D (four cells per thread): after the Tbar halo a lane requests Ei and D of BOTH its
 // pairs (flagged pairs excepted), then updates pair 0, stores it, updates pair 1 (the L2 prefetch for the successor leaves
 // within it), stores it.  No load of the state follows a store.  IMEX, OUT_SAVE and the two-cell kernels
@@ -67,34 +73,34 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     const unsigned k0 = (unsigned)t * C;
     double *P0 = smem, *P1 = smem + 3 * T;
     double *sEw = smem + 6 * T + t, *sh = sEw + C * T, *sTw = sh + C * T;
-    const int pset = param_set(a, col);                  // ebm_set_column_params (set 0 without a table)
+    EBM_STAMP(0);
+    EBM_STAMPW(0);                                        // per wave: first instruction
+    // The head: every scalar word that depends only on the launch arguments and the column — this wave's zero-line flag word
+    // and the successor column's two (ZERO_LINES: scalar loads, like the parameter block: nothing of them waits in a VGPR), the
+    // step's scalars, the column's forcing offset and parameter set — in one batch behind one wait (StepHead, ebm_device.h).
+    // What needs more than that (the forcing schedule, the noise, Tm) follows phase A's vector requests.
+    // BATCH_HEAD: the four-cell kernels of the reference's step.  IMEX and the two-cell kernels keep the head they had — every
+    // word asked for where it is first used, the forcing before the loads, the loads inside the Newton loop
+    // (step_head_in_place): with the batch the IMEX headline shape measured 0.85 % slower, twice, and the two-cell kernels
+    // need up to 28 more VGPRs, five waves per SIMD becoming four (profiles/EXPERIMENTS.md, r30).
+    constexpr bool BATCH_HEAD = C == 4 && !IMEX;
+    static_assert(BATCH_HEAD || !ZERO_LINES, "the eliding kernel has the batched head");
+    static_assert(BATCH_HEAD || !PHI_DERIVED, "the in-place head loads phi, never Ei");
+    StepHead hd;
+    if constexpr (BATCH_HEAD) hd = step_head<ZERO_LINES, TT>(a, col, (unsigned)__builtin_amdgcn_readfirstlane(t >> 6));
+    else hd = step_head_in_place(a, col);
+    const int pset = hd.pset;                            // ebm_set_column_params (set 0 without a table)
     ConstParams &p = *reinterpret_cast<ConstParams *>(reinterpret_cast<uintptr_t>(a.p + pset));
     const double *const geom = a.geom + pset * a.set_stride;
     const double *const gX = geom + G_X * a.gstride;
     double *const st = a.state + (size_t)col * (size_t)a.pitch;         // wave-uniform
-    const double Tm = p.Tm;
-    EBM_STAMP(0);
-    EBM_STAMPW(0);                                        // per wave: first instruction
     // Warm start (src/miz.jl:47,52-54,64).  The reference carries T0 itself between steps; the
     // active-set iteration only uses its sign pattern, so between steps the library carries that
     // pattern (one bit per cell) and writes the fp64 T0 field on diagnostic launches only.
     unsigned short *const cmask = a.amask + (size_t)col * T;            // wave-uniform
-    // ZERO_LINES: this wave's flag word, and the two words that hold the flags of the 2 KiB of the successor column that
-    // this wave prefetches (scalar loads, like the parameter block: nothing of them waits in a VGPR)
-    unsigned zold = 0, znew = 0, znext0 = 0, znext1 = 0;
-    if constexpr (ZERO_LINES) {
-        const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane(t >> 6);
-        zold = zero_flag_word<TT>(a, col, wave);
-        if (a.prefetch > 0 && col + a.prefetch < a.ncol) {
-            znext0 = zero_flag_word<TT>(a, col + a.prefetch, (2u * wave) % (TT / 64)) >> (4u * ((2u * wave) / (TT / 64)));
-            znext1 = zero_flag_word<TT>(a, col + a.prefetch, (2u * wave + 1u) % (TT / 64)) >> (4u * ((2u * wave + 1u) / (TT / 64)));
-        }
-    }
-    const double ct = a.sched ? a.sched[a.slot].ct : a.ct;              // per-step scalars (scalar loads)
-    const double ft = a.sched ? a.sched[a.slot].ft : a.ft;
-    ColumnNoise nz;
-    if (a.noise) nz.load(a, col);
-    const double f = step_forcing(a, nz, col, ft, a.sched ? a.sched[a.slot].tyear : a.tyear, a.sched ? a.sched[a.slot].n : a.step);
+    const unsigned zold = hd.zold, znext0 = hd.znext0, znext1 = hd.znext1;
+    unsigned znew = 0;
+    const double ct = hd.ct;                              // per-step scalars
     const bool diag = OUT == OUT_DIAG || (MAYDIAG && a.write_diag);
 
     // ---------------- phase A: loads, water temperature, T0-system coefficients ----------
@@ -102,41 +108,88 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // LDS stash.  The second and later Newton iterations (a changed active set: < 0.1 % of column-steps at the
     // reference's time steps, every second one with the extension's long ones) form the rows again from the stashed h
     // and the two coefficient tables and call the same solve — one copy of the solve in the kernel.
+    // Order of the requests (first iteration): the state (Ew, Ei or phi, h: their first consumers, concentration and
+    // water_temperature, come long before the tables' — after the r halo), the mask word, then the geometry (tlo, tup, x);
+    // the forcing, the noise record and Tm are formed under the loads' latency, before their first use.  The
+    // sched_barriers pin that order; tests/test_host_step_head_order.py reads it in the assembly.
+    // (they stand before the Newton loop, not in its first iteration: with the forcing inside it the loop's body is too
+    // large for hipcc to peel that iteration, and the whole kernel spills)
     double ph[C], rd[C], xs[C];
-    unsigned smask = cmask[t];                            // active set: bit i <=> T0_i < Tm
+    double Ew[C], hk[C], xk0[C], tlo0[C], tup0[C];
+    [[maybe_unused]] double Ei[C];                        // PHI_DERIVED (Ei is not kept: phase D loads its pairs again, as it always has)
+    unsigned smask;                                       // active set: bit i <=> T0_i < Tm
+    double Tm, f;
+    ColumnNoise nz;
+    if constexpr (!BATCH_HEAD) {
+        Tm = p.Tm;
+        if (a.noise) nz.load(a, col);
+        f = step_forcing(a, nz, col, hd.ft, hd.fcol, hd.tyear, hd.n);
+        smask = cmask[t];
+    } else {
+        // (the lane's cell index is made opaque per load group: the addresses are formed here, in the wave-uniform base +
+        // 32-bit offset form, and none is kept.  Not `volatile`, like StepHead's pin: after a volatile asm hipcc reads the
+        // forcing schedule and N_c below with per-lane vector loads, which wait behind the state's)
+        unsigned kl = k0;
+        asm("" : "+v"(kl));
+        // (ZERO_LINES: a flagged pair is not loaded, it holds +0.0 — the same concentration and water_temperature of the
+        // same bits)
+        if constexpr (ZERO_LINES) load_state_unless_zero<C, TT>(st + S_Ew * a.fstride, kl, Ew, zold >> S_Ew);
+        else load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
+        if constexpr (PHI_DERIVED) {
+            if constexpr (ZERO_LINES) {
+                load_state_unless_zero<C, TT>(st + S_Ei * a.fstride, kl, Ei, zold >> S_Ei);
+                load_state_unless_zero<C, TT>(st + S_h * a.fstride, kl, hk, zold >> S_h);
+            } else {
+                load_state<C, TT>(st + S_Ei * a.fstride, kl, Ei);
+                load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+            }
+        } else {
+            load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
+            load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+        }
+        smask = cmask[t];
+        __builtin_amdgcn_sched_barrier(0);
+        asm("" : "+v"(kl));
+        load_chunk<C>(geom + G_LO * a.gstride, kl, tlo0);
+        load_chunk<C>(geom + G_UP * a.gstride, kl, tup0);
+        load_chunk<C>(gX, kl, xk0);
+        __builtin_amdgcn_sched_barrier(0);
+        // under the loads: the parameter block's Tm, the noise record (before the workgroup's first barrier) and the forcing
+        Tm = p.Tm;
+        if (a.noise) nz.load(a, col);
+        f = step_forcing(a, nz, col, hd.ft, hd.fcol, hd.tyear, hd.n);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     int it = 0;
     bool again;
     do {
         double tlo[C], tup[C], dd[C];
-        // (the lane's cell index is made opaque inside the loop: hoisted out of it, the six addresses
+        // (!BATCH_HEAD: the lane's cell index is made opaque inside the loop: hoisted out of it, the six addresses
         // would live as per-lane 64-bit pointers instead of the wave-uniform base + 32-bit offset form)
         unsigned kl = k0;
-        asm volatile("" : "+v"(kl));
-        load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
-        load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
+        if constexpr (!BATCH_HEAD) {
+            asm volatile("" : "+v"(kl));
+            load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
+            load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
+        }
         if (it == 0) {
-            double Ew[C], hk[C], xk[C], r[C];
-            // (ZERO_LINES: a flagged pair is not loaded, it holds +0.0 — the same concentration and water_temperature of the
-            // same bits)
-            if constexpr (ZERO_LINES) load_state_unless_zero<C, TT>(st + S_Ew * a.fstride, kl, Ew, zold >> S_Ew);
-            else load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
-            if constexpr (PHI_DERIVED) {
-                // (Ei is not kept: phase D loads its pairs again, as it always has)
-                double Ei[C];
-                if constexpr (ZERO_LINES) {
-                    load_state_unless_zero<C, TT>(st + S_Ei * a.fstride, kl, Ei, zold >> S_Ei);
-                    load_state_unless_zero<C, TT>(st + S_h * a.fstride, kl, hk, zold >> S_h);
-                } else {
-                    load_state<C, TT>(st + S_Ei * a.fstride, kl, Ei);
-                    load_state<C, TT>(st + S_h * a.fstride, kl, hk);
-                }
+            double r[C];
+            if constexpr (BATCH_HEAD) {
 #pragma unroll
-                for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);
+                for (int i = 0; i < C; ++i) {
+                    tlo[i] = tlo0[i];
+                    tup[i] = tup0[i];
+                }
             } else {
+                load_state<C, TT>(st + S_Ew * a.fstride, kl, Ew);
                 load_state<C, TT>(st + S_phi * a.fstride, kl, ph);
                 load_state<C, TT>(st + S_h * a.fstride, kl, hk);
+                load_chunk<C>(gX, kl, xk0);
             }
-            load_chunk<C>(gX, kl, xk);
+            if constexpr (PHI_DERIVED) {
+#pragma unroll
+                for (int i = 0; i < C; ++i) ph[i] = concentration(p, Ei[i], hk[i]);
+            }
             // Padding cells (k >= nlat) need no special case in phases A and B: their state and table
             // entries are zero, so their rows are decoupled (lo = up = 0, g = phi = 0) and finite.
 #pragma unroll
@@ -157,11 +210,16 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             // peels the first Newton iteration of this kernel and of miz_resident_kernel, and with it their whole code)
 #pragma unroll
             for (int i = 0; i < C; ++i)
-                rd[i] = t0_rhs(p, insolation(p, xk[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
+                rd[i] = t0_rhs(p, insolation(p, xk0[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
             __syncthreads();                                  // r halo reads done before P0 is reused
         } else {
             // second and later iterations (a changed active set): the right-hand side does not depend on the set and
             // is still in registers, like phi; only the rows' ingredients are fetched / formed again — the same values
+            if constexpr (BATCH_HEAD) {
+                asm volatile("" : "+v"(kl));
+                load_chunk<C>(geom + G_LO * a.gstride, kl, tlo);
+                load_chunk<C>(geom + G_UP * a.gstride, kl, tup);
+            }
 #pragma unroll
             for (int i = 0; i < C; ++i) dd[i] = t0_diag_excess(p, sh[i * T]);
         }

@@ -109,9 +109,10 @@ struct ColumnNoise {
 #endif
     }
 };
-// The forcing of a one-step launch (global step n): column_forcing, plus N_c after its update if the handle has noise
-__device__ __forceinline__ double step_forcing(const StepArgs &a, ColumnNoise &nz, int col, double ft, double tyear, long long n) {
-    const double f = column_forcing(a, col, ft, tyear);
+// The forcing of a one-step launch (global step n): column_forcing — with the column's offset `fcol` as the kernel's head
+// has loaded it (StepHead) — plus N_c after its update if the handle has noise
+__device__ __forceinline__ double step_forcing(const StepArgs &a, ColumnNoise &nz, int col, double ft, double fcol, double tyear, long long n) {
+    const double f = schedule_forcing(a, col, a.fcol ? ft + fcol : ft, tyear);
     return a.noise ? f + nz.advance(noise_innovation(a.seed, nz.stream, n)) : f;
 }
 
