@@ -86,6 +86,8 @@ SIGNATURES = {
     "ebm_ensemble_range_device": [_h, _i, _ip, _dp, _dev],
     "ebm_ensemble_histogram": [_h, _i, _ip, _dp, _i, _dp, _dp, _dp],
     "ebm_ensemble_histogram_device": [_h, _i, _ip, _dp, _i, _dp, _dp, _dev],
+    "ebm_ensemble_covariance": [_h, _i, _i, _dp, _dp, _dp, _dp],
+    "ebm_ensemble_covariance_device": [_h, _i, _i, _dp, _dp, _dp, _dev],
     "ebm_column_misfits": [_h, _i, _ip, _i, _dp, _dp, _dp],
     "ebm_column_misfits_device": [_h, _i, _ip, _i, _dp, _dp, _dev],
     "ebm_column_scalars": [_h, _i, _ip, _dp, _dp],

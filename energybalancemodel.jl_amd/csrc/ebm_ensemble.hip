@@ -47,9 +47,6 @@ static_assert(kSumsBlock % kWalkBatch == 0 && kRangeBlock % kWalkBatch == 0 && k
 
 typedef const __attribute__((address_space(4))) double ConstDouble;      // never written by a kernel: scalar loads
 
-// natural index of stored index p (units of a row of 2T units) in a pair-split row
-__device__ __forceinline__ int natural_unit(int p, int T, bool split) { return !split ? p : (p < T ? 2 * p : 2 * (p - T) + 1); }
-
 // ---- the partials' skeleton -----------------------------------------------------------------------------------------------
 
 // What a lane of a partials kernel stands for and reads

@@ -1,6 +1,7 @@
 // Host runtime, fields (ebm_runtime.h lists the units): set / get with the validity bookkeeping, device views, hemispheric
 // means, and the two diffusion operators that work on caller-supplied fields (ebm_diffusion, ebm_zonal_diffusion).
 #include <cmath>
+#include <cstring>
 
 #include "ebm_runtime.h"
 #include "ebm_tables.h"
@@ -269,6 +270,49 @@ int ensemble_reduce(ebm_ctx *h, int nvars, const int *fields, const double *w, c
     return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), (size_t)nslots * (size_t)nvars * (size_t)h->nlat, r.s, who);
 }
 
+// ebm_ensemble_covariance and its _device form (include/ebm_hip.h): the checks of the ensemble reductions on handle, fields
+// and weights, the call's own on the two centers, then the rows where they lie and the two launches of ebm_covariance.hip into
+// dev_out (the caller's device buffer) or, for host_out, into the handle's own and down.  Synchronous.
+int ensemble_covariance(ebm_ctx *h, int field_a, int field_b, const double *w, const double *center_a, const double *center_b,
+                        double *host_out, double *dev_out, const char *who) {
+    const std::string me(who);
+    const int fields[2] = {field_a, field_b};
+    if (int rc = ensemble_check(h, 2, fields, false, w, host_out || dev_out, me)) return rc;
+    const size_t nlat = (size_t)h->nlat, npitch = (size_t)h->pitch;
+    const double *const center[2] = {center_a, center_b};
+    for (int v = 0; v < 2; ++v)
+        for (size_t k = 0; center[v] && k < nlat; ++k)
+            if (!std::isfinite(center[v][k]))
+                return fail(EBM_ERR_ARG, me + ": center_" + "ab"[v] + "[" + std::to_string(k) + "] is not finite");
+    // rule 6 of the definition: one field against itself about one center
+    const bool symmetric = field_a == field_b && ((!center_a && !center_b) ||
+                                                  (center_a && center_b && !std::memcmp(center_a, center_b, sizeof(double) * nlat)));
+    EnsembleRows r;
+    if (int rc = ensemble_open(h, 2, fields, w, who, r)) return rc;
+    ebm_ctx::Covariance &b = h->covariance;
+    const int nblocks = (h->ncol + ebm::kCovBlock - 1) / ebm::kCovBlock;
+    HIPCHK(b.partial.reserve((size_t)nblocks * npitch * npitch));
+    if (!dev_out) HIPCHK(b.out.reserve(nlat * nlat));
+    if ((center_a || center_b) && !b.center.get()) {     // both rows once; the padding cells stay zero
+        HIPCHK(b.center.reserve(2 * npitch));
+        HIPCHK(hipMemsetAsync(b.center.get(), 0, sizeof(double) * 2 * npitch, r.s));
+    }
+    hipError_t e = hipSuccess;
+    for (int v = 0; v < 2 && e == hipSuccess; ++v)
+        if (center[v]) e = hipMemcpyAsync(b.center.get() + v * npitch, center[v], sizeof(double) * nlat, hipMemcpyHostToDevice, r.s);
+    ebm::CovarianceArgs a{};
+    a.row_a = r.row[0]; a.row_b = r.row[1];
+    a.split_a = r.split_mask & 1u; a.split_b = (r.split_mask >> 1) & 1u; a.symmetric = symmetric;
+    a.w = r.w;
+    a.center_a = center_a ? b.center.get() : nullptr;
+    a.center_b = center_b ? b.center.get() + npitch : nullptr;
+    a.partial = b.partial.get();
+    a.out = dev_out ? dev_out : b.out.get();
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nblocks = nblocks; a.threads = h->cfg.threads;
+    if (e == hipSuccess) e = ebm::launch_ensemble_covariance(a, r.s);
+    return ensemble_close(e, dev_out ? nullptr : host_out, b.out.get(), nlat * nlat, r.s, who);
+}
+
 // ebm_column_misfits and its _device form (include/ebm_hip.h): the checks of the ensemble reductions on handle and fields, the
 // call's own on targets and rw, then the rows where they lie and the one launch of ebm_misfit.hip into dev_out (the caller's
 // device buffer) or, for host_out, into the handle's own and down.  Synchronous.
@@ -462,6 +506,16 @@ int ebm_ensemble_sums(ebm_handle_t h, int nvars, const int *fields, const double
 
 int ebm_ensemble_sums_device(ebm_handle_t h, int nvars, const int *fields, const double *w, const double *center, double *dev_out) {
     return ensemble_reduce(h, nvars, fields, w, {EnsembleCall::SUMS, ebm::kSumsBlock, center, nullptr, nullptr, 0}, nullptr, dev_out, "ebm_ensemble_sums_device");
+}
+
+int ebm_ensemble_covariance(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a, const double *center_b,
+                            double *out) {
+    return ensemble_covariance(h, field_a, field_b, w, center_a, center_b, out, nullptr, "ebm_ensemble_covariance");
+}
+
+int ebm_ensemble_covariance_device(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a,
+                                   const double *center_b, double *dev_out) {
+    return ensemble_covariance(h, field_a, field_b, w, center_a, center_b, nullptr, dev_out, "ebm_ensemble_covariance_device");
 }
 
 int ebm_ensemble_range(ebm_handle_t h, int nvars, const int *fields, const double *w, double *out) {

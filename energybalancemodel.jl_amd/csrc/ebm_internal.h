@@ -69,6 +69,9 @@ struct StepArgs {
 // fields as a one-step launch leaves them and of the prognostic fields between one-step launches.  With two
 // cells per thread the pair is the chunk and the layout is the natural one.
 __host__ __device__ constexpr unsigned split_index(unsigned t, unsigned j, unsigned T) { return j * 2u * T + 2u * t; }
+// ... read backwards, in units of one pair (16 bytes; a row has 2T of them): the natural unit that stored unit p of a row
+// stands for — p itself unless the row is held pair-split (ebm_ensemble.hip, ebm_covariance.hip)
+__host__ __device__ constexpr int natural_unit(int p, int T, bool split) { return !split ? p : (p < T ? 2 * p : 2 * (p - T) + 1); }
 
 // The zero-line flags of a MIZ handle (miz_step_kernel, ZERO_LINES; ebm_device.h): zero_flag_count 32-bit words, one per
 // (column, wave), which lie behind the ncol rows of `threads` mask words in the allocation of StepArgs::amask — so the
@@ -267,6 +270,24 @@ struct EnsembleArgs {
 hipError_t launch_ensemble_sums(const EnsembleArgs &a, hipStream_t s);
 hipError_t launch_ensemble_range(const EnsembleArgs &a, hipStream_t s);
 hipError_t launch_ensemble_histogram(const EnsembleArgs &a, hipStream_t s);
+// ebm_ensemble_covariance (ebm_covariance.hip): out[i][j] = sum over the columns of a * b, a the weighted, centred and
+// NaN-cleaned cell of row_a at latitude i and b the centred and NaN-cleaned cell of row_b at latitude j, in the order of the
+// definition (include/ebm_hip.h) — blocks of kCovBlock columns, inside a block one fp64 MFMA per four columns in ascending
+// order, into partial[block][stored i][stored j], then the blocks in ascending order.  Two launches.  The rows are read where
+// they lie (split_a, split_b: the handle holds that row pair-split; partial is indexed by the stored cells of both); the
+// centers and out are in natural latitude order.  symmetric: rule 6 of the definition — only j >= i is computed, out[j][i] is
+// a copy.
+constexpr int kCovBlock = 512;       // columns per block of the covariance: part of the definition (include/ebm_hip.h)
+struct CovarianceArgs {
+    const double *row_a, *row_b;     // [ncol][pitch]
+    bool split_a, split_b, symmetric;
+    const double *w;                 // [ncol], finite; never written by a kernel
+    const double *center_a, *center_b;      // [pitch] each, padding zero, or null: nothing is subtracted
+    double *partial;                 // [nblocks][pitch][pitch]
+    double *out;                     // [nlat][nlat], natural
+    int pitch, nlat, ncol, nblocks, threads;
+};
+hipError_t launch_ensemble_covariance(const CovarianceArgs &a, hipStream_t s);
 // ebm_column_misfits (ebm_misfit.hip): out[t][0][c] = J and out[t][1][c] = N of column c against target t, summed along the
 // column in the order of the definition (include/ebm_hip.h).  One launch, one wave per column.  row[v], split_mask: as above.
 // target[t][v][pitch] and rw[v][pitch] (null: every entry 1.0) in natural latitude order; their padding cells are never read

@@ -160,6 +160,11 @@ struct ebm_ctx {
     struct Ensemble {
         DevVec<double> partial, w, center, edges, out;
     } ensemble;
+    // ebm_ensemble_covariance, kept between calls: the block partials ([nblocks][pitch][pitch]), the two uploaded centers
+    // ([2][pitch], natural order, padding zero) and the result of the host variant ([nlat][nlat]); the weights are ensemble.w
+    struct Covariance {
+        DevVec<double> partial, center, out;
+    } covariance;
     // ebm_column_misfits, kept between calls: the uploaded targets ([8][12][pitch]) and rw ([12][pitch]), natural order,
     // padding zero, and the result of the host variant ([8][2][ncol])
     struct Misfit {

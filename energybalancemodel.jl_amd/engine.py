@@ -317,6 +317,48 @@ class Engine:
         return self._reduced("ebm_ensemble_histogram", (len(names), int(nbins) + 2, self.nlat), dev_ptr, len(ids), field_ids(ids),
                              dptr(w), int(nbins), dptr(lo), dptr(hi))
 
+    def check_covariance_args(self, name_a, name_b=None, weights=None, center_a=None, center_b=None):
+        """The host-side checks of ``ensemble_covariance`` (no device call; the rules of ebm_ensemble_covariance in
+        include/ebm_hip.h): returns (field id of ``name_a``, field id of ``name_b`` — of ``name_a`` again when ``name_b`` is
+        None —, weights [ncol] or None, center_a [nlat] or None, center_b [nlat] or None) with contiguous float64 arrays.
+        The fields are looked at first, then the weights, then the centers; the message names the offending column or the
+        center and its latitude."""
+        ids = []
+        for arg, n in (("name_a", name_a), ("name_b", name_a if name_b is None else name_b)):
+            if not isinstance(n, str):
+                raise ValueError(f"{arg}: expected one field name, got {n!r}")
+            ids.append(self._fields((n,), arg=arg)[1][0])
+        w = self._check_weights(weights)
+        centers = []
+        for arg, c in (("center_a", center_a), ("center_b", center_b)):
+            c = None if c is None else as_f64(c, (self.nlat,))
+            if c is not None and not np.isfinite(c).all():
+                k = int(np.flatnonzero(~np.isfinite(c))[0])
+                raise ValueError(f"{arg}[{k}] = {c[k]} is not finite")
+            centers.append(c)
+        return ids[0], ids[1], w, centers[0], centers[1]
+
+    def ensemble_covariance(self, name_a, name_b=None, weights=None, center_a=None, center_b=None) -> np.ndarray:
+        """ebm_ensemble_covariance (the definition is in include/ebm_hip.h): ndarray [nlat, nlat], ``[i, j]`` = the sum over
+        the columns of a * b with a = w_c * (x - center_a[i]), x the cell of ``name_a`` at latitude i, and b = y -
+        center_b[j], y the cell of ``name_b`` (None: ``name_a``) at latitude j, reduced on the device with the fp64 matrix
+        instruction.  a and b are +0.0 where w_c == 0 or the cell is NaN (the sentinels of Ti and Tw): a zero weight removes
+        the member; +-Inf follows IEEE (Inf * 0 is NaN).  ``weights`` [ncol] (None: all 1.0; negative ones are legal),
+        ``center_a``, ``center_b`` [nlat] (None: nothing is subtracted).  The order is fixed — blocks of 512 columns, inside
+        a block one matrix instruction per four columns in ascending order, then the block partials in ascending order — so
+        the bits do not depend on the run, the launch geometry or the layout the handle holds the rows in; no field is
+        converted.  One field against itself about one center (both None, or equal bit for bit) is computed for j >= i only
+        and mirrored: symmetric to the bit.  Each element is within (n + ceil(ncol / 512)) * 2^-53 * sum|a * b| * (1 + 2^-4)
+        of the exact sum of its terms, n the members with nonzero weight.  StaleFieldError for a stale diagnostic field, as
+        ``hemispheric_mean``.  The step clock, the counters and ``field_step`` are unchanged."""
+        return self.ensemble_covariance_device(name_a, name_b, weights, center_a, center_b, _HOST)
+
+    def ensemble_covariance_device(self, name_a, name_b, weights, center_a, center_b, dev_ptr: int):
+        """Same reduction, the packed [nlat, nlat] result left on the device at ``dev_ptr`` (e.g. the ``data_ptr()`` of a
+        torch tensor on this engine's device: the payload of an all-reduce between shards)."""
+        fa, fb, w, ca, cb = self.check_covariance_args(name_a, name_b, weights, center_a, center_b)
+        return self._reduced("ebm_ensemble_covariance", (self.nlat, self.nlat), dev_ptr, fa, fb, dptr(w), dptr(ca), dptr(cb))
+
     def _check_misfit_args(self, names, targets, rweights=None):
         """The host-side checks of ``column_misfits`` (no device call): returns (names, field ids, targets [ntargets, nvars,
         nlat], rweights [nvars, nlat] or None) with contiguous float64 arrays.  The field rules are those of

@@ -574,7 +574,69 @@ class EnsembleMoments:
         return {n: {"value": value[i], "halfwidth": half[i]} for i, n in enumerate(names)}
 
 
-class EnsembleRun(ColumnExchange, EnsembleMoments):
+class CovarianceMixin(EnsembleMoments):
+    """Covariances and EOFs across the members in terms of two more methods of the class it is mixed into:
+    ``ensemble_covariance(name_a, name_b, weights, center_a, center_b) -> ndarray [nlat, nlat]`` and
+    ``ensemble_covariance_tensor(...)``, the same as a device tensor — and of ``ensemble_sums`` for the means.  EnsembleRun
+    is one."""
+
+    def covariance(self, name_a, name_b=None, weights=None, dist=None) -> dict:
+        """The weighted covariance ACROSS the members of ``name_a`` at latitude i with ``name_b`` (None: ``name_a``) at
+        latitude j: ``{"mean_a": [nlat], "mean_b": [nlat], "cov": [nlat, nlat], "n": [nlat, nlat]}``.  One pass of
+        ebm_ensemble_sums gives S0 and the means S1 / S0 of both fields; one pass of ebm_ensemble_covariance centred on those
+        means gives the matrix of sums, which is divided ONCE, on the host, by ``n[i, j] = min(S0_a[i], S0_b[j])`` — the sum
+        of the weights wherever no cell is NaN.  (Where the NaN sentinels of Ti or Tw thin a latitude out, the members that
+        have both cells of a pair are at most that n; such entries are the sum over those members divided by n.)  A pair
+        with n == 0 is NaN, and a latitude without a contributor is centred on 0.0 (``moments_center``).  nlat^2 numbers
+        leave the device, never the fields.  ``weights`` [ncol of this shard] as in ``moments``.
+        With ``dist`` the sums and then the matrices of the shards are all-reduced (SUM), so every rank returns the
+        covariance of the whole ensemble.  Each shard's matrix is defined to the bit (ebm_ensemble_covariance); adding the
+        shards' matrices adds the same terms in another order than the unsharded call does, so the two are NOT equal bit for
+        bit, for the reason ``moments`` gives for the sums: they agree within the sum of their error bounds, each
+        (n_members + blocks) * 2^-53 * sum|terms| * (1 + 2^-4) per element, plus one rounded add per further shard."""
+        name_b = name_a if name_b is None else name_b
+        names = (name_a,) if name_b == name_a else (name_a, name_b)
+        s1 = np.asarray(self.reduced_sums(names, weights, None, dist))
+        m = moments_from_sums(s1)
+        mean_a, mean_b = m["mean"][0], m["mean"][-1]
+        ca = moments_center(mean_a)
+        cb = ca if name_b == name_a else moments_center(mean_b)
+        c = np.asarray(self._across_ranks(dist, "covariance", name_a, name_b, weights, ca, cb))
+        n = np.minimum.outer(m["weight"][0], m["weight"][-1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cov = np.where(n == 0.0, np.nan, c / n)
+        return {"mean_a": mean_a, "mean_b": mean_b, "cov": cov, "n": n}
+
+    def eofs(self, name, nmodes, weights=None, quad=None, dist=None) -> dict:
+        """The leading ``nmodes`` EOFs (principal components) of ``name`` across the members: ``{"modes": [nmodes, nlat],
+        "variance": [nmodes], "explained": [nmodes]}``.  ``covariance(name)`` is taken on the device; rows and columns are
+        scaled by the square roots of the quadrature weights ``quad`` [nlat] >= 0 (None: all 1.0), so that the modes are
+        orthonormal under sum_k quad_k u_k v_k; ``numpy.linalg.eigh`` runs on the host on that [nlat, nlat] matrix.  The
+        modes come back in the field's own units (the eigenvectors divided by sqrt(quad); 0.0 where quad is 0) in
+        descending order of variance, each with its largest-magnitude entry positive (the first of several), with their
+        eigenvalues and their fractions of the total variance (the trace).  ValueError where the covariance is not finite
+        (a latitude without a contributing member, as the NaN sentinels of Ti and Tw can leave one)."""
+        c = self.covariance(name, None, weights, dist)["cov"]
+        nlat = c.shape[0]
+        if isinstance(nmodes, (bool, np.bool_)) or not isinstance(nmodes, (int, np.integer)) or not 1 <= int(nmodes) <= nlat:
+            raise ValueError(f"nmodes: expected an int between 1 and {nlat}, got {nmodes!r}")
+        q = np.ones(nlat) if quad is None else np.asarray(quad, dtype=np.float64)
+        if q.shape != (nlat,) or not (np.isfinite(q) & (q >= 0.0)).all():
+            raise ValueError(f"quad: expected {nlat} finite quadrature weights >= 0")
+        if not np.isfinite(c).all():
+            raise ValueError(f"eofs: the covariance of {name!r} is not finite (a latitude without a contributing member, or Inf in a cell)")
+        s = np.sqrt(q)
+        vals, vecs = np.linalg.eigh(s[:, None] * c * s[None, :])
+        order = np.argsort(vals)[::-1][:int(nmodes)]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            modes = np.where(s > 0.0, vecs[:, order].T / s, 0.0)
+        big = np.argmax(np.abs(modes), axis=1)
+        modes = modes * np.where(modes[np.arange(len(order)), big] < 0.0, -1.0, 1.0)[:, None]
+        total = float(np.sum(vals))
+        return {"modes": modes, "variance": vals[order], "explained": vals[order] / total if total > 0.0 else np.full(len(order), np.nan)}
+
+
+class EnsembleRun(ColumnExchange, CovarianceMixin):
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
     ``init`` maps prognostic names to [ncol, nlat] arrays (or [nlat], broadcast to all
@@ -886,6 +948,19 @@ class EnsembleRun(ColumnExchange, EnsembleMoments):
     def ensemble_histogram_tensor(self, names, lo, hi, nbins, weights=None):
         """The same as a float64 torch tensor ON THE DEVICE (ebm_ensemble_histogram_device), ready for RCCL."""
         return self._reduced_tensor(names, int(nbins) + 2, lambda ptr: self.engine.ensemble_histogram_device(names, lo, hi, nbins, ptr, weights))
+
+    def ensemble_covariance(self, name_a, name_b=None, weights=None, center_a=None, center_b=None):
+        """This shard's matrix of sums across its members for every pair of latitudes (ebm_ensemble_covariance): ndarray
+        [nlat, nlat].  See ``Engine.ensemble_covariance``; ``covariance`` centres it on the ensemble means and ``eofs``
+        diagonalises it."""
+        return self.engine.ensemble_covariance(name_a, name_b, weights, center_a, center_b)
+
+    def ensemble_covariance_tensor(self, name_a, name_b=None, weights=None, center_a=None, center_b=None):
+        """The same as a float64 torch tensor [nlat, nlat] ON THE DEVICE (ebm_ensemble_covariance_device), ready to be
+        all-reduced over RCCL."""
+        out = self._device_tensor(self.st.nx, self.st.nx)
+        self.engine.ensemble_covariance_device(name_a, name_b, weights, center_a, center_b, out.data_ptr())
+        return out
 
     def misfits(self, names, targets, rweights=None):
         """This shard's per-member misfits to the target profiles (ebm_column_misfits): ndarray [ntargets, 2, ncol] of J and

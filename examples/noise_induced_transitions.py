@@ -12,10 +12,13 @@ every N steps and a member that has fallen takes no further step — its state s
 the same and the script also prints the share of column-steps that were not taken.  With `--quantiles` the yearly table
 is followed, per F, by the profile of T(x) and phi(x) across the members at the end of the run: the ensemble mean beside the
 median and the 5-95 % band (EnsembleRun.moments and EnsembleRun.quantiles, both reduced on the device) — where members sit
-on both branches the mean describes none of them.
+on both branches the mean describes none of them.  With `--eofs N` it is followed, per F, by the N leading EOFs of T(x) across
+the members (EnsembleRun.eofs: the nlat x nlat covariance reduced on the device by ebm_ensemble_covariance, diagonalised on the
+host under the grid's trapezoid weights) and the fraction of the variance each explains — with members on two branches the
+first EOF is the difference between the branches.
 
     python examples/noise_induced_transitions.py [--nlat 180] [--nt 2000] [--forcings -2,0,2] [--members 64]
-        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0] [--until] [--quantiles]
+        [--years 20] [--sigma 4.0] [--tau 0.1] [--seed 1] [--max-years 60] [--every 0] [--until] [--quantiles] [--eofs 0]
 """
 import argparse
 import os
@@ -50,7 +53,11 @@ def main():
                          "x = X (EnsembleRun.first_passage_scalar), and print those first-passage times")
     ap.add_argument("--quantiles", action="store_true",
                     help="after the yearly table: mean, median and 5-95 %% band of T(x) and phi(x) across the members, per F")
+    ap.add_argument("--eofs", type=int, default=0, metavar="N",
+                    help="after the yearly table: the N leading EOFs of T(x) across the members, per F (0: none)")
     args = ap.parse_args()
+    if args.eofs < 0 or args.eofs > args.nlat:
+        ap.error("--eofs N needs 0 <= N <= nlat")
     if args.until and not args.every:
         ap.error("--until needs --every N: the level is tested every N steps")
     if args.until_edge is not None and (not args.every or args.until):
@@ -133,6 +140,12 @@ def main():
         for i in range(nf):
             w = (np.arange(nf * n) // n == i).astype(np.float64)
             profiles.append((run.moments(("T", "phi"), w), run.quantiles(("T", "phi"), (0.05, 0.5, 0.95), w)))
+    eofs = []
+    if args.eofs:
+        quad = np.gradient(st.x)                           # trapezoid weights of the grid, up to the halved ends
+        quad[[0, -1]] *= 0.5
+        for i in range(nf):
+            eofs.append(run.eofs("T", args.eofs, (np.arange(nf * n) // n == i).astype(np.float64), quad))
     run.close()
     avgT = out["avg"][0]                                   # [years, members]
     fell = avgT < threshold
@@ -149,6 +162,11 @@ def main():
             for k in lats:
                 v = q[name]["value"][:, k]
                 print(f"  {name:>3s}  {st.x[k]:5.3f}  {m[name]['mean'][k]:7.3f}  {v[0]:7.3f}  {v[1]:7.3f}  {v[2]:7.3f}")
+    for i, e in enumerate(eofs):
+        print(f"\nF = {F[i]:.2f}, end of year {args.years}, EOFs of T(x) across the {n} members (explained variance: "
+              + ", ".join(f"{v:.3f}" for v in e["explained"]) + "):   x  " + "  ".join(f"EOF {j + 1}" for j in range(args.eofs)))
+        for k in lats:
+            print(f"       {st.x[k]:5.3f}  " + "  ".join(f"{e['modes'][j, k]:6.3f}" for j in range(args.eofs)))
 
 
 if __name__ == "__main__":

@@ -164,7 +164,7 @@ const char *ebm_version(void);
  * T, h) and the fp64 warm start EBM_F_T0 are written only by steps that were asked to (ebm_step with
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
- * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_column_misfits*, ebm_column_scalars*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
+ * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_ensemble_covariance*, ebm_column_misfits*, ebm_column_scalars*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
  * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
@@ -653,6 +653,79 @@ int ebm_ensemble_histogram(ebm_handle_t h, int nvars, const int *fields, const d
                            const double *hi, double *out);
 int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, const double *w, int nbins, const double *lo,
                                   const double *hi, double *dev_out);
+
+/* COVARIANCE ACROSS THE MEMBERS, per PAIR of latitudes: how field_a at latitude i co-varies with field_b at latitude j over
+ * the columns of the handle — the matrix whose eigenvectors are the EOFs of an ensemble that sits on two branches, whose rows
+ * are the correlation of the ice edge with the tropics, and which an ensemble Kalman update takes for its background
+ * covariance — reduced on the device, so that nlat^2 doubles cross the bus, or enter an all-reduce between shards, instead of
+ * O(state).  The one dense contraction of the library: it runs on the fp64 matrix instruction of gfx950.  (The covariance of
+ * every latitude with a few SCALARS is ebm_ensemble_sums with the scalars' deviations for member weights.)  THIS TEXT IS THE
+ * DEFINITION.
+ *   Arguments.  field_a, field_b: solution variables of the model under the rules of ebm_ensemble_sums (one piece of code
+ *     checks them for both), prognostic or diagnostic; EBM_F_T0 is not one; the two may be equal.  w[ncol]: host array of
+ *     member weights, NULL = every w_c = 1.0; finite; negative weights are legal.  center_a[nlat], center_b[nlat]: host
+ *     arrays in natural latitude order, finite, NULL = nothing is subtracted.  out[nlat][nlat], on the host: row i belongs to
+ *     field_a at latitude i, column j to field_b at latitude j, both in natural latitude order; the _device variant writes
+ *     the same packed array into the caller's device buffer dev_out.
+ *   Terms.  For column c, with x the cell of field_a at latitude i and y the cell of field_b at latitude j:
+ *     da = x - center_a[i] (da = x when center_a is NULL), a = w_c * da and b = y - center_b[j] (b = y when center_b is
+ *     NULL) — two rounded differences and one rounded product.  a is replaced by +0.0 when w_c == 0.0 or x is NaN; b is
+ *     replaced by +0.0 when w_c == 0.0 or y is NaN.  So a zero weight removes the member (its cells may hold anything, Inf
+ *     included), and a NaN sentinel of Ti or Tw (src/miz.jl:193-194) contributes nothing to any pair it is in.
+ *     out[i][j] = the sum over c of a * b.  +-Inf in a contributing cell is data and follows IEEE — in particular Inf * 0 is
+ *     NaN: an infinite cell of a member at i makes out[i][j] NaN wherever that member's b is zero, a cleaned NaN sentinel
+ *     included.  The number of contributors per latitude is S0 of ebm_ensemble_sums; this call returns none.
+ *   Order.  The products and adds of a group of four members are ONE v_mfma_f64_16x16x4_f64 and their bits are the
+ *     hardware's, so this text does not restate them operation by operation; it fixes everything around them:
+ *     1. Block B holds the columns 512 B ... min(512 B + 511, ncol - 1) (kCovBlock = 512).
+ *     2. The partial of a block starts at +0.0 and takes the block's members in ascending groups of four, one matrix
+ *        instruction per group: partial <- mfma(a[0..3], b[0..3], partial).  A tail group of fewer than four is padded
+ *        with terms a = b = +0.0.
+ *     3. out[i][j] = partial_0 + partial_1 + ..., the block partials in ascending B with plain rounded adds.  With one block
+ *        the result is that block's partial.  No atomic is involved.
+ *     4. The same call on the same data gives the same bits on every run.
+ *     5. The bits depend neither on the launch geometry (cells_per_thread) nor on the layout the handle holds the rows in:
+ *        every out[i][j] sees the same chain over the members, whichever tile of the kernel it falls in.
+ *     6. When field_a == field_b and the two centers are both NULL or equal bit for bit, out[i][j] is defined for j >= i
+ *        only, and out[j][i] is a copy of out[i][j] — inside the tiles on the diagonal too.  The result is symmetric to
+ *        the bit.  (Otherwise out[i][j] and out[j][i] differ in which factor carries w_c.)  The work that is skipped is
+ *        decided per 32 x 32 block of stored cells, see "How it runs": towards half of it as nlat grows.
+ *   Accuracy.  With n the number of members with w_c != 0, nblocks = ceil(ncol / 512) and T_ij = the sum over c of |a * b|:
+ *     |out[i][j] - the exact sum of the stated terms| <= (n + nblocks) * 2^-53 * T_ij * (1 + 2^-4), for any order of correctly
+ *     rounded multiplies, adds or fused multiply-adds inside the instruction; the last factor covers the second-order terms
+ *     (and the 64-bit-mantissa reference of the tests).
+ *   Across shards.  Each shard's matrix is defined as above.  Adding the matrices of several shards adds the same terms in
+ *     another order than the unsharded call does: the two agree within the sum of their bounds, not bit for bit.
+ *   Validity, layout, bookkeeping, ordering: those of ebm_ensemble_sums, through the same code.  A diagnostic field that is
+ *     older than the state fails with EBM_ERR_STALE exactly as ebm_hemispheric_mean does (the same message); phi, left
+ *     underived by state-only one-step launches, is made current first; rows are read in whatever layout the handle holds
+ *     them and no field is converted (ebm_state_conversions does not grow) — only the indexing of the centers and of the
+ *     output is un-permuted; cells between nlat and the row pitch never reach a result; the step clock, counters[0..3] and
+ *     ebm_field_step are unchanged and the two launches are not counted; both calls are synchronous on the handle's stream,
+ *     the two launch chains joined first.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle or out, a field that is not a solution variable of the
+ * model, a non-finite w[c] (the message names the column), a non-finite center entry (the message names the center, a or b,
+ * and the latitude); EBM_ERR_STALE as above.
+ * How it runs (csrc/ebm_covariance.hip): one kernel forms the block partials — grid (tiles of field_b) x (tiles of field_a)
+ * x (member blocks), 256 lanes owning 64 x 64 STORED cells, so that its accesses are whole 128-byte lines in either layout;
+ * sixteen members at a time pass through 20 KiB of LDS, the A side centred, weighted and NaN-cleaned on the way in, the B
+ * side centred and NaN-cleaned, the next sixteen in flight under the matrix instructions; each of the four waves owns
+ * 32 x 32 as 2 x 2 accumulators; LDS rows are padded to 80 doubles so that the operand reads are free of bank conflicts —
+ * and a second one adds the block partials per element in ascending order and writes the natural index, under rule 6 both
+ * out[i][j] and out[j][i].  Under rule 6 a 64 x 64 tile, and inside a tile each wave's 32 x 32 block, does nothing if the
+ * natural cells it stands for hold no pair with j >= i; a block that holds one is computed whole, its elements with j < i
+ * are never read.  In natural rows that skips (t - 1) / 2t of the blocks, t = ceil(nlat / 32) per side; in pair-split rows a
+ * block stands for every other pair of a 64-cell span and two blocks of overlapping spans are both kept, so fewer are
+ * skipped.  Tiles and waves that hold only padding do nothing either.  Plain vector loads
+ * and stores, no atomics, no scratch.  Device memory, kept by the handle and reused: ceil(ncol / 512) * pitch^2 doubles of
+ * block partials (pitch: nlat rounded up to the launch geometry's row, a multiple of 128), 2 * pitch doubles of centers,
+ * the weights of ebm_ensemble_sums (ncol doubles), and nlat^2 doubles for the host variant's result.  For nlat x ncol =
+ * 180 x 4096 (pitch 256): 4 MiB + 4 KiB + 32 KiB + 253 KiB; 1024 x 16384: 256 MiB + 16 KiB + 128 KiB + 8 MiB; 4096 x 2048:
+ * 512 MiB + 64 KiB + 16 KiB + 128 MiB. */
+int ebm_ensemble_covariance(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a,
+                            const double *center_b, double *out);
+int ebm_ensemble_covariance_device(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a,
+                                   const double *center_b, double *dev_out);
 
 /* PER-MEMBER MISFITS TO TARGET PROFILES, reduced ALONG each column on the device: for every column c and every one of
  * ntargets target profiles, J = the weighted squared distance of the column's profiles to the target and N = the number of

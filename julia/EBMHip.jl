@@ -360,6 +360,43 @@ function ensemble_sums_device!(h::Handle, names::Vector{Symbol}, devout::Ptr{Cdo
 end
 
 """
+    ensemble_covariance(h, name_a, name_b=name_a; ncol, nlat, weights=nothing, center_a=nothing, center_b=nothing) -> Matrix{Float64}
+    ensemble_covariance_device!(h, name_a, name_b, devout; weights=nothing, center_a=nothing, center_b=nothing)
+
+Covariance across the columns for every pair of latitudes, reduced on the device with the fp64 matrix instruction
+(`ebm_ensemble_covariance`; the definition is in the header): `out[i, j] = sum_c (w_c (x_c[i] - center_a[i])) (y_c[j] -
+center_b[j])`, `x` the cells of `name_a` and `y` those of `name_b`; a zero weight removes the member and a NaN cell
+contributes nothing.  `weights`: `ncol` values (`nothing`: all 1.0); the centers: `nlat` values each (`nothing`: nothing is
+subtracted).  One field against itself about one center gives a matrix that is symmetric to the bit.  The `_device!` form
+writes the packed row-major array (`out[i][j]` at `i * nlat + j`, 0-based) to the device pointer `devout`.
+"""
+function ensemble_covariance(h::Handle, name_a::Symbol, name_b::Symbol=name_a; ncol::Integer, nlat::Integer, weights=nothing,
+                             center_a=nothing, center_b=nothing)
+    out = Matrix{Float64}(undef, nlat, nlat)
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    ca = center_a === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(center_a)
+    cb = center_b === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(center_b)
+    weights === nothing || length(weights) == ncol || error("weights: expected $ncol values")
+    center_a === nothing || length(center_a) == nlat || error("center_a: expected $nlat values")
+    center_b === nothing || length(center_b) == nlat || error("center_b: expected $nlat values")
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_covariance(h.ptr::Ptr{Cvoid}, FIELD[name_a]::Cint, FIELD[name_b]::Cint,
+                                                               w::Ptr{Cdouble}, ca::Ptr{Cdouble}, cb::Ptr{Cdouble},
+                                                               out::Ptr{Cdouble})::Cint), "ebm_ensemble_covariance")
+    return permutedims(out)          # the C array is row-major
+end
+
+function ensemble_covariance_device!(h::Handle, name_a::Symbol, name_b::Symbol, devout::Ptr{Cdouble}; weights=nothing,
+                                     center_a=nothing, center_b=nothing)
+    w = weights === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(weights)
+    ca = center_a === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(center_a)
+    cb = center_b === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(center_b)
+    GC.@preserve h check(@ccall(libebm.ebm_ensemble_covariance_device(h.ptr::Ptr{Cvoid}, FIELD[name_a]::Cint, FIELD[name_b]::Cint,
+                                                                      w::Ptr{Cdouble}, ca::Ptr{Cdouble}, cb::Ptr{Cdouble},
+                                                                      devout::Ptr{Cdouble})::Cint),
+                         "ebm_ensemble_covariance_device")
+end
+
+"""
     ensemble_range(h, names; ncol, nlat, weights=nothing) -> Array{Float64,3}
     ensemble_range_device!(h, names, devout; weights=nothing)
     ensemble_histogram(h, names, lo, hi, nbins; ncol, nlat, weights=nothing) -> Array{Float64,3}
