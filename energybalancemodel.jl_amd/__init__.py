@@ -14,7 +14,7 @@ from .infrastructure import (  # noqa: F401
 from .ensemble import (  # noqa: F401
     EnsembleRun, shard_columns, gather_columns, broadcast_inputs, hemispheric_mean,
     selection_parents, gklt_run, gklt_lineage, gklt_estimate, resample_plan, ResamplePlan, ColumnExchange,
-    moments_from_sums, assimilation_weights, scalar_spec,
+    moments_from_sums, assimilation_weights, scalar_spec, gaspari_cohn,
 )
 
 Vec = "numpy.ndarray[float64]"  # the reference's Vec = Vector{Float64} (src/infrastructure.jl:13)

@@ -90,6 +90,8 @@ SIGNATURES = {
     "ebm_ensemble_covariance_device": [_h, _i, _i, _dp, _dp, _dp, _dev],
     "ebm_column_misfits": [_h, _i, _ip, _i, _dp, _dp, _dp],
     "ebm_column_misfits_device": [_h, _i, _ip, _i, _dp, _dp, _dev],
+    "ebm_update_columns": [_h, _i, _ip, _i, _dp, _dp, _d, _dev, _dp, _dp],
+    "ebm_update_columns_device": [_h, _i, _ip, _i, _dev, _dp, _d, _dev, _dp, _dp],
     "ebm_column_scalars": [_h, _i, _ip, _dp, _dp],
     "ebm_column_scalars_device": [_h, _i, _ip, _dp, _dev],
     "ebm_run_series_scalars": [_h, _ll, _i, _dp, _i, _i, _i, _ip, _dp, _dp],

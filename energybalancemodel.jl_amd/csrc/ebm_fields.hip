@@ -1,5 +1,6 @@
 // Host runtime, fields (ebm_runtime.h lists the units): set / get with the validity bookkeeping, device views, hemispheric
-// means, and the two diffusion operators that work on caller-supplied fields (ebm_diffusion, ebm_zonal_diffusion).
+// means, the ensemble reductions, the ensemble Kalman update (ebm_update_columns) and the two diffusion operators that work on
+// caller-supplied fields (ebm_diffusion, ebm_zonal_diffusion).
 #include <cmath>
 #include <cstring>
 
@@ -390,6 +391,93 @@ int get_scratch(ebm_ctx *h) {
     return EBM_OK;
 }
 
+// ebm_update_columns and its _device form (include/ebm_hip.h): every check before anything of the handle changes; then what one
+// ebm_set_field per listed field does to the book, minus the conversion to the natural layout (the kernels take the rows where
+// they lie); then the innovations of all columns staged from the state as it is at entry, and the product per field — the
+// host variant's gain uploaded one field at a time into the handle's one pitch^2 buffer.  Synchronous.
+int update_columns(ebm_ctx *h, int nvars, const int *fields, int obs_field, const double *gain, bool gain_on_device, const double *target,
+                   double scale, const double *dev_perturb, const double *lo, const double *hi, const char *who) {
+    const std::string me(who);
+    if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
+    if (!fields || !gain || !target) return fail(EBM_ERR_ARG, me + ": null argument");
+    if (nvars < 1 || nvars > ebm::kUpdateMaxFields)
+        return fail(EBM_ERR_ARG, me + ": nvars = " + std::to_string(nvars) + " is outside 1 ... " + std::to_string(ebm::kUpdateMaxFields));
+    for (int v = 0; v < nvars; ++v) {
+        if (!h->book.has(fields[v]) || h->book.is_diagnostic(fields[v]))
+            return fail(EBM_ERR_ARG, me + ": fields[" + std::to_string(v) + "] is not a prognostic field of this model");
+        for (int u = 0; u < v; ++u)
+            if (fields[u] == fields[v]) return fail(EBM_ERR_ARG, me + ": field " + field_name(fields[v]) + " is listed twice");
+    }
+    if (!h->book.has(obs_field) || quantity_of(h->model, obs_field) < 0)
+        return fail(EBM_ERR_ARG, me + ": obs_field is not a solution variable of this model");
+    if (!std::isfinite(scale)) return fail(EBM_ERR_ARG, me + ": scale is not finite");
+    const size_t nlat = (size_t)h->nlat, npitch = (size_t)h->pitch;
+    for (size_t i = 0; !gain_on_device && i < (size_t)nvars * nlat * nlat; ++i)
+        if (!std::isfinite(gain[i]))
+            return fail(EBM_ERR_ARG, me + ": gain[" + std::to_string(i / (nlat * nlat)) + "][" + std::to_string(i / nlat % nlat) + "][" +
+                                         std::to_string(i % nlat) + "] is not finite (field " + field_name(fields[i / (nlat * nlat)]) +
+                                         ", k = " + std::to_string(i / nlat % nlat) + ", j = " + std::to_string(i % nlat) + ")");
+    for (size_t j = 0; j < nlat; ++j)
+        if (std::isinf(target[j]))
+            return fail(EBM_ERR_ARG, me + ": target[" + std::to_string(j) + "] is infinite (finite, or NaN for no observation)");
+    const double inf = HUGE_VAL;
+    ebm::UpdateArgs a{};
+    for (int v = 0; v < nvars; ++v) {
+        a.lo[v] = lo ? lo[v] : -inf;
+        a.hi[v] = hi ? hi[v] : inf;
+        if (a.lo[v] != a.lo[v] || a.hi[v] != a.hi[v] || a.lo[v] > a.hi[v])
+            return fail(EBM_ERR_ARG, me + ": lo[" + std::to_string(v) + "], hi[" + std::to_string(v) + "] are not bounds with lo <= hi (NaN is none; -Inf / +Inf: no bound)");
+    }
+    if (gain_on_device && reinterpret_cast<uintptr_t>(gain) % 16)
+        return fail(EBM_ERR_ARG, me + ": the device gain is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(dev_perturb) % 8) return fail(EBM_ERR_ARG, me + ": dev_perturb is not 8-byte aligned");
+    if (int rc = check_current(h, obs_field, who)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    // device memory first: a failed allocation leaves the book as it was
+    ebm_ctx::Update &b = h->update;
+    const bool fresh_target = !b.target.get();
+    HIPCHK(b.target.reserve(npitch));
+    if (!gain_on_device) HIPCHK(b.gain.reserve(npitch * npitch));
+    const bool borrowed = (bool)h->scratch;              // the staged innovations: [ncol][pitch], one owner (ebm_runtime.h)
+    if (!borrowed) HIPCHK(h->resample.stage.reserve((size_t)h->ncol * npitch));
+    // what ebm_set_field does before it writes a prognostic field (phi current where it lies, then no longer derived; no
+    // zero-line flag trusted) — not the conversion: the rows are taken in the layout they have
+    if (h->model == EBM_MODEL_MIZ)
+        if (int rc = state_written_outside(h)) return rc;
+    const hipStream_t s = main_stream(h);                // joins the two launch chains: every column's last step has ended
+    if (fresh_target) HIPCHK(hipMemsetAsync(b.target.get(), 0, sizeof(double) * npitch, s));
+    hipError_t e = hipMemcpyAsync(b.target.get(), target, sizeof(double) * nlat, hipMemcpyHostToDevice, s);
+    for (int v = 0; v < nvars; ++v) {
+        a.row[v] = h->field[fields[v]];
+        if (h->book.held_split(fields[v])) a.split_mask |= 1u << v;
+    }
+    a.obs = h->field[obs_field];
+    a.obs_split = h->book.held_split(obs_field);
+    a.target = b.target.get();
+    a.perturb = dev_perturb;
+    a.d = borrowed ? h->scratch.get() : h->resample.stage.get();
+    a.scale = scale;
+    a.pitch = (int)h->pitch; a.nlat = h->nlat; a.ncol = h->ncol; a.nvars = nvars; a.threads = h->cfg.threads;
+    if (e == hipSuccess) e = ebm::launch_update_innovations(a, s);
+    if (gain_on_device) {                                // one launch over a grid z of fields
+        a.gain = gain; a.gain_field = (long long)(nlat * nlat); a.gain_row = (long long)nlat;
+        if (e == hipSuccess) e = ebm::launch_update_product(a, s);
+    } else {
+        for (int v = 0; v < nvars && e == hipSuccess; ++v) {
+            ebm::UpdateArgs one = a;
+            one.row[0] = a.row[v]; one.lo[0] = a.lo[v]; one.hi[0] = a.hi[v]; one.split_mask = (a.split_mask >> v) & 1u; one.nvars = 1;
+            one.gain = b.gain.get(); one.gain_field = 0; one.gain_row = h->pitch;
+            e = hipMemcpy2DAsync(b.gain.get(), sizeof(double) * npitch, gain + (size_t)v * nlat * nlat, sizeof(double) * nlat,
+                                 sizeof(double) * nlat, nlat, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = ebm::launch_update_product(one, s);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(who, e);
+    for (int v = 0; v < nvars; ++v) h->book.field_set(fields[v]);       // the prognostic state changed: the diagnostics are older
+    return EBM_OK;
+}
+
 // The parameters of the zonal operator: the handle's vector, or the one set ebm_set_column_params installed
 const ebm::Params &zonal_params(const ebm_ctx *h) { return h->sets.n ? h->sets.host[0] : h->p; }
 // The zonal tables (ebm_tables::build_zonal_tables) on the device, with the segmented sweep's scratch behind them.  Built on
@@ -543,6 +631,16 @@ int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntarget
 int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target, const double *rw,
                               double *dev_out) {
     return column_misfits(h, nvars, fields, ntargets, target, rw, nullptr, dev_out, "ebm_column_misfits_device");
+}
+
+int ebm_update_columns(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *gain, const double *target,
+                       double scale, const double *dev_perturb, const double *lo, const double *hi) {
+    return update_columns(h, nvars, fields, obs_field, gain, false, target, scale, dev_perturb, lo, hi, "ebm_update_columns");
+}
+
+int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *dev_gain, const double *target,
+                              double scale, const double *dev_perturb, const double *lo, const double *hi) {
+    return update_columns(h, nvars, fields, obs_field, dev_gain, true, target, scale, dev_perturb, lo, hi, "ebm_update_columns_device");
 }
 
 int ebm_column_scalars(ebm_handle_t h, int nscal, const int *spec, const double *level, double *out) {

@@ -288,6 +288,29 @@ struct CovarianceArgs {
     int pitch, nlat, ncol, nblocks, threads;
 };
 hipError_t launch_ensemble_covariance(const CovarianceArgs &a, hipStream_t s);
+// ebm_update_columns (ebm_update.hip): row[v][c][k] <- clamp(row[v][c][k] + sum_j gain[v][k][j] * d[c][j]) in the order of the
+// definition (include/ebm_hip.h) — d staged first for all columns by launch_update_innovations from obs as it lies, then one
+// fp64 MFMA per four observation cells in ascending order, d the A operand.  row[v], obs: [ncol][pitch], read and written where
+// they lie (bit v of split_mask, obs_split: the handle holds that row pair-split).  gain, target, perturb and d are in natural
+// latitude order: gain[v] at gain + v * gain_field, its row k at k * gain_row (only k, j < nlat are read); target[pitch];
+// perturb [ncol][nlat] packed or null; d [ncol][pitch], every cell at or beyond nlat written +0.0.
+constexpr int kUpdateMaxFields = 5;
+struct UpdateArgs {
+    double *row[kUpdateMaxFields];
+    unsigned split_mask;
+    bool obs_split;
+    const double *obs;
+    const double *gain;
+    long long gain_field, gain_row;
+    const double *target;
+    const double *perturb;
+    double *d;
+    double scale;
+    double lo[kUpdateMaxFields], hi[kUpdateMaxFields];    // -Inf / +Inf: no bound
+    int pitch, nlat, ncol, nvars, threads;
+};
+hipError_t launch_update_innovations(const UpdateArgs &a, hipStream_t s);
+hipError_t launch_update_product(const UpdateArgs &a, hipStream_t s);
 // ebm_column_misfits (ebm_misfit.hip): out[t][0][c] = J and out[t][1][c] = N of column c against target t, summed along the
 // column in the order of the definition (include/ebm_hip.h).  One launch, one wave per column.  row[v], split_mask: as above.
 // target[t][v][pitch] and rw[v][pitch] (null: every entry 1.0) in natural latitude order; their padding cells are never read

@@ -6,8 +6,8 @@
 //                     fused, and where a raw snapshot lies in the staging buffer: SaveWalk, RawStaging
 //   ebm_runtime.hip   errors, options, create / destroy, sync, counters, timers, stamps, self-test, launch info
 //   ebm_fields.hip    field I/O with the validity bookkeeping, device views, hemispheric means, the one host path of the three
-//                     ensemble reductions (ebm_ensemble.hip) and of the column misfits (ebm_misfit.hip), the two diffusion
-//                     operators
+//                     ensemble reductions (ebm_ensemble.hip) and of the column misfits (ebm_misfit.hip), the ensemble
+//                     Kalman update (ebm_update.hip), the two diffusion operators
 //   ebm_columns.hip   per-column forcing, schedules, noise and parameter sets; the step clock and the time table; resampling
 //   ebm_drive.hip     step launches, graph replay, fused ranges, series, integrate, equilibrate, run-until
 // Not part of the public interface.
@@ -145,7 +145,8 @@ struct ebm_ctx {
     DevBuf<double> scratch;                        // ebm_diffusion / ebm_zonal_diffusion: three fields, kept between calls
     // ebm_resample_columns, kept between calls: the list of moved columns — (destination, parent) pairs — in pinned host
     // memory and on the device, the event after which the pinned list may be refilled (the upload has read it), and the
-    // staging rows of a handle that has no `scratch`
+    // staging rows of a handle that has no `scratch` (ebm_update_columns stages its innovations in the same rows: calls on one
+    // stream, one after the other)
     struct Resample {
         PinnedBuf<int> host;
         size_t host_cap = 0;                       // pairs
@@ -170,6 +171,11 @@ struct ebm_ctx {
     struct Misfit {
         DevVec<double> target, rw, out;
     } misfit;
+    // ebm_update_columns, kept between calls: one field's gain ([pitch][pitch], host variant) and the uploaded target ([pitch]).
+    // The staged innovations are not its own: they lie in `scratch` or, where the handle has none, in resample.stage
+    struct Update {
+        DevVec<double> gain, target;
+    } update;
     DevVec<double> scalars_out;                    // ebm_column_scalars: the result of the host variant ([12][ncol]), kept between calls
     // ebm_integrate's device buffers, kept between calls while the shape stays the same: the annual-mean sums
     // [var][ncol*pitch] (pair-split layout), the means and the seasonal snapshots [var][ncol*pitch] in the natural layout, the

@@ -98,6 +98,7 @@ class Engine:
             raise ValueError(f"unknown model {model!r}: expected 'MIZ', 'Classic' or the extension 'MIZ_IMEX'")
         self.lib = _lib.load()
         self.model, self.grid_kind = model, grid_kind
+        self.device = int(device)
         self.x = as_f64(x)
         self.nlat, self.ncol, self.dt = int(self.x.shape[0]), int(ncol), float(dt)
         self.params = as_f64(params25, (len(PARAM_ORDER),))
@@ -398,6 +399,88 @@ class Engine:
         names, ids, y, r = self._check_misfit_args(names, targets, rweights)
         return self._reduced("ebm_column_misfits", (y.shape[0], 2, self.ncol), dev_ptr, len(ids), field_ids(ids), int(y.shape[0]),
                              dptr(y), dptr(r))
+
+    def _device_index(self) -> int:
+        return int(getattr(self, "device", 0))
+
+    def _on_my_gpu(self, tensor) -> bool:
+        """Is the torch tensor on the GPU this engine was created on (the device index counts, not only the device type)?"""
+        return bool(tensor.is_cuda) and tensor.device.index == self._device_index()
+
+    def check_update_args(self, names, obs_name, gain, target, scale=1.0, perturb=None, bounds=None):
+        """The host-side checks of ``update_columns`` (no device call; the rules of ebm_update_columns in include/ebm_hip.h):
+        returns (names, field ids, field id of ``obs_name``, gain, target [nlat], scale, perturb, lo [nvars], hi [nvars]).
+        ``gain`` comes back as a contiguous float64 ndarray [nvars, nlat, nlat] or, given a torch tensor on a GPU, as that
+        tensor (checked for shape, dtype and contiguity; its entries are not looked at); ``perturb`` as the torch tensor or
+        None.  The fields are looked at first, then the gain, the target, the scale, the perturbation and the bounds."""
+        names = as_names(names)
+        if not 1 <= len(names) <= 5:
+            raise ValueError(f"names: expected between 1 and 5 prognostic fields of the {self.model} model")
+        for n in names:
+            if not isinstance(n, str) or n not in self.prognostic:
+                raise ValueError(f"names: {n!r} is not a prognostic field of the {self.model} model (expected some of "
+                                 f"{', '.join(self.prognostic)})")
+        _refuse_repeats(names)
+        if not isinstance(obs_name, str):
+            raise ValueError(f"obs_name: expected one field name, got {obs_name!r}")
+        obs_id = self._fields((obs_name,), arg="obs_name")[1][0]
+        shape = (len(names), self.nlat, self.nlat)
+        if hasattr(gain, "data_ptr"):                    # a torch tensor: the _device call
+            if not self._on_my_gpu(gain) or str(gain.dtype) != "torch.float64" or not gain.is_contiguous():
+                raise ValueError(f"gain: a tensor must be a contiguous float64 tensor on the engine's GPU (cuda:{self._device_index()})")
+            if tuple(gain.shape) not in (shape, shape[1:] if len(names) == 1 else shape):
+                raise ValueError(f"gain: expected shape {shape}, got {tuple(gain.shape)}")
+        else:
+            gain = np.ascontiguousarray(gain, dtype=np.float64)
+            if len(names) == 1 and gain.shape == shape[1:]:
+                gain = gain[None]
+            if gain.shape != shape:
+                raise ValueError(f"gain: expected shape {shape}, got {gain.shape}")
+            if not np.isfinite(gain).all():
+                v, k, j = (int(i[0]) for i in np.nonzero(~np.isfinite(gain)))
+                raise ValueError(f"gain[{v}][{k}][{j}] = {gain[v, k, j]} is not finite (field {names[v]}, k = {k}, j = {j})")
+        y = as_f64(target, (self.nlat,))
+        if np.isinf(y).any():
+            j = int(np.flatnonzero(np.isinf(y))[0])
+            raise ValueError(f"target[{j}] = {y[j]}: expected finite values, or NaN for no observation")
+        if not np.isfinite(float(scale)):
+            raise ValueError(f"scale = {scale!r} is not finite")
+        if perturb is not None:
+            if not hasattr(perturb, "data_ptr") or not self._on_my_gpu(perturb) or str(perturb.dtype) != "torch.float64" \
+                    or not perturb.is_contiguous() or tuple(perturb.shape) != (self.ncol, self.nlat):
+                raise ValueError(f"perturb: expected a contiguous float64 tensor [{self.ncol}, {self.nlat}] on the engine's GPU "
+                                 f"(cuda:{self._device_index()})")
+        lo, hi = np.full(len(names), -np.inf), np.full(len(names), np.inf)
+        for n, b in (bounds or {}).items():
+            if n not in names:
+                raise ValueError(f"bounds: {n!r} is not one of the updated fields")
+            l, h = (-np.inf if b[0] is None else float(b[0])), (np.inf if b[1] is None else float(b[1]))
+            if np.isnan(l) or np.isnan(h) or l > h:
+                raise ValueError(f"bounds[{n!r}] = {b!r}: expected (lo, hi) with lo <= hi, None or +-Inf for no bound")
+            lo[names.index(n)], hi[names.index(n)] = l, h
+        return names, [FIELD[n] for n in names], obs_id, gain, y, float(scale), perturb, lo, hi
+
+    def update_columns(self, names, obs_name, gain, target, scale=1.0, perturb=None, bounds=None):
+        """ebm_update_columns (the definition is in include/ebm_hip.h): every member moved by a linear map of its own
+        innovation, on the device — for each field f of ``names`` (prognostic ones), ``x_f[c, k] += sum_j gain[f, k, j] *
+        d[c, j]`` with ``d[c, j] = (target[j] + perturb[c, j]) - scale * xo[c, j]``, xo the cell of ``obs_name`` (any solution
+        variable; it may be one of ``names``: the innovations are formed from the state at entry).  d is +0.0 where ``target``
+        is NaN ("no observation here") or xo is NaN.  ``gain`` [len(names), nlat, nlat]: an ndarray, or a contiguous float64
+        torch tensor on the engine's GPU, which is taken where it lies (ebm_update_columns_device); ``perturb``: None or a
+        float64 torch tensor [ncol, nlat] on the engine's GPU; ``bounds``: dict name -> (lo, hi), applied to the new value
+        with strict comparisons (NaN passes; None or +-Inf: no bound).  The sum runs on the fp64 matrix instruction in a
+        fixed order — four observation cells per instruction, ascending — so the bits do not depend on the run, the launch
+        geometry or the layout the handle holds the rows in; no field is converted; ``x + acc`` is one rounded add.
+        Afterwards the handle is as after ``set_field`` of every listed field: the diagnostic fields and T0 are stale, the
+        step clock, the counters and the noise state are unchanged.  StaleFieldError for a stale ``obs_name``."""
+        names, ids, obs_id, g, y, scale, e, lo, hi = self.check_update_args(names, obs_name, gain, target, scale, perturb, bounds)
+        eptr = None if e is None else C.c_void_p(e.data_ptr())
+        if isinstance(g, np.ndarray):
+            check(self.lib.ebm_update_columns(self._h, len(ids), field_ids(ids), obs_id, dptr(g), dptr(y), scale, eptr, dptr(lo), dptr(hi)),
+                  "ebm_update_columns")
+        else:
+            check(self.lib.ebm_update_columns_device(self._h, len(ids), field_ids(ids), obs_id, C.c_void_p(g.data_ptr()), dptr(y), scale,
+                                                     eptr, dptr(lo), dptr(hi)), "ebm_update_columns_device")
 
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""

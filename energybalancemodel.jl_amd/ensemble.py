@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import PARAM_ORDER, StaleFieldError
 from .engine import Engine, as_names, param_matrix, param_vector
 from .infrastructure import default_parval
 from .noise import check_args as check_noise_args
@@ -636,7 +637,127 @@ class CovarianceMixin(EnsembleMoments):
         return {"modes": modes, "variance": vals[order], "explained": vals[order] / total if total > 0.0 else np.full(len(order), np.nan)}
 
 
-class EnsembleRun(ColumnExchange, CovarianceMixin):
+def gaspari_cohn(r) -> np.ndarray:
+    """The Gaspari-Cohn taper (1999, eq. 4.10): the compactly supported fifth-order piecewise rational function of
+    r = distance / half-width >= 0 that resembles a Gaussian — 1 at r = 0, decreasing monotonically, exactly 0 for r >= 2.
+    The Schur product of a sample covariance with it removes the spurious long-range correlations of a small ensemble and
+    keeps the matrix positive semi-definite.  A host function: ``enkf`` applies it to nlat^2 numbers."""
+    r = np.abs(np.asarray(r, dtype=np.float64))
+    out = np.zeros_like(r)
+    a = r <= 1.0
+    b = (r > 1.0) & (r < 2.0)
+    ra, rb = r[a], r[b]
+    out[a] = (((-0.25 * ra + 0.5) * ra + 0.625) * ra - 5.0 / 3.0) * ra ** 2 + 1.0
+    out[b] = (((rb / 12.0 - 0.5) * rb + 0.625) * rb + 5.0 / 3.0) * rb ** 2 - 5.0 * rb + 4.0 - 2.0 / (3.0 * rb)
+    return np.clip(out, 0.0, 1.0)
+
+
+MIZ_UPDATE_BOUNDS = {"Ei": (None, 0.0), "Ew": (0.0, None), "h": (0.0, None), "D": (0.0, "Dmax"), "phi": (0.0, 1.0)}
+
+
+class KalmanMixin(CovarianceMixin):
+    """The ensemble Kalman update in terms of the reductions above and ONE writer: ``update_columns(names, obs_name, gain,
+    target, scale, perturb, bounds)`` of the class it is mixed into (ebm_update_columns), plus ``st.x`` for the taper and,
+    for the perturbed-observation filter, ``obs_noise(sd, generator)`` -> [ncol, nlat] on the device.  EnsembleRun is one."""
+
+    def default_update_bounds(self, names) -> dict:
+        """The per-field bounds ``enkf`` applies when given none (none here; EnsembleRun knows its model's)."""
+        return {}
+
+    def kalman_gains(self, names, obs_name, obs, obs_var, localize=None, inflation=1.0, dist=None) -> dict:
+        """The host part of ``enkf``: ``{"gain": [len(names), nlat, nlat], "mean_o": [nlat], "var_o": [nlat], "observed":
+        bool [nlat], "members": n}``.  P_oo = ``covariance(obs_name)`` and P_fo = ``covariance(f, obs_name)`` per field, each
+        all-reduced over ``dist`` as ``covariance`` does and scaled to the unbiased estimate (n / (n - 1), n the members of the
+        whole ensemble); with J the observed cells (``obs`` not NaN): S = rho o P_oo[J, J] * inflation + diag(obs_var[J]),
+        G_f[:, J] = inflation * (rho o P_fo[:, J]) S^-1 by one Cholesky-free ``numpy.linalg.solve`` of the m x m system, zeros
+        in the columns of unobserved cells.  rho = ``gaspari_cohn(|x_i - x_j| / localize)``, or all ones without ``localize``."""
+        names = as_names(names)
+        x = np.asarray(self.st.x, dtype=np.float64)
+        nlat = x.shape[0]
+        y = np.asarray(obs, dtype=np.float64)
+        if y.shape != (nlat,) or np.isinf(y).any():
+            raise ValueError(f"obs: expected [{nlat}] finite values, NaN where nothing was observed")
+        R = np.broadcast_to(np.asarray(obs_var, dtype=np.float64), (nlat,))
+        J = ~np.isnan(y)
+        if not (np.isfinite(R[J]) & (R[J] > 0.0)).all():
+            raise ValueError("obs_var: expected finite values > 0 at the observed cells")
+        if not (np.isfinite(inflation) and inflation > 0.0):
+            raise ValueError(f"inflation = {inflation!r}: expected a finite factor > 0")
+        if localize is not None and not (np.isfinite(localize) and localize > 0.0):
+            raise ValueError(f"localize = {localize!r}: expected None or a half-width in x > 0")
+        rho = np.ones((nlat, nlat)) if localize is None else gaspari_cohn(np.abs(x[:, None] - x[None, :]) / float(localize))
+        oo = self.covariance(obs_name, None, None, dist)
+        n = float(np.max(oo["n"]))
+        if not n > 1.0:
+            raise ValueError("enkf: needs more than one member")
+        unbias = n / (n - 1.0)
+        P_oo = oo["cov"] * unbias
+        if not np.isfinite(P_oo[np.ix_(J, J)]).all():
+            raise ValueError(f"enkf: the covariance of {obs_name!r} is not finite at the observed cells (a latitude without a "
+                             "contributing member: observe it where it exists, or mark the cell unobserved)")
+        S = rho[np.ix_(J, J)] * P_oo[np.ix_(J, J)] * float(inflation) + np.diag(R[J])
+        gain = np.zeros((len(names), nlat, nlat))
+        for v, f in enumerate(names):
+            P_fo = oo["cov"] * unbias if f == obs_name else self.covariance(f, obs_name, None, dist)["cov"] * unbias
+            B = float(inflation) * rho[:, J] * np.where(np.isfinite(P_fo[:, J]), P_fo[:, J], 0.0)
+            gain[v][:, J] = np.linalg.solve(S, B.T).T if J.any() else 0.0      # S is symmetric
+        return {"gain": gain, "mean_o": oo["mean_a"], "var_o": np.diag(P_oo).copy(), "observed": J, "members": int(n)}
+
+    def _innovation_statistics(self, obs_name, obs, J, dist):
+        """Mean and spread of ``obs_name`` across the members against ``obs`` at the observed cells J (two passes of the sums)."""
+        m = self.moments((obs_name,), None, dist)[obs_name]
+        innov = (obs - m["mean"])[J]
+        return {"bias": float(np.mean(innov)) if J.any() else np.nan, "rmse": float(np.sqrt(np.mean(innov ** 2))) if J.any() else np.nan,
+                "spread": float(np.sqrt(np.mean(m["var"][J]))) if J.any() else np.nan}
+
+    def enkf(self, names, obs_name, obs, obs_var, method="denkf", localize=None, inflation=1.0, bounds=None, generator=None,
+             dist=None) -> dict:
+        """One analysis step of an ensemble Kalman filter on the fields ``names`` (prognostic) from observations ``obs``
+        [nlat] of ``obs_name`` (NaN: not observed) with error variance ``obs_var`` (scalar or [nlat]).  Built from the
+        reductions and ONE write: means from ``reduced_sums``, P_oo and P_fo from ``covariance``, the gains on the host
+        (``kalman_gains``: nlat^2 numbers leave the device, never a field), then ``update_columns`` moves every member on the
+        device by G_f applied to its own innovation.  ``localize``: the half-width in x of the Gaspari-Cohn taper applied to
+        both covariances by a Schur product (None: none) — possible because the update is in gain form, which a
+        member-space transform could not do; ``inflation`` multiplies both covariances.
+        ``method="denkf"`` (Sakov and Oke 2008, the deterministic filter): target = obs - mean_o / 2, scale = 1/2, no
+        perturbation — the mean moves by the full gain, the anomalies by half of it.  ``method="perturbed"``: target = obs,
+        scale = 1 and every member sees its own noisy copy of the observations, sqrt(obs_var) * randn drawn by torch on the
+        device with ``generator``.
+        With ``dist`` the sums and covariances are all-reduced, the gain is then the same on every rank, and each shard
+        applies it to its own members: rank-local after the all-reduce, so a sharded update equals the unsharded one up to
+        the cross-shard bound ``covariance`` states.
+        Returns dict(gain_shape, observed (the number of observed cells), members, prior, posterior): ``prior`` and
+        ``posterior`` hold bias, rmse and spread of ``obs_name`` against ``obs`` at the observed cells, from the ensemble sums
+        before and after; ``posterior`` is None where ``obs_name`` is a diagnostic field, which the update leaves stale until
+        the next diagnostic step.
+        MIZ models: the update is linear algebra on Ei, Ew, h, D, phi and knows nothing of their meaning, so each field is
+        bounded afterwards — by default Ei <= 0, Ew >= 0, h >= 0, 0 <= D <= Dmax, 0 <= phi <= 1 (``bounds``: dict name ->
+        (lo, hi) replaces the default of that field).  Cross-field consistency — D = 0 where Ei = 0, the concentration that
+        belongs to Ei and h, and so on — is restored only by the model's own step (src/miz.jl:109-117, 74-80), as after any
+        ``set_field``.  Classic model (E, Tg): nothing to bound."""
+        names = as_names(names)
+        if method not in ("denkf", "perturbed"):
+            raise ValueError(f"method = {method!r}: expected 'denkf' or 'perturbed'")
+        y = np.asarray(obs, dtype=np.float64)
+        k = self.kalman_gains(names, obs_name, y, obs_var, localize, inflation, dist)
+        J = k["observed"]
+        prior = self._innovation_statistics(obs_name, y, J, dist)
+        use = dict(self.default_update_bounds(names))
+        use.update(bounds or {})
+        use = {n: b for n, b in use.items() if n in names}
+        if method == "denkf":
+            self.update_columns(names, obs_name, k["gain"], y - 0.5 * k["mean_o"], 0.5, None, use)
+        else:
+            sd = np.where(J, np.sqrt(np.where(J, np.broadcast_to(np.asarray(obs_var, dtype=np.float64), y.shape), 0.0)), 0.0)
+            self.update_columns(names, obs_name, k["gain"], y, 1.0, self.obs_noise(sd, generator), use)
+        try:
+            posterior = self._innovation_statistics(obs_name, y, J, dist)
+        except StaleFieldError:
+            posterior = None
+        return {"gain_shape": k["gain"].shape, "observed": int(J.sum()), "members": k["members"], "prior": prior, "posterior": posterior}
+
+
+class EnsembleRun(ColumnExchange, KalmanMixin):
     """``ncol`` independent columns of one model on one GPU (this rank's shard).
 
     ``init`` maps prognostic names to [ncol, nlat] arrays (or [nlat], broadcast to all
@@ -1008,6 +1129,26 @@ class EnsembleRun(ColumnExchange, CovarianceMixin):
             else:
                 self.resample(parents)
         return dict(J=J, N=N, weights=res["weights"], ess=res["ess"], log_evidence=res["log_evidence"], parents=parents)
+
+    def update_columns(self, names, obs_name, gain, target, scale=1.0, perturb=None, bounds=None):
+        """Every member moved by ``gain`` applied to its own innovation, on the device (ebm_update_columns).  See
+        ``Engine.update_columns``; ``enkf`` forms the gain."""
+        self.engine.update_columns(names, obs_name, gain, target, scale, perturb, bounds)
+
+    def obs_noise(self, sd, generator=None):
+        """[ncol, nlat] float64 on this run's device: sd[j] * randn, drawn by torch with ``generator`` (a torch.Generator of
+        that device, or None for the default one)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        e = torch.randn((self.ncol, self.st.nx), dtype=torch.float64, device=dev, generator=generator)
+        return (e * torch.as_tensor(np.ascontiguousarray(sd, dtype=np.float64), device=dev)).contiguous()
+
+    def default_update_bounds(self, names) -> dict:
+        """MIZ: Ei <= 0, Ew >= 0, h >= 0, 0 <= D <= Dmax (of the parameters the run was created with), 0 <= phi <= 1."""
+        if not self.engine.model.startswith("MIZ"):
+            return {}
+        dmax = float(self.engine.params[PARAM_ORDER.index("Dmax")])
+        return {n: tuple(dmax if b == "Dmax" else b for b in MIZ_UPDATE_BOUNDS[n]) for n in names if n in MIZ_UPDATE_BOUNDS}
 
     def field_tensor(self, name):
         """A packed [ncol, nlat] device tensor copy of a field (device-to-device)."""

@@ -165,7 +165,7 @@ const char *ebm_version(void);
  * write_diag, the last step of ebm_run / ebm_run_fused with diag_last, the seasonal and last steps of
  * ebm_integrate).  A read of one of them — ebm_get_field, ebm_get_field_device, ebm_hemispheric_mean*,
  * ebm_ensemble_sums*, ebm_ensemble_range*, ebm_ensemble_histogram*, ebm_ensemble_covariance*, ebm_column_misfits*, ebm_column_scalars*, ebm_field_device_ptr — while the state is NEWER than the field (steps taken since without diagnostics, or
- * a prognostic field overwritten with ebm_set_field) fails with EBM_ERR_STALE; the message names the step
+ * a prognostic field overwritten with ebm_set_field or ebm_update_columns*, the other writer of prognostic fields) fails with EBM_ERR_STALE; the message names the step
  * that last wrote the field and the state's step.  Nothing stale is ever returned silently — in particular
  * not the T0 a caller would checkpoint as the warm start (src/miz.jl:47,64).  ebm_field_step reports both
  * steps; ebm_get_field_as_of returns the field as of an EXPLICITLY named step (the 0-based global index of
@@ -774,6 +774,75 @@ int ebm_column_misfits(ebm_handle_t h, int nvars, const int *fields, int ntarget
                        double *out);
 int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int ntargets, const double *target,
                               const double *rw, double *dev_out);
+
+/* ENSEMBLE KALMAN UPDATE: every member moved by a linear map of its own innovation,
+ *     x_f[c][k] += sum_j G_f[k][j] * d[c][j],      d[c][j] = (target[j] + e[c][j]) - scale * xo[c][j],
+ * for every listed prognostic field f, on the device — the write that the reductions above lacked.  With G the Kalman gain
+ * formed on the host from ebm_ensemble_covariance (nlat^2 numbers, which a Schur product can localise there) this is the
+ * analysis step of an EnKF: target = y, scale = 1 and e = observation noise is the perturbed-observation filter;
+ * target = y - mean/2, scale = 1/2, e = NULL is the deterministic one (EnsembleRun.enkf).  An (ncol x nlat) . (nlat x nlat)
+ * product per field, the second dense contraction of the library: it runs on the fp64 matrix instruction of gfx950.  No field
+ * leaves the device.  THIS TEXT IS THE DEFINITION.
+ *   Arguments.  fields[nvars]: PROGNOSTIC fields of the model (MIZ and MIZ_IMEX: Ei, Ew, h, D, phi; classic: E, Tg), each at
+ *     most once, 1 <= nvars <= 5.  obs_field: any solution variable under the rules of ebm_ensemble_sums, prognostic or
+ *     diagnostic; it may be one of `fields`.  gain[nvars][nlat][nlat]: host array, gain[v][k][j] maps observation cell j to
+ *     cell k of fields[v], natural latitude order, every entry finite; the _device variant takes the same packed array at a
+ *     16-byte aligned device address and does not look at its entries.  target[nlat]: host array, finite or NaN; NaN means
+ *     "no observation here", as in ebm_column_misfits.  scale: finite.  dev_perturb[ncol][nlat]: packed DEVICE array of
+ *     e[c][j], or NULL.  lo[nvars], hi[nvars]: host arrays of per-field bounds, either may be NULL = none.
+ *   Innovation.  For column c and observation cell j < nlat, with xo the cell of obs_field: s = scale * xo, t = target[j] +
+ *     e[c][j] (t = target[j] when dev_perturb is NULL), d = t - s — one rounded product, one rounded add, one rounded
+ *     subtract, nothing contracted into a fused multiply-add.  d is replaced by +0.0 where target[j] is NaN or xo is NaN (the
+ *     sentinels of Ti and Tw, src/miz.jl:193-194).  ALL innovations are formed from the state as it is at entry, before any
+ *     field is written — also when obs_field is one of the fields.
+ *   Increment.  For field v and state cell k the accumulator starts at +0.0 and takes the observation cells in ascending
+ *     groups of four, ONE v_mfma_f64_16x16x4_f64 per group: acc <- mfma(d[c][j .. j+3], gain[v][k][j .. j+3], acc), d always
+ *     the A operand.  The products and adds inside the instruction are the hardware's; this text fixes everything around
+ *     them.  A tail group is padded with terms d = g = +0.0; a group wholly past nlat is not issued.  The j axis is never
+ *     split: no partials, no atomics.  Every (c, k) sees the same chain whichever tile, wave and register of the kernel it
+ *     falls in, so the bits depend neither on the launch geometry (cells_per_thread) nor on the layout the handle holds the
+ *     rows in, and the same call on the same data gives the same bits on every run.
+ *   Write.  x_new = x + acc, ONE rounded add — so a cell holding -0.0 with acc = +0.0 becomes +0.0, also under a gain of
+ *     zeros.  Then, with bounds: x_new = lo[v] if x_new < lo[v]; then x_new = hi[v] if x_new > hi[v].  The comparisons are
+ *     strict; a NaN x_new passes through; -Inf / +Inf bounds mean none and give the bits of the unbounded call.
+ *   Accuracy.  The stated terms of (c, k) are p_j = d[c][j] * gain[v][k][j], j < nlat, n_obs of them nonzero.  Inside a
+ *     group the hardware forms four products and adds them to acc in some order, each operation — multiply, add or fused
+ *     multiply-add — correctly rounded: a term passes through at most one product rounding and then one add per term that
+ *     joins the same sum after it, and only nonzero terms round (x + 0 is exact).  So a term sees at most n_obs roundings,
+ *     each of relative size 2^-53 on a partial sum bounded by sum_j |p_j| (1 + O(2^-53)), and
+ *       |acc - the exact sum of the stated terms| <= n_obs * 2^-53 * sum_j |d * g| * (1 + 2^-4);
+ *     the last factor covers the second-order terms (and the 64-bit-mantissa reference of the tests), as in
+ *     ebm_ensemble_covariance.  x_new adds the one rounding of x + acc: 2^-53 |x + acc|.
+ *   Validity and bookkeeping: exactly those of one ebm_set_field per listed field with the new values, through the same
+ *     code of the field book — the diagnostic fields and the fp64 T0 become stale (EBM_ERR_STALE names the step that wrote
+ *     them and the state's step, "with prognostic fields overwritten since"), the next step loads phi as it then is, the
+ *     zero-line flags lose their trust, a graph-replaying ebm_run takes its first step directly.  A stale obs_field fails
+ *     with EBM_ERR_STALE exactly as ebm_hemispheric_mean does (the same message); phi, left underived by state-only one-step
+ *     launches, is made current first.  Unchanged: the step clock, counters[0..3], the warm-start active set, the noise
+ *     state, every per-column setting.
+ *   Layout.  Rows are read AND written in whatever layout the handle holds them; only gain, target, dev_perturb and the
+ *     staged innovations are indexed by natural latitude.  No field is converted: ebm_state_conversions does not grow.  Cells
+ *     between nlat and the row pitch are never written.
+ *   Ordering.  Synchronous on the handle's stream, the two launch chains joined first.
+ * Refusals leave the handle bit for bit as it was: EBM_ERR_ARG for a NULL handle, fields, gain or target, nvars outside
+ * 1 ... 5, a field that is not prognostic or is listed twice, an obs_field that is not a solution variable, a non-finite
+ * scale, a non-finite gain entry (host variant; the message names field, k and j), an infinite target entry, a NaN bound or
+ * lo[v] > hi[v], a device gain that is not 16-byte aligned or a dev_perturb that is not 8-byte aligned; EBM_ERR_STALE as above.
+ * How it runs (csrc/ebm_update.hip): kernel 1 stages d for all columns, one lane per 16-byte unit of the row of obs_field
+ * where it lies, into [ncol][pitch] doubles in natural order with +0.0 beyond nlat — the scratch of ebm_diffusion where the
+ * handle has it, else the staging rows of ebm_resample_columns.  Kernel 2 is the tiled product: grid (tiles of 64 STORED
+ * cells) x (tiles of 64 members) x (fields), 256 lanes; sixteen observation cells at a time pass through 9 KiB of LDS — 32
+ * bytes of d of one member and four gain entries of one state cell per lane — the next sixteen in flight under the matrix
+ * instructions; each of the four waves owns 32 x 32 as 2 x 2 accumulators; LDS lines are padded to 18 doubles so that the
+ * operand reads are free of bank conflicts; then the add, the clamp and the store, sixteen lanes a whole 128-byte line of a
+ * row.  Tiles and waves that hold only padding do nothing.  The host variant uploads gain one field at a time into one
+ * pitch^2 buffer and launches the product per field; the _device variant is one launch over a grid z of fields.  Plain
+ * vector loads and stores, no atomics, no scratch memory.  Device memory, kept by the handle and reused: pitch^2 doubles of gain
+ * (host variant), pitch doubles of target, and the borrowed ncol * pitch of innovations. */
+int ebm_update_columns(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *gain, const double *target,
+                       double scale, const double *dev_perturb, const double *lo, const double *hi);
+int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *dev_gain,
+                              const double *target, double scale, const double *dev_perturb, const double *lo, const double *hi);
 
 /* COLUMN SCALARS: numbers that reduce ALONG a column — the integral or mean of a field over a band of latitudes, and the
  * position of an edge: where, walking poleward, a field first reaches a level (the ice edge: the first cell with phi >= 0.15).

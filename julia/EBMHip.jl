@@ -397,6 +397,50 @@ function ensemble_covariance_device!(h::Handle, name_a::Symbol, name_b::Symbol, 
 end
 
 """
+    update_columns!(h, names, obs_name, gain, target; nlat, scale=1.0, dev_perturb=C_NULL, lo=nothing, hi=nothing)
+    update_columns_device!(h, names, obs_name, dev_gain, target; scale=1.0, dev_perturb=C_NULL, lo=nothing, hi=nothing)
+
+The ensemble Kalman update on the device (`ebm_update_columns`; the definition is in the header): for every prognostic field
+`f` of `names`, `x_f[c, k] += sum_j gain[f][k, j] * d[c, j]` with `d[c, j] = (target[j] + e[c, j]) - scale * xo[c, j]`, `xo` the
+cell of `obs_name`, on the fp64 matrix instruction.  `gain`: one `nlat x nlat` matrix per field (a vector of matrices, or an
+`nlat x nlat x nvars` array indexed `[k, j, v]`); it is passed row-major (`gain[v][k][j]`), as the C array is.  `target`: `nlat`
+values, `NaN` where nothing was observed.  `dev_perturb`: a device pointer to `e[ncol][nlat]`, or `C_NULL`.  `lo`, `hi`: one
+bound per field, or `nothing`.  The `_device!` form takes the packed gain at a 16-byte aligned device pointer.  Afterwards the
+handle is as after `set_field!` of every listed field.
+"""
+function update_columns!(h::Handle, names, obs_name::Symbol, gain, target; nlat::Integer, scale::Real=1.0,
+                         dev_perturb::Ptr{Cdouble}=Ptr{Cdouble}(C_NULL), lo=nothing, hi=nothing)
+    f = Cint[FIELD[n] for n in names]
+    g = Array{Float64}(undef, nlat, nlat, length(f))          # [j, k, v] column-major = gain[v][k][j] row-major
+    for v in eachindex(f)
+        gv = gain isa AbstractVector ? gain[v] : view(gain, :, :, v)
+        size(gv) == (nlat, nlat) || error("gain: expected $nlat x $nlat per field")
+        g[:, :, v] = permutedims(gv)
+    end
+    y = Vector{Float64}(target)
+    length(y) == nlat || error("target: expected $nlat values")
+    l = lo === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(lo)
+    u = hi === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(hi)
+    GC.@preserve h check(@ccall(libebm.ebm_update_columns(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint}, FIELD[obs_name]::Cint,
+                                                          g::Ptr{Cdouble}, y::Ptr{Cdouble}, Float64(scale)::Cdouble,
+                                                          dev_perturb::Ptr{Cdouble}, l::Ptr{Cdouble}, u::Ptr{Cdouble})::Cint),
+                         "ebm_update_columns")
+end
+
+function update_columns_device!(h::Handle, names, obs_name::Symbol, dev_gain::Ptr{Cdouble}, target; scale::Real=1.0,
+                                dev_perturb::Ptr{Cdouble}=Ptr{Cdouble}(C_NULL), lo=nothing, hi=nothing)
+    f = Cint[FIELD[n] for n in names]
+    y = Vector{Float64}(target)
+    l = lo === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(lo)
+    u = hi === nothing ? Ptr{Cdouble}(C_NULL) : Vector{Float64}(hi)
+    GC.@preserve h check(@ccall(libebm.ebm_update_columns_device(h.ptr::Ptr{Cvoid}, length(f)::Cint, f::Ptr{Cint},
+                                                                 FIELD[obs_name]::Cint, dev_gain::Ptr{Cdouble}, y::Ptr{Cdouble},
+                                                                 Float64(scale)::Cdouble, dev_perturb::Ptr{Cdouble},
+                                                                 l::Ptr{Cdouble}, u::Ptr{Cdouble})::Cint),
+                         "ebm_update_columns_device")
+end
+
+"""
     ensemble_range(h, names; ncol, nlat, weights=nothing) -> Array{Float64,3}
     ensemble_range_device!(h, names, devout; weights=nothing)
     ensemble_histogram(h, names, lo, hi, nbins; ncol, nlat, weights=nothing) -> Array{Float64,3}
