@@ -1,7 +1,9 @@
 // The tridiagonal solve of one meridian by one workgroup (chunk partition + parallel cyclic reduction in LDS) and the
 // halo exchanges between neighbouring threads.
 #pragma once
+#ifndef EBM_SOLVE_ON_HOST   // tests/host_solve_main.cpp plays this header on the host and brings its own stand-ins; no build of the library defines it
 #include "ebm_device.h"
+#endif
 
 namespace ebm {
 

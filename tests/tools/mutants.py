@@ -3,7 +3,7 @@
     python tests/tools/mutants.py list
     python tests/tools/mutants.py check [LIST ...]        (CPU, no build; no argument: every list)
     python tests/tools/mutants.py build LIST [NAME ...]   (CPU; csrc lists only: one full build per mutant under build/)
-    python tests/tools/mutants.py run   LIST [NAME ...]   (GPU box, or CPU for the host, plan and savesol lists)
+    python tests/tools/mutants.py run   LIST [NAME ...]   (GPU box, or CPU for the host, plan, savesol and solve lists)
 
 The lists are the data modules tests/tools/mutants_<list>.py, found by file name: KIND, TESTS (the pytest arguments that must
 catch every mutant), LIMIT (seconds per pytest session) and MUTANTS, tuples (name, anchor, replacement[, file[, "survives"]]).

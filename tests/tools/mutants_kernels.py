@@ -119,11 +119,12 @@ MUTANTS = [
     ("resident_floe_size_not_written_back", "            sD(i) = valid ? o.q[Q_D] : 0.0;\n", ""),
     ("resident_vote_reads_only_the_first_wave", "for (int w = 0; w < TT / 64; ++w) any |= F[w];", "for (int w = 0; w < 1; ++w) any |= F[w];"),
     ("wave_halo_takes_its_own_edge", "const double pl = E[w > 0 ? w - 1 : 0],", "const double pl = E[w],"),
-    # (two buffer-aliasing mutants of the compact solve were tried and are NOT in this list — the reduction's second buffer
-    # overlapping the first by a third, the interface solution written into the buffer the reduction is still read from: both
-    # are RACES between waves that resume from the same barrier within a few cycles of each other, both passed every test on
-    # the box, and no test can catch such a race deterministically (no GPU sanitizer on this pool).  The buffer plan is argued
-    # in the comments of partition_solve_r instead.  What a wrong buffer does deterministically is covered by the next one.)
+    # (two buffer-aliasing mutants of the compact solve are NOT in this list — the reduction's second buffer overlapping the
+    # first by a third, the interface solution written into the buffer the reduction is still read from: both are RACES
+    # between waves that resume from the same barrier within a few cycles of each other, and both passed every test on the
+    # box by luck of timing.  They are in tests/tools/mutants_solve.py, with every barrier of the solve removed once: the
+    # host play of tests/test_host_solve.py runs the threads of a barrier interval in many orders and kills them all, on the
+    # CPU.  What a wrong buffer does deterministically on the device is covered by the next one.)
     ("compact_summaries_overrun_into_the_state", "double *const W1 = COMPACT ? P0 : P1;", "double *const W1 = P1;"),
     ("resident_state_words_one_slot_low", "win[((4 + 4 * (F) + (i)) * T) >> 13][((4 + 4 * (F) + (i)) * T) & 8191]", "win[((3 + 4 * (F) + (i)) * T) >> 13][((3 + 4 * (F) + (i)) * T) & 8191]"),
     # eighth batch: ebm_integrate's fused stretches
