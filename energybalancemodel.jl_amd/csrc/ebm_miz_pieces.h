@@ -297,6 +297,40 @@ __device__ __forceinline__ bool newton_iteration(const double (&lo)[C], const do
     }
 }
 
+// The same iteration for a caller that exchanges g's halo itself and takes the vote itself (the one-step kernels of the
+// batched head: g goes round with r on the first pass, and the vote's barrier carries the Tbar halo — ebm_miz_step.h):
+// masked_concentration is newton_iteration's g; newton_solve_given_halo forms the rows from it and its halo gl, gr, solves,
+// and sets the new active set.  The same expressions in the same order as newton_iteration: the same bits.  Returns whether
+// THIS thread's set changed.  P1 must be free on entry and P0 after the solve's first barrier; on exit P0 may still be read
+// (partition_solve_r).
+template <int C>
+__device__ __forceinline__ void masked_concentration(const double (&ph)[C], unsigned smask, double (&g)[C]) {
+#pragma unroll
+    for (int i = 0; i < C; ++i) g[i] = ((smask >> i) & 1u) ? ph[i] : 0.0;
+}
+template <int C, int TT>
+__device__ __forceinline__ int newton_solve_given_halo(const double (&lo)[C], const double (&up)[C], const double (&dd)[C],
+                                                       const double (&g)[C], double gl, double gr, const double (&rd)[C],
+                                                       double (&xs)[C], unsigned &smask, int t, int T, unsigned k0, int nlat,
+                                                       double *P0, double *P1) {
+    double ra[C], rb[C], rc[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        ra[i] = lo[i] * left_of(g, i, gl);
+        rc[i] = up[i] * right_of(g, i, gr);
+        rb[i] = -__builtin_fma(lo[i] + up[i], g[i], dd[i]);
+    }
+    partition_solve<C, TT>(ra, rb, rc, rd, xs, t, T, P0, P1);
+    unsigned snew = 0;
+#pragma unroll
+    for (int i = 0; i < C; ++i) snew |= (xs[i] < 0.0) ? (1u << i) : 0u;
+    const int nvalid = nlat - (int)k0;                // padding rows never count as a change
+    snew &= nvalid >= C ? ~0u : (nvalid > 0 ? (1u << nvalid) - 1u : 0u);
+    const int changed = snew != smask;
+    smask = snew;
+    return changed;
+}
+
 // ---- savesol! from registers (src/infrastructure.jl:549-591) -----------------------------------
 // One pair of cells (2j, 2j+1 of this thread) of every saved quantity: running sum for the annual
 // mean (crossmean, src/utilities.jl:390-395: per-cell sum over the year's steps in step order) and/or

@@ -2,6 +2,14 @@
 #pragma once
 #include "ebm_miz_pieces.h"
 
+// A/B builds of the first Newton pass's two exchanges (MERGE_RG, TBAR_VOTE in miz_step_kernel): =0 gives the order before them
+#ifndef EBM_MERGE_RG
+#define EBM_MERGE_RG 1
+#endif
+#ifndef EBM_TBAR_VOTE
+#define EBM_TBAR_VOTE 1
+#endif
+
 namespace ebm {
 
 // MIZ step: one workgroup per meridian.
@@ -14,7 +22,12 @@ namespace ebm {
 // LDS map (doubles; per-cell arrays hold cell i of thread t at i*T + t: lane-consecutive,
 // conflict-free):
 //   P0 = [0,3T), P1 = [3T,6T)    cyclic-reduction ping-pong; idle otherwise, then borrowed for
-//                                the r / g / Tbar halo exchanges
+//                                the r / g / Tbar halo exchanges.  BATCH_HEAD, first Newton pass: r's two words and g's
+//                                first in P0[0, 3T), g's last in P1[0, T), one barrier for both (halo_exchange_two);
+//                                above 256 threads Tbar's two words in P1[0, 2T), published after the solve's last
+//                                barrier and before the active-set vote, whose barrier is the exchange's
+//                                (publish_then_vote): 16 barriers on the one-solve path at T = 1024 where 18 stood
+//                                (the barrier plan)
 //   sEw, sh, sTw = [6T, 6T+3CT)  Ew, h, Tw of every cell, parked across the T0 solve so that the
 //                                solve has the register file to itself
 //
@@ -86,6 +99,12 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     constexpr bool BATCH_HEAD = C == 4 && !IMEX;
     static_assert(BATCH_HEAD || !ZERO_LINES, "the eliding kernel has the batched head");
     static_assert(BATCH_HEAD || !PHI_DERIVED, "the in-place head loads phi, never Ei");
+    // MERGE_RG, TBAR_VOTE: the two barriers the batched-head kernels leave out of the first Newton pass (see the loop below).
+    // -DEBM_MERGE_RG=0 / -DEBM_TBAR_VOTE=0 give the order before them, for A/B builds.
+    // TBAR_VOTE only above 256 threads: at 256, where four workgroups share a CU and fill each other's barrier intervals, the
+    // 1024 x 16384 shape measured 0.6 % SLOWER with it, twice, and neither faster nor slower with MERGE_RG alone
+    // (profiles/EXPERIMENTS.md, r34); at 512 (two per CU) and 1024 (one) the two together are faster.
+    constexpr bool MERGE_RG = BATCH_HEAD && EBM_MERGE_RG, TBAR_VOTE = BATCH_HEAD && TT > 256 && EBM_TBAR_VOTE;
     StepHead hd;
     if constexpr (BATCH_HEAD) hd = step_head<ZERO_LINES, TT>(a, col, (unsigned)__builtin_amdgcn_readfirstlane(t >> 6));
     else hd = step_head_in_place(a, col);
@@ -162,8 +181,12 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     }
     int it = 0;
     bool again;
+    // TBAR_VOTE: Ti, Tbar and Tbar's halo are formed inside the loop, under the vote (below); phase D finds them here
+    [[maybe_unused]] double Ti[C];
+    double tb[C], tbl, tbr;
     do {
         double tlo[C], tup[C], dd[C];
+        [[maybe_unused]] double g[C], gl, gr;             // MERGE_RG / TBAR_VOTE: the masked concentration and its halo
         // (!BATCH_HEAD: the lane's cell index is made opaque inside the loop: hoisted out of it, the six addresses
         // would live as per-lane 64-bit pointers instead of the wave-uniform base + 32-bit offset form)
         unsigned kl = k0;
@@ -204,14 +227,26 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
             EBM_STAMP(1);
             EBM_STAMPW(1);                                    // per wave: inputs arrived
             double rl, rr;
-            halo_exchange(P0, P0 + T, t, T, r[0], r[C - 1], rl, rr);
+            if constexpr (MERGE_RG) {
+                // r and g are both functions of the loaded state and the mask word alone: one exchange, one barrier, carries
+                // the four words (r's two and g's first in P0, g's last in P1[0, T): P1 is free until the solve)
+                masked_concentration(ph, smask, g);
+                halo_exchange_two(P0, P1, t, T, r[0], r[C - 1], g[0], g[C - 1], rl, rr, gl, gr);
+            } else {
+                halo_exchange(P0, P0 + T, t, T, r[0], r[C - 1], rl, rr);
+            }
             EBM_STAMP(2);
             // (this loop stays in the kernels — the same two lines in all three: moved into a helper, it changes how hipcc
             // peels the first Newton iteration of this kernel and of miz_resident_kernel, and with it their whole code)
 #pragma unroll
             for (int i = 0; i < C; ++i)
                 rd[i] = t0_rhs(p, insolation(p, xk0[i], ct), tlo[i], tup[i], left_of(r, i, rl), r[i], right_of(r, i, rr), f);
-            __syncthreads();                                  // r halo reads done before P0 is reused
+            // r halo reads done before P0 is reused (!MERGE_RG: by newton_iteration's g exchange).  MERGE_RG: the barrier now
+            // stands between the neighbour's read of g's last value in P1[t] and THIS thread's chunk summary W1[t] = P1[t],
+            // the solve's very first write.  (P0's three words would do without it: the solve writes P0 only after its own
+            // first barrier.)  It may stand anywhere between halo_exchange_two's reads and the solve; removed, the host play
+            // reports the race (tests/test_host_step_lds.py).
+            __syncthreads();
         } else {
             // second and later iterations (a changed active set): the right-hand side does not depend on the set and
             // is still in registers, like phi; only the rows' ingredients are fetched / formed again — the same values
@@ -226,7 +261,38 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
         EBM_STAMP(3);
         // ---------------- phase B: active-set Newton, src/miz.jl:33-68 --------------------
         ++it;
-        again = newton_iteration<C, TT>(tlo, tup, dd, ph, rd, xs, smask, t, T, k0, nlat, P0, P1);
+        if constexpr (MERGE_RG || TBAR_VOTE) {
+            // Barrier by barrier, first pass: (1) halo_exchange_two's: r's and g's words are written.  (2) the one above: the
+            // neighbours have read them; W1 may take P1.  (3 ..) the solve's.  (last) the vote, which is also the Tbar
+            // exchange's barrier.  A second or later pass — the set changed — starts with today's g exchange through
+            // P0[0, 2T): free, the interface solution Y was last read before the vote's barrier.
+            if (!MERGE_RG || it > 1) {
+                masked_concentration(ph, smask, g);
+                halo_exchange(P0, P0 + T, t, T, g[0], g[C - 1], gl, gr);
+            }
+            const int changed = newton_solve_given_halo<C, TT>(tlo, tup, dd, g, gl, gr, rd, xs, smask, t, T, k0, nlat, P0, P1);
+            if constexpr (TBAR_VOTE) {
+                // The Tbar halo does not depend on the vote's outcome: after back-substitution the lane has all that Tbar
+                // needs, so it publishes its first and last Tbar in P1[0, 2T) — free once the solve's last barrier is passed;
+                // P0 is not, Y may still be read there — BEFORE the vote, whose barrier then serves the exchange.  The
+                // expressions are phase D's, in its order.  If the vote says "again", the words are dropped: the next pass
+                // forms them anew from its own solution.  Its g exchange writes P0 only, and its W1 write to P1 comes after
+                // that exchange's barrier, hence after every thread's read of the dropped words (which stands before the
+                // thread's write to P0, in program order).
+#pragma unroll
+                for (int i = 0; i < C; ++i) {
+                    const double T0i = xs[i] + Tm;                            // new warm start, :64
+                    const double ti = jl_min(T0i, Tm);                        // ice_temp, :31,65
+                    Ti[i] = (sh[i * T] == 0.0) ? 0.0 : ti;                    // Ti: zeroref!, :66
+                    tb[i] = Ti[i] * ph[i] + (1.0 - ph[i]) * sTw[i * T];       // Tbar, :21-26
+                }
+                again = publish_then_vote(P1, t, T, tb[0], tb[C - 1], changed, tbl, tbr);
+            } else {
+                again = __syncthreads_or(changed) != 0;
+            }
+        } else {
+            again = newton_iteration<C, TT>(tlo, tup, dd, ph, rd, xs, smask, t, T, k0, nlat, P0, P1);
+        }
     } while (again && it < kMaxNewton);
     count_newton(a, col, t, it, again ? 1 : 0);
     {
@@ -247,20 +313,23 @@ __global__ void __launch_bounds__(TT, 4) miz_step_kernel(const StepArgs a) {
     // (GRID == 0: sub-, main and super-diagonal of par.D*get_diffop — on the identity grid the physics stencil and the
     // solver's plain coefficients are the same three tables (build_tables) — are loaded pair by pair with Ei and D below:
     // all four cells' worth at once do not fit the cell updates' register budget at every workgroup size)
-    double tb[C];
     {
         double T0[C];
 #pragma unroll
         for (int i = 0; i < C; ++i) {
             T0[i] = xs[i] + Tm;                                       // new warm start, :64
-            const double ti = jl_min(T0[i], Tm);                      // ice_temp, :31,65
-            xs[i] = (sh[i * T] == 0.0) ? 0.0 : ti;                    // Ti: zeroref!, :66
-            tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * sTw[i * T];       // Tbar, :21-26
+            if constexpr (TBAR_VOTE) {
+                xs[i] = Ti[i];                                        // formed under the last pass's vote, like tb
+            } else {
+                const double ti = jl_min(T0[i], Tm);                  // ice_temp, :31,65
+                xs[i] = (sh[i * T] == 0.0) ? 0.0 : ti;                // Ti: zeroref!, :66
+                tb[i] = xs[i] * ph[i] + (1.0 - ph[i]) * sTw[i * T];   // Tbar, :21-26
+            }
         }
         if (MAYDIAG && diag) store_chunk<C>(st + S_T0 * a.fstride, T0, k0, nlat);
     }
-    double tbl, tbr;
-    halo_exchange(P0, P0 + T, t, T, tb[0], tb[C - 1], tbl, tbr);
+    // (TBAR_VOTE: the halo came with the vote)
+    if constexpr (!TBAR_VOTE) halo_exchange(P0, P0 + T, t, T, tb[0], tb[C - 1], tbl, tbr);
     EBM_STAMP(7);
     EBM_STAMPW(3);                                        // per wave: Tbar halo done
     // Whole-line stores.  A lane owns 8*C contiguous bytes of every field in the natural layout; written pair by

@@ -3,6 +3,8 @@
 #pragma once
 #ifndef EBM_SOLVE_ON_HOST   // tests/host_solve_main.cpp plays this header on the host and brings its own stand-ins; no build of the library defines it
 #include "ebm_device.h"
+#else
+int __syncthreads_or(int);     // the vote, as tests/host_step_lds_main.cpp plays it; the solve's own player never calls it
 #endif
 
 namespace ebm {
@@ -41,6 +43,43 @@ __device__ __forceinline__ void halo_exchange_waves(double *E, int t, int T, dou
     if (lane == 63) r = w + 1 < nw ? nr : 0.0;
     left = l;
     right = r;
+}
+
+// Two halo exchanges behind one barrier, for two quantities that both exist before it (the one-step kernels' first Newton
+// pass: r and the masked g).  a's first and last values and b's first go through P0's 3T doubles, b's last through P1[0, T).
+// On entry P0 and P1[0, T) must be free.  On exit the neighbours may still be reading all four words: the caller puts a
+// barrier between this call and its next write to P0 or to P1[0, T) — partition_solve_r's very first write is W1 = P1[t].
+__device__ __forceinline__ void halo_exchange_two(double *P0, double *P1, int t, int T, double afirst, double alast,
+                                                  double bfirst, double blast, double &aleft, double &aright,
+                                                  double &bleft, double &bright) {
+    P0[t] = afirst;
+    P0[T + t] = alast;
+    P0[2 * T + t] = bfirst;
+    P1[t] = blast;
+    __syncthreads();
+    const int tl = t > 0 ? t - 1 : 0, tr = t + 1 < T ? t + 1 : t;
+    const double al = P0[T + tl], ar = P0[tr], bl = P1[tl], br = P0[2 * T + tr];
+    aleft = t > 0 ? al : 0.0;
+    aright = t + 1 < T ? ar : 0.0;
+    bleft = t > 0 ? bl : 0.0;
+    bright = t + 1 < T ? br : 0.0;
+}
+
+// A halo exchange whose barrier is the workgroup's vote: every thread publishes its first and last value in P1[0, 2T), the
+// vote (did any thread's `changed` differ from zero) is the barrier, the neighbours' words are read after it.  For a caller
+// that has just left partition_solve_r (not COMPACT): P1 is free once the solve's last barrier is passed — P0 is not, the
+// interface solution Y may still be read there.  On exit the neighbours may still be reading P1[0, 2T): the caller's next
+// write to it (a solve's W1) must come after another barrier.  Returns the vote.
+__device__ __forceinline__ bool publish_then_vote(double *P1, int t, int T, double first, double last, int changed,
+                                                  double &left, double &right) {
+    P1[t] = first;
+    P1[T + t] = last;
+    const bool any = __syncthreads_or(changed) != 0;
+    const int tl = t > 0 ? t - 1 : 0, tr = t + 1 < T ? t + 1 : t;
+    const double l = P1[T + tl], r = P1[tr];
+    left = t > 0 ? l : 0.0;
+    right = t + 1 < T ? r : 0.0;
+    return any;
 }
 
 // ---- tridiagonal solve of one meridian, T threads x C rows -----------------------------------
