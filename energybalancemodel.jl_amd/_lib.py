@@ -92,6 +92,9 @@ SIGNATURES = {
     "ebm_column_misfits_device": [_h, _i, _ip, _i, _dp, _dp, _dev],
     "ebm_update_columns": [_h, _i, _ip, _i, _dp, _dp, _d, _dev, _dp, _dp],
     "ebm_update_columns_device": [_h, _i, _ip, _i, _dev, _dp, _d, _dev, _dp, _dp],
+    "ebm_spd_solve_device": [_h, _i, _ll, _dev, _ll, _dev, _ll, _ip],
+    "ebm_kalman_gain_device": [_h, _i, _dp, _dp, _d, _d, _dev, C.POINTER(C.c_void_p), _dev, _ip],
+    "ebm_kalman_gain_phases": [_h, C.POINTER(C.c_float)],
     "ebm_column_scalars": [_h, _i, _ip, _dp, _dp],
     "ebm_column_scalars_device": [_h, _i, _ip, _dp, _dev],
     "ebm_run_series_scalars": [_h, _ll, _i, _dp, _i, _i, _i, _ip, _dp, _dp],

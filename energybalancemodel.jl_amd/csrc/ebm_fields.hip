@@ -478,6 +478,136 @@ int update_columns(ebm_ctx *h, int nvars, const int *fields, int obs_field, cons
     return EBM_OK;
 }
 
+// ebm_spd_solve_device and ebm_kalman_gain_device (include/ebm_hip.h; the kernels and the order of every operation are in
+// ebm_gain.hip).  Neither reads or writes a field, the clock or a counter: the book never hears of them.
+constexpr long long round_up_block(long long m) { return (m + ebm::kGainBlock - 1) / ebm::kGainBlock * ebm::kGainBlock; }
+bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// the handle's share of a solve of mp unknowns: the block inverses and the flag (with `extra` more words behind it)
+int reserve_solve(ebm_ctx *h, long long mp, size_t extra) {
+    HIPCHK(h->gain.inv.reserve((size_t)mp * ebm::kGainBlock));
+    HIPCHK(h->gain.words.reserve(1 + extra));
+    return EBM_OK;
+}
+// flag = 0, the factorisation, the two solves: enqueued, not awaited
+hipError_t enqueue_solve(const ebm::SolveArgs &a, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(a.flag, 0, sizeof(int), s);
+    if (e == hipSuccess) e = ebm::launch_spd_factor(a, s);
+    if (e == hipSuccess) e = ebm::launch_spd_solve(a, s);
+    return e;
+}
+
+int spd_solve_device(ebm_ctx *h, int m, long long nrhs, double *dev_S, long long lds, double *dev_B, long long ldb, int *info) {
+    const std::string me("ebm_spd_solve_device");
+    if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
+    if (!dev_S || !dev_B || !info) return fail(EBM_ERR_ARG, me + ": null argument");
+    if (m < 1 || nrhs < 0) return fail(EBM_ERR_ARG, me + ": m = " + std::to_string(m) + ", nrhs = " + std::to_string(nrhs) + ": expected m >= 1 and nrhs >= 0");
+    const long long mp = round_up_block(m);
+    if (lds < mp || ldb < mp)
+        return fail(EBM_ERR_ARG, me + ": lds = " + std::to_string(lds) + ", ldb = " + std::to_string(ldb) + ": both must be >= m rounded up to 64 = " +
+                                     std::to_string(mp) + " (the caller pads S with the identity and B with zeros)");
+    if (!aligned16(dev_S) || !aligned16(dev_B)) return fail(EBM_ERR_ARG, me + ": dev_S or dev_B is not 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = reserve_solve(h, mp, 0)) return rc;
+    const hipStream_t s = main_stream(h);
+    ebm::SolveArgs a{dev_S, lds, dev_B, ldb, nrhs, h->gain.inv.get(), h->gain.words.get(), (int)mp};
+    int pivot = 0;
+    hipError_t e = enqueue_solve(a, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&pivot, a.flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(me, e);
+    *info = pivot;
+    if (pivot) return fail(EBM_ERR_ARG, me + ": S is not positive definite: pivot " + std::to_string(pivot) + " is not > 0 (info = " + std::to_string(pivot) + ")");
+    return EBM_OK;
+}
+
+int kalman_gain_device(ebm_ctx *h, int nvars, const double *obs, const double *obs_var, double localize, double factor,
+                       const double *dev_Poo, double *const *dev_Pfo, double *dev_gain, int *info) {
+    const std::string me("ebm_kalman_gain_device");
+    if (!h) return fail(EBM_ERR_ARG, me + ": null handle");
+    if (!obs || !obs_var || !dev_Poo || !dev_Pfo || !dev_gain || !info) return fail(EBM_ERR_ARG, me + ": null argument");
+    if (nvars < 1 || nvars > ebm::kUpdateMaxFields)
+        return fail(EBM_ERR_ARG, me + ": nvars = " + std::to_string(nvars) + " is outside 1 ... " + std::to_string(ebm::kUpdateMaxFields));
+    for (int v = 0; v < nvars; ++v) {
+        if (!dev_Pfo[v]) return fail(EBM_ERR_ARG, me + ": Pfo_addr[" + std::to_string(v) + "] is null");
+        if (!aligned16(dev_Pfo[v])) return fail(EBM_ERR_ARG, me + ": Pfo_addr[" + std::to_string(v) + "] is not 16-byte aligned");
+    }
+    if (!aligned16(dev_Poo) || !aligned16(dev_gain)) return fail(EBM_ERR_ARG, me + ": dev_Poo or dev_gain is not 16-byte aligned");
+    if (!std::isfinite(factor) || !(factor > 0.0)) return fail(EBM_ERR_ARG, me + ": factor is not finite and > 0");
+    if (localize != localize) return fail(EBM_ERR_ARG, me + ": localize is NaN (a half-width in x > 0, or <= 0 for no taper)");
+    const int nlat = h->nlat;
+    std::vector<int> words;                                  // J, padded to mp with 0 (never read), then pos
+    std::vector<int> pos((size_t)nlat, -1);
+    for (int j = 0; j < nlat; ++j) {
+        if (std::isinf(obs[j])) return fail(EBM_ERR_ARG, me + ": obs[" + std::to_string(j) + "] is infinite (finite, or NaN for no observation)");
+        if (obs[j] != obs[j]) continue;
+        if (!std::isfinite(obs_var[j]) || !(obs_var[j] > 0.0))
+            return fail(EBM_ERR_ARG, me + ": obs_var[" + std::to_string(j) + "] is not finite and > 0 at an observed cell");
+        pos[(size_t)j] = (int)words.size();
+        words.push_back(j);
+    }
+    const int m = (int)words.size();
+    const long long mp = round_up_block(m);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t gain_words = (size_t)nvars * (size_t)nlat * (size_t)nlat;
+    if (m == 0) {                                            // nothing observed: a gain of zeros, no solve
+        const hipStream_t s = main_stream(h);
+        HIPCHK(hipMemsetAsync(dev_gain, 0, sizeof(double) * gain_words, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *info = 0;
+        return EBM_OK;
+    }
+    ebm_ctx::Gain &b = h->gain;
+    if (int rc = reserve_solve(h, mp, (size_t)mp + (size_t)nlat)) return rc;
+    HIPCHK(b.S.reserve((size_t)mp * (size_t)mp));
+    HIPCHK(b.B.reserve((size_t)nvars * (size_t)nlat * (size_t)mp));
+    HIPCHK(b.obs_var.reserve((size_t)nlat));
+    words.resize((size_t)mp, 0);
+    words.insert(words.end(), pos.begin(), pos.end());
+    for (Event &ev : b.mark)
+        if (!ev) HIPCHK(hipEventCreate(ev.out()));
+    const hipStream_t s = main_stream(h);                    // joins the two launch chains
+    int *const index = b.words.get() + 1;
+    // pageable sources (`words`, the caller's obs_var): on every path below the stream is awaited before this returns
+    hipError_t e = hipMemcpyAsync(index, words.data(), sizeof(int) * words.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.obs_var.get(), obs_var, sizeof(double) * (size_t)nlat, hipMemcpyHostToDevice, s);
+    ebm::GainArgs g{};
+    g.Poo = dev_Poo;
+    for (int v = 0; v < nvars; ++v) g.Pfo[v] = dev_Pfo[v];
+    g.x = x_table(h);
+    g.obs_var = b.obs_var.get();
+    g.index = index; g.pos = index + mp; g.flag = b.words.get();
+    g.localize = localize; g.factor = factor;
+    g.S = b.S.get(); g.B = b.B.get(); g.gain = dev_gain;
+    g.nlat = nlat; g.nvars = nvars; g.m = m; g.mp = (int)mp;
+    ebm::SolveArgs a{g.S, mp, g.B, mp, (long long)nvars * nlat, b.inv.get(), b.words.get(), (int)mp};
+    int pivot = 0;
+    b.timed = false;
+    auto mark = [&](int i) { if (e == hipSuccess) e = hipEventRecord(b.mark[i].get(), s); };
+    if (e == hipSuccess) e = hipMemsetAsync(a.flag, 0, sizeof(int), s);
+    mark(0);
+    if (e == hipSuccess) e = ebm::launch_gain_assemble(g, s);
+    mark(1);
+    if (e == hipSuccess) e = ebm::launch_spd_factor(a, s);
+    mark(2);
+    if (e == hipSuccess) e = ebm::launch_spd_solve(a, s);
+    mark(3);
+    if (e == hipSuccess) e = ebm::launch_gain_scatter(g, s);
+    mark(4);
+    if (e == hipSuccess) e = hipMemcpyAsync(&pivot, a.flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);                       // nothing pending may still read `words` or obs_var
+        return hip_fail(me, e);
+    }
+    b.timed = true;
+    *info = pivot;
+    if (pivot)
+        return fail(EBM_ERR_ARG, me + ": the innovation covariance is not positive definite: pivot " + std::to_string(pivot) +
+                                     " is not > 0, at observed latitude " + std::to_string(words[(size_t)pivot - 1]) +
+                                     " (a NaN or a negative variance in dev_Poo there?)");
+    return EBM_OK;
+}
+
 // The parameters of the zonal operator: the handle's vector, or the one set ebm_set_column_params installed
 const ebm::Params &zonal_params(const ebm_ctx *h) { return h->sets.n ? h->sets.host[0] : h->p; }
 // The zonal tables (ebm_tables::build_zonal_tables) on the device, with the segmented sweep's scratch behind them.  Built on
@@ -641,6 +771,23 @@ int ebm_update_columns(ebm_handle_t h, int nvars, const int *fields, int obs_fie
 int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *dev_gain, const double *target,
                               double scale, const double *dev_perturb, const double *lo, const double *hi) {
     return update_columns(h, nvars, fields, obs_field, dev_gain, true, target, scale, dev_perturb, lo, hi, "ebm_update_columns_device");
+}
+
+int ebm_spd_solve_device(ebm_handle_t h, int m, long long nrhs, double *dev_S, long long lds, double *dev_B, long long ldb, int *info) {
+    return spd_solve_device(h, m, nrhs, dev_S, lds, dev_B, ldb, info);
+}
+
+int ebm_kalman_gain_device(ebm_handle_t h, int nvars, const double *obs, const double *obs_var, double localize, double factor,
+                           const double *dev_Poo, double **Pfo_addr, double *dev_gain, int *info) {
+    return kalman_gain_device(h, nvars, obs, obs_var, localize, factor, dev_Poo, Pfo_addr, dev_gain, info);
+}
+
+int ebm_kalman_gain_phases(ebm_handle_t h, float *elapsed_ms) {
+    if (!h || !elapsed_ms) return fail(EBM_ERR_ARG, "ebm_kalman_gain_phases: null argument");
+    if (!h->gain.timed) return fail(EBM_ERR_ARG, "ebm_kalman_gain_phases: no ebm_kalman_gain_device call of this handle has run a solve yet");
+    HIPCHK(hipSetDevice(h->device));
+    for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(elapsed_ms + i, h->gain.mark[i].get(), h->gain.mark[i + 1].get()));
+    return EBM_OK;
 }
 
 int ebm_column_scalars(ebm_handle_t h, int nscal, const int *spec, const double *level, double *out) {

@@ -326,5 +326,37 @@ struct MisfitArgs {
     int pitch, nlat, ncol, nvars, threads;
 };
 hipError_t launch_column_misfits(const MisfitArgs &a, hipStream_t s);
+// ebm_spd_solve_device and ebm_kalman_gain_device (ebm_gain.hip): X . S = B for a symmetric positive definite S by a blocked
+// Cholesky factorisation, in the order of the definition (include/ebm_hip.h).  Everything works on mp = m rounded up to
+// kGainBlock: S is [mp][lds >= mp] with the identity in its padding, B is [nrhs][ldb >= mp] with +0.0 in its padding columns.
+// inv: [mp / kGainBlock][kGainBlock][kGainBlock], the inverses of the diagonal blocks of L.  flag: one int, 0 before the first
+// launch; the 1-based index of the first pivot that is not > 0 afterwards, and then every later launch does nothing.
+constexpr int kGainBlock = 64;       // nb of the blocked factorisation: part of the definition (include/ebm_hip.h)
+struct SolveArgs {
+    double *S;
+    long long lds;
+    double *B;
+    long long ldb, nrhs;
+    double *inv;
+    int *flag;
+    int mp;
+};
+hipError_t launch_spd_factor(const SolveArgs &a, hipStream_t s);     // 3 launches per block column (the last one: 1)
+hipError_t launch_spd_solve(const SolveArgs &a, hipStream_t s);      // 2 launches
+// The compacted system of the observed cells J (index[a], a < m, ascending; pos[j] = a where index[a] == j, else -1):
+// assemble writes S and, per field v < nvars, the rows (v * nlat + k) of B; scatter writes gain[v][k][j] = X or +0.0.
+struct GainArgs {
+    const double *Poo;               // [nlat][nlat]
+    const double *Pfo[kUpdateMaxFields];
+    const double *x;                 // st.x [nlat]
+    const double *obs_var;           // [nlat]
+    const int *index, *pos;          // [m], [nlat]
+    const int *flag;                 // the solve's: scatter does nothing where it is set
+    double localize, factor;         // localize <= 0: rho == 1.0
+    double *S, *B, *gain;            // [mp][mp], [nvars * nlat][mp], [nvars][nlat][nlat]
+    int nlat, nvars, m, mp;
+};
+hipError_t launch_gain_assemble(const GainArgs &a, hipStream_t s);   // 2 launches
+hipError_t launch_gain_scatter(const GainArgs &a, hipStream_t s);
 
 }  // namespace ebm

@@ -176,7 +176,17 @@ struct ebm_ctx {
     struct Update {
         DevVec<double> gain, target;
     } update;
-    DevVec<double> scalars_out;                    // ebm_column_scalars: the result of the host variant ([12][ncol]), kept between calls
+    // ebm_spd_solve_device and ebm_kalman_gain_device, kept between calls: the inverses of the diagonal blocks of L
+    // ([mp / 64][64][64]) and words[0], the bad-pivot flag; for the gain also the compacted system S ([mp][mp]) and B
+    // ([nvars * nlat][mp]), the uploaded obs_var ([nlat]) and, behind the flag, the observed cells ([mp]) and their inverse
+    // map ([nlat]), and five events around the four phases of the last gain.  mp = the observed cells rounded up to 64
+    struct Gain {
+        DevVec<double> inv, S, B, obs_var;
+        DevVec<int> words;
+        Event mark[5];                             // around assembly, factor, solve, scatter of the last gain (ebm_kalman_gain_phases)
+        bool timed = false;
+    } gain;
+    DevVec<double> scalars_out;                  // ebm_column_scalars: the result of the host variant ([12][ncol]), kept between calls
     // ebm_integrate's device buffers, kept between calls while the shape stays the same: the annual-mean sums
     // [var][ncol*pitch] (pair-split layout), the means and the seasonal snapshots [var][ncol*pitch] in the natural layout, the
     // raw snapshots staged as two halves of [var][chunk][ncol][pitch] (ebm::RawStaging), the hemispheric means [var][ncol]

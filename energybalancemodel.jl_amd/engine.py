@@ -482,6 +482,81 @@ class Engine:
             check(self.lib.ebm_update_columns_device(self._h, len(ids), field_ids(ids), obs_id, C.c_void_p(g.data_ptr()), dptr(y), scale,
                                                      eptr, dptr(lo), dptr(hi)), "ebm_update_columns_device")
 
+    def _check_gpu_matrix(self, t, arg, shape=None):
+        """A contiguous float64 torch tensor on the engine's GPU (of ``shape``, if given), as ``check_update_args`` asks of a
+        device gain."""
+        if not hasattr(t, "data_ptr") or not self._on_my_gpu(t) or str(t.dtype) != "torch.float64" or not t.is_contiguous():
+            raise ValueError(f"{arg}: expected a contiguous float64 tensor on the engine's GPU (cuda:{self._device_index()})")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{arg}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    @staticmethod
+    def _raise_with_info(rc, info, what):
+        try:
+            check(rc, what)
+        except _lib.EBMError as err:
+            err.info = int(info.value)
+            raise
+
+    def spd_solve(self, S, B, m=None):
+        """ebm_spd_solve_device (the definition is in include/ebm_hip.h): X . S = B for a symmetric positive definite ``S``, in
+        place, by a blocked Cholesky factorisation on the fp64 matrix instruction.  ``S`` [rows, lds] and ``B`` [nrhs, ldb]:
+        contiguous float64 torch tensors on the engine's GPU; the system is the leading ``m`` x ``m`` of S (None: all of its
+        rows) and rows, lds and ldb must be >= m rounded up to 64, S padded with the identity and B with zeros by the caller.
+        On return the lower triangle of S holds L and the rows of B hold X.  EBMError (``.info`` = the 1-based index of the
+        first bad pivot) where S is not positive definite.  The handle's fields, clock and counters are untouched.  torch's
+        current stream is awaited first (here and in ``kalman_gain_tensor``): the handle's own stream does not wait for it."""
+        S, B = self._check_gpu_matrix(S, "S"), self._check_gpu_matrix(B, "B")
+        if S.dim() != 2 or B.dim() != 2:
+            raise ValueError(f"S, B: expected two matrices, got shapes {tuple(S.shape)} and {tuple(B.shape)}")
+        m = int(S.shape[0]) if m is None else int(m)
+        mp = (m + 63) // 64 * 64
+        if m < 1 or min(S.shape[0], S.shape[1], B.shape[1]) < mp:
+            raise ValueError(f"S {tuple(S.shape)}, B {tuple(B.shape)}: expected m >= 1 and the rows and the row length of S and the "
+                             f"row length of B >= m rounded up to 64 = {mp} (pad S with the identity and B with zeros)")
+        import torch
+        torch.cuda.current_stream(self._device_index()).synchronize()      # the handle's stream does not wait for torch's
+        info = C.c_int(0)
+        rc = self.lib.ebm_spd_solve_device(self._h, m, int(B.shape[0]), C.c_void_p(S.data_ptr()), int(S.shape[1]),
+                                           C.c_void_p(B.data_ptr()), int(B.shape[1]), C.byref(info))
+        self._raise_with_info(rc, info, "ebm_spd_solve_device")
+
+    def kalman_gain_tensor(self, obs, obs_var, localize, factor, P_oo, P_fo):
+        """ebm_kalman_gain_device (the definition is in include/ebm_hip.h): the Kalman gains [len(P_fo), nlat, nlat] as a new
+        torch tensor on the engine's GPU — what ``update_columns`` takes — from covariances already there.  ``obs`` [nlat]
+        (NaN: not observed), ``obs_var`` scalar or [nlat], ``localize``: the half-width in x of the Gaspari-Cohn taper (None
+        or <= 0: none), ``factor``: what multiplies both covariances (inflation * n / (n - 1) for sums divided by n), ``P_oo``
+        and every entry of ``P_fo`` (1 to 5; an entry may be ``P_oo`` itself): contiguous float64 [nlat, nlat] tensors on the
+        engine's GPU.  Assembly, factorisation, solve and scatter run on the device in a fixed order: the same bits on every
+        run.  EBMError (``.info`` = the bad pivot; the message names the observed latitude) where the innovation covariance
+        is not positive definite.  The handle's fields, clock and counters are untouched."""
+        import torch
+        nlat = self.nlat
+        y = as_f64(obs, (nlat,))
+        R = np.ascontiguousarray(np.broadcast_to(np.asarray(obs_var, dtype=np.float64), (nlat,)))
+        P_fo = list(P_fo)
+        if not 1 <= len(P_fo) <= 5:
+            raise ValueError(f"P_fo: expected between 1 and 5 matrices, got {len(P_fo)}")
+        self._check_gpu_matrix(P_oo, "P_oo", (nlat, nlat))
+        for v, p in enumerate(P_fo):
+            self._check_gpu_matrix(p, f"P_fo[{v}]", (nlat, nlat))
+        gain = torch.empty((len(P_fo), nlat, nlat), dtype=torch.float64, device=P_oo.device)
+        addr = (C.c_void_p * len(P_fo))(*[p.data_ptr() for p in P_fo])
+        torch.cuda.current_stream(self._device_index()).synchronize()      # the handle's stream does not wait for torch's
+        info = C.c_int(0)
+        rc = self.lib.ebm_kalman_gain_device(self._h, len(P_fo), dptr(y), dptr(R), 0.0 if localize is None else float(localize),
+                                             float(factor), C.c_void_p(P_oo.data_ptr()), addr, C.c_void_p(gain.data_ptr()), C.byref(info))
+        self._raise_with_info(rc, info, "ebm_kalman_gain_device")
+        return gain
+
+    def kalman_gain_phases(self) -> dict:
+        """ebm_kalman_gain_phases: milliseconds between HIP events around the assembly, the factorisation, the two solves
+        and the scatter of this engine's last ``kalman_gain_tensor`` that ran a solve."""
+        ms = (C.c_float * 4)()
+        check(self.lib.ebm_kalman_gain_phases(self._h, ms), "ebm_kalman_gain_phases")
+        return dict(zip(("assembly", "factor", "solve", "scatter"), (float(v) for v in ms)))
+
     def get_field_device(self, name: str, dev_ptr: int):
         """Device-to-device copy of a field, packed [ncol][nlat], to ``dev_ptr``."""
         check(self.lib.ebm_get_field_device(self._h, FIELD[name], C.c_void_p(dev_ptr)),

@@ -664,14 +664,19 @@ class KalmanMixin(CovarianceMixin):
         """The per-field bounds ``enkf`` applies when given none (none here; EnsembleRun knows its model's)."""
         return {}
 
-    def kalman_gains(self, names, obs_name, obs, obs_var, localize=None, inflation=1.0, dist=None) -> dict:
+    def kalman_gains(self, names, obs_name, obs, obs_var, localize=None, inflation=1.0, dist=None, solver="host") -> dict:
         """The host part of ``enkf``: ``{"gain": [len(names), nlat, nlat], "mean_o": [nlat], "var_o": [nlat], "observed":
         bool [nlat], "members": n}``.  P_oo = ``covariance(obs_name)`` and P_fo = ``covariance(f, obs_name)`` per field, each
         all-reduced over ``dist`` as ``covariance`` does and scaled to the unbiased estimate (n / (n - 1), n the members of the
         whole ensemble); with J the observed cells (``obs`` not NaN): S = rho o P_oo[J, J] * inflation + diag(obs_var[J]),
         G_f[:, J] = inflation * (rho o P_fo[:, J]) S^-1 by one Cholesky-free ``numpy.linalg.solve`` of the m x m system, zeros
-        in the columns of unobserved cells.  rho = ``gaspari_cohn(|x_i - x_j| / localize)``, or all ones without ``localize``."""
+        in the columns of unobserved cells.  rho = ``gaspari_cohn(|x_i - x_j| / localize)``, or all ones without ``localize``.
+        ``solver="device"``: the same on the device (``_gains_on_device``), ``"gain"`` a torch tensor there, which
+        ``update_columns`` takes where it lies; nothing of size nlat^2 touches the host.  Not with ``dist`` (ValueError): a
+        sharded run uses the host solver."""
         names = as_names(names)
+        if solver not in ("host", "device"):
+            raise ValueError(f"solver = {solver!r}: expected 'host' or 'device'")
         x = np.asarray(self.st.x, dtype=np.float64)
         nlat = x.shape[0]
         y = np.asarray(obs, dtype=np.float64)
@@ -685,6 +690,11 @@ class KalmanMixin(CovarianceMixin):
             raise ValueError(f"inflation = {inflation!r}: expected a finite factor > 0")
         if localize is not None and not (np.isfinite(localize) and localize > 0.0):
             raise ValueError(f"localize = {localize!r}: expected None or a half-width in x > 0")
+        if solver == "device":
+            if _sharded(dist):
+                raise ValueError('solver="device" is for one shard: with `dist` use solver="host" (the all-reduce of the device '
+                                 "covariances is not built)")
+            return self._gains_on_device(names, obs_name, y, R, J, localize, float(inflation), dist)
         rho = np.ones((nlat, nlat)) if localize is None else gaspari_cohn(np.abs(x[:, None] - x[None, :]) / float(localize))
         oo = self.covariance(obs_name, None, None, dist)
         n = float(np.max(oo["n"]))
@@ -703,6 +713,41 @@ class KalmanMixin(CovarianceMixin):
             gain[v][:, J] = np.linalg.solve(S, B.T).T if J.any() else 0.0      # S is symmetric
         return {"gain": gain, "mean_o": oo["mean_a"], "var_o": np.diag(P_oo).copy(), "observed": J, "members": int(n)}
 
+    def _gains_on_device(self, names, obs_name, y, R, J, localize, inflation, dist) -> dict:
+        """``kalman_gains`` with the covariances, the m x m system, its blocked Cholesky solve and the gain all on the device
+        (ebm_kalman_gain_device), in terms of two more methods of the class it is mixed into: ``ensemble_covariance_tensor``
+        and ``kalman_gain_tensor``.  One pass of the sums gives the weights and means of all fields, as in ``covariance``;
+        every matrix of sums is written by ebm_ensemble_covariance_device and divided on the device by
+        n[i, j] = min(S0_a[i], S0_b[j]); ``factor = inflation * n / (n - 1)``.  One shard only: ``kalman_gains`` refuses
+        ``dist`` with this solver.  O(nlat) numbers come to the host: the sums, and the
+        diagonal of P_oo for ``var_o``.  EBMError where the innovation covariance is not positive definite (a NaN covariance
+        at an observed cell is reported so, with its latitude)."""
+        import torch
+        fields = (obs_name,) + tuple(f for f in names if f != obs_name)
+        m = moments_from_sums(np.asarray(self.reduced_sums(fields, None, None, dist)))
+        n = float(np.max(m["weight"][0]))
+        if not n > 1.0:
+            raise ValueError("enkf: needs more than one member")
+        unbias = n / (n - 1.0)
+        centers = [moments_center(m["mean"][i]) for i in range(len(fields))]
+
+        def cov(i):
+            t = self.ensemble_covariance_tensor(fields[i], obs_name, None, centers[i], centers[0])
+            wa, wo = (torch.as_tensor(np.ascontiguousarray(m["weight"][q]), device=t.device) for q in (i, 0))
+            cnt = torch.minimum(wa[:, None], wo[None, :])
+            return torch.where(cnt == 0.0, torch.full_like(t, float("nan")), t / cnt).contiguous()
+
+        P = {0: cov(0)}
+        P_fo = []
+        for f in names:
+            i = fields.index(f)
+            if i not in P:
+                P[i] = cov(i)
+            P_fo.append(P[i])
+        gain = self.kalman_gain_tensor(y, R, localize, inflation * unbias, P[0], P_fo)
+        var_o = torch.diagonal(P[0]).cpu().numpy() * unbias
+        return {"gain": gain, "mean_o": m["mean"][0], "var_o": var_o, "observed": J, "members": int(n)}
+
     def _innovation_statistics(self, obs_name, obs, J, dist):
         """Mean and spread of ``obs_name`` across the members against ``obs`` at the observed cells J (two passes of the sums)."""
         m = self.moments((obs_name,), None, dist)[obs_name]
@@ -711,7 +756,7 @@ class KalmanMixin(CovarianceMixin):
                 "spread": float(np.sqrt(np.mean(m["var"][J]))) if J.any() else np.nan}
 
     def enkf(self, names, obs_name, obs, obs_var, method="denkf", localize=None, inflation=1.0, bounds=None, generator=None,
-             dist=None) -> dict:
+             dist=None, solver="host") -> dict:
         """One analysis step of an ensemble Kalman filter on the fields ``names`` (prognostic) from observations ``obs``
         [nlat] of ``obs_name`` (NaN: not observed) with error variance ``obs_var`` (scalar or [nlat]).  Built from the
         reductions and ONE write: means from ``reduced_sums``, P_oo and P_fo from ``covariance``, the gains on the host
@@ -734,12 +779,15 @@ class KalmanMixin(CovarianceMixin):
         bounded afterwards — by default Ei <= 0, Ew >= 0, h >= 0, 0 <= D <= Dmax, 0 <= phi <= 1 (``bounds``: dict name ->
         (lo, hi) replaces the default of that field).  Cross-field consistency — D = 0 where Ei = 0, the concentration that
         belongs to Ei and h, and so on — is restored only by the model's own step (src/miz.jl:109-117, 74-80), as after any
-        ``set_field``.  Classic model (E, Tg): nothing to bound."""
+        ``set_field``.  Classic model (E, Tg): nothing to bound.
+        ``solver="device"``: the gains are formed and solved on the device (``kalman_gains``) and handed to ``update_columns``
+        as the tensor they are — an analysis step then moves O(nlat) numbers over the bus.  One shard only (ValueError with
+        ``dist``)."""
         names = as_names(names)
         if method not in ("denkf", "perturbed"):
             raise ValueError(f"method = {method!r}: expected 'denkf' or 'perturbed'")
         y = np.asarray(obs, dtype=np.float64)
-        k = self.kalman_gains(names, obs_name, y, obs_var, localize, inflation, dist)
+        k = self.kalman_gains(names, obs_name, y, obs_var, localize, inflation, dist, solver)
         J = k["observed"]
         prior = self._innovation_statistics(obs_name, y, J, dist)
         use = dict(self.default_update_bounds(names))
@@ -754,7 +802,7 @@ class KalmanMixin(CovarianceMixin):
             posterior = self._innovation_statistics(obs_name, y, J, dist)
         except StaleFieldError:
             posterior = None
-        return {"gain_shape": k["gain"].shape, "observed": int(J.sum()), "members": k["members"], "prior": prior, "posterior": posterior}
+        return {"gain_shape": tuple(k["gain"].shape), "observed": int(J.sum()), "members": k["members"], "prior": prior, "posterior": posterior}
 
 
 class EnsembleRun(ColumnExchange, KalmanMixin):
@@ -1134,6 +1182,11 @@ class EnsembleRun(ColumnExchange, KalmanMixin):
         """Every member moved by ``gain`` applied to its own innovation, on the device (ebm_update_columns).  See
         ``Engine.update_columns``; ``enkf`` forms the gain."""
         self.engine.update_columns(names, obs_name, gain, target, scale, perturb, bounds)
+
+    def kalman_gain_tensor(self, obs, obs_var, localize, factor, P_oo, P_fo):
+        """The Kalman gains [len(P_fo), nlat, nlat] as a torch tensor ON THE DEVICE from covariances already there
+        (ebm_kalman_gain_device).  See ``Engine.kalman_gain_tensor``; ``kalman_gains(solver="device")`` feeds it."""
+        return self.engine.kalman_gain_tensor(obs, obs_var, localize, factor, P_oo, P_fo)
 
     def obs_noise(self, sd, generator=None):
         """[ncol, nlat] float64 on this run's device: sd[j] * randn, drawn by torch with ``generator`` (a torch.Generator of

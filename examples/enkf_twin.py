@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--method", choices=("denkf", "perturbed"), default="denkf")
     ap.add_argument("--localize", type=float, default=0.3, help="half-width in x of the Gaspari-Cohn taper (0: none)")
     ap.add_argument("--inflation", type=float, default=1.0)
+    ap.add_argument("--solver", choices=("host", "device"), default="host",
+                    help="where the Kalman gain is formed: numpy.linalg.solve on the host, or ebm_kalman_gain_device")
     ap.add_argument("--sigma", type=float, default=4.0, help="stationary standard deviation of the forcing noise (W m^-2)")
     ap.add_argument("--tau", type=float, default=0.1, help="e-folding time of the forcing noise (years)")
     ap.add_argument("--seed", type=int, default=1)
@@ -77,7 +79,7 @@ def main():
         obs[seen] = T[seen] + rng.normal(0.0, args.obs_sigma, len(seen))
         before = rms(filtered, T), rms(free, T)              # T goes stale with the analysis, until the next diagnostic step
         res = filtered.enkf(PROG[:-1], "T", obs, args.obs_sigma ** 2, method=args.method, localize=args.localize or None,
-                            inflation=args.inflation)
+                            inflation=args.inflation, solver=args.solver)
         assert res["observed"] == len(seen) and res["gain_shape"] == (5, st.nx, st.nx)
         print(f"{(cycle + 1) * args.every * st.dt:10.3f}  {res['observed']:9d}  {before[0]:17.4f}  {before[1]:13.4f}  {res['prior']['spread']:18.4f}")
     for run in (truth, filtered, free):

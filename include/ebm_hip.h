@@ -844,6 +844,73 @@ int ebm_update_columns(ebm_handle_t h, int nvars, const int *fields, int obs_fie
 int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *dev_gain,
                               const double *target, double scale, const double *dev_perturb, const double *lo, const double *hi);
 
+/* KALMAN GAIN ON THE DEVICE: the middle of the filter, between ebm_ensemble_covariance_device and
+ * ebm_update_columns_device — a symmetric positive definite solve in fp64 by a blocked Cholesky factorisation on the matrix
+ * instruction of gfx950, so that an analysis step moves O(nlat) numbers over the bus.  THIS TEXT IS THE DEFINITION.
+ *   The system.  S is m x m, symmetric positive definite, row-major, full storage; the right-hand sides are the ROWS of B
+ *     ([nrhs][m]); the result X has X . S = B (S is symmetric: numpy.linalg.solve(S, B.T).T).  Everything works on mp = m
+ *     rounded up to nb = 64 with the identity in the padding of S and +0.0 in the padding columns of B, so that no step below
+ *     has a tail and the padding never reaches a result.  T = mp / 64 block columns; A_ij is the 64 x 64 tile (i, j) of S.
+ *   Products.  Every matrix product below is, per element, ONE chain acc <- mfma(x[t .. t+3], y[t .. t+3], acc) of
+ *     v_mfma_f64_16x16x4_f64 over the contraction index t = 0, 4, 8, ... ascending, from +0.0, the left factor the A operand,
+ *     whichever tile, wave and register the element falls in.  Nothing else is contracted into a fused multiply-add.
+ *   Factor, right-looking, for k = 0 ... T - 1:
+ *     (a) the diagonal tile A_kk, for its columns j = 0 ... 63 in turn: s = sqrt(a[j][j]); a[i][j] <- a[i][j] / s for i > j;
+ *         a[i][c] <- a[i][c] - a[i][j] * a[c][j] for j < c <= i; a[j][j] <- s.  The first pivot a[j][j] that is not > 0 (a
+ *         NaN is not) records its 1-based index 64 k + j + 1; the sweep goes on regardless, and every later step of the call
+ *         does nothing.  Then W = inverse of L_kk by forward substitution per column c: W[i][c] = ((i == c ? 1 : 0) -
+ *         sum_{c <= j < i} L[i][j] * W[j][c]) / L[i][i], the terms subtracted one by one in ascending j.
+ *     (b) the panel: A_ik <- A_ik . W^T for i > k (contraction over the 64 columns of the tile).
+ *     (c) the trailing tiles: A_ij <- A_ij - L_ik . L_jk^T for i >= j > k, one rounded subtraction after the chain.  Only
+ *         tiles of the lower triangle are read or written (the diagonal tiles whole; their strict upper parts are scratch).
+ *   Solve.  Forward, k ascending:   W = B_k - sum_{t < 64 k} Y[.][t] * L[64 k + c][t];        Y_k = W . inv(L_kk)^T.
+ *           Backward, k descending: W = Y_k - sum_{t >= 64 (k + 1)} X[.][t] * L[t][64 k + c];  X_k = W . inv(L_kk).
+ *     The sums run over ALL earlier (later) columns in one chain; W = B_k - acc is one rounded subtraction.  Rows are
+ *     independent: a workgroup owns 64 of them for the whole walk and writes W and then the result to B in place.
+ *   ebm_spd_solve_device: the solver on caller-owned device buffers.  dev_S [mp][lds], dev_B [nrhs][ldb], lds, ldb >= mp, both
+ *     16-byte aligned; the caller has padded them as above (or m is a multiple of 64).  On return the lower triangle of S
+ *     holds L, B holds X and *info = 0.  If S is not positive definite, *info is the 1-based index of the first bad pivot,
+ *     the call returns EBM_ERR_ARG with a message naming that index, and B is unspecified.
+ *   ebm_kalman_gain_device: obs[nlat] (host; NaN = unobserved, J = the observed cells ascending, m of them), obs_var[nlat]
+ *     (host; read at the observed cells), localize (half-width in x of the taper; <= 0: none), factor (inflation * n / (n - 1)
+ *     for covariance sums divided by n), dev_Poo and Pfo_addr[v], v < nvars (a HOST array of device addresses): packed
+ *     [nlat][nlat] device matrices, read only (Pfo_addr[v] may be dev_Poo) — typed double ** although nothing is written
+ *     through it: const double *const * is what it means —, dev_gain [nvars][nlat][nlat], what ebm_update_columns_device
+ *     takes.  Covariances, not field ids, so
+ *     that a sharded run can all-reduce them first.  Assembly, one rounding per operation in this order:
+ *       S[a][b]          = (rho(J[a], J[b]) * Poo[J[a]][J[b]]) * factor + (a == b ? obs_var[J[a]] : 0.0)
+ *       B[v nlat + k][a] = (factor * rho(k, J[a])) * Pfo_v[k][J[a]],  a non-finite Pfo entry taken as +0.0
+ *     rho(i, j) = the Gaspari-Cohn taper of r = |x_i - x_j| / localize: for r <= 1 (((-r/4 + 1/2) r + 5/8) r - 5/3) r^2 + 1, for
+ *     1 < r < 2 (((r/12 - 1/2) r + 5/8) r + 5/3) r^2 - 5 r + 4 - 2/(3 r), else 0, clipped to [0, 1], evaluated left to right as
+ *     written (gaspari_cohn of the Python package, bit for bit); exactly 1.0 without localisation.  Then the solve with
+ *     nrhs = nvars * nlat, and gain[v][k][J[a]] = X[v nlat + k][a], +0.0 in every column of an unobserved cell.  No observed
+ *     cell at all: a gain of +0.0 and no solve.  A bad pivot — a NaN covariance at an observed cell is one — returns
+ *     EBM_ERR_ARG with *info set and a message naming the pivot and its observed latitude J[info - 1]; dev_gain is unspecified.
+ *   Determinism.  The order of every operation is fixed above and depends on nothing but m and nrhs: the same call on the same
+ *     data gives the same bits on every run, for every cells_per_thread and whatever layout the handle holds its rows in (the
+ *     covariances are natural-order matrices).
+ *   Ordering and bookkeeping.  Synchronous on the handle's stream, the two launch chains joined first.  Neither call reads or
+ *     writes a field: no field's validity, the step clock, the counters and ebm_state_conversions do not change, and the
+ *     launches are not counted.
+ * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle or pointer, a device pointer that is not 16-byte
+ * aligned, m < 1, nrhs < 0, lds or ldb < mp; nvars outside 1 ... 5, an infinite obs entry, an obs_var entry at an observed
+ * cell that is not finite and > 0, a factor that is not finite and > 0, a NaN localize; and the bad pivot above.
+ * How it runs (csrc/ebm_gain.hip): 256-lane workgroups, 64 x 64 tiles, each wave 32 x 32 as 2 x 2 accumulators, operands
+ * staged sixteen t at a time through 9 KiB of LDS in lines padded to 18 doubles, the next sixteen in flight under the matrix
+ * instructions.  (a) is one workgroup with the tile in 32.5 KiB + 16.25 KiB of LDS, two barriers per column; (b) is T - k - 1
+ * workgroups and (c) (T - k - 1)^2, of which the upper half return at once: three launches per block column.  Each solve
+ * direction is ONE launch of ceil(nrhs / 64) workgroups; a workgroup re-reads only what it wrote itself, behind a block-level
+ * fence and a barrier.  Assembly and scatter are one lane per element.  Plain vector loads and stores, no atomics, no scratch
+ * memory.  Device memory, kept by the handle, reused and freed by ebm_destroy: 64 mp doubles of block inverses and one int
+ * of flag; for the gain also mp^2 doubles of S, nvars * nlat * mp of B, nlat of obs_var and mp + nlat ints of index lists. */
+int ebm_spd_solve_device(ebm_handle_t h, int m, long long nrhs, double *dev_S, long long lds, double *dev_B, long long ldb, int *info);
+int ebm_kalman_gain_device(ebm_handle_t h, int nvars, const double *obs, const double *obs_var, double localize, double factor,
+                           const double *dev_Poo, double **Pfo_addr, double *dev_gain, int *info);
+/* elapsed_ms[4]: the time between HIP events on the handle's stream around the assembly, the factorisation, the two solves and
+ * the scatter of the LAST ebm_kalman_gain_device call of this handle that ran a solve (EBM_ERR_ARG: there was none, or a
+ * NULL argument).  Measurement only; the events are always recorded (five per call). */
+int ebm_kalman_gain_phases(ebm_handle_t h, float *elapsed_ms);
+
 /* COLUMN SCALARS: numbers that reduce ALONG a column — the integral or mean of a field over a band of latitudes, and the
  * position of an edge: where, walking poleward, a field first reaches a level (the ice edge: the first cell with phi >= 0.15).
  * The number this model is known for, per member, without a field leaving the device.  THIS TEXT IS THE DEFINITION.

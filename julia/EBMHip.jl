@@ -441,6 +441,45 @@ function update_columns_device!(h::Handle, names, obs_name::Symbol, dev_gain::Pt
 end
 
 """
+    spd_solve_device!(h, m, nrhs, dev_S, lds, dev_B, ldb) -> info
+    kalman_gain_device!(h, obs, obs_var, dev_Poo, dev_Pfo, dev_gain; localize=0.0, factor=1.0) -> info
+
+The Kalman gain on the device (`ebm_spd_solve_device`, `ebm_kalman_gain_device`; the definition is in the header): `X * S = B` for
+a symmetric positive definite `S` by a blocked Cholesky factorisation on the fp64 matrix instruction, in place on device
+buffers padded to a multiple of 64, and the gain `[nvars][nlat][nlat]` built with it from covariances already on the device.
+`obs`: `nlat` values, `NaN` = unobserved; `obs_var`: `nlat` values; `dev_Pfo`: a vector of device pointers, one per field.  A
+matrix that is not positive definite raises with the bad pivot in the message.
+"""
+function spd_solve_device!(h::Handle, m::Integer, nrhs::Integer, dev_S::Ptr{Cdouble}, lds::Integer, dev_B::Ptr{Cdouble}, ldb::Integer)
+    info = Ref{Cint}(0)
+    GC.@preserve h check(@ccall(libebm.ebm_spd_solve_device(h.ptr::Ptr{Cvoid}, Cint(m)::Cint, Clonglong(nrhs)::Clonglong,
+                                                            dev_S::Ptr{Cdouble}, Clonglong(lds)::Clonglong, dev_B::Ptr{Cdouble},
+                                                            Clonglong(ldb)::Clonglong, info::Ptr{Cint})::Cint),
+                         "ebm_spd_solve_device")
+    return Int(info[])
+end
+
+function kalman_gain_device!(h::Handle, obs, obs_var, dev_Poo::Ptr{Cdouble}, dev_Pfo::Vector{Ptr{Cdouble}}, dev_gain::Ptr{Cdouble};
+                             localize::Real=0.0, factor::Real=1.0)
+    y = Vector{Float64}(obs)
+    r = Vector{Float64}(obs_var)
+    info = Ref{Cint}(0)
+    GC.@preserve h check(@ccall(libebm.ebm_kalman_gain_device(h.ptr::Ptr{Cvoid}, length(dev_Pfo)::Cint, y::Ptr{Cdouble}, r::Ptr{Cdouble},
+                                                              Float64(localize)::Cdouble, Float64(factor)::Cdouble,
+                                                              dev_Poo::Ptr{Cdouble}, dev_Pfo::Ptr{Ptr{Cdouble}}, dev_gain::Ptr{Cdouble},
+                                                              info::Ptr{Cint})::Cint),
+                         "ebm_kalman_gain_device")
+    return Int(info[])
+end
+
+"The HIP-event times (ms) of assembly, factor, solves and scatter of the handle's last `kalman_gain_device!` (`ebm_kalman_gain_phases`)."
+function kalman_gain_phases(h::Handle)
+    ms = zeros(Cfloat, 4)
+    GC.@preserve h check(@ccall(libebm.ebm_kalman_gain_phases(h.ptr::Ptr{Cvoid}, ms::Ptr{Cfloat})::Cint), "ebm_kalman_gain_phases")
+    return ms
+end
+
+"""
     ensemble_range(h, names; ncol, nlat, weights=nothing) -> Array{Float64,3}
     ensemble_range_device!(h, names, devout; weights=nothing)
     ensemble_histogram(h, names, lo, hi, nbins; ncol, nlat, weights=nothing) -> Array{Float64,3}
