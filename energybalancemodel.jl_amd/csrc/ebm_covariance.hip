@@ -8,33 +8,26 @@
 //              the centers, bound the padding and decide what rule 6 skips.  The columns of the block pass through LDS
 //              sixteen at a time: lane (unit u = lane & 31, column lane >> 5) loads 16 bytes of each row, a wave two whole
 //              512-byte runs of four lines; the A side is centred, weighted and NaN-cleaned on its way into LDS, the B side
-//              centred and NaN-cleaned; the next sixteen are loaded into registers before the MFMAs of these start.  Each of
-//              the four waves owns 32 x 32 of the tile as 2 x 2 accumulators; per group of four columns it reads two A and
-//              two B operands (lane & 15 the cell, lane >> 4 the column of the group) and issues four MFMAs.  LDS rows are
-//              80 doubles: 160 words = 32 mod 64 banks, so the two rows that a half-wave reads fall on disjoint banks.
-//              20 KiB of LDS.  The accumulators go to partial[block][stored i][stored j], each 16-lane group a whole line.
+//              centred and NaN-cleaned; the next sixteen are loaded into registers before the MFMAs of these start.  Both
+//              sides are staged k-major (ebm_mfma_tile.h, which owns the tile, the operands and the accumulators): 20 KiB of
+//              LDS.  The accumulators go to partial[block][stored i][stored j], each 16-lane group a whole line.
 //   finish     grid (columns of out / 256) x (rows of out).  A lane owns one out[i][j], finds the stored cells of i and j,
 //              adds the blocks in ascending order and writes the natural index — under rule 6 only for j >= i, and then
 //              out[j][i] as well (that store has a stride of nlat doubles across a wave: uncoalesced).
 // Rule 6 skips whole tiles and, inside a tile, a wave's whole 32 x 32 block, where the natural cells they stand for hold no
 // pair with j >= i; a block that holds one is computed whole and its elements with j < i are never read.
-// Every output element sees the same chain whichever tile, wave and register it falls in: acc = mfma(a[4], b[4], acc) over
-// the groups of its block, ascending.  A tail group is padded with +0.0 terms; a group wholly past the block's last column
+// Every output element sees the same chain (ebm_mfma_tile.h) whichever tile, wave and register it falls in, over the groups
+// of four columns of its block.  A tail group is padded with +0.0 terms; a group wholly past the block's last column
 // is not issued.  Nothing else is contracted (-ffp-contract=off): d = x - center, a = w * d are rounded once each.
 // Plain vector loads and stores; no scratch.
 #include "ebm_internal.h"
+#include "ebm_mfma_tile.h"
 
 namespace ebm {
 
-constexpr int kCovTile = 64;                   // stored cells per side of a workgroup's tile; the pitch is a multiple of 128
-constexpr int kCovLanes = 256;                 // four waves, 2 x 2 over the tile
-constexpr int kCovChunk = 16;                  // columns in LDS together: two per lane and side
-constexpr int kCovRow = kCovTile + 16;         // doubles per LDS row (see above)
 constexpr int kCovFinishLanes = 256;
-static_assert(kCovBlock % kCovChunk == 0 && kCovChunk % 4 == 0, "a block is whole chunks, a chunk whole MFMA groups");
-static_assert(kCovLanes == 32 * (kCovChunk / 2) && kCovTile == 64, "the staging map: 32 units x 8 columns, twice");
-
-typedef double cov_acc __attribute__((ext_vector_type(4)));
+static_assert(kCovBlock % kTileChunk == 0, "a block is whole chunks");
+static_assert(kTileLanes == 32 * (kTileChunk / 2) && kTileSide == 64, "the staging map: 32 units x 8 columns, twice");
 
 // the natural cells [lo, hi] that the stored units first ... first + n - 1 of a row stand for (n <= 32 divides T: a run never
 // straddles the two halves of a split row, and natural_unit ascends along it)
@@ -52,7 +45,7 @@ struct CovStage {
 __device__ __forceinline__ CovStage open_stage(const double *row, const double *center, bool split, int tile, long long c0,
                                                const CovarianceArgs &a) {
     CovStage s;
-    const int p = tile * (kCovTile / 2) + (threadIdx.x & 31), u = natural_unit(p, a.threads, split);
+    const int p = tile * (kTileSide / 2) + (threadIdx.x & 31), u = natural_unit(p, a.threads, split);
     s.col = reinterpret_cast<const double2 *>(row) + c0 * (a.pitch / 2) + p;
     s.centered = center != nullptr;
     s.c = s.centered ? reinterpret_cast<const double2 *>(center)[u] : make_double2(0.0, 0.0);
@@ -68,8 +61,8 @@ __device__ __forceinline__ double cov_term(double x, double c, bool centered, do
     return (in && w != 0.0 && x == x) ? t : 0.0;
 }
 
-__global__ void __launch_bounds__(kCovLanes) covariance_partials_kernel(const CovarianceArgs a) {
-    __shared__ double sa[kCovChunk][kCovRow], sb[kCovChunk][kCovRow];
+__global__ void __launch_bounds__(kTileLanes) covariance_partials_kernel(const CovarianceArgs a) {
+    __shared__ tile_k_major sa[kTileChunk], sb[kTileChunk];
     const int tj = blockIdx.x, ti = blockIdx.y;
     const long long blk = blockIdx.z;
     int ilo, ihi, jlo, jhi;
@@ -83,17 +76,13 @@ __global__ void __launch_bounds__(kCovLanes) covariance_partials_kernel(const Co
     const CovStage A = open_stage(a.row_a, a.center_a, a.split_a, ti, c0, a), B = open_stage(a.row_b, a.center_b, a.split_b, tj, c0, a);
     const int su = threadIdx.x & 31, sm = threadIdx.x >> 5;      // staging: the unit of the tile, the column of a half chunk
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;  // MFMA: the wave's 32 x 32 is at (r0, q0) of the tile
-    const int r0 = (wave >> 1) * 32, q0 = (wave & 1) * 32, lk = lane >> 4, lc = lane & 15;
+    const int r0 = tile_lane(threadIdx.x).r0, q0 = tile_lane(threadIdx.x).q0;    // the wave's 32 x 32 of the tile
     natural_span(ti * 32 + r0 / 2, 16, a.threads, a.split_a, ilo, ihi);
     natural_span(tj * 32 + q0 / 2, 16, a.threads, a.split_b, jlo, jhi);
     const bool mine = ilo < a.nlat && jlo < a.nlat && !(a.symmetric && ilo > jhi);     // wave-uniform
 
-    cov_acc acc[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[s][t] = cov_acc{0.0, 0.0, 0.0, 0.0};
+    tile_acc acc[2][2];
+    tile_clear(acc);
 
     double2 xa[2], xb[2];
     double wc[2];
@@ -108,7 +97,7 @@ __global__ void __launch_bounds__(kCovLanes) covariance_partials_kernel(const Co
         }
     };
     load(0);
-    for (int m0 = 0; m0 < ncols; m0 += kCovChunk) {
+    for (int m0 = 0; m0 < ncols; m0 += kTileChunk) {
         __syncthreads();                                   // the MFMAs of the chunk before have read LDS
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -118,32 +107,12 @@ __global__ void __launch_bounds__(kCovLanes) covariance_partials_kernel(const Co
                 make_double2(cov_term<false>(xb[h].x, B.c.x, B.centered, wc[h], B.in0), cov_term<false>(xb[h].y, B.c.y, B.centered, wc[h], B.in1));
         }
         __syncthreads();
-        if (m0 + kCovChunk < ncols) load(m0 + kCovChunk);  // in flight under the MFMAs
-        if (!mine) continue;
-#pragma unroll
-        for (int k0 = 0; k0 < kCovChunk; k0 += 4) {
-            if (m0 + k0 >= ncols) break;                   // a group wholly past the last column is not part of the chain
-            double av[2], bv[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                av[s] = sa[k0 + lk][r0 + 16 * s + lc];
-                bv[s] = sb[k0 + lk][q0 + 16 * s + lc];
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[t], acc[s][t], 0, 0, 0);
-        }
+        if (m0 + kTileChunk < ncols) load(m0 + kTileChunk);  // in flight under the MFMAs
+        if (mine) tile_mfma(acc, sa, sb, (ncols - m0 + 3) / 4);      // a group wholly past the last column is not issued
     }
     if (!mine) return;
-    // D of v_mfma_f64_16x16x4_f64: register g of a lane is row (lane >> 4) + 4 g, column lane & 15
-    double *const part = a.partial + (blk * a.pitch + (ti * kCovTile + r0 + lk)) * a.pitch + tj * kCovTile + q0 + lc;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) part[(long long)(16 * s + 4 * g) * a.pitch + 16 * t] = acc[s][t][g];
+    double *const part = a.partial + (blk * a.pitch + ti * kTileSide) * a.pitch + tj * kTileSide;
+    for_each_element(acc, [&](int r, int c, double v) { part[(long long)r * a.pitch + c] = v; });
 }
 
 // the stored cell of natural cell k of a row
@@ -165,8 +134,8 @@ __global__ void __launch_bounds__(kCovFinishLanes) covariance_finish_kernel(cons
 }
 
 hipError_t launch_ensemble_covariance(const CovarianceArgs &a, hipStream_t s) {
-    const unsigned tiles = (unsigned)(a.pitch / kCovTile);
-    covariance_partials_kernel<<<dim3(tiles, tiles, (unsigned)a.nblocks), kCovLanes, 0, s>>>(a);
+    const unsigned tiles = (unsigned)(a.pitch / kTileSide);
+    covariance_partials_kernel<<<dim3(tiles, tiles, (unsigned)a.nblocks), kTileLanes, 0, s>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     covariance_finish_kernel<<<dim3((unsigned)((a.nlat + kCovFinishLanes - 1) / kCovFinishLanes), (unsigned)a.nlat), kCovFinishLanes, 0, s>>>(a);

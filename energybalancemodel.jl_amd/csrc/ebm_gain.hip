@@ -21,41 +21,26 @@
 //              W and then the result are written to B in place; a workgroup re-reads only what it wrote itself, behind a
 //              block-level fence and a barrier.
 //   scatter    one lane per element of the gain: gain[v][k][j] = X[v * nlat + k][pos[j]], +0.0 where cell j is unobserved.
-// Every product above is ONE chain per element whichever tile, wave and register it falls in: acc = mfma(x[4], y[4], acc)
-// over the groups t = 0, 4, 8, ... of the contraction, ascending, from +0.0; the left factor is always the A operand.  The
-// tiles follow ebm_update.hip: 256 lanes, 64 x 64 per workgroup, each wave 32 x 32 as 2 x 2 accumulators, operands staged
-// sixteen t at a time through [line][18] doubles of LDS, the next sixteen loaded before the MFMAs of these start.  Nothing
-// else is contracted (-ffp-contract=off).  A launch that finds the flag set does nothing.  Plain vector loads and stores, no
-// atomics, no scratch.
+// Every product above is ONE chain per element (ebm_mfma_tile.h, which owns the tile, the operands and the accumulators)
+// whichever tile, wave and register it falls in, over the groups t = 0, 4, 8, ... of the contraction.  Both factors are
+// staged line-major, sixteen t at a time, the next sixteen loaded before the MFMAs of these start.  Nothing else is contracted
+// (-ffp-contract=off).  A launch that finds the flag set does nothing.  Plain vector loads and stores, no atomics, no scratch.
 #include "ebm_internal.h"
+#include "ebm_mfma_tile.h"
 
 namespace ebm {
 
-constexpr int kGainLanes = 256;                // four waves, 2 x 2 over the tile
-constexpr int kGainChunk = 16;                 // t in LDS together
-constexpr int kGainRow = kGainChunk + 2;       // doubles per LDS line (ebm_update.hip)
+constexpr int kGainLanes = kTileLanes;         // of every kernel here: a block of the factorisation is a tile
 constexpr int kGainTileWords = kGainBlock * kGainBlock;
-static_assert(kGainLanes == 4 * kGainBlock && kGainChunk == 16 && kGainBlock == 64, "the staging map: 64 lines x 4 quads of four t");
-
-typedef double gain_acc __attribute__((ext_vector_type(4)));
-typedef double gain_lds[kGainRow];
-
-__device__ __forceinline__ void clear(gain_acc (&acc)[2][2]) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[s][t] = gain_acc{0.0, 0.0, 0.0, 0.0};
-}
+static_assert(kGainBlock == kTileSide && kTileLanes == 4 * kTileSide && kTileChunk == 16, "the staging map: 64 lines x 4 quads of four t");
 
 // acc[r][c] += sum_{t < nk} X[r][t] * (TB ? Y[t][c] : Y[c][t]), r, c < 64, nk a multiple of 16; rows r >= xrows of X are +0.0
 // and not loaded.  Every global load of the call has landed in LDS before its last barrier.
 template <bool TB>
-__device__ __forceinline__ void tile_product(gain_acc (&acc)[2][2], gain_lds *sx, gain_lds *sy, const double *X, long long ldx,
+__device__ __forceinline__ void tile_product(tile_acc (&acc)[2][2], tile_line_major *sx, tile_line_major *sy, const double *X, long long ldx,
                                              int xrows, const double *Y, long long ldy, int nk) {
     const int sl = threadIdx.x >> 2, sq = threadIdx.x & 3;           // staging: line sl, four t from 4 sq
     const int tl = threadIdx.x >> 4, c4 = 4 * (threadIdx.x & 15);    // ... of a transposed Y: row tl of the chunk, four c from c4
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r0 = (wave >> 1) * 32, q0 = (wave & 1) * 32, lk = lane >> 4, lc = lane & 15;
     const bool xin = sl < xrows;
     const double *const xp = X + (long long)(xin ? sl : 0) * ldx + 4 * sq;
     const double *const yp = TB ? Y + (long long)tl * ldy + c4 : Y + (long long)sl * ldy + 4 * sq;
@@ -68,7 +53,7 @@ __device__ __forceinline__ void tile_product(gain_acc (&acc)[2][2], gain_lds *sx
         }
     };
     if (nk > 0) load(0);                                   // nk == 0: nothing behind X or Y may be touched
-    for (int t0 = 0; t0 < nk; t0 += kGainChunk) {
+    for (int t0 = 0; t0 < nk; t0 += kTileChunk) {
         __syncthreads();                                   // the MFMAs of the chunk before have read LDS
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -77,35 +62,9 @@ __device__ __forceinline__ void tile_product(gain_acc (&acc)[2][2], gain_lds *sx
             else sy[sl][4 * sq + i] = yv[i];
         }
         __syncthreads();
-        if (t0 + kGainChunk < nk) load(t0 + kGainChunk);   // in flight under the MFMAs
-#pragma unroll
-        for (int k0 = 0; k0 < kGainChunk; k0 += 4) {
-            double av[2], bv[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                av[s] = sx[r0 + 16 * s + lc][k0 + lk];
-                bv[s] = sy[q0 + 16 * s + lc][k0 + lk];
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[t], acc[s][t], 0, 0, 0);
-        }
+        if (t0 + kTileChunk < nk) load(t0 + kTileChunk);   // in flight under the MFMAs
+        tile_mfma(acc, sx, sy, kTileChunk / 4);
     }
-}
-
-// D of v_mfma_f64_16x16x4_f64: register g of acc[s][t] of a lane is row r0 + 16 s + 4 g + (lane >> 4), column q0 + 16 t +
-// (lane & 15) of the tile.  f(row, column, value) for the lane's sixteen elements.
-template <class F>
-__device__ __forceinline__ void for_each_element(const gain_acc (&acc)[2][2], F f) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r0 = (wave >> 1) * 32, q0 = (wave & 1) * 32, lk = lane >> 4, lc = lane & 15;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) f(r0 + 16 * s + 4 * g + lk, q0 + 16 * t + lc, acc[s][t][g]);
 }
 
 // ---- factor -----------------------------------------------------------------------------------------------------------------
@@ -160,25 +119,25 @@ __global__ void __launch_bounds__(kGainLanes) spd_diagonal_kernel(const SolveArg
 }
 
 __global__ void __launch_bounds__(kGainLanes) spd_panel_kernel(const SolveArgs a, const int k) {
-    __shared__ double sx[kGainBlock][kGainRow], sy[kGainBlock][kGainRow];
+    __shared__ tile_line_major sx[kTileSide], sy[kTileSide];
     if (*a.flag) return;
     const int i = k + 1 + blockIdx.x;
     double *const tile = a.S + (long long)i * kGainBlock * a.lds + k * kGainBlock;
-    gain_acc acc[2][2];
-    clear(acc);
+    tile_acc acc[2][2];
+    tile_clear(acc);
     tile_product<false>(acc, sx, sy, tile, a.lds, kGainBlock, a.inv + (long long)k * kGainTileWords, kGainBlock, kGainBlock);
     for_each_element(acc, [&](int r, int c, double v) { tile[(long long)r * a.lds + c] = v; });
 }
 
 __global__ void __launch_bounds__(kGainLanes) spd_trailing_kernel(const SolveArgs a, const int k) {
-    __shared__ double sx[kGainBlock][kGainRow], sy[kGainBlock][kGainRow];
+    __shared__ tile_line_major sx[kTileSide], sy[kTileSide];
     const int j = k + 1 + blockIdx.x, i = k + 1 + blockIdx.y;
     if (j > i || *a.flag) return;                                    // the lower triangle only
     const double *const li = a.S + (long long)i * kGainBlock * a.lds + k * kGainBlock;
     const double *const lj = a.S + (long long)j * kGainBlock * a.lds + k * kGainBlock;
     double *const tile = a.S + (long long)i * kGainBlock * a.lds + j * kGainBlock;
-    gain_acc acc[2][2];
-    clear(acc);
+    tile_acc acc[2][2];
+    tile_clear(acc);
     tile_product<false>(acc, sx, sy, li, a.lds, kGainBlock, lj, a.lds, kGainBlock);
     for_each_element(acc, [&](int r, int c, double v) {
         double *const p = tile + (long long)r * a.lds + c;
@@ -190,15 +149,15 @@ __global__ void __launch_bounds__(kGainLanes) spd_trailing_kernel(const SolveArg
 
 template <bool BACKWARD>
 __global__ void __launch_bounds__(kGainLanes) spd_solve_kernel(const SolveArgs a) {
-    __shared__ double sx[kGainBlock][kGainRow], sy[kGainBlock][kGainRow];
+    __shared__ tile_line_major sx[kTileSide], sy[kTileSide];
     if (*a.flag) return;
     const long long row0 = (long long)blockIdx.x * kGainBlock;
     const int xrows = (int)(a.nrhs - row0 < kGainBlock ? a.nrhs - row0 : kGainBlock), T = a.mp / kGainBlock;
     double *const rows = a.B + row0 * a.ldb;
     for (int step = 0; step < T; ++step) {
         const int k = BACKWARD ? T - 1 - step : step, k0 = k * kGainBlock;
-        gain_acc acc[2][2];
-        clear(acc);
+        tile_acc acc[2][2];
+        tile_clear(acc);
         if (BACKWARD)       // the block columns behind k, already X, times the tiles of L below the diagonal one: L[t][k0 + c]
             tile_product<true>(acc, sx, sy, rows + k0 + kGainBlock, a.ldb, xrows, a.S + (long long)(k0 + kGainBlock) * a.lds + k0, a.lds,
                                a.mp - k0 - kGainBlock);
@@ -211,7 +170,7 @@ __global__ void __launch_bounds__(kGainLanes) spd_solve_kernel(const SolveArgs a
         });
         __threadfence_block();                             // W is read back by other lanes of this workgroup
         __syncthreads();
-        clear(acc);
+        tile_clear(acc);
         tile_product<BACKWARD>(acc, sx, sy, rows + k0, a.ldb, xrows, a.inv + (long long)k * kGainTileWords, kGainBlock, kGainBlock);
         for_each_element(acc, [&](int r, int c, double v) {
             if (r < xrows) rows[(long long)r * a.ldb + k0 + c] = v;

@@ -273,10 +273,10 @@ hipError_t launch_ensemble_histogram(const EnsembleArgs &a, hipStream_t s);
 // ebm_ensemble_covariance (ebm_covariance.hip): out[i][j] = sum over the columns of a * b, a the weighted, centred and
 // NaN-cleaned cell of row_a at latitude i and b the centred and NaN-cleaned cell of row_b at latitude j, in the order of the
 // definition (include/ebm_hip.h) — blocks of kCovBlock columns, inside a block one fp64 MFMA per four columns in ascending
-// order, into partial[block][stored i][stored j], then the blocks in ascending order.  Two launches.  The rows are read where
-// they lie (split_a, split_b: the handle holds that row pair-split; partial is indexed by the stored cells of both); the
-// centers and out are in natural latitude order.  symmetric: rule 6 of the definition — only j >= i is computed, out[j][i] is
-// a copy.
+// order (the chain of ebm_mfma_tile.h), into partial[block][stored i][stored j], then the blocks in ascending order.  Two
+// launches.  The rows are read where they lie (split_a, split_b: the handle holds that row pair-split; partial is indexed by
+// the stored cells of both); the centers and out are in natural latitude order.  symmetric: rule 6 of the definition — only
+// j >= i is computed, out[j][i] is a copy.
 constexpr int kCovBlock = 512;       // columns per block of the covariance: part of the definition (include/ebm_hip.h)
 struct CovarianceArgs {
     const double *row_a, *row_b;     // [ncol][pitch]
@@ -290,10 +290,11 @@ struct CovarianceArgs {
 hipError_t launch_ensemble_covariance(const CovarianceArgs &a, hipStream_t s);
 // ebm_update_columns (ebm_update.hip): row[v][c][k] <- clamp(row[v][c][k] + sum_j gain[v][k][j] * d[c][j]) in the order of the
 // definition (include/ebm_hip.h) — d staged first for all columns by launch_update_innovations from obs as it lies, then one
-// fp64 MFMA per four observation cells in ascending order, d the A operand.  row[v], obs: [ncol][pitch], read and written where
-// they lie (bit v of split_mask, obs_split: the handle holds that row pair-split).  gain, target, perturb and d are in natural
-// latitude order: gain[v] at gain + v * gain_field, its row k at k * gain_row (only k, j < nlat are read); target[pitch];
-// perturb [ncol][nlat] packed or null; d [ncol][pitch], every cell at or beyond nlat written +0.0.
+// fp64 MFMA per four observation cells in ascending order, d the A operand (the chain of ebm_mfma_tile.h).  row[v], obs:
+// [ncol][pitch], read and written where they lie (bit v of split_mask, obs_split: the handle holds that row pair-split).
+// gain, target, perturb and d are in natural latitude order: gain[v] at gain + v * gain_field, its row k at k * gain_row (only
+// k, j < nlat are read); target[pitch]; perturb [ncol][nlat] packed or null; d [ncol][pitch], every cell at or beyond nlat
+// written +0.0.
 constexpr int kUpdateMaxFields = 5;
 struct UpdateArgs {
     double *row[kUpdateMaxFields];
@@ -327,8 +328,9 @@ struct MisfitArgs {
 };
 hipError_t launch_column_misfits(const MisfitArgs &a, hipStream_t s);
 // ebm_spd_solve_device and ebm_kalman_gain_device (ebm_gain.hip): X . S = B for a symmetric positive definite S by a blocked
-// Cholesky factorisation, in the order of the definition (include/ebm_hip.h).  Everything works on mp = m rounded up to
-// kGainBlock: S is [mp][lds >= mp] with the identity in its padding, B is [nrhs][ldb >= mp] with +0.0 in its padding columns.
+// Cholesky factorisation, in the order of the definition (include/ebm_hip.h), every product a chain of ebm_mfma_tile.h on
+// tiles of kGainBlock x kGainBlock.  Everything works on mp = m rounded up to kGainBlock:
+// S is [mp][lds >= mp] with the identity in its padding, B is [nrhs][ldb >= mp] with +0.0 in its padding columns.
 // inv: [mp / kGainBlock][kGainBlock][kGainBlock], the inverses of the diagonal blocks of L.  flag: one int, 0 before the first
 // launch; the 1-based index of the first pivot that is not > 0 afterwards, and then every later launch does nothing.
 constexpr int kGainBlock = 64;       // nb of the blocked factorisation: part of the definition (include/ebm_hip.h)

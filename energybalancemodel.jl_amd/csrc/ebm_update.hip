@@ -11,29 +11,21 @@
 //                tile stands for do, which pick the rows of the gain and bound the padding.  The observation cells pass
 //                through LDS sixteen at a time: lane (quad q = lane & 3, line lane >> 2) loads 32 bytes of d of one member
 //                and four gain entries of one state cell, four lanes a whole 128-byte line; the next sixteen are loaded into
-//                registers before the MFMAs of these start.  LDS holds both sides as [line][18] doubles: 36 words per line,
-//                so the sixteen lines x two cells that a half-wave reads for an operand fall on 32 distinct even banks.
-//                4.5 KiB x 2.  Each of the four waves owns 32 x 32 of the tile as 2 x 2 accumulators; per group of four
-//                observation cells it reads two A (d) and two B (gain) operands (lane & 15 the member or the state cell,
-//                lane >> 4 the cell of the group) and issues four MFMAs.  Then the add, the clamp and the store: D register g
-//                of a lane is member (lane >> 4) + 4 g, state cell lane & 15, so sixteen lanes write one whole line of a row.
-// Every (c, k) sees the same chain whichever tile, wave and register it falls in: acc = mfma(d[4], g[4], acc) over the groups
-// j = 0, 4, 8, ... < nlat, ascending, from +0.0; d is always the A operand.  A tail group is padded with +0.0 terms on both
-// sides; a group wholly past nlat is not issued.  Nothing else is contracted (-ffp-contract=off): s = scale * xo,
-// t = target + e, d = t - s and x + acc are rounded once each.  Cells at or beyond nlat of a row, and rows at or beyond ncol,
-// are never written.  Plain vector loads and stores; no scratch.
+//                registers before the MFMAs of these start.  Both sides are staged line-major (ebm_mfma_tile.h, which owns
+//                the tile, the operands and the accumulators), d as the left factor: 9 KiB of LDS.  Then the add, the clamp
+//                and the store: the sixteen lanes that share a row of the tile write one whole line of a row of the field.
+// Every (c, k) sees the same chain (ebm_mfma_tile.h) whichever tile, wave and register it falls in, over the groups
+// j = 0, 4, 8, ... < nlat.  A tail group is padded with +0.0 terms on both sides; a group wholly past nlat is not issued.
+// Nothing else is contracted (-ffp-contract=off): s = scale * xo, t = target + e, d = t - s and x + acc are rounded once
+// each.  Cells at or beyond nlat of a row, and rows at or beyond ncol, are never written.  Plain vector loads and stores; no
+// scratch.
 #include "ebm_internal.h"
+#include "ebm_mfma_tile.h"
 
 namespace ebm {
 
-constexpr int kUpdTile = 64;                   // members, and stored cells, per side of a workgroup's tile
-constexpr int kUpdLanes = 256;                 // four waves, 2 x 2 over the tile
-constexpr int kUpdChunk = 16;                  // observation cells in LDS together
-constexpr int kUpdRow = kUpdChunk + 2;         // doubles per LDS line (see above)
 constexpr int kInnovLanes = 64;                // units per workgroup of the innovations: 128 cells, which the pitch is a multiple of
-static_assert(kUpdLanes == 4 * kUpdTile && kUpdChunk == 16, "the staging map: 64 lines x 4 quads of four cells");
-
-typedef double upd_acc __attribute__((ext_vector_type(4)));
+static_assert(kTileLanes == 4 * kTileSide && kTileChunk == 16, "the staging map: 64 lines x 4 quads of four cells");
 
 // one innovation: +0.0 for no observation (a NaN target), a NaN cell of obs_field or padding
 __device__ __forceinline__ double innovation(double xo, double y, double e, bool perturbed, double scale, bool in) {
@@ -65,30 +57,26 @@ __global__ void __launch_bounds__(kInnovLanes) update_innovations_kernel(const U
 // two halves of a split row, and natural_unit ascends along it: the run is padding iff this cell is)
 __device__ __forceinline__ int first_natural_cell(int first, int T, bool split) { return 2 * natural_unit(first, T, split); }
 
-__global__ void __launch_bounds__(kUpdLanes) update_product_kernel(const UpdateArgs a) {
-    __shared__ double sd[kUpdTile][kUpdRow], sg[kUpdTile][kUpdRow];
+__global__ void __launch_bounds__(kTileLanes) update_product_kernel(const UpdateArgs a) {
+    __shared__ tile_line_major sd[kTileSide], sg[kTileSide];
     const int tk = blockIdx.x, tc = blockIdx.y, v = blockIdx.z;
     const bool split = (a.split_mask >> v) & 1u;
-    if (first_natural_cell(tk * (kUpdTile / 2), a.threads, split) >= a.nlat) return;       // padding only (natural cells ascend)
+    if (first_natural_cell(tk * (kTileSide / 2), a.threads, split) >= a.nlat) return;       // padding only (natural cells ascend)
 
     // staging: line sl of the tile — member c0 + sl of d, stored cell s0 + sl of the field — and four cells 4 sq ... of the chunk
     const int sl = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    const int c0 = tc * kUpdTile, s0 = tk * kUpdTile;
+    const int c0 = tc * kTileSide, s0 = tk * kTileSide;
     const bool member_in = c0 + sl < a.ncol;
     const double2 *const drow = reinterpret_cast<const double2 *>(a.d + (long long)(member_in ? c0 + sl : 0) * a.pitch) + 2 * sq;
     const int ks = 2 * natural_unit((s0 + sl) >> 1, a.threads, split) + (sl & 1);          // the natural cell of the staged gain row
     const bool cell_in = ks < a.nlat;
     const double *const grow = a.gain + (long long)v * a.gain_field + (long long)(cell_in ? ks : 0) * a.gain_row + 4 * sq;
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;      // MFMA: the wave's 32 x 32 is at (r0, q0) of the tile
-    const int r0 = (wave >> 1) * 32, q0 = (wave & 1) * 32, lk = lane >> 4, lc = lane & 15;
+    const int r0 = tile_lane(threadIdx.x).r0, q0 = tile_lane(threadIdx.x).q0;      // the wave's 32 x 32 of the tile
     const bool mine = c0 + r0 < a.ncol && first_natural_cell((s0 + q0) / 2, a.threads, split) < a.nlat;      // wave-uniform
 
-    upd_acc acc[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[s][t] = upd_acc{0.0, 0.0, 0.0, 0.0};
+    tile_acc acc[2][2];
+    tile_clear(acc);
 
     double2 xd[2];
     double xg[4];
@@ -100,43 +88,29 @@ __global__ void __launch_bounds__(kUpdLanes) update_product_kernel(const UpdateA
         for (int i = 0; i < 4; ++i) xg[i] = (cell_in && j0 + 4 * sq + i < a.nlat) ? grow[j0 + i] : 0.0;    // the j-tail: +0.0 terms
     };
     load(0);
-    for (int j0 = 0; j0 < a.nlat; j0 += kUpdChunk) {
+    for (int j0 = 0; j0 < a.nlat; j0 += kTileChunk) {
         __syncthreads();                                   // the MFMAs of the chunk before have read LDS
         *reinterpret_cast<double2 *>(&sd[sl][4 * sq]) = xd[0];
         *reinterpret_cast<double2 *>(&sd[sl][4 * sq + 2]) = xd[1];
         *reinterpret_cast<double2 *>(&sg[sl][4 * sq]) = make_double2(xg[0], xg[1]);
         *reinterpret_cast<double2 *>(&sg[sl][4 * sq + 2]) = make_double2(xg[2], xg[3]);
         __syncthreads();
-        if (j0 + kUpdChunk < a.nlat) load(j0 + kUpdChunk);  // in flight under the MFMAs
-        if (!mine) continue;
-#pragma unroll
-        for (int k0 = 0; k0 < kUpdChunk; k0 += 4) {
-            if (j0 + k0 >= a.nlat) break;                  // a group wholly past nlat is not part of the chain
-            double av[2], bv[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                av[s] = sd[r0 + 16 * s + lc][k0 + lk];
-                bv[s] = sg[q0 + 16 * s + lc][k0 + lk];
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[t], acc[s][t], 0, 0, 0);
-        }
+        if (j0 + kTileChunk < a.nlat) load(j0 + kTileChunk);  // in flight under the MFMAs
+        if (mine) tile_mfma(acc, sd, sg, (a.nlat - j0 + 3) / 4);     // a group wholly past nlat is not issued
     }
     if (!mine) return;
-    // D of v_mfma_f64_16x16x4_f64: register g of a lane is row (lane >> 4) + 4 g, column lane & 15
     const double lo = a.lo[v], hi = a.hi[v];
+    // for_each_element in another order: the natural cell of a column of the tile is found once, not once per element
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const int s = s0 + q0 + 16 * t + lc;                                               // the stored cell
+        const int s = s0 + tile_cell(threadIdx.x, 0, t, 0).col;                             // the stored cell
         const int k = 2 * natural_unit(s >> 1, a.threads, split) + (s & 1);
         if (k >= a.nlat) continue;                                                         // padding is never written
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int c = c0 + r0 + 16 * r + 4 * g + lk;
+                const int c = c0 + tile_cell(threadIdx.x, r, t, g).row;
                 if (c >= a.ncol) continue;
                 double *const cell = a.row[v] + (long long)c * a.pitch + s;
                 double x = *cell + acc[r][t][g];
@@ -153,8 +127,8 @@ hipError_t launch_update_innovations(const UpdateArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_update_product(const UpdateArgs &a, hipStream_t s) {
-    update_product_kernel<<<dim3((unsigned)(a.pitch / kUpdTile), (unsigned)((a.ncol + kUpdTile - 1) / kUpdTile), (unsigned)a.nvars),
-                            kUpdLanes, 0, s>>>(a);
+    update_product_kernel<<<dim3((unsigned)(a.pitch / kTileSide), (unsigned)((a.ncol + kTileSide - 1) / kTileSide), (unsigned)a.nvars),
+                            kTileLanes, 0, s>>>(a);
     return hipGetLastError();
 }
 

@@ -706,22 +706,21 @@ int ebm_ensemble_histogram_device(ebm_handle_t h, int nvars, const int *fields, 
  * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle or out, a field that is not a solution variable of the
  * model, a non-finite w[c] (the message names the column), a non-finite center entry (the message names the center, a or b,
  * and the latitude); EBM_ERR_STALE as above.
- * How it runs (csrc/ebm_covariance.hip): one kernel forms the block partials — grid (tiles of field_b) x (tiles of field_a)
- * x (member blocks), 256 lanes owning 64 x 64 STORED cells, so that its accesses are whole 128-byte lines in either layout;
+ * How it runs (csrc/ebm_covariance.hip): one kernel forms the block partials — grid (tiles of field_b) x (tiles of field_a) x
+ * (member blocks), 256 lanes owning 64 x 64 STORED cells, so that its accesses are whole 128-byte lines in either layout;
  * sixteen members at a time pass through 20 KiB of LDS, the A side centred, weighted and NaN-cleaned on the way in, the B
- * side centred and NaN-cleaned, the next sixteen in flight under the matrix instructions; each of the four waves owns
- * 32 x 32 as 2 x 2 accumulators; LDS rows are padded to 80 doubles so that the operand reads are free of bank conflicts —
- * and a second one adds the block partials per element in ascending order and writes the natural index, under rule 6 both
- * out[i][j] and out[j][i].  Under rule 6 a 64 x 64 tile, and inside a tile each wave's 32 x 32 block, does nothing if the
- * natural cells it stands for hold no pair with j >= i; a block that holds one is computed whole, its elements with j < i
- * are never read.  In natural rows that skips (t - 1) / 2t of the blocks, t = ceil(nlat / 32) per side; in pair-split rows a
- * block stands for every other pair of a 64-cell span and two blocks of overlapping spans are both kept, so fewer are
- * skipped.  Tiles and waves that hold only padding do nothing either.  Plain vector loads
- * and stores, no atomics, no scratch.  Device memory, kept by the handle and reused: ceil(ncol / 512) * pitch^2 doubles of
- * block partials (pitch: nlat rounded up to the launch geometry's row, a multiple of 128), 2 * pitch doubles of centers,
- * the weights of ebm_ensemble_sums (ncol doubles), and nlat^2 doubles for the host variant's result.  For nlat x ncol =
- * 180 x 4096 (pitch 256): 4 MiB + 4 KiB + 32 KiB + 253 KiB; 1024 x 16384: 256 MiB + 16 KiB + 128 KiB + 8 MiB; 4096 x 2048:
- * 512 MiB + 64 KiB + 16 KiB + 128 MiB. */
+ * side centred and NaN-cleaned, the next sixteen in flight under the matrix instructions; the tile, its operands and its
+ * accumulators are those of csrc/ebm_mfma_tile.h, both sides staged k-major — and a second one adds the block partials per
+ * element in ascending order and writes the natural index, under rule 6 both out[i][j] and out[j][i].  Under rule 6 a 64 x 64
+ * tile, and inside a tile each wave's 32 x 32 block, does nothing if the natural cells it stands for hold no pair with j >=
+ * i; a block that holds one is computed whole, its elements with j < i are never read.  In natural rows that skips (t - 1) /
+ * 2t of the blocks, t = ceil(nlat / 32) per side; in pair-split rows a block stands for every other pair of a 64-cell span
+ * and two blocks of overlapping spans are both kept, so fewer are skipped.  Tiles and waves that hold only padding do nothing
+ * either.  Plain vector loads and stores, no atomics, no scratch.  Device memory, kept by the handle and reused: ceil(ncol /
+ * 512) * pitch^2 doubles of block partials (pitch: nlat rounded up to the launch geometry's row, a multiple of 128), 2 *
+ * pitch doubles of centers, the weights of ebm_ensemble_sums (ncol doubles), and nlat^2 doubles for the host variant's
+ * result.  For nlat x ncol = 180 x 4096 (pitch 256): 4 MiB + 4 KiB + 32 KiB + 253 KiB; 1024 x 16384: 256 MiB + 16 KiB + 128
+ * KiB + 8 MiB; 4096 x 2048: 512 MiB + 64 KiB + 16 KiB + 128 MiB. */
 int ebm_ensemble_covariance(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a,
                             const double *center_b, double *out);
 int ebm_ensemble_covariance_device(ebm_handle_t h, int field_a, int field_b, const double *w, const double *center_a,
@@ -833,12 +832,12 @@ int ebm_column_misfits_device(ebm_handle_t h, int nvars, const int *fields, int 
  * handle has it, else the staging rows of ebm_resample_columns.  Kernel 2 is the tiled product: grid (tiles of 64 STORED
  * cells) x (tiles of 64 members) x (fields), 256 lanes; sixteen observation cells at a time pass through 9 KiB of LDS — 32
  * bytes of d of one member and four gain entries of one state cell per lane — the next sixteen in flight under the matrix
- * instructions; each of the four waves owns 32 x 32 as 2 x 2 accumulators; LDS lines are padded to 18 doubles so that the
- * operand reads are free of bank conflicts; then the add, the clamp and the store, sixteen lanes a whole 128-byte line of a
- * row.  Tiles and waves that hold only padding do nothing.  The host variant uploads gain one field at a time into one
- * pitch^2 buffer and launches the product per field; the _device variant is one launch over a grid z of fields.  Plain
- * vector loads and stores, no atomics, no scratch memory.  Device memory, kept by the handle and reused: pitch^2 doubles of gain
- * (host variant), pitch doubles of target, and the borrowed ncol * pitch of innovations. */
+ * instructions; the tile, its operands and its accumulators are those of csrc/ebm_mfma_tile.h, both sides staged line-major;
+ * then the add, the clamp and the store, sixteen lanes a whole 128-byte line of a row.  Tiles and waves that hold only padding
+ * do nothing.  The host variant uploads gain one field at a time into one pitch^2 buffer and launches the product per field;
+ * the _device variant is one launch over a grid z of fields.  Plain vector loads and stores, no atomics, no scratch
+ * memory.  Device memory, kept by the handle and reused: pitch^2 doubles of gain (host variant), pitch doubles of target, and
+ * the borrowed ncol * pitch of innovations. */
 int ebm_update_columns(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *gain, const double *target,
                        double scale, const double *dev_perturb, const double *lo, const double *hi);
 int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int obs_field, const double *dev_gain,
@@ -895,10 +894,10 @@ int ebm_update_columns_device(ebm_handle_t h, int nvars, const int *fields, int 
  * Refusals leave the handle as it was: EBM_ERR_ARG for a NULL handle or pointer, a device pointer that is not 16-byte
  * aligned, m < 1, nrhs < 0, lds or ldb < mp; nvars outside 1 ... 5, an infinite obs entry, an obs_var entry at an observed
  * cell that is not finite and > 0, a factor that is not finite and > 0, a NaN localize; and the bad pivot above.
- * How it runs (csrc/ebm_gain.hip): 256-lane workgroups, 64 x 64 tiles, each wave 32 x 32 as 2 x 2 accumulators, operands
- * staged sixteen t at a time through 9 KiB of LDS in lines padded to 18 doubles, the next sixteen in flight under the matrix
- * instructions.  (a) is one workgroup with the tile in 32.5 KiB + 16.25 KiB of LDS, two barriers per column; (b) is T - k - 1
- * workgroups and (c) (T - k - 1)^2, of which the upper half return at once: three launches per block column.  Each solve
+ * How it runs (csrc/ebm_gain.hip): every product is the 256-lane, 64 x 64 tile of csrc/ebm_mfma_tile.h, operands staged
+ * line-major sixteen t at a time through 9 KiB of LDS, the next sixteen in flight under the matrix instructions.  (a) is
+ * one workgroup with the tile in 32.5 KiB + 16.25 KiB of LDS, two barriers per column; (b) is T - k - 1 workgroups and (c)
+ * (T - k - 1)^2, of which the upper half return at once: three launches per block column.  Each solve
  * direction is ONE launch of ceil(nrhs / 64) workgroups; a workgroup re-reads only what it wrote itself, behind a block-level
  * fence and a barrier.  Assembly and scatter are one lane per element.  Plain vector loads and stores, no atomics, no scratch
  * memory.  Device memory, kept by the handle, reused and freed by ebm_destroy: 64 mp doubles of block inverses and one int

@@ -5,7 +5,7 @@ tests/tools/mutants.py, whose list, anchor rule and build this file uses unchang
     python tests/tools/mutants.py build covariance        (CPU: one full build per mutant under build/)
     python tests/tools/mutants.py run covariance          (GPU box: tests/test_gpu_ensemble_cov.py against each build)
 
-What tests/test_gpu_ensemble_cov.py does with each: profiles/r31_covariance_mutants.txt.
+What tests/test_gpu_ensemble_cov.py does with each: profiles/r31_covariance_mutants.txt, profiles/r36_dense_tile_mutants.txt.
   tail_group_dropped              a group of fewer than four members at the end of a block is not issued
   b_side_keeps_nan                the NaN cleaning of the B side is skipped: a sentinel of the column field poisons its column
   mirror_wrong_triangle           the finish computes j <= i from partials that rule 6 never wrote, and mirrors those
@@ -18,16 +18,21 @@ What tests/test_gpu_ensemble_cov.py does with each: profiles/r31_covariance_muta
                                   block partials; the bit-for-bit tests compare the library with itself (layouts, geometries,
                                   runs), where both sides add in the same wrong order; and on integer data every order is
                                   exact.  It is kept as a control, not counted as a kill.
+One mutant of the shared tile (csrc/ebm_mfma_tile.h), which breaks the update and the gain as well; it is listed here only:
+  d_map_rows_packed               register g of an accumulator is taken for row g of its 16, not row 4 g: three of every four
+                                  results go to a wrong cell of the workgroup's own tile
 """
 KIND = "csrc"
 TESTS = ("tests/test_gpu_ensemble_cov.py", "-m", "gpu")
 LIMIT = 300
 MUTANTS = [
-    ("tail_group_dropped", "if (m0 + k0 >= ncols) break;", "if (m0 + k0 + 4 > ncols) break;"),
+    ("tail_group_dropped", "(ncols - m0 + 3) / 4", "(ncols - m0) / 4"),
     ("b_side_keeps_nan", "return (in && w != 0.0 && x == x) ? t : 0.0;", "return (in && w != 0.0 && (x == x || !WEIGHTED)) ? t : 0.0;"),
     ("mirror_wrong_triangle", "if (j >= a.nlat || (a.symmetric && j < i)) return;", "if (j >= a.nlat || (a.symmetric && j > i)) return;"),
     ("weight_zero_contributes", "return (in && w != 0.0 && x == x) ? t : 0.0;", "return (in && x == x) ? t : 0.0;"),
     ("last_cell_is_padding", "s.in0 = 2 * u < a.nlat;", "s.in0 = 2 * u < a.nlat - 1;"),
     ("blocks_descending", "for (int b = 1; b < a.nblocks; ++b) r = r + part[b * stride];",
      "for (int b = 1; b < a.nblocks; ++b) r = r + part[(a.nblocks - b) * stride];", None, "survives"),
+    ("d_map_rows_packed", "return {l.r0 + 16 * s + 4 * g + l.lk, l.q0 + 16 * t + l.lc};",
+     "return {l.r0 + 16 * s + g + l.lk, l.q0 + 16 * t + l.lc};", "ebm_mfma_tile.h"),
 ]

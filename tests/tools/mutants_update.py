@@ -23,7 +23,7 @@ KIND = "csrc"
 TESTS = ("tests/test_gpu_update_columns.py", "-m", "gpu")
 LIMIT = 400
 MUTANTS = [
-    ("tail_group_dropped", "if (j0 + k0 >= a.nlat) break;", "if (j0 + k0 + 4 > a.nlat) break;"),
+    ("tail_group_dropped", "(a.nlat - j0 + 3) / 4", "(a.nlat - j0) / 4"),
     ("nan_obs_is_data", "return (in && y == y && xo == xo) ? d : 0.0;", "return (in && y == y) ? d : 0.0;"),
     ("clamp_not_strict", "x = x < lo ? lo : x;", "x = x <= lo ? lo : x;"),
     ("clamp_catches_nan", "x = x < lo ? lo : x;", "x = !(x >= lo) ? lo : x;"),
