@@ -68,7 +68,7 @@ def assert_same_bits(a, b, what=""):
 # ---- grid and time -----------------------------------------------------------------------------------------------------------
 
 # steps per year: the explicit model is stable for nt >= nlat^2 / 4; 4096 is stepped by the implicit extension only
-_STEPS_PER_YEAR = {2: 2000, 3: 2000, 65: 2000, 180: 2000, 258: 20000, 513: 70000, 1025: 270000, 4096: 2000}
+_STEPS_PER_YEAR = {2: 2000, 3: 2000, 65: 2000, 180: 2000, 257: 20000, 258: 20000, 513: 70000, 1025: 270000, 4096: 2000}
 
 
 def steps_per_year(nlat):

@@ -239,6 +239,65 @@ def test_one_year_and_min_years(pkg):
     assert got["years"].min() >= 5 and got["converged"].any()
 
 
+def test_model_time_continues_from_the_step_clock(pkg):
+    """Every other case here starts at step 0.  From a step clock of three years the years of the call are steps
+    clock0 + (y - 1) nt onwards, as the second handle's plain runs take them: the fields are as of step
+    clock0 + nt * years - 1 (check_against_reference asks field_step for it)."""
+    setup = Setup(pkg, "MIZ", "sin", 16, 200, 4)
+    setup.clock0 = 3 * 200
+    got, _, _ = check_against_reference(setup, ("T",), 3, tol=[1e9])
+    assert (got["years"] == 2).all() and got["converged"].all()
+
+
+# nlat -> the row of each column's one ice cell.  The check kernel walks a column with 256 threads, four waves whose maxima
+# meet in LDS: 65 rows are one wave and one lane of the second; 193 reach the fourth wave with one lane (row 192); 257 are one
+# full stride and row 256, the first of the second; 513 two full strides and one row.  Rows 200 and 255 lie in the fourth
+# wave's 192 .. 255, rows 256, 300 and 511 in the second stride, 512 in the third.
+CHECK_ROWS = {65: (0, 33, 63, 64), 193: (10, 100, 191, 192), 257: (100, 200, 255, 256), 513: (200, 300, 511, 512)}
+
+
+@pytest.mark.parametrize("nlat", sorted(CHECK_ROWS))
+def test_residuals_are_the_max_of_the_year_end_differences(pkg, nlat):
+    """The residuals against NumPy's max |cur - prev| over the fields a second handle gives at two consecutive year ends, bit
+    for bit: a max of exact differences does not depend on the order of the reduction.  Which rows differ is chosen, not
+    drawn: every column is warm open water (h = Ei = 0 in every row, and they stay exactly 0 while nothing freezes) but for
+    ONE cell of pack ice, in a different row per column (CHECK_ROWS), so h and Ei differ between the two year ends in that
+    row alone — the test asserts it — while T differs in every row.  A "year" is 16 steps of 5e-7 years: real steps, and the
+    ice cell neither melts away nor spreads in 32 of them."""
+    rows = CHECK_ROWS[nlat]
+    ncol, nt, names = len(rows), 16, ("T", "h", "Ei")
+    st = pkg.SpaceTime("sin", nlat, nt, 1)
+    g = load_golden("miz_sin_180_2000.npz")
+    state = {k: np.zeros((ncol, nlat)) for k in PROG + ("T0",)}
+    state["Ew"][:] = 21.0
+    for c, r in enumerate(rows):
+        for k in state:
+            state[k][c, r] = g[f"s1000_{k}"][-1]                     # the fixture's polar cell: phi = 1, h = 1.9 m
+    vec = pkg.engine.param_vector(pkg.default_parameters("MIZ"), pkg.default_parval)
+
+    def engine():
+        eng = pkg.Engine("MIZ", st.grid_kind, st.x, vec, 5e-7, ncol, device=0)
+        eng.set_time_table(st.t)
+        eng.set_state(state)
+        return eng
+    with engine() as ref:
+        ref.run(0, nt, None, True, 64)
+        prev = {k: ref.get_field(k) for k in names}
+        ref.run(nt, nt, None, True, 64)
+        cur = {k: ref.get_field(k) for k in names}
+    for c, r in enumerate(rows):
+        for k in ("h", "Ei"):
+            assert list(np.flatnonzero(cur[k][c] != prev[k][c])) == [r], (k, c, r)
+        assert np.count_nonzero(cur["T"][c] != prev["T"][c]) >= nlat - 1
+    with engine() as eng:
+        got = eng.equilibrate(nt, 2, None, {k: 1e9 for k in names})
+    assert (got["years"] == 2).all() and got["converged"].all()
+    for k in names:
+        want = np.max(np.abs(cur[k] - prev[k]), axis=1)
+        assert (want > 0.0).all(), k
+        assert np.array_equal(got["resid"][k].view(np.int64), want.view(np.int64)), (k, got["resid"][k], want)
+
+
 def test_sharding_invariance(pkg):
     setup = Setup(pkg, "MIZ", "sin", 180, 2000, 12)
     got, snaps, tol = check_against_reference(setup, ("T",), MAX_YEARS)

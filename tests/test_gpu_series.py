@@ -169,6 +169,35 @@ def test_hemispheric_mean_at_tile_boundaries(pkg, nlat):
             assert np.array_equal(out.cpu().numpy(), want, equal_nan=True), (nlat, name, "device output")
 
 
+@pytest.mark.parametrize("nlat", [257, 258])
+def test_both_mean_kernels_at_the_launcher_rule(pkg, nlat):
+    """The launcher gives ONE field of a meridian of more than 256 terms (nlat - 1 > 256) to the 256-lane kernel and everything
+    else to the 64-lane one: 257 latitudes are the last shape the small kernel takes with one field, 258 the first the large
+    one takes.  The series of each of three fields alone, and of the three together (always 64 lanes), against the
+    reference's sequential sum restated in NumPy on the downloaded fields, bit for bit — and so the same bits from both
+    kernels.  test_hemispheric_mean_at_tile_boundaries already holds the 256-lane kernel to that sum at 513 latitudes and
+    more, through ebm_hemispheric_mean; it runs neither side of the rule's threshold and never several fields."""
+    model, grid, ncol, cells, every, K, nsteps, names = "MIZ", "sin", 3, 4, 4, 4, 8, ("T", "phi", "Ei")
+
+    def series(which):
+        eng, st = make_engine(pkg, model, grid, nlat, ncol, cells)
+        first = first_step(st)
+        with eng:
+            return eng.run_series(first, nsteps, every, which, forcing_of(first, nsteps), K)
+    ref, st = make_engine(pkg, model, grid, nlat, ncol, cells)
+    first = first_step(st)
+    with ref:
+        _, host = by_hand(pkg, ref, st, model, first, nsteps, every, K, names, forcing_of(first, nsteps))
+    assert np.isfinite(host).all()
+    together = series(names)
+    assert together.shape == host.shape == (3, nsteps // every, ncol)
+    for v, n in enumerate(names):
+        alone = series((n,))
+        assert same_bits(alone[0], host[v]), (nlat, n, "one field")
+        assert same_bits(together[v], host[v]), (nlat, n, "three fields")
+        assert same_bits(alone[0], together[v]), (nlat, n)
+
+
 # ---- options and per-column settings -------------------------------------------------------------------------------------
 
 def install_members(pkg, model, ncol_total):

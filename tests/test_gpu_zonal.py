@@ -108,3 +108,32 @@ def test_zonal_substep_arguments(pkg):
     with pkg.Engine("Classic", stc.grid_kind, stc.x, pkg.engine.param_vector(parc, pkg.default_parval), stc.dt, 12, device=0) as engc:
         with pytest.raises(pkg.EBMError, match="MIZ handle"):
             engc.zonal_diffusion(T, 4)
+
+
+# ---- the edges of the unrolled loops and the segmented path at its smallest ----------------------------------------------
+# (the comparison is test_zonal_substep_matches_both_restatements itself: the same two restatements, the same 1e-12 bars)
+
+@pytest.mark.parametrize("cells", [2, 4])
+@pytest.mark.parametrize("nlon", [3, 4, 17, 18, 19, 34, 35])
+def test_zonal_sweep_at_the_edges_of_its_unrolled_loops(pkg, oracle, coracle, nlon, cells):
+    """zonal_sweep_kernel loads 16 rows ahead of its recurrence: the forward sweep takes a group while l + 16 <= nlon - 2 and
+    the backward sweep, which starts at l = nlon - 3, while l >= 15; single rows do the rest.  nlon = 3: no group, one row of
+    each tail; 4: two rows of each tail; 17: tails only, 15 and 15 rows; 18: one group each and NO tail; 19: one group and
+    one tail row each; 34: two groups, no tail; 35: two groups and one row.  65 latitudes (two waves, the second with one
+    lane), two members."""
+    test_zonal_substep_matches_both_restatements(pkg, oracle, coracle, "sin", 65, nlon, 2, 2000, cells)
+
+
+@pytest.mark.parametrize("nlon,nmember,segments", [(256, 3, 4), (1024, 2, 16)])
+def test_zonal_segments_at_their_smallest(pkg, oracle, coracle, nlon, nmember, segments):
+    """The segmented path decodes blockIdx.y into (member, segment).  256 longitudes are the shortest circle that is cut (4
+    segments of 64: three groups and a tail of 14 rows forward, three groups and 15 rows backward), here with three members
+    — more than one of each, and a member count that is no power of two.  1024 is the smallest nlon that zonal_segments
+    (csrc/ebm_tables.h) cuts into 16 — 16 divides it with 64 unknowns left per segment, 32 would leave 32 — which no other
+    case runs: the reduced system's loops over S - 2 = 14 rows."""
+    S = 1
+    for c in (4, 8, 16, 32):                                            # zonal_segments, restated
+        if nlon % c == 0 and nlon // c >= 64:
+            S = c
+    assert S == segments
+    test_zonal_substep_matches_both_restatements(pkg, oracle, coracle, "sin", 65, nlon, nmember, 2000, 4)

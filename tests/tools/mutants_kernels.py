@@ -26,7 +26,8 @@ MUTANTS = [
     ("lateral_growth_guard_inverted", "if (hk == 0.0) lat_grow = 0.0;", "if (hk != 0.0) lat_grow = 0.0;"),
     ("welding_quadratic", "const double weld = p.c_weld * ph * (Dk * Dk * Dk);", "const double weld = p.c_weld * ph * (Dk * Dk);"),
     ("concentration_not_capped", "if (phi_n > 1.0) phi_n = 1.0;", ""),
-    ("halo_left_is_own_value", "left = t > 0 ? l : 0.0;", "left = t > 0 ? first : 0.0;"),
+    ("halo_left_is_own_value", "const double l = E1[tl], r = E0[tr];\n    left = t > 0 ? l : 0.0;",
+     "const double l = E1[tl], r = E0[tr];\n    left = t > 0 ? first : 0.0;"),
     ("back_substitution_drops_left_interface", "x[i] = __builtin_fma(-cp[i], x[i + 1], __builtin_fma(lp[i], L, dp[i]));",
      "x[i] = __builtin_fma(-cp[i], x[i + 1], dp[i]);"),
     # (an EQUIVALENT mutant, kept as a control: with E == +-0 both forms give +-0 — the suite cannot and need not see it)
@@ -47,9 +48,14 @@ MUTANTS = [
     ("insolation_seasonal_sign", "return p.S0 - p.S1 * xk * ct - p.S2 * (xk * xk);", "return p.S0 + p.S1 * xk * ct - p.S2 * (xk * xk);"),
     ("t0_conduction_ignores_hmin", "return __builtin_fma(p.k, fast_rcp((hk == 0.0) ? p.hmin : hk), p.B);", "return __builtin_fma(p.k, fast_rcp(hk), p.B);"),
     # (the second EQUIVALENT control: at T0 == Tm exactly both branches of the piecewise-linear system agree)
-    ("active_set_includes_melting_point", "snew |= (xs[i] < 0.0) ? (1u << i) : 0u;", "snew |= (xs[i] <= 0.0) ? (1u << i) : 0u;",
+    ("active_set_includes_melting_point",
+     "partition_solve<C, TT, COMPACT>(ra, rb, rc, rd, xs, t, T, P0, P1);\n    unsigned snew = 0;\n#pragma unroll\n"
+     "    for (int i = 0; i < C; ++i) snew |= (xs[i] < 0.0) ? (1u << i) : 0u;",
+     "partition_solve<C, TT, COMPACT>(ra, rb, rc, rd, xs, t, T, P0, P1);\n    unsigned snew = 0;\n#pragma unroll\n"
+     "    for (int i = 0; i < C; ++i) snew |= (xs[i] <= 0.0) ? (1u << i) : 0u;",
      "ebm_miz_pieces.h", "survives"),
-    ("active_rows_ignore_concentration", "g[i] = ((smask >> i) & 1u) ? ph[i] : 0.0;", "g[i] = ((smask >> i) & 1u) ? 1.0 : 0.0;"),
+    ("active_rows_ignore_concentration", "    double g[C];\n#pragma unroll\n    for (int i = 0; i < C; ++i) g[i] = ((smask >> i) & 1u) ? ph[i] : 0.0;",
+     "    double g[C];\n#pragma unroll\n    for (int i = 0; i < C; ++i) g[i] = ((smask >> i) & 1u) ? 1.0 : 0.0;"),
     ("classic_ocean_heat_flux_sign", "Ek = Ek + p.dt * (Cc - p.M * Tk + p.Fb);", "Ek = Ek + p.dt * (Cc - p.M * Tk - p.Fb);"),
     # (merged with resident_extension_matrix_diagonal_sign: the step and the resident kernel share imex_row)
     ("extension_matrix_diagonal_sign", "rb = 1.0 + p.theta_imex * (lo + up);", "rb = 1.0 - p.theta_imex * (lo + up);"),
@@ -59,8 +65,12 @@ MUTANTS = [
     ("solver_table_uses_wrong_spacing", "double l = p.D * g1[k] / (g3[k] * g4[k]);", "double l = p.D * g1[k] / (g2[k] * g4[k]);", "ebm_tables.h"),
     ("classic_ghost_diagonal_sign", "kdiag[k] = one - (dtD * g1[k]) / p.cg;", "kdiag[k] = one + (dtD * g1[k]) / p.cg;", "ebm_tables.h"),
     ("model_time_at_step_start", "return nt > 0.0 ? (double)(2 * step + 1) / (2.0 * nt) : 0.0;", "return nt > 0.0 ? (double)(2 * step) / (2.0 * nt) : 0.0;", "ebm_drive.hip"),
-    ("lastonly_keeps_one_step_too_many", "s.raw = stage && (!lastonly || tinx > total - nt);", "s.raw = stage && (!lastonly || tinx >= total - nt);", "ebm_drive.hip"),
-    ("winter_snapshot_one_step_late", "s.season = ti == winter_inx ? 1 :", "s.season = ti == winter_inx + 1 ? 1 :", "ebm_drive.hip"),
+    # (lastonly_keeps_one_step_too_many left this list when its line moved to ebm_savesol.h: on the device all it does is keep
+    # nt + 1 snapshots where the caller's array holds nt, so the last one is copied past the end of the caller's buffer and the
+    # test process dies — profiles/r03_mutants.log.  A mutant of this list stays inside the buffers.  The same change is
+    # raw_kept_from_the_step_before_the_last_year of tests/tools/mutants_savesol.py, which the host walk kills without a buffer)
+    ("winter_snapshot_one_step_late", "if (ti == c.winter_inx) s.season = SEASON_WINTER;", "if (ti == c.winter_inx + 1) s.season = SEASON_WINTER;",
+     "ebm_savesol.h"),
     ("annual_mean_divides_by_nt_minus_1", "m.x = s.x / nt;", "m.x = s.x / (nt - 1.0);"),
     ("annual_sum_not_restarted", "z.x = 0.0;", "z.x = s.x;"),
     # (the one term expression of the library: hemispheric_means_of_column, which every mean of every entry point goes through)
@@ -76,7 +86,12 @@ MUTANTS = [
     ("extension_lower_diagonal_sign", "ra = -(p.theta_imex * lo);", "ra = (p.theta_imex * lo);"),
     ("classic_ghost_layer_uses_this_steps_sun", "const double S_ip1 = Sb[i] - (p.S1 * ct_next) * xk[i];", "const double S_ip1 = Sb[i] - (p.S1 * ct) * xk[i];"),
     # fifth batch: the solver's own algebra, the store paths of the two launch geometries, the iteration's control flow
-    ("column_offsets_all_take_the_first", "double f = a.fcol ? ft + a.fcol[col] : ft;", "double f = a.fcol ? ft + a.fcol[0] : ft;"),
+    ("column_offsets_all_take_the_first", "return schedule_forcing(a, col, a.fcol ? ft + a.fcol[col] : ft, tyear);",
+     "return schedule_forcing(a, col, a.fcol ? ft + a.fcol[0] : ft, tyear);", "ebm_device.h"),
+    # (the column's offset has two more readers since the step head: the words asked for in place, and the batched head)
+    ("resident_column_offset_takes_the_first", "h.fcol = a.fcol ? a.fcol[col] : 0.0;", "h.fcol = a.fcol ? a.fcol[0] : 0.0;", "ebm_device.h"),
+    ("batched_head_column_offset_takes_the_first", "reinterpret_cast<uintptr_t>(a.fcol + col) : spare)[0];",
+     "reinterpret_cast<uintptr_t>(a.fcol) : spare)[0];", "ebm_device.h"),
     ("partition_interface_row_sign", "const double RB = __builtin_fma(ce, vn, __builtin_fma(-ae, cp[C - 2], be));", "const double RB = __builtin_fma(ce, vn, __builtin_fma(ae, cp[C - 2], be));"),
     ("second_level_left_coupling_sign", "lq[i] = -(a2[i] * lq[i - 1]) * w;", "lq[i] = (a2[i] * lq[i - 1]) * w;"),
     ("cyclic_reduction_lower_sign", "const double nqa = -(qa * am) * r;", "const double nqa = (qa * am) * r;"),
@@ -111,7 +126,12 @@ MUTANTS = [
     ("zonal_segment_end_takes_the_wrong_neighbour", "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)((s_ + 1) % S) * P], sg[o + (size_t)s_ * P]); };",
      "auto rhs = [&](int s_) { return __builtin_fma(a, su[o + (size_t)s_ * P], sg[o + (size_t)s_ * P]); };"),
     ("zonal_reduced_diagonal_without_the_spike_sum", "const double a2 = a * ep_last, B2 = B - a * cp_last - a * alpha;", "const double a2 = a * ep_last, B2 = B - a * cp_last;", "ebm_tables.h"),
-    ("integrate_restarts_model_time", "f, diag, clock0 + tinx - 1,", "f, diag, tinx - 1,", "ebm_drive.hip"),
+    # (two sites since integrate_impl walks ebm_savesol.h's items: the fused stretches and the single steps)
+    ("integrate_restarts_model_time", "rc = fused_range(h, it.first, clock0 + it.first, (int)it.n,", "rc = fused_range(h, it.first, it.first, (int)it.n,",
+     "ebm_drive.hip"),
+    ("integrate_single_steps_restart_model_time", "s.diag() ? 1 : 0, clock0 + it.first,", "s.diag() ? 1 : 0, it.first,", "ebm_drive.hip"),
+    ("equilibrate_year_restarts_model_time", "rc = fused_range(h, 0, clock0 + (long long)(y - 1) * nt, nt,", "rc = fused_range(h, 0, (long long)(y - 1) * nt, nt,",
+     "ebm_drive.hip"),
     ("as_of_query_inverted", "    if (have != step)", "    if (have == step)", "ebm_fields.hip"),
     # seventh batch: the LDS-resident fused-K kernel, its compact solve, its halo exchange and its vote
     ("resident_diagnostics_of_the_first_step", "const bool diag = a.write_diag != 0 && step + 1 == nloop;", "const bool diag = a.write_diag != 0 && step == 0;"),
@@ -129,10 +149,13 @@ MUTANTS = [
     ("resident_state_words_one_slot_low", "win[((4 + 4 * (F) + (i)) * T) >> 13][((4 + 4 * (F) + (i)) * T) & 8191]", "win[((3 + 4 * (F) + (i)) * T) >> 13][((3 + 4 * (F) + (i)) * T) & 8191]"),
     # eighth batch: ebm_integrate's fused stretches
     ("resident_sums_of_the_second_pair_land_on_the_first", "(unsigned)((i / 2) * 2 * T) + 2u * (unsigned)td,", "2u * (unsigned)td,"),
-    ("integrate_fused_stretch_restarts_its_forcing", "(int)n, f_steps ? f_steps + (tinx - 1) : nullptr, 0, h->integrate_spl,", "(int)n, f_steps, 0, h->integrate_spl,", "ebm_drive.hip"),
-    ("integrate_fused_stretch_one_table_entry_late", "rc = fused_range(h, tinx - 1, clock0 + tinx - 1,", "rc = fused_range(h, tinx, clock0 + tinx - 1,", "ebm_drive.hip"),
+    ("integrate_fused_stretch_restarts_its_forcing", "(int)it.n, f, 0, h->integrate_spl,", "(int)it.n, f_steps, 0, h->integrate_spl,", "ebm_drive.hip"),
+    ("integrate_fused_stretch_one_table_entry_late", "rc = fused_range(h, it.first, clock0 + it.first,", "rc = fused_range(h, it.first + 1, clock0 + it.first,",
+     "ebm_drive.hip"),
     # (the step plan is one function now: the loop body reads the same result, so the winter step, fused through or
-    # not, is not taken for a snapshot step)
-    ("integrate_fuses_through_the_winter_snapshot", "s.snapshot = (ti == winter_inx && (winter || hm_winter)) || (ti == summer_inx && (summer || hm_summer));",
-     "s.snapshot = ti == summer_inx && (summer || hm_summer);", "ebm_drive.hip"),
+    # not, is not taken for a snapshot step.  Since ebm_savesol.h the stretch's end is next_event's — stretch_runs_through_a_
+    # wanted_season of the savesol list — and what this flag still decides is that the winter step stores the diagnostic
+    # fields and leaves every field in the natural layout before its snapshot is copied)
+    ("integrate_fuses_through_the_winter_snapshot", "s.snapshot = (ti == c.winter_inx && c.want_winter) || (ti == c.summer_inx && c.want_summer);",
+     "s.snapshot = ti == c.summer_inx && c.want_summer;", "ebm_savesol.h"),
 ]
